@@ -22,8 +22,10 @@ KGMA_F_CHAIN_REPLAY -- the mode the API mirrors run by default and the one whose
 the reference's Float64 order), plus the hit gather for N > 1.  Inputs (the ASCII genome) are resident in
 HBM before the timed region starts.
 
-Secondary (N = 1 only, outside the timed region): the same step without the chain (exact integers + local
-tie resolver: `exact_mode_step`), and the chr22-size record of BASELINE configs[1] (a 0.2 ms step).
+A plain run sets up, warms up, times --steps steps, writes the last timed step's hits if --dump-outputs is
+given, and prints the result line.  Only with --full (N = 1 only, outside the timed region): the same step
+without the chain (exact integers + local tie resolver: `exact_mode_step`), the chr22-size record of BASELINE
+configs[1] (a 0.2 ms step), the CPU oracle baselines and the count of planted genes found.
 
 Prints ONE JSON line on rank 0.
 """
@@ -38,7 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "kmergma.jl_amd"))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E: 8 TB/s spec
 ALGO_BYTES_PER_BASE = 0.25     # scan kernel reads the 2-bit genome once
 PACK_BYTES_PER_BASE = 1.25     # pack kernel: 1 B ASCII read + 0.25 B 2-bit interleaved copy written (the bit-plane copy is only made for kernels that read it)
 N_RECORDS = 100
@@ -128,6 +130,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--dump-hits", default="", help="rank 0 writes the last step's hit list here (JSON; tests compare N ranks with one)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed step's hit records here, one float64 DIR/hits_<field>.npy per field")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary workloads and CPU baselines and count the planted genes found")
     args = ap.parse_args()
 
     import numpy as np
@@ -216,23 +222,20 @@ def main():
         elapsed = float(t.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            # (before anything else calls the library: step_hits returns a view of a buffer the next step reuses;
+            #  every field is an integer below 2^53 or a Float64, so float64 holds it exactly)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name in _lib.HIT_DTYPE.names:
+                if name != "reserved":
+                    col = np.zeros(0) if hits is None else hits[name]
+                    np.save(os.path.join(args.dump_outputs, "hits_%s.npy" % name), np.asarray(col, dtype=np.float64))
         ms_per_step = elapsed * 1e3 / args.steps
         value = total_bases * args.steps / elapsed / 1e6
         avg_scan_ms = sum(scan_ms) / len(scan_ms)
         avg_pack_ms = sum(pack_ms) / len(pack_ms)
         achieved = ALGO_BYTES_PER_BASE * my_bases / (avg_scan_ms * 1e-3) / 1e9
         traffic, traffic_src, pmc_extra = pmc_profile(ctx.kernel_name(), my_bases)
-        n_found = 0
-        if hits is not None and len(hits):
-            hc = np.asarray(hits["contig"], dtype=np.int64)
-            starts = np.asarray(hits["cmi"], dtype=np.int64) - 5
-            by_rec = {}
-            for c, s in zip(hc.tolist(), starts.tolist()):
-                by_rec.setdefault(c, []).append(s)
-            for c, pos, data in plants:
-                arr = by_rec.get(c)
-                if arr is not None and np.any(np.abs(np.asarray(arr) - pos) <= 40):
-                    n_found += 1
         out = {
             "metric": "Mbp scanned/sec (whole node) at k=6, 1 ref cluster", "value": round(value, 1),
             "unit": "Mbp/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -256,7 +259,7 @@ def main():
                                       " (Float64 chain of the tied pairs included)" + (" + RCCL all_gather of the hit records (inside the timed region)" if world > 1 else "")),
                        "k": 6, "windowsize": W, "n_ref_clusters": 1, "genome_bases": total_bases,
                        "bases_per_gpu_rank0": my_bases, "n_hits": 0 if hits is None else int(len(hits)),
-                       "n_planted": len(plants), "n_planted_found": n_found, "sharding": "records across GPUs (strong scaling)"},
+                       "n_planted": len(plants), "sharding": "records across GPUs (strong scaling)"},
             "roofline": {"bound": "lds+valu", "contracted_bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
                          "traffic_source": traffic_src, "pmc": pmc_extra,
@@ -277,7 +280,20 @@ def main():
             with open(args.dump_hits, "w") as fh:
                 json.dump({"columns": cols, "hits": [] if hits is None else [[int(h[c]) for c in cols] for h in hits]}, fh)
         out["per_rank"] = {"rank0_records": [int(rec0), int(rec1)], "rank0_bases": int(my_bases), "world": int(world)}
-        if world == 1 and not args.no_secondary:
+        if args.full:
+            n_found = 0
+            if hits is not None and len(hits):
+                hc = np.asarray(hits["contig"], dtype=np.int64)
+                starts = np.asarray(hits["cmi"], dtype=np.int64) - 5
+                by_rec = {}
+                for c, s in zip(hc.tolist(), starts.tolist()):
+                    by_rec.setdefault(c, []).append(s)
+                for c, pos, data in plants:
+                    arr = by_rec.get(c)
+                    if arr is not None and np.any(np.abs(np.asarray(arr) - pos) <= 40):
+                        n_found += 1
+            out["config"]["n_planted_found"] = n_found
+        if args.full and world == 1 and not args.no_secondary:
             # the same step without the chain (exact integers + the local tie resolver), for the record
             for _ in range(2):
                 ctx.step_hits(genome, _lib.MODE_SINGLE, buff, 0, 0)
@@ -291,7 +307,7 @@ def main():
                                       "n_hits": int(len(he_)), "n_tie_flagged": int(ste["n_tie_flagged"]),
                                       "n_at_threshold": int(ste["n_at_threshold"]),
                                       "note": "flags = 0: not guaranteed reference-identical where n_tie_flagged + n_at_threshold > 0"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n = min(rec_len, 1_000_000_000)
             seq = genome.fetch(0, 1, n)
             v, nh = cpu_baseline(seq, refs, thr)
@@ -305,7 +321,7 @@ def main():
                                                           "share of the host), scanned concurrently by the same oracle, best of 2"}
             del seq
     genome.free()
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         # BASELINE configs[1]: chr22-size record (0.25 ms steps; the round-1 headline), outside the timed region
         g2, _ = workloads.make_chr22_like(ctx, refs["genes"], seed=22)
         for _ in range(150):
