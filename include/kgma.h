@@ -194,9 +194,11 @@ void kgma_destroy(kgma_ctx *ctx);
  *     (KGMA_HIT_AT_THRESHOLD / KGMA_HIT_TIE), and KGMA_F_CHAIN_REPLAY decides them from the reference's own running value
  *     (replayed on the device from the caller's table, bit for bit).  kgma_hit.D / kgma_dip.D_* are then round(d * 2kN^2) with N a power of
  *     two (kgma_kfv_scale), kgma_hit.dist the Float64 distance.
- * Requires 2 <= k <= 10, k < min(windowsizes) (src/API.jl:70,177) and at most 65535 k-mers per window (windowsize - k + 1:
- * the window counts are 16-bit; the reference itself has no bound, src/ReferenceGeneration.jl:35-40); KGMA_E_UNSUPPORTED
- * otherwise, and for S/N KFVs whose largest possible D = sum S^2 + N^2 n^2 does not fit 61 bits.
+ * Requires 1 <= k <= 15 (a k-mer is at most 30 bits of the 2-bit genome), k < min(windowsizes) (src/API.jl:70,177) and at most
+ * 65535 k-mers per window (windowsize - k + 1; the reference itself has no bound, src/ReferenceGeneration.jl:35-40);
+ * KGMA_E_UNSUPPORTED otherwise, and for S/N KFVs whose largest possible D = sum S^2 + N^2 n^2 does not fit 61 bits.
+ * At k >= 11 the library reads `ref` once for its non-zero entries and keeps no 4^k copy, on the host or on the device
+ * (kgma_set_refs_sparse takes those entries directly: a dense KFV at k = 15 is 8 GiB).
  * Threshold semantics: with D the exact integer form of the distance (d = D / (2 k N^2)) a window
  * is below thr iff D < T, T = ceil(thr * 2kN^2 * (1 - 2^-30)).  The 2^-30 guard band stands for the
  * rounding noise of the reference's rolling Float64 chain (GenomeMiner.jl:77): windows whose exact
@@ -204,6 +206,13 @@ void kgma_destroy(kgma_ctx *ctx);
  * kgma_stats.n_at_threshold).  Away from the distance lattice T = ceil(thr * 2kN^2) exactly. */
 int kgma_set_refs(kgma_ctx *ctx, int32_t k, int32_t m, const double *ref, const int64_t *windowsizes,
                   const double *thr, const int64_t *n_refs);
+
+/* The same references given by their non-zero entries: KFV j has nnz[j] entries, keys[] / vals[] hold them KFV after KFV.  Keys are
+ * natural k-mer values (0-based, first base most significant: the reference's index - 1), strictly increasing within a KFV; every
+ * other entry is 0.  Exactly kgma_set_refs on the dense vectors (S/N inference, the Float64 form, every error and message), for
+ * 1 <= k <= 15; KGMA_E_ARG for a key >= 4^k or out of order. */
+int kgma_set_refs_sparse(kgma_ctx *ctx, int32_t k, int32_t m, const int64_t *nnz, const uint32_t *keys, const double *vals,
+                         const int64_t *windowsizes, const double *thr, const int64_t *n_refs);
 
 /* Change thresholds only (thr[m]). */
 int kgma_set_thresholds(kgma_ctx *ctx, const double *thr);
@@ -301,7 +310,8 @@ int kgma_host_semiglobal_cigar(const uint8_t *a, int64_t m, const uint8_t *b, in
 /* HOST-side helper (no device): the reference's running Float64 distance kmerDist (src/GenomeMiner.jl:46-47,70-77; the same
  * update in src/OmnGenomeMiner.jl:73-74,101-108) of one sequence, from its first window on, sampled at the windows of
  * the given intervals (1-based window starts, sorted, disjoint): what KGMA_F_CHAIN_REPLAY runs for the (record, KFV) pairs
- * that contain a rounding-dependent tie.  Two-call pattern via cap / *n_out as elsewhere. */
+ * that contain a rounding-dependent tie.  1 <= k <= 15; `ref` is the dense 4^k vector.  Two-call pattern via cap / *n_out as
+ * elsewhere. */
 int kgma_host_chain_values(const uint8_t *seq, int64_t len, const double *ref, int32_t k, int64_t windowsize,
                            const int64_t *win_lo, const int64_t *win_hi, int64_t n_intervals, double *out, int64_t cap,
                            int64_t *n_out);

@@ -29,6 +29,7 @@
 #include <functional>
 #include <thread>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/kgma.h"
@@ -108,7 +109,41 @@ struct KfvInfo {
     int ref_form = -1;        // how the Float64 entries follow from S, bit for bit, so that the device can form them from S (the chain
                               // kernel does): 0 = RN(S * RN(1/N)) (`answer .* (1/N)`, src/ReferenceGeneration.jl:35,40), 1 = RN(S / N)
                               // (`KFVs[i] ./= lens[i]`, :118) reproduced by the kernel's own division step, -1 = neither
+    // k >= 11 (sparse): no 4^k table exists -- S and ref above stay empty, and the KFV is its non-zero entries in increasing natural
+    // k-mer value (sk), their Float64 values (sv) and, integer form, their S (sS); sp_off / sp_log2: its open-addressed device table
+    bool sparse = false;
+    std::vector<uint32_t> sk;
+    std::vector<double> sv;
+    std::vector<int64_t> sS;
+    size_t sp_off = 0;
+    int sp_log2 = 0;
+    size_t sp_find(uint64_t x) const
+    {
+        const auto it = std::lower_bound(sk.begin(), sk.end(), (uint32_t)x);
+        return it != sk.end() && *it == (uint32_t)x ? (size_t)(it - sk.begin()) : SIZE_MAX;
+    }
+    double ref_at(uint64_t x) const
+    {
+        if (!sparse) return ref[(size_t)x];
+        const size_t i = sp_find(x);
+        return i == SIZE_MAX ? 0.0 : sv[i];
+    }
+    int64_t S_at(uint64_t x) const
+    {
+        if (!sparse) return S[(size_t)x];
+        const size_t i = sp_find(x);
+        return i == SIZE_MAX ? 0 : sS[i];
+    }
+    // the KFV for the host chain (kgma_chain.h): the dense table, or the sparse one
+    void chain_ref(ChainJob &J) const
+    {
+        if (sparse) { J.ref = nullptr; J.sp_keys = sk.data(); J.sp_vals = sv.data(); J.sp_n = (int64_t)sk.size(); }
+        else { J.ref = ref.data(); J.sp_keys = nullptr; J.sp_vals = nullptr; J.sp_n = 0; }
+    }
 };
+
+// dwords of one wave slot's count table in global memory (cmode 1: 4^k 16-bit counters; 4: the wide hash table, 16 bytes per entry)
+inline int64_t generic_ctab_dwords(const GenParams &gg) { return gg.cmode == 4 ? (int64_t)4 << gg.hash_log2m : ((int64_t)1 << (2 * gg.k)) / 2; }
 
 struct Group {
     int64_t W;
@@ -260,6 +295,7 @@ struct kgma_ctx {
     std::map<std::vector<int>, int16_t *> sinter;   // k = 7 stream kernel: interleaved int16 S tables per launch group (device)
     int32_t *d_StabC = nullptr;       // the same tables in the stream kernel's index order ((hi bits << k) | lo bits)
     double *d_Rtab = nullptr;         // m x 4^k Float64, device index order: the KFVs as given (only when one of them is not S/N)
+    uint8_t *d_sparse = nullptr;      // k >= 11: the KFVs' open-addressed tables of non-zero entries (KfvInfo::sp_off: keys, S, Float64)
     uint32_t *d_gctab = nullptr; int64_t gctab_cap = 0;   // generic kernel at k >= 8: count tables of its wave slots (dwords)
     int64_t *d_Wtab = nullptr;        // window size per KFV (export_kernel's tie gather)
     int16_t *d_diff = nullptr; int64_t diff_cap = 0;   // two-kernel cluster path: per-window self-match differences of a tile chunk
@@ -683,6 +719,7 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_Stab) (void)hipFree(ctx->d_Stab);
     if (ctx->d_StabC) (void)hipFree(ctx->d_StabC);
     if (ctx->d_Rtab) (void)hipFree(ctx->d_Rtab);
+    if (ctx->d_sparse) (void)hipFree(ctx->d_sparse);
     if (ctx->d_gctab) (void)hipFree(ctx->d_gctab);
     for (auto &kv2 : ctx->sinter) (void)hipFree(kv2.second);
     if (ctx->d_Wtab) (void)hipFree(ctx->d_Wtab);
@@ -954,105 +991,215 @@ int kgma_set_thresholds(kgma_ctx *ctx, const double *thr)
     return KGMA_OK;
 }
 
+}  // extern "C"
+
+// the generic kernels' view of a sparse KFV (k >= 11): its device table, S values (integer form) or Float64 ones
+static void set_sparse_params(const kgma_ctx *ctx, const KfvInfo &f, GenParams &gg, bool fp)
+{
+    const size_t P = (size_t)1 << f.sp_log2;
+    gg.S = nullptr; gg.R = nullptr;
+    gg.sp_keys = reinterpret_cast<const uint32_t *>(ctx->d_sparse + f.sp_off);
+    gg.sp_vals = reinterpret_cast<const uint64_t *>(ctx->d_sparse + f.sp_off + (fp ? 12 : 4) * P);
+    gg.sp_log2 = f.sp_log2;
+}
+
+// One KFV of kgma_set_refs / kgma_set_refs_sparse from its non-zero entries (natural k-mer values, increasing; their values): the
+// window checks, the S/N inference, the Float64 form and its magnitude bound, fits32 / big_ok, ref_form, the threshold and every
+// error and message -- ONE routine for both entry points, so their semantics are the same by construction.  Every test and sum runs
+// over the non-zero entries only, which is exact: a zero entry passes each test (0 * N is the integer 0, S = 0 gives RN(0 * invN)
+// = RN(0 / N) = 0) and adds +0.0 or 0 to each sum (sumR2 in increasing k-mer value: the dense left-to-right sum's bits).  Fills
+// f.sk / f.sv and, integer form, f.sS; the dense tables are the caller's business.
+static int kfv_from_nonzeros(kgma_ctx *ctx, int32_t k, int j, std::vector<uint32_t> &&kj, std::vector<double> &&nz, const int64_t *windowsizes,
+                             const double *thr, const int64_t *n_refs, KfvInfo &f)
+{
+    f.W = windowsizes[j];
+    if (k >= f.W)   // src/API.jl:70,177
+        return fail(ctx, KGMA_E_ARG, "the average reference sequence length %lld exceeds/is equal to the chosen kmer length %d. please reduce k.",
+                    (long long)f.W, k);
+    const int64_t nk = f.W - k + 1;
+    if (nk > KGMA_MAX_NK_WIDE)
+        return fail(ctx, KGMA_E_UNSUPPORTED, "window size %lld: at most %d k-mers per window are supported (16-bit window counts)", (long long)f.W,
+                    KGMA_MAX_NK_WIDE);
+    // Is the KFV S/N with integer S (what gen_ref_ws_cons / cluster_ref_API produce: an average of integer histograms)?  Then the
+    // device computes in exact integers.  Anything else -- refVec::Vector{Float64} may be any vector (src/GenomeMiner.jl:6,
+    // src/OmnGenomeMiner.jl:9) -- takes the Float64 form of the generic kernel.  "Is S/N": every entry times N within 1e-14
+    // (relative) of a non-negative integer, i.e. S/N up to the rounding of its own division or multiplication (a looser test
+    // finds "N" for irrational vectors too: 1/sqrt(2)-weighted averages are within 5e-13 of S/665857, a convergent).
+    auto is_s_over_n = [&](const int64_t cand, const double tol) {
+        for (const double e : nz) {
+            const double v = e * (double)cand, rv = std::nearbyint(v);
+            if (!(std::fabs(v - rv) <= tol * std::max(1.0, std::fabs(v))) || rv < 0 || rv > 2.0e9) return false;
+        }
+        return true;
+    };
+    int64_t N = 0;
+    bool fp = false;
+    for (size_t i = 0; i < nz.size(); i++)
+        if (!std::isfinite(nz[i])) return fail(ctx, KGMA_E_ARG, "KFV %d entry %lld is not finite", j + 1, (long long)kj[i]);
+    if (n_refs) {
+        N = n_refs[j];
+        if (N < 1) return fail(ctx, KGMA_E_ARG, "n_refs[%d] = %lld", j, (long long)N);
+        if (!is_s_over_n(N, 1e-14)) fp = true;
+    } else {
+        for (int64_t cand = 1; cand <= (1 << 20) && N == 0; cand++)
+            if (is_s_over_n(cand, 1e-14)) N = cand;
+        if (N == 0) fp = true;
+    }
+    f.sk = std::move(kj);
+    f.sv = std::move(nz);
+    for (const double e : f.sv) f.sumR2 += e * e;                      // (the Float64 kernels' first-window identity)
+    __int128 s2 = 0;
+    if (fp) {
+        // Float64 form.  The host keeps every distance on an integer lattice D = round(d * 2kN^2) with N a power of two chosen so
+        // that the largest possible D stays below 2^61 (resolution 1 / (2kN^2): 8e-14 at k = 6 for windows of a few hundred k-mers)
+        double r2 = 0, amax = 0;
+        for (const double e : f.sv) { r2 += e * e; amax = std::max(amax, std::fabs(e)); }
+        const double fmax = r2 + (double)nk * (double)nk + 2.0 * (double)nk * amax + 1.0;     // >= sum (ref - c)^2 for any window
+        int q = 20;
+        while (q > 0 && fmax * std::ldexp(1.0, 2 * q) >= std::ldexp(1.0, 61)) q--;
+        if (fmax >= std::ldexp(1.0, 61)) return fail(ctx, KGMA_E_UNSUPPORTED, "KFV %d: entries of magnitude %.3g are outside the device path's range", j + 1, amax);
+        f.fp = true; f.N = (int64_t)1 << q;
+        f.Smax = INT64_MAX; f.sumS2 = 0;
+        f.fits32 = false; f.big_ok = false; f.ref_form = -1;
+        f.thr = thr[j];
+        threshold_band(thr[j], k, f.N, &f.T, &f.T_hi, ctx->band_log2);
+        return KGMA_OK;
+    }
+    f.N = N;
+    f.sS.resize(f.sv.size());
+    for (size_t i = 0; i < f.sv.size(); i++) {
+        const double rv = std::nearbyint(f.sv[i] * (double)N);
+        f.sS[i] = (int64_t)rv;
+        f.Smax = std::max(f.Smax, (int64_t)rv);
+        s2 += (__int128)f.sS[i] * f.sS[i];
+    }
+    // What the kernels keep in 32 bits: the int32 kernels E = (D - D0)/(2N) and N * (count difference); the 16-bit counter form of
+    // stream8_kernel the LOCAL prefix of a 64-window step, |e| <= Smax + N n per window (its carries are 64-bit); the generic
+    // kernel nothing (int64 throughout: D itself must fit)
+    const __int128 dmax = s2 + (__int128)N * N * nk * nk;
+    f.fits32 = !(dmax / (2 * N) >= ((__int128)1 << 29) || (__int128)N * nk >= ((__int128)1 << 30));
+    f.big_ok = (__int128)64 * ((__int128)f.Smax + (__int128)N * nk) <= ((__int128)1 << 30) && N < ((int64_t)1 << 22);
+    if (dmax >= ((__int128)1 << 61))
+        return fail(ctx, KGMA_E_UNSUPPORTED, "KFV %d: N = %lld with %lld k-mers per window exceeds the int64 range of the device path", j + 1,
+                    (long long)N, (long long)nk);
+    f.sumS2 = (int64_t)s2;
+    {
+        const double invN = 1.0 / (double)N, Nd = (double)N;
+        bool mul = true, div = true;
+        for (size_t i = 0; i < f.sv.size() && (mul || div); i++) {
+            const double Sd = (double)f.sS[i], q = Sd * invN;
+            mul = mul && f.sv[i] == q;
+            div = div && f.sv[i] == std::fma(std::fma(-q, Nd, Sd), invN, q) && f.sv[i] == Sd / Nd;
+        }
+        f.ref_form = mul ? 0 : (div ? 1 : -1);
+    }
+    f.thr = thr[j];
+    threshold_band(thr[j], k, N, &f.T, &f.T_hi, ctx->band_log2);
+    return KGMA_OK;
+}
+
+// kgma_set_refs at k >= 11, from each KFV's non-zero entries: kfv_from_nonzeros, and on the device per KFV an open-addressed table of
+// those entries (load <= 1/2) instead of the 4^k tables.
+static int set_refs_sparse_core(kgma_ctx *ctx, int32_t k, int32_t m, std::vector<std::vector<uint32_t>> &keys,
+                                std::vector<std::vector<double>> &vals, const int64_t *windowsizes, const double *thr, const int64_t *n_refs)
+{
+    std::vector<KfvInfo> kv((size_t)m);
+    for (int j = 0; j < m; j++) {
+        KfvInfo &f = kv[(size_t)j];
+        const int rc = kfv_from_nonzeros(ctx, k, j, std::move(keys[(size_t)j]), std::move(vals[(size_t)j]), windowsizes, thr, n_refs, f);
+        if (rc != KGMA_OK) return rc;
+        f.sparse = true;
+    }
+    // device tables: per KFV [keys: 2^p u32 | S: 2^p int64 | Float64: 2^p], keys in the kernels' index order (kgma_device.h, GenParams)
+    size_t total = 0;
+    for (int j = 0; j < m; j++) {
+        KfvInfo &f = kv[(size_t)j];
+        int lg = 6;
+        while (((size_t)1 << lg) < 2 * f.sk.size()) lg++;
+        f.sp_log2 = lg;
+        f.sp_off = total;
+        total += ((size_t)20 << lg);
+    }
+    std::vector<uint8_t> host(total, 0);
+    for (int j = 0; j < m; j++) {
+        const KfvInfo &f = kv[(size_t)j];
+        const size_t P = (size_t)1 << f.sp_log2;
+        uint32_t *hk = reinterpret_cast<uint32_t *>(host.data() + f.sp_off);
+        int64_t *hs = reinterpret_cast<int64_t *>(host.data() + f.sp_off + 4 * P);
+        double *hr = reinterpret_cast<double *>(host.data() + f.sp_off + 12 * P);
+        for (size_t i = 0; i < P; i++) hk[i] = KGMA_SP_EMPTY;
+        for (size_t i = 0; i < f.sk.size(); i++) {
+            const uint32_t key = device_index_of(f.sk[i], k);
+            uint32_t h = (key * 2654435761u) >> (32 - f.sp_log2);
+            while (hk[h] != KGMA_SP_EMPTY) h = (h + 1u) & (uint32_t)(P - 1);
+            hk[h] = key;
+            hs[h] = f.fp ? 0 : f.sS[i];
+            hr[h] = f.sv[i];
+        }
+    }
+    for (void *p : {(void *)ctx->d_Stab, (void *)ctx->d_StabC, (void *)ctx->d_Rtab, (void *)ctx->d_sparse, (void *)ctx->d_Wtab}) if (p) (void)hipFree(p);
+    ctx->d_Stab = nullptr; ctx->d_StabC = nullptr; ctx->d_Rtab = nullptr; ctx->d_sparse = nullptr; ctx->d_Wtab = nullptr;
+    for (auto &kv2 : ctx->sinter) (void)hipFree(kv2.second);
+    ctx->sinter.clear();
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_sparse), total));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_sparse, host.data(), total, hipMemcpyHostToDevice));
+    {
+        std::vector<int64_t> wt((size_t)m);
+        for (int j = 0; j < m; j++) wt[(size_t)j] = kv[(size_t)j].W;
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_Wtab), wt.size() * sizeof(int64_t)));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_Wtab, wt.data(), wt.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    ctx->k = k;
+    ctx->m = m;
+    ctx->kfv.swap(kv);
+    for (double *p : ctx->d_dist) if (p) (void)hipFree(p);
+    ctx->d_dist.assign((size_t)m, nullptr);
+    ctx->dist_cap.assign((size_t)m, 0);
+    ctx->last_mode = -1;
+    ctx->tk_uid = 0;
+    return KGMA_OK;
+}
+
+extern "C" {
+
 int kgma_set_refs(kgma_ctx *ctx, int32_t k, int32_t m, const double *ref, const int64_t *windowsizes,
                   const double *thr, const int64_t *n_refs)
 {
     if (!ctx) return KGMA_E_ARG;
     if (!ref || !windowsizes || !thr || m < 1) return fail(ctx, KGMA_E_ARG, "null argument or m < 1");
-    if (k < 2 || k > 10) return fail(ctx, KGMA_E_UNSUPPORTED, "k = %d: the device path supports 2 <= k <= 10", k);
+    if (k < 1 || k > KGMA_MAX_K) return fail(ctx, KGMA_E_UNSUPPORTED, "k = %d: the device path supports 1 <= k <= %d", k, KGMA_MAX_K);
     (void)hipSetDevice(ctx->device);
     const int64_t NB = (int64_t)1 << (2 * k);
+    if (k >= KGMA_WIDE_MIN_K) {
+        // (one pass over the caller's vectors: their non-zero entries; no 4^k copy is kept)
+        std::vector<std::vector<uint32_t>> keys((size_t)m);
+        std::vector<std::vector<double>> vals((size_t)m);
+        for (int j = 0; j < m; j++) {
+            const double *r = ref + (size_t)j * (size_t)NB;
+            for (int64_t x = 0; x < NB; x++)
+                if (r[x] != 0.0) { keys[(size_t)j].push_back((uint32_t)x); vals[(size_t)j].push_back(r[x]); }
+        }
+        return set_refs_sparse_core(ctx, k, m, keys, vals, windowsizes, thr, n_refs);
+    }
     std::vector<KfvInfo> kv((size_t)m);
     for (int j = 0; j < m; j++) {
         KfvInfo &f = kv[(size_t)j];
-        f.W = windowsizes[j];
-        if (k >= f.W)   // src/API.jl:70,177
-            return fail(ctx, KGMA_E_ARG, "the average reference sequence length %lld exceeds/is equal to the chosen kmer length %d. please reduce k.",
-                        (long long)f.W, k);
-        const int64_t nk = f.W - k + 1;
-        if (nk > KGMA_MAX_NK_WIDE)
-            return fail(ctx, KGMA_E_UNSUPPORTED, "window size %lld: at most %d k-mers per window are supported (16-bit window counts)", (long long)f.W,
-                        KGMA_MAX_NK_WIDE);
         const double *r = ref + (size_t)j * (size_t)NB;
-        // Is the KFV S/N with integer S (what gen_ref_ws_cons / cluster_ref_API produce: an average of integer histograms)?  Then the
-        // device computes in exact integers.  Anything else -- refVec::Vector{Float64} may be any vector (src/GenomeMiner.jl:6,
-        // src/OmnGenomeMiner.jl:9) -- takes the Float64 form of the generic kernel.  "Is S/N": every entry times N within 1e-14
-        // (relative) of a non-negative integer, i.e. S/N up to the rounding of its own division or multiplication (a looser test
-        // finds "N" for irrational vectors too: 1/sqrt(2)-weighted averages are within 5e-13 of S/665857, a convergent).
-        // (only the non-zero entries can fail: a KFV at k = 10 has a million entries, nearly all of them zero, and the inference
-        //  below tries up to 2^20 candidates)
+        // (only the non-zero entries can fail a test: a KFV at k = 10 has a million entries, nearly all of them zero)
+        std::vector<uint32_t> keys;
         std::vector<double> nz;
         for (int64_t x = 0; x < NB; x++)
-            if (r[x] != 0.0) nz.push_back(r[x]);
-        auto is_s_over_n = [&](const int64_t cand, const double tol) {
-            for (const double e : nz) {
-                const double v = e * (double)cand, rv = std::nearbyint(v);
-                if (!(std::fabs(v - rv) <= tol * std::max(1.0, std::fabs(v))) || rv < 0 || rv > 2.0e9) return false;
-            }
-            return true;
-        };
-        int64_t N = 0;
-        bool fp = false;
-        for (int64_t x = 0; x < NB; x++)
-            if (!std::isfinite(r[x])) return fail(ctx, KGMA_E_ARG, "KFV %d entry %lld is not finite", j + 1, (long long)x);
-        if (n_refs) {
-            N = n_refs[j];
-            if (N < 1) return fail(ctx, KGMA_E_ARG, "n_refs[%d] = %lld", j, (long long)N);
-            if (!is_s_over_n(N, 1e-14)) fp = true;
-        } else {
-            for (int64_t cand = 1; cand <= (1 << 20) && N == 0; cand++)
-                if (is_s_over_n(cand, 1e-14)) N = cand;
-            if (N == 0) fp = true;
-        }
+            if (r[x] != 0.0) { keys.push_back((uint32_t)x); nz.push_back(r[x]); }
+        const int rc = kfv_from_nonzeros(ctx, k, j, std::move(keys), std::move(nz), windowsizes, thr, n_refs, f);
+        if (rc != KGMA_OK) return rc;
+        // k <= 10: the dense tables (natural k-mer order) the kernels' uploads below and the host replays read
         f.ref.assign(r, r + NB);
-        for (int64_t x = 0; x < NB; x++) f.sumR2 += r[x] * r[x];          // (the Float64 kernels' first-window identity)
-        __int128 s2 = 0;
-        if (fp) {
-            // Float64 form.  The host keeps every distance on an integer lattice D = round(d * 2kN^2) with N a power of two chosen so
-            // that the largest possible D stays below 2^61 (resolution 1 / (2kN^2): 8e-14 at k = 6 for windows of a few hundred k-mers)
-            double r2 = 0, amax = 0;
-            for (int64_t x = 0; x < NB; x++) { r2 += r[x] * r[x]; amax = std::max(amax, std::fabs(r[x])); }
-            const double fmax = r2 + (double)nk * (double)nk + 2.0 * (double)nk * amax + 1.0;     // >= sum (ref - c)^2 for any window
-            int q = 20;
-            while (q > 0 && fmax * std::ldexp(1.0, 2 * q) >= std::ldexp(1.0, 61)) q--;
-            if (fmax >= std::ldexp(1.0, 61)) return fail(ctx, KGMA_E_UNSUPPORTED, "KFV %d: entries of magnitude %.3g are outside the device path's range", j + 1, amax);
-            f.fp = true; f.N = (int64_t)1 << q;
-            f.S.clear(); f.Smax = INT64_MAX; f.sumS2 = 0;
-            f.fits32 = false; f.big_ok = false; f.ref_form = -1;
-            f.thr = thr[j];
-            threshold_band(thr[j], k, f.N, &f.T, &f.T_hi, ctx->band_log2);
-            continue;
+        if (!f.fp) {
+            f.S.assign((size_t)NB, 0);
+            for (size_t i = 0; i < f.sk.size(); i++) f.S[f.sk[i]] = f.sS[i];
         }
-        f.N = N;
-        f.S.resize((size_t)NB);
-        for (int64_t x = 0; x < NB; x++) {
-            const double rv = std::nearbyint(r[x] * (double)N);
-            f.S[(size_t)x] = (int64_t)rv;
-            f.Smax = std::max(f.Smax, (int64_t)rv);
-            s2 += (__int128)f.S[(size_t)x] * f.S[(size_t)x];
-        }
-        // What the kernels keep in 32 bits: the int32 kernels E = (D - D0)/(2N) and N * (count difference); the 16-bit counter form of
-        // stream8_kernel the LOCAL prefix of a 64-window step, |e| <= Smax + N n per window (its carries are 64-bit); the generic
-        // kernel nothing (int64 throughout: D itself must fit)
-        const __int128 dmax = s2 + (__int128)N * N * nk * nk;
-        f.fits32 = !(dmax / (2 * N) >= ((__int128)1 << 29) || (__int128)N * nk >= ((__int128)1 << 30));
-        f.big_ok = (__int128)64 * ((__int128)f.Smax + (__int128)N * nk) <= ((__int128)1 << 30) && N < ((int64_t)1 << 22);
-        if (dmax >= ((__int128)1 << 61))
-            return fail(ctx, KGMA_E_UNSUPPORTED, "KFV %d: N = %lld with %lld k-mers per window exceeds the int64 range of the device path", j + 1,
-                        (long long)N, (long long)nk);
-        f.sumS2 = (int64_t)s2;
-        {
-            const double invN = 1.0 / (double)N, Nd = (double)N;
-            bool mul = true, div = true;
-            for (int64_t x = 0; x < NB && (mul || div); x++) {
-                const double Sd = (double)f.S[(size_t)x], q = Sd * invN;
-                mul = mul && r[x] == q;
-                div = div && r[x] == std::fma(std::fma(-q, Nd, Sd), invN, q) && r[x] == Sd / Nd;
-            }
-            f.ref_form = mul ? 0 : (div ? 1 : -1);
-        }
-        f.thr = thr[j];
-        threshold_band(thr[j], k, N, &f.T, &f.T_hi, ctx->band_log2);
+        f.sk.clear(); f.sv.clear(); f.sS.clear();
+        f.sk.shrink_to_fit(); f.sv.shrink_to_fit(); f.sS.shrink_to_fit();
     }
     // upload the plane-index permuted tables
     std::vector<int32_t> tab((size_t)m * (size_t)NB, 0);
@@ -1064,6 +1211,7 @@ int kgma_set_refs(kgma_ctx *ctx, int32_t k, int32_t m, const double *ref, const 
             tab[(size_t)j * (size_t)NB + device_index_of((uint32_t)v, k)] = (int32_t)kv[(size_t)j].S[(size_t)v];
     }
     if (ctx->d_Rtab) { (void)hipFree(ctx->d_Rtab); ctx->d_Rtab = nullptr; }
+    if (ctx->d_sparse) { (void)hipFree(ctx->d_sparse); ctx->d_sparse = nullptr; }
     (void)any_fp;
     {
         // the KFVs as given (Float64), in the kernels' index order: what the Float64 form of the generic kernel and its chain
@@ -1106,6 +1254,43 @@ int kgma_set_refs(kgma_ctx *ctx, int32_t k, int32_t m, const double *ref, const 
     ctx->last_mode = -1;
     ctx->tk_uid = 0;
     return KGMA_OK;
+}
+
+// The same references as their non-zero entries: nnz[j] (keys, vals) pairs per KFV, natural k-mer values (0-based, first base most
+// significant), strictly increasing.  k <= 10: the dense vectors, through kgma_set_refs.
+int kgma_set_refs_sparse(kgma_ctx *ctx, int32_t k, int32_t m, const int64_t *nnz, const uint32_t *keys, const double *vals,
+                         const int64_t *windowsizes, const double *thr, const int64_t *n_refs)
+{
+    if (!ctx) return KGMA_E_ARG;
+    if (!nnz || !windowsizes || !thr || m < 1) return fail(ctx, KGMA_E_ARG, "null argument or m < 1");
+    if (k < 1 || k > KGMA_MAX_K) return fail(ctx, KGMA_E_UNSUPPORTED, "k = %d: the device path supports 1 <= k <= %d", k, KGMA_MAX_K);
+    const uint64_t NB = (uint64_t)1 << (2 * k);
+    int64_t total = 0;
+    for (int j = 0; j < m; j++) {
+        if (nnz[j] < 0 || (uint64_t)nnz[j] > NB) return fail(ctx, KGMA_E_ARG, "nnz[%d] = %lld", j, (long long)nnz[j]);
+        total += nnz[j];
+    }
+    if (total > 0 && (!keys || !vals)) return fail(ctx, KGMA_E_ARG, "null argument or m < 1");
+    int64_t at = 0;
+    for (int j = 0; j < m; j++)
+        for (int64_t i = 0; i < nnz[j]; i++, at++)
+            if ((uint64_t)keys[at] >= NB || (i > 0 && keys[at] <= keys[at - 1]))
+                return fail(ctx, KGMA_E_ARG, "KFV %d: key %lld is not below 4^k or not above the one before it", j + 1, (long long)keys[at]);
+    if (k < KGMA_WIDE_MIN_K) {
+        std::vector<double> dense((size_t)m * (size_t)NB, 0.0);
+        at = 0;
+        for (int j = 0; j < m; j++)
+            for (int64_t i = 0; i < nnz[j]; i++, at++) dense[(size_t)j * (size_t)NB + keys[at]] = vals[at];
+        return kgma_set_refs(ctx, k, m, dense.data(), windowsizes, thr, n_refs);
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<std::vector<uint32_t>> kk((size_t)m);
+    std::vector<std::vector<double>> vv((size_t)m);
+    at = 0;
+    for (int j = 0; j < m; j++)
+        for (int64_t i = 0; i < nnz[j]; i++, at++)
+            if (vals[at] != 0.0) { kk[(size_t)j].push_back(keys[at]); vv[(size_t)j].push_back(vals[at]); }   // (explicit zeros: absent)
+    return set_refs_sparse_core(ctx, k, m, kk, vv, windowsizes, thr, n_refs);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1987,7 +2172,8 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     // The generic kernel (kgma_generic.hip; one KFV per launch) takes the whole scan when a KFV is served by nothing else: a general
     // Float64 KFV, a window of more than 2031 k-mers or a prefix beyond int32 where the 16-bit stream8 form does not apply
     // (k < 5, k > 7, S beyond int16 at k = 7, N >= 2^22).  KGMA_KERNEL=generic (testing): always.
-    bool generic_all = kenv && !strcmp(kenv, "generic");
+    // k = 1 and k >= 11: only the generic kernel's 32-bit counter and wide hash forms serve them
+    bool generic_all = (kenv && !strcmp(kenv, "generic")) || k == 1 || k >= KGMA_WIDE_MIN_K;
     for (int j = 0; j < m_used; j++) {
         const KfvInfo &f = ctx->kfv[(size_t)j];
         if (f.fp || ((f.W - k + 1 > KGMA_MAX_NK || !f.fits32) && !(s8_all && c16_ok(f)))) generic_all = true;
@@ -2369,12 +2555,16 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
                 gg.thr_lo = f.thr * (1.0 - std::ldexp(1.0, -ctx->band_log2)); gg.thr_hi = f.thr * (1.0 + std::ldexp(1.0, -ctx->band_log2));
                 gg.sumR2 = f.sumR2; gg.SF = 1.0 / (double)k; gg.inv_scale = gp.inv_scale[0];
                 gg.tie_rel = 9.313225746154785e-10;
-                gg.S = ctx->d_Stab + (size_t)j * (size_t)NBk;
-                gg.R = ctx->d_Rtab ? ctx->d_Rtab + (size_t)j * (size_t)NBk : nullptr;
-                if (f.fp && !gg.R) return fail(ctx, KGMA_E_STATE, "internal: no Float64 table for KFV %d", j + 1);
+                if (f.sparse) {
+                    set_sparse_params(ctx, f, gg, f.fp);
+                } else {
+                    gg.S = ctx->d_Stab + (size_t)j * (size_t)NBk;
+                    gg.R = ctx->d_Rtab ? ctx->d_Rtab + (size_t)j * (size_t)NBk : nullptr;
+                    if (f.fp && !gg.R) return fail(ctx, KGMA_E_STATE, "internal: no Float64 table for KFV %d", j + 1);
+                }
                 generic_set_mode(gg, (int)(maxws - k + 1));           // (one geometry for every launch of the scan: its longest window decides)
-                if (gg.cmode == 1) {
-                    rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * (NBk / 2));
+                if (gg.cmode == 1 || gg.cmode == 4) {
+                    rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * generic_ctab_dwords(gg));
                     if (rc) return rc;
                     gg.ctab = ctx->d_gctab;
                 }
@@ -2563,6 +2753,7 @@ struct TieResolver {
     std::vector<const uint8_t *> pre_ptr; // per dip: residues gathered on the device behind the scan, or nullptr
     static constexpr int64_t MAX_SPAN = 1 << 22;
     static constexpr int64_t MAX_PREFETCH = (int64_t)256 << 20;
+    std::unordered_map<uint32_t, int32_t> spcnt{};   // k >= 11: the window's counts (no 4^k table)
 
     // One gather launch + one download for all case-(A) dips (instead of a blocking copy per dip).
     void prefetch()
@@ -2639,6 +2830,11 @@ struct TieResolver {
         if (!g && !ctx->fetch) return r;                    // no residues at hand (dips came from another GPU, no residue source set)
         const KfvInfo &f = ctx->kfv[(size_t)kfv];
         if (f.fp) return r;                                 // (a Float64 KFV has no exact lattice to replay on: its near ties stay flagged for the chain)
+        // k = 1: no local decision either.  The replay starts from the exact distance as a stand-in for the reference's running value;
+        // with four k-mers the increments are a handful of values repeated, their rounding errors add up instead of cancelling (1e-9
+        // relative over 400 Mb), and the tied windows of a dip -- long plateaus of one exact distance on this coarse lattice -- are
+        // ordered by exactly those low bits.  The ties stay flagged (KGMA_HIT_TIE) and KGMA_F_CHAIN_REPLAY decides them.
+        if (ctx->k == 1) return r;
         const int k = ctx->k;
         const int64_t NB = (int64_t)1 << (2 * k);
         const uint64_t mask = (uint64_t)NB - 1;
@@ -2662,12 +2858,14 @@ struct TieResolver {
             seq = seqbuf.data();
             fetch_ms += now_ms() - tf0;
         }
-        if (cnt.empty()) cnt.assign((size_t)NB, 0);
+        if (!f.sparse && cnt.empty()) cnt.assign((size_t)NB, 0);
+        spcnt.clear();
+        auto C = [&](const uint64_t x) -> int32_t & { return f.sparse ? spcnt[(uint32_t)x] : cnt[(size_t)x]; };
         touched.clear();
         uint64_t km = 0;
         for (int64_t i = 0; i < W; i++) {
             km = ((km << 2) & mask) | (uint64_t)res_code(seq[(size_t)i]);
-            if (i >= k - 1) { if (cnt[(size_t)km]++ == 0) touched.push_back((uint32_t)km); }
+            if (i >= k - 1) { if (C(km)++ == 0) touched.push_back((uint32_t)km); }
         }
         uint64_t left = 0, right = 0;
         for (int64_t i = 0; i < k - 1; i++) left = (left << 2) | (uint64_t)res_code(seq[(size_t)i]);
@@ -2688,10 +2886,10 @@ struct TieResolver {
             left = ((left << 2) & mask) | (uint64_t)res_code(seq[(size_t)(o + k - 1)]);
             right = ((right << 2) & mask) | (uint64_t)res_code(seq[(size_t)(o + W)]);
             if (left != right) {
-                const int64_t cl = cnt[(size_t)left], cr = cnt[(size_t)right];
+                const int64_t cl = C(left), cr = C(right);
                 double t = (double)(1 + cr);
-                t = t + f.ref[(size_t)left];
-                t = t - f.ref[(size_t)right];
+                t = t + f.ref_at(left);
+                t = t - f.ref_at(right);
                 t = t - (double)cl;
                 const double inc = SF * t;
                 const double sum = dist + inc;
@@ -2711,9 +2909,9 @@ struct TieResolver {
                     if (ef <= 53 || std::fabs(err) == half_ulp || es != e0) sensitive = true;
                 }
                 dist = sum;
-                D += 2 * N * N + 2 * N * ((f.S[(size_t)left] - N * cl) - (f.S[(size_t)right] - N * cr));
-                if (cnt[(size_t)right]++ == 0) touched.push_back((uint32_t)right);
-                cnt[(size_t)left]--;
+                D += 2 * N * N + 2 * N * ((f.S_at(left) - N * cl) - (f.S_at(right) - N * cr));
+                if (C(right)++ == 0) touched.push_back((uint32_t)right);
+                C(left)--;
             }
             const int64_t w = s + 1;
             if (w >= cand_lo) {
@@ -2721,7 +2919,7 @@ struct TieResolver {
                 if (D == Dmin && dist < best) { best = dist; best_pos = w; improved = true; }
             }
         }
-        for (uint32_t x : touched) cnt[(size_t)x] = 0;
+        if (!f.sparse) for (uint32_t x : touched) cnt[(size_t)x] = 0;
         if (!consistent) return r;
         (void)include_start;
         r.ok = true; r.sensitive = sensitive; r.improved = improved; r.pos = best_pos;
@@ -2984,7 +3182,7 @@ static int chain_kernel_for(const kgma_ctx *ctx, const KfvInfo &f)
                     chain_slots_per_cu(k, f.Smax <= 32767, 1, nk, !f.fits32) >= 1;
     if (s8 && !(ge && atoi(ge) == 1)) return 1;
     if (ge && atoi(ge) == 0) return 0;
-    return k >= 2 && k <= 10 && nk >= 1 && nk <= KGMA_MAX_NK_WIDE && generic_chain_slots_per_cu(k, nk) >= 1 ? 2 : 0;
+    return k >= 1 && k <= KGMA_MAX_K && nk >= 1 && nk <= KGMA_MAX_NK_WIDE && generic_chain_slots_per_cu(k, nk) >= 1 ? 2 : 0;
 }
 
 static int chain_on_device(kgma_ctx *ctx, const kgma_genome *g, std::vector<ChainPair> &pairs, std::vector<char> &done, ChainDevInfo &info)
@@ -3317,10 +3515,11 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
                 gg.k = k; gg.nk = gp.nk; gg.N = (int32_t)f.N; gg.kfv_id = j + 1; gg.fp = 1;
                 gg.n_slots = (int32_t)((int64_t)std::max(1, ctx->n_cus) * generic_chain_slots_per_cu(k, gp.nk));
                 gg.sumR2 = f.sumR2; gg.SF = 1.0 / (double)k;
-                gg.R = ctx->d_Rtab + (size_t)j * (size_t)((int64_t)1 << (2 * k));
+                if (f.sparse) set_sparse_params(ctx, f, gg, true);
+                else gg.R = ctx->d_Rtab + (size_t)j * (size_t)((int64_t)1 << (2 * k));
                 generic_set_mode(gg, gp.nk);
-                if (gg.cmode == 1) {
-                    rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * (((int64_t)1 << (2 * k)) / 2));
+                if (gg.cmode == 1 || gg.cmode == 4) {
+                    rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * generic_ctab_dwords(gg));
                     if (rc) return rc;
                     gg.ctab = ctx->d_gctab;
                 }
@@ -3417,7 +3616,7 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
             size_t off = 0;
             for (const Rec &r : recs) if (r.c == p.c) off = r.dw_off;
             ChainJob &J = jobs[u];
-            J.seq = nullptr; J.packed = reinterpret_cast<const uint32_t *>(pin + off_first) + off; J.n_res = f.W; J.ref = f.ref.data();
+            J.seq = nullptr; J.packed = reinterpret_cast<const uint32_t *>(pin + off_first) + off; J.n_res = f.W; f.chain_ref(J);
             J.k = k; J.W = f.W; J.last_window = 1; J.iv = &one; J.n_iv = 1; J.out = &first[u]; J.n_out = 0; J.ok = false;
         }
         run_chain_jobs(jobs.data(), jobs.size(), 1);
@@ -3730,7 +3929,7 @@ static int chain_decide(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64
             for (size_t u = r.p0; u < r.p1; u++) {
                 Pair &p = *hostp[u];
                 ChainJob J;
-                J.seq = nullptr; J.packed = ctx->h_chain + r.dw_off; J.n_res = r.need; J.ref = ctx->kfv[(size_t)p.j].ref.data(); J.k = k;
+                J.seq = nullptr; J.packed = ctx->h_chain + r.dw_off; J.n_res = r.need; ctx->kfv[(size_t)p.j].chain_ref(J); J.k = k;
                 J.W = ctx->kfv[(size_t)p.j].W; J.last_window = p.last; J.iv = p.iv.data(); J.n_iv = p.iv.size();
                 J.out = p.val.data(); J.n_out = 0; J.ok = false;
                 jobs.push_back(J);
@@ -3947,7 +4146,7 @@ int kgma_chain_values(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32
         HIP_TRY(ctx, hipMemcpy(codes.data(), g->d_inter + 2 * g->cd[(size_t)contig].word_off, dw * 4, hipMemcpyDeviceToHost));
         static const ChainInterval one{1, 1};
         ChainJob J;
-        J.seq = nullptr; J.packed = codes.data(); J.n_res = f.W; J.ref = f.ref.data(); J.k = ctx->k; J.W = f.W; J.last_window = 1;
+        J.seq = nullptr; J.packed = codes.data(); J.n_res = f.W; f.chain_ref(J); J.k = ctx->k; J.W = f.W; J.last_window = 1;
         J.iv = &one; J.n_iv = 1; J.out = out; J.n_out = 0; J.ok = false;
         run_chain_jobs(&J, 1, 1);
         return J.ok && J.n_out == 1 ? KGMA_OK : fail(ctx, KGMA_E_HIP, "internal: first window of record %lld", (long long)contig);

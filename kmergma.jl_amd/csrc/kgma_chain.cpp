@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <cstring>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "kgma_chain.h"
@@ -76,9 +77,96 @@ struct PackedCodes {
     }
 };
 
+// k >= 11: the KFV as its sorted non-zero entries (an absent k-mer is 0) and the window's counts in a hash map -- O(nnz + window)
+// instead of O(4^k) per job.  Same operations on the same values in the same order as chain_walk below.
+template <class Codes>
+void chain_walk_sparse(ChainJob &J, const Codes code)
+{
+    J.ok = false;
+    const int k = J.k;
+    const int64_t W = J.W;
+    const uint64_t mask = ((uint64_t)1 << (2 * k)) - 1;
+    const int64_t last = J.last_window;
+    if (k < 1 || W < k || last < 1 || J.n_res < W + last - 1 || J.n_iv == 0) return;
+    const uint32_t *sk = J.sp_keys, *sk_end = J.sp_keys + J.sp_n;
+    auto ref = [&](const uint64_t x) -> double {
+        const uint32_t *it = std::lower_bound(sk, sk_end, (uint32_t)x);
+        return it != sk_end && *it == (uint32_t)x ? J.sp_vals[it - sk] : 0.0;
+    };
+    std::unordered_map<uint32_t, int32_t> cnt;
+    cnt.reserve((size_t)(2 * W));
+    uint64_t km = 0;
+    for (int64_t i = 0; i < W; i++) {
+        km = ((km << 2) & mask) | code(i);
+        if (i >= k - 1) cnt[(uint32_t)km]++;
+    }
+    // First window: the reference sums (ref[x] - cnt[x])^2 over every x in increasing order.  Where both are 0 the term is
+    // (0.0 - 0.0)^2 = +0.0, and adding +0.0 to the running sum (never -0.0: it starts at +0.0 and every term is >= +0.0) leaves its
+    // bits unchanged -- so the sum over the UNION of the KFV's non-zero keys and the window's k-mers, merged in increasing natural
+    // k-mer value, is the reference's value bit for bit.
+    std::vector<std::pair<uint32_t, int32_t>> wk(cnt.begin(), cnt.end());
+    std::sort(wk.begin(), wk.end());
+    double sq = 0.0;
+    {
+        size_t a = 0, b = 0;
+        const size_t na = (size_t)J.sp_n, nb = wk.size();
+        while (a < na || b < nb) {
+            double r = 0.0, c = 0.0;
+            if (b >= nb || (a < na && sk[a] < wk[b].first)) { r = J.sp_vals[a]; a++; }
+            else if (a >= na || wk[b].first < sk[a]) { c = (double)wk[b].second; b++; }
+            else { r = J.sp_vals[a]; c = (double)wk[b].second; a++; b++; }
+            const double d = r - c;
+            sq += d * d;
+        }
+    }
+    const double SF = 1.0 / (double)k;                 // src/API.jl:86,204
+    double dist = (SF * 0.5) * sq;                     // GenomeMiner.jl:29,46-47 / OmnGenomeMiner.jl:73-74
+    uint64_t left = 0, right = 0;
+    for (int64_t i = 0; i < k - 1; i++) left = (left << 2) | code(i);
+    for (int64_t i = W - k + 1; i < W; i++) right = (right << 2) | code(i);
+
+    const ChainInterval *iv = J.iv;
+    size_t ii = 0;
+    double *o = J.out;
+    int64_t cur_lo = iv[0].lo, cur_hi = iv[0].hi;
+    auto sample = [&](int64_t w, double v) {
+        if (w < cur_lo) return;
+        *o++ = v;
+        if (w == cur_hi) {
+            ii++;
+            if (ii < J.n_iv) { cur_lo = iv[ii].lo; cur_hi = iv[ii].hi; }
+            else { cur_lo = INT64_MAX; cur_hi = INT64_MAX; }
+        }
+    };
+    sample(1, dist);
+    auto pl = code.cursor(k - 1), pr = code.cursor(W);
+    for (int64_t w = 2; w <= last; w++) {              // roll window w-1 -> w  (GenomeMiner.jl:60-77)
+        left = ((left << 2) & mask) | pl.next();
+        right = ((right << 2) & mask) | pr.next();
+        if (left != right) {
+            int32_t &cl = cnt[(uint32_t)left];
+            const int32_t clv = cl;
+            cl = clv - 1;
+            if (clv - 1 == 0) cnt.erase((uint32_t)left);
+            int32_t &cr = cnt[(uint32_t)right];
+            const int32_t crv = cr;
+            cr = crv + 1;
+            double t = (double)(1 + crv);
+            t = t + ref(left);
+            t = t - ref(right);
+            t = t - (double)clv;
+            dist += SF * t;
+        }
+        sample(w, dist);
+    }
+    J.n_out = (int64_t)(o - J.out);
+    J.ok = true;
+}
+
 template <class Codes>
 void chain_walk(ChainJob &J, const Codes code)
 {
+    if (!J.ref) { chain_walk_sparse(J, code); return; }
     J.ok = false;
     const int k = J.k;
     const int64_t W = J.W, NB = (int64_t)1 << (2 * k);
@@ -384,7 +472,7 @@ extern "C" int kgma_host_chain_values(const uint8_t *seq, int64_t len, const dou
                                       const int64_t *win_lo, const int64_t *win_hi, int64_t n_intervals, double *out,
                                       int64_t cap, int64_t *n_out)
 {
-    if (!seq || !ref || !win_lo || !win_hi || !out || !n_out || k < 1 || k > 10 || windowsize < k || len < windowsize || n_intervals < 1)
+    if (!seq || !ref || !win_lo || !win_hi || !out || !n_out || k < 1 || k > kgma::KGMA_MAX_K || windowsize < k || len < windowsize || n_intervals < 1)
         return KGMA_E_ARG;
     std::vector<kgma::ChainInterval> iv((size_t)n_intervals);
     int64_t total = 0, prev = 0;
@@ -402,6 +490,15 @@ extern "C" int kgma_host_chain_values(const uint8_t *seq, int64_t len, const dou
     }
     kgma::ChainJob J;
     J.seq = seq; J.packed = nullptr; J.n_res = len; J.ref = ref; J.k = k; J.W = windowsize; J.last_window = iv.back().hi;
+    J.sp_keys = nullptr; J.sp_vals = nullptr; J.sp_n = 0;
+    std::vector<uint32_t> sk;
+    std::vector<double> sv;
+    if (k >= kgma::KGMA_WIDE_MIN_K) {                  // (the non-zero entries: no 4^k count table for the walk)
+        const int64_t NB = (int64_t)1 << (2 * k);
+        for (int64_t x = 0; x < NB; x++)
+            if (ref[x] != 0.0) { sk.push_back((uint32_t)x); sv.push_back(ref[x]); }
+        J.ref = nullptr; J.sp_keys = sk.data(); J.sp_vals = sv.data(); J.sp_n = (int64_t)sk.size();
+    }
     J.iv = iv.data(); J.n_iv = iv.size(); J.out = out; J.n_out = 0; J.ok = false;
     kgma::run_chain_jobs(&J, 1, 1);
     return J.ok && J.n_out == total ? KGMA_OK : KGMA_E_ARG;

@@ -18,7 +18,10 @@ struct ChainJob {
     const uint32_t *packed;    // (seq == nullptr) the record as 2-bit codes, 16 residues per dword, first residue = bits 0-1
                                // (the device's interleaved genome copy: src/Consts.jl:22-28 codes, N as T)
     int64_t n_res;             // residues available (>= W + last_window - 1)
-    const double *ref;         // the KFV as given (natural k-mer order, src/Kmers.jl:37-43)
+    const double *ref;         // the KFV as given (natural k-mer order, src/Kmers.jl:37-43) -- or, when nullptr (k >= 11: no 4^k table):
+    const uint32_t *sp_keys;   // its non-zero entries, natural k-mer values in increasing order,
+    const double *sp_vals;     // their values
+    int64_t sp_n;
     int k;
     int64_t W;
     int64_t last_window;

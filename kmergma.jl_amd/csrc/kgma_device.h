@@ -180,10 +180,25 @@ struct GenParams {
     uint32_t *ctab;                      // k >= 8: 4^k / 2 dwords of counters per wave slot (global memory)
     // where the wave keeps its counts (generic_set_mode): 0 = 4^k 16-bit counters in LDS (k <= 7), 1 = the same in global memory,
     // 2 = a hash table of the window's distinct k-mers in LDS (k >= 8, windows of at most KGMA_HASH_MAX_NK k-mers): 2^hash_log2m
-    // dwords per wave, rebuilt from the window every hash_rebuild steps
+    // dwords per wave, rebuilt from the window every hash_rebuild steps;  k >= 11 (kgma_generic.hip, "wide" tables): 3 = a hash table
+    // of 2^hash_log2m entries of 16 bytes (key, 32-bit count, the KFV's value) per wave in LDS (windows of at most KGMA_WIDE_LDS_MAX_NK
+    // k-mers), 4 = the same table in global memory (ctab, 4 << hash_log2m dwords per wave slot);  k = 1: 5 = four 32-bit counters in LDS
     int32_t cmode, hash_log2m, hash_rebuild;
+    // k >= 11: the KFV as an open-addressed table of its non-zero entries in global memory (no 4^k table exists): 2^sp_log2 slots,
+    // keys in the kernels' index order (0xFFFFFFFF: empty, at least half of the slots), values as 64-bit patterns -- the int32 S entry
+    // sign-extended (integer form) or the Float64 entry's bits (Float64 form, chain kernel).  An absent key is 0.
+    const uint32_t *sp_keys;
+    const uint64_t *sp_vals;
+    int32_t sp_log2;
 };
 constexpr int KGMA_HASH_MAX_NK = 1983;                         // count field of 11 bits: n + 64 <= 2047
+constexpr int KGMA_WIDE_MIN_K = 11;                            // k-mers of 2k > 20 bits: the wide tables (cmode 3 / 4) and the sparse KFV
+constexpr int KGMA_MAX_K = 15;                                 // 2k <= 30 bits: a k-mer is one dword of the 2-bit genome copy
+// cmode 3 up to this many k-mers per window (4096 entries, 64 KiB per wave, 2 waves per CU, >= 23 steps between rebuilds); measured at k = 12,
+// 400 Mb: LDS / global 9.3 / 4.6 Gbp/s at n = 989, 4.8 / 3.9 at 1489, 4.6 / 3.1 at 1989, 1.4 / 3.0 at 2989 (EXPERIMENTS)
+constexpr int KGMA_WIDE_LDS_MAX_NK = 2048;
+constexpr int KGMA_WIDE_LDS_NK_CAP = 8192 - 64 - 1024 - 512;   // ... the most an LDS table can serve: 8192 entries, 128 KiB (one wave per CU)
+constexpr uint32_t KGMA_SP_EMPTY = 0xFFFFFFFFu;
 
 // Count-table stream kernel (kgma_stream.hip): one wave per stream of consecutive window starts.
 constexpr int KGMA_STREAM_MIN_WINDOWS = 2048;                  // shorter streams waste their warm-up (n k-mers)

@@ -1,4 +1,4 @@
-// kgma_generic.hip -- the count-table stream walk without the specialisations of kgma_stream.hip: any 2 <= k <= 10, windows of
+// kgma_generic.hip -- the count-table stream walk without the specialisations of kgma_stream.hip: any 1 <= k <= 15, windows of
 // up to 65535 k-mers, 64-bit integer prefix -- or a Float64 running value for KFVs that are not S/N (refVec::Vector{Float64},
 // src/GenomeMiner.jl:6, src/OmnGenomeMiner.jl:9, may be any vector).  It serves what the tuned kernels do not: windows of more
 // than 2031 k-mers at k < 5 or k > 7, prefixes beyond int32 where the 16-bit stream8 form does not apply, and every general
@@ -17,6 +17,7 @@
 //                  directly computed distance; windows within a relative 2^-30 of thr are "at threshold", minima within
 //                  tie_rel of each other are reported as tied (nmin > 1) -- what rounding noise could decide differently in the
 //                  reference is flagged, exactly as in the integer form.
+// k = 1 keeps four 32-bit counters per wave (CM 5); k >= 11 a wide hash table per wave over a sparse KFV (CM 3 / 4, see WCounts).
 // Records are REC_WIDE: (minE_hi : minE) and (exitE_hi : exitE) hold the int64 E or the Float64 distance's bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -252,6 +253,13 @@ struct Counts {
                 }
             }
             oldp = wop & H_CNT; olds = wos & H_CNT;
+        } else if constexpr (CM == 5) {
+            // k = 1: one 32-bit counter per k-mer (a homopolymer window of 65535 k-mers holds n + 64 in flight: no 16-bit pairs)
+            cp = C[kp]; cs = C[ks];
+            uint32_t wop = 0, wos = 0;
+            if (actE) wop = atomicAdd(&C[kp], 1u);
+            if (actL) wos = atomicSub(&C[ks], 1u);
+            oldp = wop; olds = wos;
         } else {
             const uint32_t shp = 16u * (kp & 1u), shs = 16u * (ks & 1u);
             uint32_t wcp, wcs, wop = 0, wos = 0;
@@ -275,13 +283,207 @@ struct Counts {
     }
 };
 
+// ---- k >= 11: wide hash tables and the sparse KFV (cmode 3: in LDS, 4: in global memory, GLOBAL) ----------------------------
+// A k-mer has up to 30 bits and a count may reach n + 64 = 65599: neither fits the dword entry of CM 2.  A wave's table of M = 2^log2m
+// entries is three arrays: keys[M] (0 never used, 1 tombstone, H_LIVE | k-mer), counts[M] (32 bits) and vals[M] (64 bits: the KFV's
+// value of the entry's k-mer, looked up in the sparse KFV table -- GenParams::sp_keys -- when the k-mer is inserted, so that a k-mer
+// that stays or leaves costs no lookup).  Buckets of four keys (one 16-byte read per probe), linear probing over buckets, the never-
+// used suffix per bucket, tombstones and the periodic rebuild exactly as CM 2; a search that does not end in 8 x buckets iterations
+// reports a fault instead of hanging.  Counts and keys are separate words: a claimed entry's count is 0 (never-used entries are cleared
+// and an entry becomes a tombstone only at count 0), phase B adds to the count word, phase C turns a key at count 0 into a tombstone.
+// Windows shorter than a step (nk < 64): a lane's leaving k-mer may be entered by a lower lane IN THIS STEP, i.e. not be present yet
+// when its search starts -- a leaving search that reaches a bucket with a never-used entry without finding it starts over from its
+// home bucket (the entering searches progress meanwhile), so it ends in every case.
+// In global memory (GLOBAL: windows of more than KGMA_WIDE_LDS_MAX_NK k-mers, a table per wave slot sized to the window) every read
+// goes past the vector L1 and every group of writes is waited for before the next read, as CM 1.
+constexpr uint32_t W_LIVE = 0x80000000u;
+
+template <bool G>
+struct WCounts {
+    uint32_t *K, *Cn;
+    uint64_t *Vv;
+    int lane, CW;                                                     // CW: dwords of the table (4 M)
+    uint32_t bmask;                                                   // buckets - 1
+    int hshift;                                                       // 32 - log2(buckets)
+    bool fault;
+    const uint32_t *spk;
+    const uint64_t *spv;
+    uint32_t spmask;
+    int spshift;
+
+    __device__ __forceinline__ void init(uint32_t *C, const int log2m, const GenParams &g, const int ln)
+    {
+        const int M = 1 << log2m;
+        K = C; Cn = C + M; Vv = reinterpret_cast<uint64_t *>(C + 2 * M);
+        lane = ln; CW = 4 * M; fault = false;
+        bmask = (uint32_t)(M / 4 - 1); hshift = 32 - (log2m - 2);
+        spk = g.sp_keys; spv = g.sp_vals; spmask = (1u << g.sp_log2) - 1u; spshift = 32 - g.sp_log2;
+    }
+    static __device__ __forceinline__ uint32_t ld(const uint32_t *p)
+    {
+        if constexpr (G) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else return *p;
+    }
+    static __device__ __forceinline__ uint64_t ld64(const uint64_t *p)
+    {
+        if constexpr (G) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else return *p;
+    }
+    // (global: this wave's table operations are complete -- in L2, where every read of the table is served -- before its next reads.
+    //  The table is private to the wave and every access goes past the vector L1, so waiting for the wave's own memory operations
+    //  orders them, as CM 1 does; the release fence -- an L2 write-back -- runs once per table clear only)
+    static __device__ __forceinline__ void drain()
+    {
+        if constexpr (G) asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+    }
+    static __device__ __forceinline__ void st64(uint64_t *p, const uint64_t v)
+    {
+        if constexpr (G) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else *p = v;
+    }
+    static __device__ __forceinline__ uint32_t add(uint32_t *p, const uint32_t v)
+    {
+        if constexpr (G) return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else return atomicAdd(p, v);
+    }
+    static __device__ __forceinline__ uint32_t cas(uint32_t *p, uint32_t expect, const uint32_t v)
+    {
+        if constexpr (G) {
+            __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return expect;
+        } else {
+            return atomicCAS(p, expect, v);
+        }
+    }
+
+    __device__ __forceinline__ void clear()
+    {
+        if constexpr (G) {
+            for (int i = lane; i < CW / 2; i += 64) K[i] = 0u;         // (keys and counts)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        } else {
+            const u32x4_t z = {0u, 0u, 0u, 0u};
+            for (int i = lane; i < CW / 8; i += 64) reinterpret_cast<u32x4_t *>(K)[i] = z;
+        }
+    }
+    // the KFV's value of a k-mer: the sparse table, open addressing with linear probing; it has an empty slot, so the walk ends
+    __device__ __forceinline__ uint64_t lookup(const uint32_t key) const
+    {
+        uint32_t h = (key * 2654435761u) >> spshift;
+        for (uint32_t it = 0; it <= spmask; it++) {
+            const uint32_t kk = spk[h];
+            if (kk == key) return spv[h];
+            if (kk == KGMA_SP_EMPTY) break;
+            h = (h + 1u) & spmask;
+        }
+        return 0;
+    }
+
+    struct Probe { uint32_t key, b, tomb, slot; bool done, ins; };
+    __device__ __forceinline__ uint32_t home(const uint32_t key) const { return (key * 2654435761u) >> hshift; }
+    __device__ __forceinline__ Probe probe_of(const uint32_t key, const bool on) const
+    {
+        Probe s;
+        s.key = key; s.b = home(key) & bmask; s.tomb = H_NONE; s.slot = 0; s.done = !on; s.ins = false;
+        return s;
+    }
+    template <bool INSERT>
+    __device__ __forceinline__ void probe_step(Probe &s)
+    {
+        if (s.done) return;
+        u32x4_t v;
+        if constexpr (G) { v.x = ld(K + 4u * s.b); v.y = ld(K + 4u * s.b + 1); v.z = ld(K + 4u * s.b + 2); v.w = ld(K + 4u * s.b + 3); }
+        else v = *reinterpret_cast<const u32x4_t *>(K + 4u * s.b);
+        const uint32_t tag = W_LIVE | s.key;
+        if (v.x == tag || v.y == tag || v.z == tag || v.w == tag) {
+            s.slot = 4u * s.b + (v.x == tag ? 0u : (v.y == tag ? 1u : (v.z == tag ? 2u : 3u)));
+            s.done = true;
+            return;
+        }
+        if constexpr (!INSERT) {
+            // (not found up to a bucket with a never-used entry: entered by a lower lane of this step and not claimed yet -- look again)
+            s.b = v.w == 0u ? home(s.key) & bmask : (s.b + 1u) & bmask;
+        } else {
+            if (s.tomb == H_NONE) {
+                const int jt = v.x == H_TOMB ? 0 : (v.y == H_TOMB ? 1 : (v.z == H_TOMB ? 2 : (v.w == H_TOMB ? 3 : -1)));
+                if (jt >= 0) s.tomb = 4u * s.b + (uint32_t)jt;
+            }
+            if (v.w != 0u) { s.b = (s.b + 1u) & bmask; return; }
+            const uint32_t je = v.x == 0u ? 0u : (v.y == 0u ? 1u : (v.z == 0u ? 2u : 3u));
+            const uint32_t target = s.tomb != H_NONE ? s.tomb : 4u * s.b + je;
+            const uint32_t expect = s.tomb != H_NONE ? H_TOMB : 0u;
+            const uint32_t old = cas(&K[target], expect, tag);
+            if (old == expect) { s.slot = target; s.done = true; s.ins = true; }
+            else if (old == tag) { s.slot = target; s.done = true; }                  // a lane with the same k-mer was first
+            else { s.b = home(s.key) & bmask; s.tomb = H_NONE; }                      // lost to another k-mer: rescan
+        }
+    }
+    __device__ __forceinline__ void probe2(Probe &e, Probe &l)
+    {
+        const int limit = 8 * (int)(bmask + 1u);
+        int it = 0;
+        while (__ballot(!e.done || !l.done) != 0) {
+            probe_step<true>(e);
+            probe_step<false>(l);
+            if (++it > limit) { fault = true; break; }
+        }
+    }
+    // the window in front of step b re-inserted into a cleared table (values looked up again)
+    __device__ __forceinline__ void rebuild(const uint32_t *gi, const int b, const int nk, const uint32_t KM)
+    {
+        clear();
+        const int q1 = b << 6;
+        const int q0 = q1 - nk < 0 ? 0 : q1 - nk;
+        for (int base = q0; base < q1 && !fault; base += 64) {
+            const int q = base + lane;
+            const bool on = q < q1;
+            const int qq = on ? q : q0;
+            const uint32_t w0 = gi[qq >> 4], w1 = gi[(qq >> 4) + 1];
+            const uint32_t key = __builtin_amdgcn_alignbit(w1, w0, 2u * (uint32_t)(qq & 15)) & KM;
+            Probe s = probe_of(key, on), d = probe_of(0u, false);
+            probe2(s, d);
+            if (on && !fault) {
+                if (s.ins) st64(&Vv[s.slot], lookup(key));
+                add(&Cn[s.slot], 1u);
+            }
+            drain();
+        }
+    }
+
+    // One step, as Counts::step, plus the KFV's values of the entering / leaving k-mer (vp, vl; 0 for a lane without the transition)
+    __device__ __forceinline__ void step(const uint32_t kp, const uint32_t ks, const bool actE, const bool actL,
+                                         uint32_t &cp, uint32_t &cs, uint32_t &oldp, uint32_t &olds, uint64_t &vp, uint64_t &vl)
+    {
+        Probe e = probe_of(kp, actE), l = probe_of(ks, actL);
+        probe2(e, l);
+        cp = 0; cs = 0; oldp = 0; olds = 0; vp = 0; vl = 0;
+        if (fault) return;
+        if (e.ins) st64(&Vv[e.slot], lookup(kp));                     // (a claimed entry's count is 0)
+        drain();
+        if (actE) { cp = ld(&Cn[e.slot]); vp = ld64(&Vv[e.slot]); }
+        if (actL) { cs = ld(&Cn[l.slot]); vl = ld64(&Vv[l.slot]); }
+        if constexpr (G) asm volatile("s_waitcnt vmcnt(0)" : "+v"(cp), "+v"(cs) : : "memory");   // (start-of-step counts, read before the adds)
+        if (actE) oldp = add(&Cn[e.slot], 1u);
+        if (actL) olds = add(&Cn[l.slot], (uint32_t)-1);
+        if constexpr (G) asm volatile("s_waitcnt vmcnt(0)" : "+v"(oldp), "+v"(olds) : : "memory");
+        if (actL) {                                                   // (after every lane's add and subtract: the count of the next step's start)
+            if (ld(&Cn[l.slot]) == 0u) {
+                if constexpr (G) __hip_atomic_store(&K[l.slot], H_TOMB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else K[l.slot] = H_TOMB;
+            }
+        }
+        drain();
+    }
+};
+
 // TLDS (k <= 6): the KFV's table (S as int32, or the Float64 vector: 16 / 32 KiB at k = 6) is copied to the front of the
 // workgroup's LDS once -- two of the step's four dependent reads then stay in the LDS instead of going to L1 / L2.
 template <bool FP, int CM, bool TLDS>
 __global__ __launch_bounds__(1024) void gen_kernel(ScanArgs a, GenParams g)
 {
     static_assert(!(CM != 0 && TLDS), "k >= 8: the KFV's table stays in global memory");
-    constexpr bool CGLOBAL = CM == 1;
+    constexpr bool WIDE = CM == 3 || CM == 4;                         // k >= 11: wide hash tables, sparse KFV
+    constexpr bool CGLOBAL = CM == 1 || CM == 4;
     typedef std::conditional_t<FP, double, int64_t> V;
     typedef Ops<V> O;
     extern __shared__ __attribute__((aligned(16))) uint32_t gsmem[];
@@ -292,12 +494,18 @@ __global__ __launch_bounds__(1024) void gen_kernel(ScanArgs a, GenParams g)
     const int k = g.k, nk = g.nk;
     const int NB = 1 << (2 * k);
     const uint32_t KM = (uint32_t)NB - 1u;
-    const int CW = CM == 2 ? 1 << g.hash_log2m : NB / 2;              // dwords of a count table (two 16-bit counters each; CM 2: the hash table)
+    // dwords of a count table (two 16-bit counters each; CM 2: the hash table; CM 3 / 4: the wide table; CM 5: 32-bit counters)
+    const int CW = CM == 2 ? 1 << g.hash_log2m : (WIDE ? 4 << g.hash_log2m : (CM == 5 ? NB : NB / 2));
     const int TW = TLDS ? (FP ? 2 * NB : NB) : 0;                     // dwords of the table in front of the count tables
-    Counts<CM> cnt;
-    cnt.C = CGLOBAL ? g.ctab + (size_t)slot * (size_t)CW : gsmem + (size_t)TW + (size_t)wave * (size_t)CW;
-    cnt.lane = lane; cnt.CW = CW; cnt.fault = false;
-    cnt.bmask = CM == 2 ? (uint32_t)(CW / 4 - 1) : 0u; cnt.hshift = CM == 2 ? 32 - (g.hash_log2m - 2) : 0;
+    uint32_t *const ctab0 = CGLOBAL ? g.ctab + (size_t)slot * (size_t)CW : gsmem + (size_t)TW + (size_t)wave * (size_t)CW;
+    std::conditional_t<WIDE, WCounts<CM == 4>, Counts<WIDE ? 0 : CM>> cnt;
+    if constexpr (WIDE) {
+        cnt.init(ctab0, g.hash_log2m, g, lane);
+    } else {
+        cnt.C = ctab0;
+        cnt.lane = lane; cnt.CW = CW; cnt.fault = false;
+        cnt.bmask = CM == 2 ? (uint32_t)(CW / 4 - 1) : 0u; cnt.hshift = CM == 2 ? 32 - (g.hash_log2m - 2) : 0;
+    }
     if constexpr (TLDS) {
         if constexpr (FP) { for (int i = threadIdx.x; i < NB; i += blockDim.x) reinterpret_cast<double *>(gsmem)[i] = g.R[i]; }
         else { for (int i = threadIdx.x; i < NB; i += blockDim.x) reinterpret_cast<int32_t *>(gsmem)[i] = g.S[i]; }
@@ -350,18 +558,27 @@ __global__ __launch_bounds__(1024) void gen_kernel(ScanArgs a, GenParams g)
             }
             // S[kp], S[ks] / ref[kp], ref[ks] -- and then the NEXT step's genome words, one step ahead (issued after the table
             // reads: a wait for those must not wait for these)
-            V tab_p, tab_l;
-            if constexpr (FP) { tab_p = Rt[kp]; tab_l = Rt[ks]; }
-            else { tab_p = St[kp]; tab_l = St[ks]; }
+            V tab_p = 0, tab_l = 0;
+            if constexpr (!WIDE) {
+                if constexpr (FP) { tab_p = Rt[kp]; tab_l = Rt[ks]; }
+                else { tab_p = St[kp]; tab_l = St[ks]; }
+            }
             pw = load_words(b + 1);
             const bool differ = kp != ks;                             // GenomeMiner.jl:66: nothing happens if left == right
             const bool actE = differ || !haveL, actL = differ && haveL;
-            if constexpr (CM == 2) {
+            if constexpr (CM == 2 || WIDE) {
                 if (b > 0 && b % g.hash_rebuild == 0) cnt.rebuild(gi, b, nk, KM);
             }
             uint32_t cp, cs, oldp, olds;
-            cnt.step(kp, ks, actE, actL, cp, cs, oldp, olds);
-            if constexpr (CM == 2) {
+            if constexpr (WIDE) {
+                uint64_t vp, vl;                                      // (the values cached in the entries: S or the Float64 entry)
+                cnt.step(kp, ks, actE, actL, cp, cs, oldp, olds, vp, vl);
+                if constexpr (FP) { tab_p = __longlong_as_double((long long)vp); tab_l = __longlong_as_double((long long)vl); }
+                else { tab_p = (int64_t)vp; tab_l = (int64_t)vl; }
+            } else {
+                cnt.step(kp, ks, actE, actL, cp, cs, oldp, olds);
+            }
+            if constexpr (CM == 2 || WIDE) {
                 if (cnt.fault) {                                      // (wave-uniform; cannot happen: the host's rebuild period keeps never-used entries)
                     if (lane == 0) {
                         DevRecord rec;
@@ -570,7 +787,8 @@ template <int CM, bool TLDS>
 __global__ __launch_bounds__(1024) void gen_chain_kernel(ScanArgs a, GenParams g)
 {
     static_assert(!(CM != 0 && TLDS), "k >= 8: the KFV's table stays in global memory");
-    constexpr bool CGLOBAL = CM == 1;
+    constexpr bool WIDE = CM == 3 || CM == 4;
+    constexpr bool CGLOBAL = CM == 1 || CM == 4;
     typedef Ops<double> O;
     extern __shared__ __attribute__((aligned(16))) uint32_t gsmem[];
     const int lane = threadIdx.x & 63;
@@ -580,17 +798,23 @@ __global__ __launch_bounds__(1024) void gen_chain_kernel(ScanArgs a, GenParams g
     const int k = g.k, nk = g.nk;
     const int NB = 1 << (2 * k);
     const uint32_t KM = (uint32_t)NB - 1u;
-    const int CW = CM == 2 ? 1 << g.hash_log2m : NB / 2;
+    const int CW = CM == 2 ? 1 << g.hash_log2m : (WIDE ? 4 << g.hash_log2m : (CM == 5 ? NB : NB / 2));
     const int TW = TLDS ? 2 * NB : 0;                                 // (TLDS: the Float64 table in front of the count tables, as in gen_kernel)
-    Counts<CM> cnt;
-    cnt.C = CGLOBAL ? g.ctab + (size_t)slot * (size_t)CW : gsmem + (size_t)TW + (size_t)wave * (size_t)CW;
-    cnt.lane = lane; cnt.CW = CW; cnt.fault = false;
-    cnt.bmask = CM == 2 ? (uint32_t)(CW / 4 - 1) : 0u; cnt.hshift = CM == 2 ? 32 - (g.hash_log2m - 2) : 0;
+    uint32_t *const ctab0 = CGLOBAL ? g.ctab + (size_t)slot * (size_t)CW : gsmem + (size_t)TW + (size_t)wave * (size_t)CW;
+    std::conditional_t<WIDE, WCounts<CM == 4>, Counts<WIDE ? 0 : CM>> cnt;
+    if constexpr (WIDE) {
+        cnt.init(ctab0, g.hash_log2m, g, lane);
+    } else {
+        cnt.C = ctab0;
+        cnt.lane = lane; cnt.CW = CW; cnt.fault = false;
+        cnt.bmask = CM == 2 ? (uint32_t)(CW / 4 - 1) : 0u; cnt.hshift = CM == 2 ? 32 - (g.hash_log2m - 2) : 0;
+    }
     if constexpr (TLDS) {
         for (int i = threadIdx.x; i < NB; i += blockDim.x) reinterpret_cast<double *>(gsmem)[i] = g.R[i];
         __syncthreads();
     }
     const double *Rt = TLDS ? reinterpret_cast<const double *>(gsmem) : g.R;
+    (void)Rt;
     const int kid = g.kfv_id;
     constexpr int CS_SPLIT = 1, CS_DETAIL = 2, CS_FULL = 4;
 
@@ -725,16 +949,23 @@ __global__ __launch_bounds__(1024) void gen_chain_kernel(ScanArgs a, GenParams g
                 ks = __builtin_amdgcn_alignbit(pw.w, pw.z, 2u * (uint32_t)(pl & 15)) & KM;
                 ks = haveL ? ks : kp;
             }
-            const double rr = Rt[kp], rl = Rt[ks];
+            double rr = 0.0, rl = 0.0;
+            if constexpr (!WIDE) { rr = Rt[kp]; rl = Rt[ks]; }
             pw = load_words(b + 1);                                   // the next step's genome words, one step ahead
             const bool differ = kp != ks;
             const bool actE = differ || !haveL, actL = differ && haveL;
-            if constexpr (CM == 2) {
+            if constexpr (CM == 2 || WIDE) {
                 if (b > 0 && b % g.hash_rebuild == 0) cnt.rebuild(gi, b, nk, KM);
             }
             uint32_t cp, cs, oldp, olds;
-            cnt.step(kp, ks, actE, actL, cp, cs, oldp, olds);
-            if constexpr (CM == 2) {
+            if constexpr (WIDE) {
+                uint64_t vp, vl;
+                cnt.step(kp, ks, actE, actL, cp, cs, oldp, olds, vp, vl);
+                rr = __longlong_as_double((long long)vp); rl = __longlong_as_double((long long)vl);
+            } else {
+                cnt.step(kp, ks, actE, actL, cp, cs, oldp, olds);
+            }
+            if constexpr (CM == 2 || WIDE) {
                 if (cnt.fault) {                                      // (wave-uniform; cannot happen, see Counts)
                     if (lane == 0) atomicOr(a.chain.status, 2u);
                     break;
@@ -841,8 +1072,28 @@ static bool generic_table_in_lds(int k) { return k <= 6; }            // 4 (S) o
 // rebuild period: 2048 entries (8 KiB per wave) up to 448 k-mers per window, 4096 up to 1400, 8192 beyond; an insertion consumes
 // at most one never-used entry, 64 insertions per step, and an eighth of the table stays never-used:
 // rebuild = (M - n - 64 - M / 8) / 64 >= 20 steps (a rebuild costs about 2.5 steps).
+// k >= 11 (wide tables, 16 bytes per entry): the smallest table of 512 ... 8192 entries that leaves at least 8 steps between rebuilds
+// in LDS (windows of up to KGMA_WIDE_LDS_MAX_NK k-mers: 16 waves per CU at 512 entries, 10 at 1024, 5 at 2048, 2 at 4096, 1 at 8192),
+// beyond that a table in global memory per wave slot sized to the window (up to 2^17 entries, 2 MiB, at 65535 k-mers) with at least
+// 16 steps between rebuilds.  k = 1: four 32-bit counters per wave.  (2 <= k <= 10 is decided below, as before.)
+static void generic_set_wide(GenParams &g, int nk_max)
+{
+    int lds_max = KGMA_WIDE_LDS_MAX_NK;
+    if (const char *e = getenv("KGMA_WIDE_LDS_NK")) lds_max = std::max(0, std::min(KGMA_WIDE_LDS_NK_CAP, atoi(e)));   // experiments
+    const bool lds = nk_max <= lds_max;
+    const int min_rebuild = lds ? 8 : 16;
+    int lg = 9;
+    while ((1 << lg) - nk_max - 64 - (1 << lg) / 8 < 64 * min_rebuild) lg++;
+    g.cmode = lds ? 3 : 4;
+    g.hash_log2m = lg;
+    const int M = 1 << lg;
+    g.hash_rebuild = std::max(1, (M - nk_max - 64 - M / 8) / 64);
+}
+
 void generic_set_mode(GenParams &g, int nk_max)
 {
+    if (g.k == 1) { g.cmode = 5; g.hash_log2m = 0; g.hash_rebuild = 0; return; }
+    if (g.k >= KGMA_WIDE_MIN_K) { generic_set_wide(g, nk_max); return; }
     g.cmode = g.k <= 7 ? 0 : 1;
     g.hash_log2m = 0; g.hash_rebuild = 0;
     const char *e = getenv("KGMA_GENERIC_HASH");                      // (0: the global count tables, for comparison and tests)
@@ -866,7 +1117,7 @@ int generic_count_mode(int k, int nk_max)
 }
 
 namespace {
-struct GenGeom { int cmode; bool tlds; int nw; size_t lds; };
+struct GenGeom { int cmode; bool tlds; int nw; size_t lds; int log2m; };
 }
 
 // waves (= streams) per workgroup and its LDS: [table (TLDS) | nw count tables] out of 160 KiB less `reserve`
@@ -874,9 +1125,13 @@ static GenGeom generic_geom_of(const GenParams &g, bool fp, size_t reserve)
 {
     GenGeom q;
     q.cmode = g.cmode;
+    q.log2m = g.hash_log2m;
     q.tlds = q.cmode == 0 && generic_table_in_lds(g.k);
-    if (q.cmode == 1) { q.nw = 4; q.lds = 0; return q; }
-    const size_t per = q.cmode == 2 ? (size_t)4 << g.hash_log2m : (size_t)2 << (2 * g.k);
+    if (q.cmode == 1 || q.cmode == 4) { q.nw = 4; q.lds = 0; return q; }
+    // (bytes per wave: CM 2 4 per entry, CM 3 16 per entry -- the same for both KFV forms, so every launch of a scan at k >= 11 has
+    //  one geometry -- CM 5 four counters of 4 bytes)
+    const size_t per = q.cmode == 2 ? (size_t)4 << g.hash_log2m : q.cmode == 3 ? (size_t)16 << g.hash_log2m : q.cmode == 5 ? (size_t)16 :
+                       (size_t)2 << (2 * g.k);
     const size_t tab = q.tlds ? ((size_t)(fp ? 8 : 4) << (2 * g.k)) : 0;
     // (ten-wave workgroups of 8 KiB hash tables, two per CU = 20 waves, measured against sixteen-wave ones: scan 89.5 against 93.8 Gbp/s,
     //  chain 83.6 against 81.6 -- no gain, the larger workgroup stays)
@@ -888,6 +1143,11 @@ static GenGeom generic_geom_of(const GenParams &g, bool fp, size_t reserve)
 
 static const void *generic_fn(bool fp, const GenGeom &q)
 {
+    if (q.cmode >= 3) {
+        if (q.cmode == 3) return fp ? reinterpret_cast<const void *>(&gen_kernel<true, 3, false>) : reinterpret_cast<const void *>(&gen_kernel<false, 3, false>);
+        if (q.cmode == 4) return fp ? reinterpret_cast<const void *>(&gen_kernel<true, 4, false>) : reinterpret_cast<const void *>(&gen_kernel<false, 4, false>);
+        return fp ? reinterpret_cast<const void *>(&gen_kernel<true, 5, false>) : reinterpret_cast<const void *>(&gen_kernel<false, 5, false>);
+    }
     if (fp) {
         if (q.cmode == 1) return reinterpret_cast<const void *>(&gen_kernel<true, 1, false>);
         if (q.cmode == 2) return reinterpret_cast<const void *>(&gen_kernel<true, 2, false>);
@@ -902,6 +1162,9 @@ static const void *generic_chain_fn(const GenGeom &q)
 {
     if (q.cmode == 1) return reinterpret_cast<const void *>(&gen_chain_kernel<1, false>);
     if (q.cmode == 2) return reinterpret_cast<const void *>(&gen_chain_kernel<2, false>);
+    if (q.cmode == 3) return reinterpret_cast<const void *>(&gen_chain_kernel<3, false>);
+    if (q.cmode == 4) return reinterpret_cast<const void *>(&gen_chain_kernel<4, false>);
+    if (q.cmode == 5) return reinterpret_cast<const void *>(&gen_chain_kernel<5, false>);
     return q.tlds ? reinterpret_cast<const void *>(&gen_chain_kernel<0, true>) : reinterpret_cast<const void *>(&gen_chain_kernel<0, false>);
 }
 
@@ -910,7 +1173,7 @@ static const void *generic_chain_fn(const GenGeom &q)
 static GenGeom generic_geom(const GenParams &g, bool fp, bool chain)
 {
     GenGeom q = generic_geom_of(g, fp, 0);
-    if (q.cmode == 1) return q;
+    if (q.cmode == 1 || q.cmode == 4) return q;
     const void *fn = chain ? generic_chain_fn(q) : generic_fn(fp, q);
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds) == hipSuccess) return q;
     (void)hipGetLastError();
@@ -928,6 +1191,8 @@ static int generic_resident(const void *fn, const GenGeom &q, int k)
     // (global count tables: 2 * 4^k bytes per slot; 16 waves per CU at k = 8, 9 (128 / 512 KiB per slot), 8 at k = 10 (2 MiB per
     //  slot: 4 GiB of tables))
     if (q.cmode == 1) blocks = std::min(blocks, k >= 10 ? 2 : 4);
+    // (k >= 11, windows beyond the LDS tables: 16 bytes per entry, 2 MiB per slot at 2^17 entries -- 8 slots per CU, as k = 10)
+    if (q.cmode == 4) blocks = std::min(blocks, q.log2m >= 16 ? 2 : 4);
     if (blocks * q.nw > 32) blocks = 32 / q.nw;
     return q.nw * (blocks < 1 ? 1 : blocks);
 }
@@ -956,7 +1221,12 @@ int generic_chain_slots_per_cu(int k, int nk)
 static hipError_t launch_gen(const void *fn, const GenGeom &q, const ScanArgs &a, const GenParams &g, hipStream_t st)
 {
     if (q.nw < 1 || g.n_slots < q.nw || g.n_slots % q.nw != 0) return hipErrorInvalidConfiguration;
-    if (q.cmode == 1 && g.ctab == nullptr) return hipErrorInvalidValue;
+    if ((q.cmode == 1 || q.cmode == 4) && g.ctab == nullptr) return hipErrorInvalidValue;
+    if ((q.cmode == 3 || q.cmode == 4) &&
+        (g.k < KGMA_WIDE_MIN_K || g.k > KGMA_MAX_K || g.hash_log2m < 9 || g.hash_log2m > 17 || g.hash_rebuild < 1 || g.nk > KGMA_MAX_NK_WIDE ||
+         (1 << g.hash_log2m) - g.nk - 64 * (g.hash_rebuild + 1) < (1 << g.hash_log2m) / 8 || g.sp_keys == nullptr || g.sp_vals == nullptr ||
+         g.sp_log2 < 1 || g.sp_log2 > 30)) return hipErrorInvalidConfiguration;
+    if (q.cmode == 5 && g.k != 1) return hipErrorInvalidConfiguration;
     if (q.cmode == 2 && (g.hash_log2m < 8 || g.hash_log2m > 13 || g.hash_rebuild < 1 || g.nk > KGMA_HASH_MAX_NK ||
                          (1 << g.hash_log2m) - g.nk - 64 * (g.hash_rebuild + 1) < 4)) return hipErrorInvalidConfiguration;
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds);
@@ -971,7 +1241,7 @@ static hipError_t launch_gen(const void *fn, const GenGeom &q, const ScanArgs &a
 hipError_t launch_generic_chain(const ScanArgs &a, const GenParams &g, hipStream_t st)
 {
     if (a.n_tiles <= 0) return hipSuccess;
-    if (g.R == nullptr) return hipErrorInvalidConfiguration;
+    if (g.cmode == 3 || g.cmode == 4 ? g.sp_vals == nullptr : g.R == nullptr) return hipErrorInvalidConfiguration;
     const GenGeom q = generic_geom(g, true, true);
     return launch_gen(generic_chain_fn(q), q, a, g, st);
 }
@@ -979,7 +1249,7 @@ hipError_t launch_generic_chain(const ScanArgs &a, const GenParams &g, hipStream
 hipError_t launch_generic(const ScanArgs &a, const GenParams &g, hipStream_t st)
 {
     if (a.n_tiles <= 0) return hipSuccess;
-    if (g.fp ? g.R == nullptr : g.S == nullptr) return hipErrorInvalidConfiguration;
+    if (g.cmode == 3 || g.cmode == 4 ? g.sp_vals == nullptr : (g.fp ? g.R == nullptr : g.S == nullptr)) return hipErrorInvalidConfiguration;
     const GenGeom q = generic_geom(g, g.fp != 0, false);
     return launch_gen(generic_fn(g.fp != 0, q), q, a, g, st);
 }

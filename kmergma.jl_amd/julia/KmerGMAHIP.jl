@@ -13,6 +13,8 @@
 # and goes to the device ONCE; no LongDNA copy of the genome is made on the host) and the per-record body of
 # the engines (src/GenomeMiner.jl:32-107, src/OmnGenomeMiner.jl:55-160).  Residues are read back only for the
 # hits: `kgma_genome_fetch` serves the alignment segments, `kgma_genome_fetch_batch` the record bodies of all hits at once.
+# Every 1 <= k <= 15 is served (kgma_set_refs); the dense refVec of the reference is passed as it is at every k (at k >= 11
+# the library keeps only its non-zero entries).
 
 module KmerGMAHIP
 

@@ -24,7 +24,7 @@ HIT_TIE, HIT_AT_THRESHOLD, HIT_TIE_RESOLVED, HIT_CHAIN = 1, 2, 4, 8
 
 EXPORTS = [
     "kgma_version", "kgma_status_string", "kgma_last_error", "kgma_create", "kgma_destroy",
-    "kgma_set_refs", "kgma_set_thresholds", "kgma_genome_from_host", "kgma_genome_synthetic",
+    "kgma_set_refs", "kgma_set_refs_sparse", "kgma_set_thresholds", "kgma_genome_from_host", "kgma_genome_synthetic",
     "kgma_genome_fetch", "kgma_genome_fetch_batch", "kgma_genome_num_contigs", "kgma_genome_contig_len", "kgma_genome_total_bases",
     "kgma_genome_free", "kgma_genome_repack", "kgma_genome_poke", "kgma_scan", "kgma_scan_device", "kgma_get_hits",
     "kgma_get_dips", "kgma_get_first_window", "kgma_get_dists", "kgma_get_stats", "kgma_stream",
@@ -116,6 +116,7 @@ def load():
     L.kgma_destroy.argtypes = [vp]
     L.kgma_destroy.restype = None
     L.kgma_set_refs.argtypes = [vp, i32, i32, P(dbl), P(i64), P(dbl), P(i64)]
+    L.kgma_set_refs_sparse.argtypes = [vp, i32, i32, P(i64), P(C.c_uint32), P(dbl), P(i64), P(dbl), P(i64)]
     L.kgma_set_thresholds.argtypes = [vp, P(dbl)]
     L.kgma_genome_from_host.argtypes = [vp, P(C.c_char_p), P(i64), i64, P(vp)]
     L.kgma_genome_from_fasta.argtypes = [vp, vp, i64, P(vp)]
@@ -356,6 +357,30 @@ class Context:
         nr = None if n_refs is None else np.asarray(n_refs, dtype=np.int64)
         self._check(load().kgma_set_refs(self._h, k, m, _np_ptr(R, C.c_double), _np_ptr(ws, C.c_int64),
                                          _np_ptr(th, C.c_double), None if nr is None else _np_ptr(nr, C.c_int64)))
+        self.k, self.m = k, m
+        self.ws = [int(w) for w in ws]
+
+    def set_refs_sparse(self, k: int, keys: Sequence[np.ndarray], vals: Sequence[np.ndarray], windowsizes: Sequence[int],
+                        thr: Sequence[float], n_refs: Optional[Sequence[int]] = None) -> None:
+        """kgma_set_refs_sparse: KFV j given by its non-zero entries -- keys[j] natural k-mer values (0-based, first base most
+        significant: the reference's index - 1), strictly increasing, vals[j] their values.  Same semantics as set_refs on the
+        dense vectors, 1 <= k <= 15 (a dense KFV at k = 15 is 8 GiB)."""
+        m = len(windowsizes)
+        ks = [np.asarray(x, dtype=np.uint32).ravel() for x in keys[:m]]
+        vs = [np.asarray(x, dtype=np.float64).ravel() for x in vals[:m]]
+        if len(ks) != m or len(vs) != m or any(a.size != b.size for a, b in zip(ks, vs)):
+            raise ValueError("need one (keys, vals) pair of equal lengths per KFV")
+        nnz = np.asarray([a.size for a in ks], dtype=np.int64)
+        K = np.ascontiguousarray(np.concatenate(ks + [np.zeros(1, np.uint32)]))
+        V = np.ascontiguousarray(np.concatenate(vs + [np.zeros(1, np.float64)]))
+        ws = np.asarray(windowsizes, dtype=np.int64)
+        th = np.asarray(list(thr)[:m], dtype=np.float64)
+        if th.size != m:
+            raise ValueError("need one threshold per KFV")
+        nr = None if n_refs is None else np.asarray(n_refs, dtype=np.int64)
+        self._check(load().kgma_set_refs_sparse(self._h, k, m, _np_ptr(nnz, C.c_int64), _np_ptr(K, C.c_uint32), _np_ptr(V, C.c_double),
+                                                _np_ptr(ws, C.c_int64), _np_ptr(th, C.c_double),
+                                                None if nr is None else _np_ptr(nr, C.c_int64)))
         self.k, self.m = k, m
         self.ws = [int(w) for w in ws]
 

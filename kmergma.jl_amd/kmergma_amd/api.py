@@ -217,6 +217,12 @@ def Omn_KmerGMA(*, genome_path, refVecs: Sequence, windowsizes: Sequence[int], c
         view.free()
 
 
+def _prep_ctx(ctx, k: int):
+    """The context for reference preparation: the device refprep entry points serve 1 <= k <= 10; beyond, the host restatement
+    (ctx=None) prepares the references and the scan still runs on `ctx`."""
+    return ctx if k <= 10 else None
+
+
 def warn_helper(k: int, do_return_dists: bool) -> None:
     """src/API.jl:8-11 (exact strings are part of the reference's tested contract)."""
     if k < 5:
@@ -234,17 +240,22 @@ def findGenes(*, genome_path: str, ref_path: str, k: int = 6, KmerDistThr=0, buf
               do_return_dists: bool = False, do_return_hit_loci: bool = False, do_return_align: bool = False,
               verbose: bool = True, KmerDist_threshold_buffer: float = 8.0, aligner: Optional[Callable] = None,
               ctx=None) -> list:
-    """`findGenes` (src/API.jl:60-104). Returns [hits, (loci), (aligns), (dists)]."""
+    """`findGenes` (src/API.jl:60-104). Returns [hits, (loci), (aligns), (dists)].
+
+    Every 1 <= k <= 15 is served.  Reference preparation runs its k-mer counting and kmer_dist batches on the device for
+    k <= 10; for k >= 11 it uses the host restatement in refprep (the device refprep entry points stop at k = 10), and the scan
+    itself runs on the device at every k."""
     if verbose:
         log.info("pre-processing references and parameters...")
     warn_helper(k, do_return_dists)
     ctx = ctx if ctx is not None else default_context()
+    prep_ctx = _prep_ctx(ctx, k)
     # reference preparation: the k-mer counting and kmer_dist batches run on the device (SURVEY 8(f)4)
-    RV, windowsize, consensus_refseq, (_S, N) = refprep.gen_ref_ws_cons(ref_path, k, return_int=True, ctx=ctx)
+    RV, windowsize, consensus_refseq, (_S, N) = refprep.gen_ref_ws_cons(ref_path, k, return_int=True, ctx=prep_ctx)
     if k >= windowsize:
         raise ValueError(f"the average reference sequence length {windowsize} exceeds/is equal to the chosen "
                          f"kmer length {k}. please reduce k. ")
-    est = refprep.estimate_optimal_threshold(RV, windowsize, buffer=KmerDist_threshold_buffer, ctx=ctx)
+    est = refprep.estimate_optimal_threshold(RV, windowsize, buffer=KmerDist_threshold_buffer, ctx=prep_ctx)
     if KmerDistThr == 0:
         KmerDistThr = est
     elif KmerDistThr < est:   # (sic) API.jl:75-76
@@ -280,19 +291,23 @@ def findGenes_cluster_mode(*, genome_path: str, ref_path: str, cluster_cutoffs=(
                            gap_open_score: int = -200, gap_extend_score: int = -1, do_return_dists: bool = False,
                            do_return_hit_loci: bool = False, do_return_align: bool = False, verbose: bool = True,
                            kmerDist_threshold_buffer: float = 7, aligner: Optional[Callable] = None, ctx=None) -> list:
-    """`findGenes_cluster_mode` (src/API.jl:161-226)."""
+    """`findGenes_cluster_mode` (src/API.jl:161-226).
+
+    Every 1 <= k <= 15 is served; for k >= 11 reference preparation uses the host restatement in refprep (the device refprep
+    entry points stop at k = 10), as in findGenes."""
     if verbose:
         log.info("pre-processing references and parameters...")
     warn_helper(k, do_return_dists)
     ctx = ctx if ctx is not None else default_context()
+    prep_ctx = _prep_ctx(ctx, k)
     RVs, windowsizes, cons, invalids, ints = refprep.cluster_ref_API(ref_path, k, cutoffs=list(cluster_cutoffs),
-                                                                      return_int=True, ctx=ctx)
+                                                                      return_int=True, ctx=prep_ctx)
     RVs, windowsizes, cons, ints = refprep.eliminate_null_params(RVs, windowsizes, cons, invalids, ints)
     if k >= min(windowsizes):
         raise ValueError("some/all of the average reference sequence lengths exceeds/is equal to the chosen "
                          f"kmer length {k}. please reduce k. ")
     KmerDistThrs = [float(x) for x in KmerDistThrs]
-    est = refprep.estimate_optimal_threshold(RVs, windowsizes, buffer=kmerDist_threshold_buffer, ctx=ctx)
+    est = refprep.estimate_optimal_threshold(RVs, windowsizes, buffer=kmerDist_threshold_buffer, ctx=prep_ctx)
     if KmerDistThrs[0] == 0:
         KmerDistThrs = est
     else:
