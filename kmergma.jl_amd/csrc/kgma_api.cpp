@@ -2563,6 +2563,8 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
                     if (f.fp && !gg.R) return fail(ctx, KGMA_E_STATE, "internal: no Float64 table for KFV %d", j + 1);
                 }
                 generic_set_mode(gg, (int)(maxws - k + 1));           // (one geometry for every launch of the scan: its longest window decides)
+                if (getenv("KGMA_GEOM_DEBUG"))
+                    fprintf(stderr, "generic scan geometry: k %d, cmode %d, log2m %d, rebuild %d\n", k, gg.cmode, gg.hash_log2m, gg.hash_rebuild);
                 if (gg.cmode == 1 || gg.cmode == 4) {
                     rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * generic_ctab_dwords(gg));
                     if (rc) return rc;
@@ -3518,6 +3520,8 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
                 if (f.sparse) set_sparse_params(ctx, f, gg, true);
                 else gg.R = ctx->d_Rtab + (size_t)j * (size_t)((int64_t)1 << (2 * k));
                 generic_set_mode(gg, gp.nk);
+                if (getenv("KGMA_GEOM_DEBUG"))
+                    fprintf(stderr, "generic chain geometry: k %d, cmode %d, log2m %d, rebuild %d\n", k, gg.cmode, gg.hash_log2m, gg.hash_rebuild);
                 if (gg.cmode == 1 || gg.cmode == 4) {
                     rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * generic_ctab_dwords(gg));
                     if (rc) return rc;

@@ -31,8 +31,29 @@ def genes(data_dir):
     return [r.sequence.upper() for r in fasta.read_fasta(os.path.join(data_dir, "Alp_V_ref.fasta"))]
 
 
+def _set_ref(ctx, ref, thr):
+    """A ref dict in either form: dense (RV, S) through set_refs, sparse (keys, vals, S: tests.helpers.sparse_family) through
+    set_refs_sparse."""
+    if "keys" in ref:
+        ctx.set_refs_sparse(ref["k"], [ref["keys"]], [ref["vals"]], [ref["ws"]], [thr], [ref["N"]])
+    else:
+        ctx.set_refs(ref["k"], [ref["RV"]], [ref["ws"]], [thr], [ref["N"]])
+
+
+def _oracle_int(contigs, ref, T, buff):
+    if "keys" in ref:
+        return orc.single_scan_int_sparse(contigs, (ref["keys"], ref["S"]), ref["N"], ref["k"], ref["ws"], T, buff, return_D=True)
+    return orc.single_scan_int(contigs, ref["S"], ref["N"], ref["k"], ref["ws"], T, buff, return_D=True)
+
+
+def _oracle_f64(contigs, ref, thr, buff, align):
+    if "keys" in ref:
+        return orc.single_scan_sparse(contigs, (ref["keys"], ref["vals"]), ref["k"], ref["ws"], thr, buff, return_dists=True, align=align)
+    return orc.single_scan(contigs, ref["RV"], ref["k"], ref["ws"], thr, buff, return_dists=True, align=align)
+
+
 def _scan_single(ctx, contigs, ref, thr, buff=50, dists=False, align=None, no_tie_resolve=False):
-    ctx.set_refs(ref["k"], [ref["RV"]], [ref["ws"]], [thr], [ref["N"]])
+    _set_ref(ctx, ref, thr)
     g = ctx.genome_from_host(contigs)
     try:
         flags = (_lib.F_RETURN_DISTS if dists else 0) | (_lib.F_NO_TIE_RESOLVE if no_tie_resolve else 0)
@@ -47,7 +68,7 @@ def _assert_single_parity(ctx, contigs, ref, thr, buff=50, align=None):
     # (1) exact arithmetic, first tied window: everything bit-identical to the integer oracle
     hits, d, D1, stats, dips = _scan_single(ctx, contigs, ref, thr, buff, dists=True, align=align, no_tie_resolve=True)
     T = orc.int_threshold(thr, k, N)
-    ohi, oD, oD1 = orc.single_scan_int(contigs, S, N, k, W, T, buff, return_D=True)
+    ohi, oD, oD1 = _oracle_int(contigs, ref, T, buff)
     assert np.array_equal(D1, oD1)
     assert np.array_equal(d, oD / (2.0 * k * N * N))
     if align is None:
@@ -56,7 +77,7 @@ def _assert_single_parity(ctx, contigs, ref, thr, buff=50, align=None):
     # (2) default mode (ties decided like the reference's Float64 update): coordinates identical to the
     # reference-order Float64 oracle except on dips still flagged as rounding-ambiguous; distances in tol
     hits, _, _, stats, dips = _scan_single(ctx, contigs, ref, thr, buff, align=align)
-    ohits, od = orc.single_scan(contigs, ref["RV"], k, W, thr, buff, return_dists=True, align=align)
+    ohits, od = _oracle_f64(contigs, ref, thr, buff, align)
     assert len(od) == len(d)
     if len(d):
         assert np.max(np.abs(d - od) / np.maximum(od, 1e-300)) < REL_TOL
@@ -82,7 +103,7 @@ def _assert_single_parity(ctx, contigs, ref, thr, buff=50, align=None):
 
 
 def _scan_single_chain(ctx, contigs, ref, thr, buff=50, align=None):
-    ctx.set_refs(ref["k"], [ref["RV"]], [ref["ws"]], [thr], [ref["N"]])
+    _set_ref(ctx, ref, thr)
     g = ctx.genome_from_host(contigs)
     try:
         ctx.scan(g, _lib.MODE_SINGLE, buff, 0, _lib.F_CHAIN_REPLAY, align)

@@ -273,9 +273,14 @@ def _float_kfvs(rng, RV, kind):
 def _assert_float_single(ctx, contigs, RV, k, W, thr, buff=50, n_refs=None):
     """Float64 KFV, single engine: (1) default mode: every distance within 1e-6 relative of the Float64 oracle, hits identical to
     it unless a dip is flagged / a window sits in the threshold band; (2) chain mode: identical, nothing flagged, chain-decided
-    hits carry the oracle's distance bit for bit."""
-    ohits, od = orc.single_scan(contigs, RV, k, W, thr, buff, return_dists=True)
-    ctx.set_refs(k, [RV], [W], [thr], n_refs)
+    hits carry the oracle's distance bit for bit.  RV may be dense or sparse: (keys, vals), set through set_refs_sparse and checked
+    with the sparse oracle."""
+    if isinstance(RV, tuple):
+        ohits, od = orc.single_scan_sparse(contigs, RV, k, W, thr, buff, return_dists=True)
+        ctx.set_refs_sparse(k, [RV[0]], [RV[1]], [W], [thr], n_refs)
+    else:
+        ohits, od = orc.single_scan(contigs, RV, k, W, thr, buff, return_dists=True)
+        ctx.set_refs(k, [RV], [W], [thr], n_refs)
     g = ctx.genome_from_host(contigs)
     try:
         ctx.scan(g, _lib.MODE_SINGLE, buff, 0, _lib.F_RETURN_DISTS, None)
