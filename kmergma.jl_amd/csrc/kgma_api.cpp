@@ -301,7 +301,8 @@ struct kgma_ctx {
     int16_t *d_diff = nullptr; int64_t diff_cap = 0;   // two-kernel cluster path: per-window self-match differences of a tile chunk
     // scan scratch
     TileDesc *d_tiles = nullptr; int64_t tiles_cap = 0;
-    // one device block: [counters 16 B: rec_count u32 @0, n_att u64 @8][D0: res_d0_slots int64][records]
+    // one device block: [counters KGMA_RES_HDR B: rec_count u32 @0, aux_used u32 @4, n_att u64 @8, n_cold u64 @16]
+    // [D0: res_d0_slots int64][aux][records]
     uint8_t *d_res = nullptr; int64_t res_bytes = 0;
     int64_t res_d0_slots = 0; unsigned int rec_cap = 0;
     std::vector<double *> d_dist;     // per KFV
@@ -2453,7 +2454,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         recs = std::max<int64_t>(recs, ctx->rec_cap);
         int64_t cap = 0;
         uint8_t *fresh = nullptr;
-        const int64_t bytes = 16 + d0_slots * 8 + KGMA_AUX_BYTES + recs * (int64_t)sizeof(DevRecord);
+        const int64_t bytes = KGMA_RES_HDR + d0_slots * 8 + KGMA_AUX_BYTES + recs * (int64_t)sizeof(DevRecord);
         int r2 = dev_reserve(ctx, fresh, cap, bytes);
         if (r2) return r2;
         if (ctx->d_res) { (void)hipFree(ctx->d_res); ctx->device_bytes -= ctx->res_bytes; }
@@ -2471,7 +2472,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     // pinned staging: [meta 16 B][D0 n_tiles*m*8][first INLINE_RECS records]
     constexpr size_t INLINE_RECS = 4096;
     const size_t d0_bytes = (size_t)ctx->res_d0_slots * sizeof(int64_t);
-    const size_t pin_need = 16 + d0_bytes + KGMA_AUX_BYTES + INLINE_RECS * sizeof(DevRecord);
+    const size_t pin_need = KGMA_RES_HDR + d0_bytes + KGMA_AUX_BYTES + INLINE_RECS * sizeof(DevRecord);
     if (pin_need > ctx->h_pin_cap) {
         if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
         ctx->h_pin = nullptr; ctx->h_pin_cap = 0;
@@ -2485,9 +2486,10 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     }
     unsigned int *h_nrecs = reinterpret_cast<unsigned int *>(ctx->h_pin);
     unsigned long long *h_natt = reinterpret_cast<unsigned long long *>(ctx->h_pin + 8);
-    int64_t *h_D0 = reinterpret_cast<int64_t *>(ctx->h_pin + 16);
-    const uint8_t *h_aux = ctx->h_pin + 16 + d0_bytes;
-    DevRecord *h_recs = reinterpret_cast<DevRecord *>(ctx->h_pin + 16 + d0_bytes + KGMA_AUX_BYTES);
+    unsigned long long *h_ncold = reinterpret_cast<unsigned long long *>(ctx->h_pin + 16);
+    int64_t *h_D0 = reinterpret_cast<int64_t *>(ctx->h_pin + KGMA_RES_HDR);
+    const uint8_t *h_aux = ctx->h_pin + KGMA_RES_HDR + d0_bytes;
+    DevRecord *h_recs = reinterpret_cast<DevRecord *>(ctx->h_pin + KGMA_RES_HDR + d0_bytes + KGMA_AUX_BYTES);
 
     if (!tiles_cached) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tiles, ctx->tiles.data(), (size_t)n_tiles * sizeof(TileDesc), hipMemcpyHostToDevice, ctx->stream));
@@ -2499,12 +2501,12 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     for (int attempt = 0;; attempt++) {
         if (attempt > 0) ctx->ov_groups = 0;                          // (a repeated scan is one plain launch)
         uint8_t *d_cnt = ctx->d_res;
-        int64_t *d_D0 = reinterpret_cast<int64_t *>(ctx->d_res + 16);
-        uint8_t *d_aux = ctx->d_res + 16 + ctx->res_d0_slots * 8;
+        int64_t *d_D0 = reinterpret_cast<int64_t *>(ctx->d_res + KGMA_RES_HDR);
+        uint8_t *d_aux = ctx->d_res + KGMA_RES_HDR + ctx->res_d0_slots * 8;
         DevRecord *d_recs = reinterpret_cast<DevRecord *>(d_aux + KGMA_AUX_BYTES);
         // (the previous scan's export_kernel normally left the counters at zero: no memset between steps)
         if (!ctx->counters_clean) {
-            HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 16, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, KGMA_RES_HDR, ctx->stream));
             HIP_TRY(ctx, hipMemsetAsync(ctx->d_done, 0, 16, ctx->stream));
         }
         ctx->counters_clean = false;
@@ -2572,6 +2574,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
                 }
                 a.D0out = d_D0; a.recs = d_recs; a.rec_count = reinterpret_cast<unsigned int *>(d_cnt); a.rec_cap = ctx->rec_cap;
                 a.n_tiles = (int32_t)n_tiles; a.n_att = reinterpret_cast<unsigned long long *>(d_cnt + 8);
+                a.n_cold = reinterpret_cast<unsigned long long *>(d_cnt + 16);
                 HIP_TRY(ctx, launch_generic(a, gg, ctx->stream));
                 ctx->stats.n_launches++;
                 continue;
@@ -2597,6 +2600,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
             a.rec_cap = ctx->rec_cap;
             a.n_tiles = (int32_t)n_tiles;
             a.n_att = reinterpret_cast<unsigned long long *>(d_cnt + 8);
+            a.n_cold = reinterpret_cast<unsigned long long *>(d_cnt + 16);
             a.tile0 = 0;
             a.n_chunk_tiles = (int32_t)n_tiles;
             a.tile_windows = ctx->tile_windows;
@@ -2685,7 +2689,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     if (n_inline) memcpy(recs.data(), h_recs, n_inline * sizeof(DevRecord));
     if (n_recs > n_inline)
         HIP_TRY(ctx, hipMemcpy(recs.data() + n_inline,
-                               reinterpret_cast<DevRecord *>(ctx->d_res + 16 + ctx->res_d0_slots * 8 + KGMA_AUX_BYTES) + n_inline,
+                               reinterpret_cast<DevRecord *>(ctx->d_res + KGMA_RES_HDR + ctx->res_d0_slots * 8 + KGMA_AUX_BYTES) + n_inline,
                                ((size_t)n_recs - n_inline) * sizeof(DevRecord), hipMemcpyDeviceToHost));
     ctx->D0.assign(h_D0, h_D0 + (size_t)n_tiles * (size_t)ctx->m);
     for (int j = 0; j < m_used; j++) {
@@ -2705,6 +2709,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
             if (tb >= 0) ctx->firstD[(size_t)j * (size_t)nc + (size_t)c] = ctx->D0[(size_t)j * (size_t)n_tiles + (size_t)tb];
         }
     ctx->stats.n_at_threshold = (int64_t)*h_natt;
+    if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "scan cold steps: %llu\n", *h_ncold);
     ctx->aux_host = h_aux;
     ctx->aux_used = *reinterpret_cast<const unsigned int *>(ctx->h_pin + 4);
     ctx->have_dists = want_dists;

@@ -150,6 +150,7 @@ struct ScanArgs {
     int32_t n_tiles;
     double *dist[KGMA_MAX_GROUP];   // per-KFV distance arrays or nullptr
     unsigned long long *n_att;      // stats: tested windows inside the threshold guard band
+    unsigned long long *n_cold;     // stats: stream8_kernel steps that left the fast path for the exact counts
     // stream8_kernel launched over a PART of the stream table (the pack / scan overlap of kgma_repack_scan_hits): `tiles`, `D0out`
     // and `n_tiles` are the part's, tile0 its first stream's index in the whole table (added to the records' tile numbers).
     // two-kernel cluster path (kgma_pos.hip): this launch covers tiles [tile0, tile0 + n_chunk_tiles);
@@ -208,6 +209,7 @@ constexpr int KGMA_STREAM_MAX_K = 7;                           // 4^k 16-bit cou
 
 // Aux region of the result block: residues under tied minima, gathered on the device (export_kernel)
 constexpr int KGMA_AUX_BYTES = 64 << 10;
+constexpr int KGMA_RES_HDR = 32;                               // counters at the head of a scan's result block (kgma_api.cpp)
 constexpr int KGMA_AUX_MAX_RANGE = 4096;                       // longest residue range gathered speculatively
 
 // One hit to re-align on the device (kgma_align.hip): its segment of the resident residue text.

@@ -1187,12 +1187,12 @@ __global__ __launch_bounds__(256) void export_kernel(uint8_t *__restrict__ res, 
                                                      unsigned int aux_cap, unsigned int *__restrict__ done)
 {
     unsigned int *cnt = reinterpret_cast<unsigned int *>(res);
-    uint8_t *aux = res + 16 + d0_slots * 8;
+    uint8_t *aux = res + KGMA_RES_HDR + d0_slots * 8;
     DevRecord *recs = reinterpret_cast<DevRecord *>(aux + KGMA_AUX_BYTES);
     if (do_gather) tie_gather_body(recs, cnt, rec_cap, tiles, cd, ascii, Wtab, aux, cnt + 1, aux_cap);
     {   // D0: 8-byte slots at the same offset in both blocks
-        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(res + 16);
-        unsigned long long *dst = reinterpret_cast<unsigned long long *>(host + 16);
+        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(res + KGMA_RES_HDR);
+        unsigned long long *dst = reinterpret_cast<unsigned long long *>(host + KGMA_RES_HDR);
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < d0_used; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i];
     }
     __shared__ unsigned int ticket;
@@ -1205,20 +1205,22 @@ __global__ __launch_bounds__(256) void export_kernel(uint8_t *__restrict__ res, 
     auto ld = [](const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
     const unsigned long long *r64 = reinterpret_cast<const unsigned long long *>(res);
     unsigned long long *h64 = reinterpret_cast<unsigned long long *>(host);
-    const unsigned long long c0 = ld(r64), c1 = ld(r64 + 1);
+    const unsigned long long c0 = ld(r64), c1 = ld(r64 + 1), c2 = ld(r64 + 2);
     unsigned int n = (unsigned int)c0, used = (unsigned int)(c0 >> 32);
     if (n > rec_cap) n = rec_cap;
     if (n > inline_recs) n = inline_recs;
     if (used > aux_cap) used = aux_cap;
-    const int64_t aux_w0 = (16 + d0_slots * 8) >> 3, aux_words = (used + 7) >> 3;
+    const int64_t aux_w0 = (KGMA_RES_HDR + d0_slots * 8) >> 3, aux_words = (used + 7) >> 3;
     for (int64_t i = threadIdx.x; i < aux_words; i += blockDim.x) h64[aux_w0 + i] = ld(r64 + aux_w0 + i);
     const int64_t rec_w0 = aux_w0 + (KGMA_AUX_BYTES >> 3), rec_words = ((int64_t)n * (int64_t)sizeof(DevRecord) + 7) >> 3;
     for (int64_t i = threadIdx.x; i < rec_words; i += blockDim.x) h64[rec_w0 + i] = ld(r64 + rec_w0 + i);
     if (threadIdx.x == 0) {
         h64[0] = c0;
         h64[1] = c1;
+        h64[2] = c2;
         __hip_atomic_store(reinterpret_cast<unsigned long long *>(res), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(reinterpret_cast<unsigned long long *>(res) + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(reinterpret_cast<unsigned long long *>(res) + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }

@@ -662,7 +662,7 @@ __global__ __launch_bounds__(1024, K >= 7 ? 2 : (C16 ? 4 : (NKFV == 1 ? (CHAIN ?
     for (int j = 0; j < NKFV; j++)
         if (j < n_kfv && a.dist[j] != nullptr) dist_mask |= 1u << j;
     // heavy k-mer (wave-uniform)
-    bool heavy = false;
+    uint32_t heavy = 0;                                               // (a word, not a bool: tested on the scalar unit)
     uint32_t Hkey = 0, hcnt = 0;
 
     const TileDesc td = a.tiles[tile];
@@ -883,6 +883,15 @@ __global__ __launch_bounds__(1024, K >= 7 ? 2 : (C16 ? 4 : (NKFV == 1 ? (CHAIN ?
         att_mask = (att_mask & ~(1u << j)) | (uni((int32_t)na) != 0 ? 1u << j : 0u);
     };
 
+    // Fast carry: steady steps of a scan launch without derived windows take the step's increments from the
+    // counts the atomics returned, and only a step that may hold a window at a threshold (or has a run open) runs the
+    // correction rounds.  n_cold counts those steps (ScanArgs::n_cold, once per wave).
+    constexpr bool FASTC = !CHAIN && !DERIVE;
+    uint32_t n_cold = 0;
+#ifdef KGMA_CHECK_FAST_CARRY
+    hot_t fast_carry[NKFV];                                           // (debug: the fast carry of a step that went cold)
+    bool fast_cold = false;
+#endif
     auto step = [&](const int b, auto generic_tag) {
         constexpr bool GENERIC = decltype(generic_tag)::value;
         const int p = (b << 6) + lane;
@@ -1015,14 +1024,24 @@ __global__ __launch_bounds__(1024, K >= 7 ? 2 : (C16 ? 4 : (NKFV == 1 ? (CHAIN ?
         asm volatile("" : "=v"(wop), "=v"(wos));
         // (`one` and `mone` = -1 live in vector registers: v_lshlrev in its short form, and the subtraction is an add of
         //  -(1 << shift) = (-1) << shift without a negation)
-        if (actE) wop = __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)(ap & ~3u), addv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (actL) wos = __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)(as & ~3u), subv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if constexpr (FASTC && !GENERIC) {
+            if (actE) {                                               // (steady: actL == actE -- one exec region for both)
+                wop = __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)(ap & ~3u), addv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wos = __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)(as & ~3u), subv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        } else {
+            if (actE) wop = __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)(ap & ~3u), addv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (actL) wos = __hip_atomic_fetch_add((lds_u32 *)(uintptr_t)(as & ~3u), subv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cp), "+v"(cs), "+v"(wop), "+v"(wos));   // (the byte loads are not known to the compiler's counters)
 
         // ---- exact counts of the entering / leaving k-mer in THIS lane's window ---------------------
         int32_t cP, cS;
         {
             uint32_t oldp, olds;
+            // fast-path steps: a lane without a transition takes its entering field for the leaving one (both are its k-mer's
+            // field), so that its difference below is 0 -- it issued no atomic, and its registers hold nothing defined
+            if constexpr (FASTC && !GENERIC) asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(wos) : "v"(wop), "v"(wos), "s"(AE));
             if constexpr (C16) {
                 asm("v_bfe_u32 %0, %1, %2, 16" : "=v"(oldp) : "v"(wop), "v"(shp));
                 asm("v_bfe_u32 %0, %1, %2, 16" : "=v"(olds) : "v"(wos), "v"(shs));
@@ -1033,6 +1052,72 @@ __global__ __launch_bounds__(1024, K >= 7 ? 2 : (C16 ? 4 : (NKFV == 1 ? (CHAIN ?
             uint64_t pendE = __builtin_amdgcn_uicmp(oldp, cp, 33 /* ne */) & AE;
             uint64_t pendL = __builtin_amdgcn_uicmp(olds, cs, 33 /* ne */) & AL;
             const uint64_t cand0 = __builtin_amdgcn_uicmp(cp, 127u, 34 /* ugt */);
+            // (heavy mode, a candidate or distances: the exact counts in this step; one scalar test, formed from words)
+            const uint64_t exact_only = (C16 ? 0 : cand0 | (uint64_t)heavy) | (uint64_t)dist_mask;
+            // ---- fast path: increments from the atomics' order ----------------------------------------------------
+            // The atomics applied the step's transitions in SOME order (every entering add, then every leaving subtract) and
+            // returned each counter as that order met it.  A key's share of the step total, the sum of its (2c + 1) terms, does
+            // not depend on the order, so increments formed from the returned fields add up to the exact total: the carry into
+            // the next step is exact without the rounds below.  A lane's prefix is off by at most N floor((P + 2)^2 / 4), P the
+            // pending lanes (0 when P = 0).  Only a step with a prefix below a threshold plus that margin, or with a run open,
+            // needs the exact counts: it goes on below (rounds, exact prefix from the unchanged carry, dip code).
+            if constexpr (FASTC && !GENERIC) {
+                if (exact_only == 0) {
+                    uint32_t d0;
+                    uint64_t borrow_out;
+                    asm("v_subb_co_u32_e64 %0, %1, %2, %3, %4" : "=v"(d0), "=s"(borrow_out) : "v"(olds), "v"(oldp), "s"(AE));
+                    const uint32_t P = (uint32_t)__builtin_popcountll(pendE) + (uint32_t)__builtin_popcountll(pendL);
+                    const uint32_t mg = P != 0 ? ((P + 2u) * (P + 2u)) >> 2 : 0u;
+                    int32_t sf[NKFV];
+#pragma unroll
+                    for (int j = 0; j < NKFV; j++) {
+                        sf[j] = 0;
+                        if (!FULL && j >= n_kfv) continue;
+                        int32_t sd = Sl[j] - Sr[j];
+                        asm volatile("" : "+v"(sd));
+                        sf[j] = __mul24(-gp.N[j], (int32_t)d0) + sd;
+                    }
+#define KGMA_SCAN_STAGE(ctrl, rmask)                                                                        \
+                    _Pragma("unroll") for (int j = 0; j < NKFV; j++) sf[j] += __builtin_amdgcn_update_dpp(0, sf[j], ctrl, rmask, 0xF, false);
+                    KGMA_SCAN_STAGE(0x111, 0xF)     // row_shr:1
+                    KGMA_SCAN_STAGE(0x112, 0xF)     // row_shr:2
+                    KGMA_SCAN_STAGE(0x114, 0xF)     // row_shr:4
+                    KGMA_SCAN_STAGE(0x118, 0xF)     // row_shr:8
+                    KGMA_SCAN_STAGE(0x142, 0xA)     // row_bcast:15 -> rows 1,3
+                    KGMA_SCAN_STAGE(0x143, 0xC)     // row_bcast:31 -> rows 2,3
+#undef KGMA_SCAN_STAGE
+                    uint64_t anyF = 0;
+                    hot_t cf[NKFV];
+#pragma unroll
+                    for (int j = 0; j < NKFV; j++) {
+                        cf[j] = h_carry[j];
+                        if (!FULL && j >= n_kfv) continue;
+                        const uint32_t mlo = (uint32_t)gp.N[j] * mg, mhi = __umulhi((uint32_t)gp.N[j], mg);   // N * margin
+                        if constexpr (BIG) {
+                            anyF |= __builtin_amdgcn_sicmp(sf[j], clamp32(h_TE[j] - h_carry[j] + (int64_t)(((uint64_t)mhi << 32) | mlo)), 40 /* slt */);
+                            cf[j] = h_carry[j] + (int64_t)__builtin_amdgcn_readlane(sf[j], 63);
+                        } else {
+                            const int32_t Ef = sf[j] + h_carry[j];
+                            // TE + natt + margin, saturated: the margin clamped in scalar registers, the sum by the adder's clamp
+                            const int32_t m32 = (mhi | (mlo >> 31)) != 0 ? 0x7FFFFFFF : (int32_t)mlo;
+                            int32_t thr;
+                            asm("v_add_i32 %0, %1, %2 clamp" : "=v"(thr) : "v"(h_TE[j]), "s"(m32));
+                            anyF |= __builtin_amdgcn_sicmp(Ef, thr, 40 /* slt */);
+                            cf[j] = __builtin_amdgcn_readlane(Ef, 63);
+                        }
+                    }
+                    if (__builtin_expect((anyF | (uint64_t)inrun_mask) == 0, 1)) {
+#pragma unroll
+                        for (int j = 0; j < NKFV; j++) h_carry[j] = cf[j];
+                        return;
+                    }
+                    n_cold++;
+#ifdef KGMA_CHECK_FAST_CARRY
+                    for (int j = 0; j < NKFV; j++) fast_carry[j] = cf[j];
+                    fast_cold = true;
+#endif
+                }
+            }
             if (!C16 && __builtin_expect(heavy || cand0 != 0, 0)) {
                 uint32_t best_key = 0, best_end = 0;
                 if (heavy) {
@@ -1057,7 +1142,7 @@ __global__ __launch_bounds__(1024, K >= 7 ? 2 : (C16 ? 4 : (NKFV == 1 ? (CHAIN ?
                     if (end > best_end) { best_end = end; best_key = x; }
                     cm &= ~ex;
                 }
-                heavy = best_end >= 128u;
+                heavy = best_end >= 128u ? 1u : 0u;
                 Hkey = best_key; hcnt = best_end;
             }
             // Rounds over the distinct k-mers with a pending lane (every round clears the pending bits of all lanes
@@ -1330,6 +1415,15 @@ __global__ __launch_bounds__(1024, K >= 7 ? 2 : (C16 ? 4 : (NKFV == 1 ? (CHAIN ?
                 anyU |= __builtin_amdgcn_sicmp(E[j], h_TE[j], 40 /* slt */) & TESTED;
             }
         }
+#ifdef KGMA_CHECK_FAST_CARRY
+        if constexpr (FASTC && !GENERIC) {
+            if (fast_cold) {
+#pragma unroll
+                for (int j = 0; j < NKFV; j++) if (h_carry[j] != fast_carry[j]) __builtin_trap();
+                fast_cold = false;
+            }
+        }
+#endif
         if (dist_mask != 0) {
 #pragma unroll
             for (int j = 0; j < NKFV; j++) {
@@ -1467,6 +1561,7 @@ __global__ __launch_bounds__(1024, K >= 7 ? 2 : (C16 ? 4 : (NKFV == 1 ? (CHAIN ?
             emit_global(a, rec);
         }
     }
+    if (n_cold != 0 && lane == 0) atomicAdd(a.n_cold, (unsigned long long)n_cold);
 }
 
 // ------------------------------------------------------------------------------------------
