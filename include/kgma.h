@@ -53,7 +53,8 @@ enum {
 /* engine selector for kgma_scan */
 enum {
     KGMA_MODE_SINGLE = 0,   /* ac_gma_testing!  src/GenomeMiner.jl:4-109   (uses KFV 1 only)          */
-    KGMA_MODE_OMN = 1       /* Omn_KmerGMA!     src/OmnGenomeMiner.jl:7-162 (all KFVs, lock-step)     */
+    KGMA_MODE_OMN = 1,      /* Omn_KmerGMA!     src/OmnGenomeMiner.jl:7-162 (all KFVs, lock-step)     */
+    KGMA_MODE_STROBE = 2    /* StrobeGMA!       src/StrobemerGMA/StrobeGenomeMiner.jl:5-95 (after kgma_set_strobe_ref) */
 };
 
 /* flags for kgma_scan */
@@ -439,6 +440,43 @@ int kgma_repack_scan_hits(kgma_ctx *ctx, kgma_genome *genome, int32_t mode, int6
 int kgma_kmer_count_batch(kgma_ctx *ctx, int32_t k, const uint8_t *seqs, const int64_t *offsets, int64_t n, double *bins);
 int kgma_kmer_dist_batch(kgma_ctx *ctx, int32_t k, const double *kfv, const uint8_t *seqs, const int64_t *offsets, int64_t n,
                          double *out);
+
+/* ---- the strobemer engine: StrobeGMA! / Strobemer_findGenes (src/StrobemerGMA/StrobeGenomeMiner.jl) ------------------------------
+ * Upload the reference of the strobemer method (gen_ref_ws_cons of src/StrobemerGMA/StrobeRefGen.jl): ref[4^(2s)] Float64 in the
+ * reference's bin order (bin = first s-mer * 4^s + second s-mer, natural values: as_UInt of the ungapped randstrobe), one window
+ * size, one threshold.  s, w_min, w_max, q are get_strobe_2_mer's parameters (src/StrobemerGMA/Strobemers.jl:45-65); a strobemer
+ * spans k = w_max + s - 1 residues.  Read literally, the reference picks as second s-mer the one at the LAST offset in
+ * w_min..w_max whose score (as_UInt(first) + as_UInt(s-mer)) % q is 0, at w_min if none is (`min_score::Int = 2 << 63` is 0), and
+ * its scan re-enters the window's own last strobemer: after step i the counts are the W - k strobemers starting at i+1 .. i+W-k
+ * plus one permanent copy of the record's strobemer W-k+1.  That is what the device computes (kgma_strobe.hip), in exact integers:
+ * the KFV must be S/N with integer S (same inference from n_refs / the entries and same threshold band as kgma_set_refs).
+ * Served: 1 <= s <= 3, 1 <= w_min <= w_max, k <= 16, q >= 1, k < windowsize, windowsize - k + 1 <= 65535.  KGMA_E_ARG where the
+ * reference would throw (s < 1, w_min < 1, w_min > w_max, q < 1, k >= windowsize); KGMA_E_UNSUPPORTED for the rest (s > 3, k > 16,
+ * longer windows, a KFV that is not S/N).  The call REPLACES the context's references: a k-mer scan after it, or a strobe scan
+ * after kgma_set_refs, returns KGMA_E_STATE.  kgma_set_thresholds works as for k-mer references. */
+int kgma_set_strobe_ref(kgma_ctx *ctx, int32_t s, int32_t w_min, int32_t w_max, int64_t q, const double *ref, int64_t windowsize,
+                        double thr, int64_t n_refs /* 0: infer */);
+
+/* The strobemer scan of every record, with the optional re-alignment of process_hit! (src/Alignment.jl:83-111) on the device.
+ * consensus == NULL: do_align = false.  Otherwise every candidate range max(CMI - buff, 1) : min(CMI + W - 1 + buff, L) is aligned
+ * against consensus[1:windowsize] (semi-global, EDNAFULL, affine gaps; StrobeGMA!'s default scores are -69 / -5) in one device
+ * batch, a candidate whose alignment score is below score_threshold is dropped -- goal_ind and currminim were updated all the
+ * same, as in the reference, where the gate does not feed back into the state machine -- and the others get the aligned range.
+ * Results through the usual getters: kgma_get_hits (kfv = 0, cmi = CMI after `CMI += 1` = the best window's step + 1, genome_pos
+ * advancing by the length of every record that is not shorter than the window), kgma_get_dips, kgma_get_first_window,
+ * kgma_get_dists (KGMA_F_RETURN_DISTS: one value per step i >= 1 in record order, L - W - 1 per record), kgma_get_stats,
+ * kgma_get_alignments (the alignments of the hits that passed the gate), kgma_scan_kernel_name ("strobe_kernel<2>").
+ * Without KGMA_F_CHAIN_REPLAY every decision is taken on exact integers (first of tied windows, strict comparisons, windows inside
+ * the threshold band count as not below) and the rounding-dependent dips are flagged KGMA_HIT_TIE / KGMA_HIT_AT_THRESHOLD, a minimum
+ * equal to the stale running minimum included.  With it, every record that holds a flagged dip or an at-threshold window is decided
+ * by a HOST replay of the reference's sequential Float64 loop over the record's residues (fetched from the device; first window
+ * summed left to right, increments in the reference's operation order): its hits carry KGMA_HIT_CHAIN and the running value as
+ * dist.  kgma_scan(KGMA_MODE_STROBE) is this call without a consensus (an align callback is refused with KGMA_E_UNSUPPORTED: the
+ * gate needs the alignment's score, which the callback does not return); kgma_scan_device(KGMA_MODE_STROBE) is its device part.
+ * NOT served for strobemer references (KGMA_E_UNSUPPORTED): kgma_chain_values, kgma_chain_export, kgma_replay_dips,
+ * kgma_resolve_ties_local, kgma_scan_aligned, kgma_repack_scan_hits, kgma_step_begin / kgma_step_end. */
+int kgma_strobe_scan(kgma_ctx *ctx, const kgma_genome *g, int64_t buff, uint32_t flags, const uint8_t *consensus, int64_t consensus_len,
+                     int32_t gap_open_score, int32_t gap_extend_score, int64_t score_threshold);
 
 /* kgma_repack_scan_hits in two halves, for step loops that have other work to queue while the GPU scans
  * (bench.py with several ranks: the hit exchange of step i overlaps the scan of step i+1).  kgma_step_begin

@@ -59,6 +59,8 @@ void generic_set_mode(GenParams &g, int nk_max);
 hipError_t launch_generic(const ScanArgs &a, const GenParams &g, hipStream_t st);
 int generic_chain_slots_per_cu(int k, int nk);
 hipError_t launch_generic_chain(const ScanArgs &a, const GenParams &g, hipStream_t st);
+int strobe_slots_per_cu(int s);
+hipError_t launch_strobe(const ScanArgs &a, const StrobeParams &g, hipStream_t st);
 hipError_t launch_pos(const ScanArgs &a, const GroupParams &gp, int j0, int nj, hipStream_t st);
 bool chain_applies(int k, int nk, int64_t n_ref, bool s16, bool need_wide);
 int chain_slots_per_cu(int k, bool s16, int nkfv, int nk, bool need_wide);
@@ -285,6 +287,10 @@ struct kgma_ctx {
     uint64_t tk_uid = 0, tk_version = 0; int tk_mode = -1, tk_k = 0; int64_t tk_maxws = 0;
     // references
     int k = 0, m = 0;
+    // strobemer references (kgma_set_strobe_ref): k = w_max + s - 1, one KFV of 4^(2s) bins whose S / ref tables are in natural bin order
+    bool strobe = false;
+    int st_s = 0, st_wmin = 0, st_wmax = 0;
+    int64_t st_q = 0;
     // The guard band around thr is 2^-band_log2 (relative): windows that close count as "at threshold", the chain replay samples
     // them, and a chain that has drifted more than half of it from the exact distances (2^-(band_log2 + 1) of max(distance, thr))
     // makes kgma_scan repeat the scan with a band wide enough for the drift it measured.  30 unless KGMA_BAND_LOG2 says otherwise
@@ -891,6 +897,7 @@ static int64_t overlap_min_bases()                                   // (KGMA_OV
 int kgma_repack_scan_hits(kgma_ctx *ctx, kgma_genome *g, int32_t mode, int64_t buff, int64_t genome_pos0, uint32_t flags,
                           kgma_hit *out, int64_t cap, int64_t *n)
 {
+    if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || !g || !n) return KGMA_E_ARG;
     // a large genome's re-encoding is left to the scan, which may run it beside its own launches (launch_overlapped)
     int rc = KGMA_OK;
@@ -934,6 +941,7 @@ static void step_worker_main(kgma_ctx *ctx)
 
 int kgma_step_begin(kgma_ctx *ctx, kgma_genome *g, int32_t mode, int64_t buff, int64_t genome_pos0, uint32_t flags)
 {
+    if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || !g) return KGMA_E_ARG;
     if (!ctx->worker) {
         ctx->worker = new StepWorker();
@@ -954,6 +962,7 @@ int kgma_step_begin(kgma_ctx *ctx, kgma_genome *g, int32_t mode, int64_t buff, i
 
 int kgma_step_end(kgma_ctx *ctx, kgma_hit *out, int64_t cap, int64_t *n)
 {
+    if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || !n) return KGMA_E_ARG;
     StepWorker *w = ctx->worker;
     if (!w || w->state.load(std::memory_order_acquire) == 0) return fail(ctx, KGMA_E_STATE, "kgma_step_end without kgma_step_begin");
@@ -1152,6 +1161,7 @@ static int set_refs_sparse_core(kgma_ctx *ctx, int32_t k, int32_t m, std::vector
     }
     ctx->k = k;
     ctx->m = m;
+    ctx->strobe = false;
     ctx->kfv.swap(kv);
     for (double *p : ctx->d_dist) if (p) (void)hipFree(p);
     ctx->d_dist.assign((size_t)m, nullptr);
@@ -1248,6 +1258,7 @@ int kgma_set_refs(kgma_ctx *ctx, int32_t k, int32_t m, const double *ref, const 
     }
     ctx->k = k;
     ctx->m = m;
+    ctx->strobe = false;
     ctx->kfv.swap(kv);
     for (double *p : ctx->d_dist) if (p) (void)hipFree(p);
     ctx->d_dist.assign((size_t)m, nullptr);
@@ -1298,6 +1309,67 @@ int kgma_set_refs_sparse(kgma_ctx *ctx, int32_t k, int32_t m, const int64_t *nnz
 // genomes
 // ------------------------------------------------------------------------------------------
 // the context's staging pair (2 x 32 MiB of pinned memory), made on first use
+// The strobemer method's reference (kgma.h): one KFV over the 4^(2s) randstrobe bins, S/N only.  kfv_from_nonzeros does the S/N
+// inference, the range checks (its "k-mers per window" W - k + 1 is the window's item count here: W - k sliding strobemers plus
+// the permanent one) and the threshold band; the tables stay in natural bin order, which is the order strobe_kernel forms.
+int kgma_set_strobe_ref(kgma_ctx *ctx, int32_t s, int32_t w_min, int32_t w_max, int64_t q, const double *ref, int64_t windowsize,
+                        double thr, int64_t n_refs)
+{
+    if (!ctx) return KGMA_E_ARG;
+    if (!ref) return fail(ctx, KGMA_E_ARG, "null argument");
+    if (s < 1 || w_min < 1 || w_min > w_max || q < 1)
+        return fail(ctx, KGMA_E_ARG, "invalid randstrobe parameters s = %d, w_min = %d, w_max = %d, q = %lld", s, w_min, w_max, (long long)q);
+    if (n_refs < 0) return fail(ctx, KGMA_E_ARG, "n_refs = %lld", (long long)n_refs);
+    const int64_t k64 = (int64_t)w_max + s - 1;
+    if (k64 >= windowsize)
+        return fail(ctx, KGMA_E_ARG, "the window size %lld does not exceed the strobemer span %lld (w_max + s - 1)", (long long)windowsize, (long long)k64);
+    if (s > KGMA_STROBE_MAX_S)
+        return fail(ctx, KGMA_E_UNSUPPORTED, "s = %d: the device path supports 1 <= s <= %d (4^(2s) window counts per wave in LDS)", s, KGMA_STROBE_MAX_S);
+    if (k64 > KGMA_STROBE_MAX_K)
+        return fail(ctx, KGMA_E_UNSUPPORTED, "w_max + s - 1 = %lld: a strobemer of at most %d residues is supported", (long long)k64, KGMA_STROBE_MAX_K);
+    (void)hipSetDevice(ctx->device);
+    const int k = (int)k64;
+    const int64_t NB = (int64_t)1 << (4 * s);
+    std::vector<KfvInfo> kv(1);
+    KfvInfo &f = kv[0];
+    {
+        std::vector<uint32_t> keys;
+        std::vector<double> nz;
+        for (int64_t x = 0; x < NB; x++)
+            if (ref[x] != 0.0) { keys.push_back((uint32_t)x); nz.push_back(ref[x]); }
+        const int rc = kfv_from_nonzeros(ctx, k, 0, std::move(keys), std::move(nz), &windowsize, &thr, n_refs > 0 ? &n_refs : nullptr, f);
+        if (rc != KGMA_OK) return rc;
+    }
+    if (f.fp) return fail(ctx, KGMA_E_UNSUPPORTED, "the strobemer engine scans KFVs that are S/N with integer S (gen_ref_ws_cons's); this one is not");
+    if (f.Smax > INT32_MAX) return fail(ctx, KGMA_E_UNSUPPORTED, "KFV entries beyond int32");
+    f.ref.assign(ref, ref + NB);
+    f.S.assign((size_t)NB, 0);
+    for (size_t i = 0; i < f.sk.size(); i++) f.S[f.sk[i]] = f.sS[i];
+    f.sk.clear(); f.sv.clear(); f.sS.clear();
+    std::vector<int32_t> tab((size_t)NB);
+    for (int64_t x = 0; x < NB; x++) tab[(size_t)x] = (int32_t)f.S[(size_t)x];
+    for (void *p : {(void *)ctx->d_Stab, (void *)ctx->d_StabC, (void *)ctx->d_Rtab, (void *)ctx->d_sparse, (void *)ctx->d_Wtab}) if (p) (void)hipFree(p);
+    ctx->d_Stab = nullptr; ctx->d_StabC = nullptr; ctx->d_Rtab = nullptr; ctx->d_sparse = nullptr; ctx->d_Wtab = nullptr;
+    for (auto &kv2 : ctx->sinter) (void)hipFree(kv2.second);
+    ctx->sinter.clear();
+    ctx->m = 0;                                                        // (no references until the uploads below have succeeded)
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_Stab), tab.size() * sizeof(int32_t)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_Stab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_Wtab), sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_Wtab, &windowsize, sizeof(int64_t), hipMemcpyHostToDevice));
+    ctx->k = k;
+    ctx->m = 1;
+    ctx->strobe = true;
+    ctx->st_s = s; ctx->st_wmin = w_min; ctx->st_wmax = w_max; ctx->st_q = q;
+    ctx->kfv.swap(kv);
+    for (double *p : ctx->d_dist) if (p) (void)hipFree(p);
+    ctx->d_dist.assign(1, nullptr);
+    ctx->dist_cap.assign(1, 0);
+    ctx->last_mode = -1;
+    ctx->tk_uid = 0;
+    return KGMA_OK;
+}
+
 static StagePipe *ctx_pipe(kgma_ctx *ctx)
 {
     if (ctx->pipe) { ctx->pipe->drain(); return ctx->pipe; }
@@ -2146,7 +2218,11 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     if (!ctx || !gc) return KGMA_E_ARG;
     kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping is updated
     if (ctx->m == 0) return fail(ctx, KGMA_E_STATE, "kgma_set_refs has not been called");
-    if (mode != KGMA_MODE_SINGLE && mode != KGMA_MODE_OMN) return fail(ctx, KGMA_E_ARG, "unknown mode %d", mode);
+    if (mode != KGMA_MODE_SINGLE && mode != KGMA_MODE_OMN && mode != KGMA_MODE_STROBE) return fail(ctx, KGMA_E_ARG, "unknown mode %d", mode);
+    const bool strobe = mode == KGMA_MODE_STROBE;
+    if (strobe != ctx->strobe)
+        return fail(ctx, KGMA_E_STATE, strobe ? "a strobemer scan needs strobemer references (kgma_set_strobe_ref)"
+                                              : "the context holds strobemer references: a k-mer scan needs kgma_set_refs");
     (void)hipSetDevice(ctx->device);
     const int k = ctx->k, m_used = mode == KGMA_MODE_SINGLE ? 1 : ctx->m;
     int64_t maxws = 0;
@@ -2174,7 +2250,8 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     // Float64 KFV, a window of more than 2031 k-mers or a prefix beyond int32 where the 16-bit stream8 form does not apply
     // (k < 5, k > 7, S beyond int16 at k = 7, N >= 2^22).  KGMA_KERNEL=generic (testing): always.
     // k = 1 and k >= 11: only the generic kernel's 32-bit counter and wide hash forms serve them
-    bool generic_all = (kenv && !strcmp(kenv, "generic")) || k == 1 || k >= KGMA_WIDE_MIN_K;
+    // (the strobemer kernel -- kgma_strobe.hip -- is a stream kernel of the same kind: one KFV, the same stream table and records)
+    bool generic_all = strobe || (kenv && !strcmp(kenv, "generic")) || k == 1 || k >= KGMA_WIDE_MIN_K;
     for (int j = 0; j < m_used; j++) {
         const KfvInfo &f = ctx->kfv[(size_t)j];
         if (f.fp || ((f.W - k + 1 > KGMA_MAX_NK || !f.fits32) && !(s8_all && c16_ok(f)))) generic_all = true;
@@ -2229,8 +2306,8 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     std::vector<int> launch_slots;
     std::vector<double> launch_weight;
     if (generic_all) {
-        stream_nw = generic_slots_per_cu(k, generic_fp, (int)(maxws - k + 1));
-        if (stream_nw < 1) return fail(ctx, KGMA_E_HIP, "the generic kernel cannot be launched (k = %d)", k);
+        stream_nw = strobe ? strobe_slots_per_cu(ctx->st_s) : generic_slots_per_cu(k, generic_fp, (int)(maxws - k + 1));
+        if (stream_nw < 1) return fail(ctx, KGMA_E_HIP, "the %s kernel cannot be launched (k = %d)", strobe ? "strobemer" : "generic", k);
     }
     if (use_stream && !generic_all)
         for (const Group &gr : groups) {
@@ -2285,7 +2362,8 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         bool s8 = use_stream;
         if (use_stream)
             for (const Group &gr : groups) s8 = s8 && group_s8(gr);
-        snprintf(ctx->kernel_name, sizeof ctx->kernel_name, generic_all ? (generic_fp ? "gen_kernel<f64,%d>" : "gen_kernel<%d>") : s8 ? "stream8_kernel<%d>" : use_stream ? "stream_kernel<%d>" : "scan_kernel<%d>", k);   // (+ pos_kernel for multi-KFV groups)
+        if (strobe) snprintf(ctx->kernel_name, sizeof ctx->kernel_name, "strobe_kernel<%d>", ctx->st_s);
+        else snprintf(ctx->kernel_name, sizeof ctx->kernel_name, generic_all ? (generic_fp ? "gen_kernel<f64,%d>" : "gen_kernel<%d>") : s8 ? "stream8_kernel<%d>" : use_stream ? "stream_kernel<%d>" : "scan_kernel<%d>", k);   // (+ pos_kernel for multi-KFV groups)
     }
 
     ctx->dips.clear();
@@ -2320,6 +2398,11 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
             if (mode == KGMA_MODE_SINGLE) {
                 const int64_t W = ctx->kfv[0].W;
                 if (L >= W) { nwin = L - W + 1; looked = L; }   // GenomeMiner.jl:37-39,60
+            } else if (strobe) {
+                // StrobeGenomeMiner.jl:36,40,48-57: the first window (virtual window start 1) and one window per step i = 1 .. L - W - 1
+                // (start i + 1); the residues looked up are the first window's and those of the strobemers up to the one at L - k - 1
+                const int64_t W = ctx->kfv[0].W;
+                if (L >= W) { nwin = std::max<int64_t>(L - W, 1); looked = std::max<int64_t>(W, L - 2); }
             } else {
                 if (L < k - 1) {
                     looked = -1;                                                   // BoundsError, :84-86
@@ -2348,7 +2431,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
             // stream stays long against its warm-up (n k-mers) and the S-table staging of its workgroup.
             {
                 int64_t want = 3, min_windows = std::max<int64_t>(8192, 8 * (maxws - k + 1));   // (a stream's warm-up is its window's n k-mers)
-                if (generic_all && generic_count_mode(k, (int)(maxws - k + 1)) == 1) min_windows = std::max<int64_t>(min_windows, (int64_t)1 << (2 * k - 2));   // (and zeroing its global count table)
+                if (generic_all && !strobe && generic_count_mode(k, (int)(maxws - k + 1)) == 1) min_windows = std::max<int64_t>(min_windows, (int64_t)1 << (2 * k - 2));   // (and zeroing its global count table)
                 if (const char *re = getenv("KGMA_STREAM_ROUNDS")) want = std::max(1, atoi(re));               // experiments
                 if (const char *re = getenv("KGMA_STREAM_ROUND_WINDOWS")) min_windows = std::max(64, atoi(re));
                 rounds = std::max(rounds, std::min<int64_t>(want, total_nwin / (slots * min_windows)));
@@ -2545,6 +2628,25 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
             a.planes = g->d_planes;
             a.inter = g->d_inter;
             a.tiles = ctx->d_tiles;
+            if (strobe) {
+                const KfvInfo &f = ctx->kfv[0];
+                StrobeParams sp;
+                memset(&sp, 0, sizeof sp);
+                sp.s = ctx->st_s; sp.w_min = ctx->st_wmin; sp.w_max = ctx->st_wmax;
+                sp.nk = (int32_t)(f.W - k);                            // the strobemers that slide; the window's permanent one comes on top
+                sp.N = (int32_t)f.N; sp.kfv_id = 1;
+                sp.n_slots = (int32_t)((int64_t)std::max(1, ctx->n_cus - ctx->reserved_cus) * stream_nw);
+                sp.T = f.T; sp.T_hi = f.T_hi; sp.sumS2 = f.sumS2; sp.inv_scale = gp.inv_scale[0];
+                sp.S = ctx->d_Stab;
+                for (int64_t v = 0; v < 128; v++)
+                    if (v % ctx->st_q == 0) sp.zero[v >> 5] |= 1u << (v & 31);
+                a.D0out = d_D0; a.recs = d_recs; a.rec_count = reinterpret_cast<unsigned int *>(d_cnt); a.rec_cap = ctx->rec_cap;
+                a.n_tiles = (int32_t)n_tiles; a.n_att = reinterpret_cast<unsigned long long *>(d_cnt + 8);
+                a.n_cold = reinterpret_cast<unsigned long long *>(d_cnt + 16);
+                HIP_TRY(ctx, launch_strobe(a, sp, ctx->stream));
+                ctx->stats.n_launches++;
+                continue;
+            }
             if (generic_all) {
                 const int j = gr.kfvs[0];
                 const KfvInfo &f = ctx->kfv[(size_t)j];
@@ -2649,7 +2751,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         // no copy-engine launch, no memset before the next scan
         (void)d_aux; (void)d_D0;
         HIP_TRY(ctx, launch_export(ctx->d_res, ctx->h_pin_dev, ctx->res_d0_slots, n_tiles * (int64_t)ctx->m, ctx->rec_cap,
-                                   (unsigned int)std::min<size_t>(INLINE_RECS, ctx->rec_cap), (flags & KGMA_F_NO_TIE_RESOLVE) ? 0 : 1,
+                                   (unsigned int)std::min<size_t>(INLINE_RECS, ctx->rec_cap), ((flags & KGMA_F_NO_TIE_RESOLVE) || strobe) ? 0 : 1,
                                    ctx->d_tiles, g->d_cd, g->d_ascii, ctx->d_Wtab, ctx->d_done, ctx->stream));
         HIP_TRY(ctx, sync_spin(ctx->stream));
         ctx->counters_clean = true;
@@ -4111,6 +4213,10 @@ int kgma_scan(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64_t buff, i
               uint32_t flags, kgma_align_fn align, void *align_user)
 {
     if (!ctx) return KGMA_E_ARG;
+    if (mode == KGMA_MODE_STROBE) {
+        if (align) return fail(ctx, KGMA_E_UNSUPPORTED, "the strobemer scan aligns on the device: kgma_strobe_scan takes the consensus");
+        return kgma_strobe_scan(ctx, g, buff, flags, nullptr, 0, 0, 0, 0);
+    }
     const int rc = scan_and_decide(ctx, g, mode, buff, flags);
     if (rc) return rc;
     return replay_hits(ctx, g, mode, buff, genome_pos0, flags, align, align_user);
@@ -4119,6 +4225,7 @@ int kgma_scan(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64_t buff, i
 int kgma_chain_values(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32_t kfv, const int64_t *win_lo, const int64_t *win_hi,
                       int64_t n_intervals, double *out, int64_t cap, int64_t *n_out)
 {
+    if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || !g || !win_lo || !win_hi || !n_out || n_intervals < 1) return KGMA_E_ARG;
     if (ctx->m == 0) return fail(ctx, KGMA_E_STATE, "kgma_set_refs has not been called");
     if (kfv < 1 || kfv > ctx->m || contig < 0 || contig >= g->n_contigs) return fail(ctx, KGMA_E_ARG, "no such record / KFV");
@@ -4189,6 +4296,7 @@ static int64_t record_windows(const kgma_ctx *ctx, int32_t mode, int64_t L)
 // can be decided where the residues are.  Called by a rank before it ships its dips (kgma_replay_dips).
 int kgma_resolve_ties_local(kgma_ctx *ctx, const kgma_genome *g)
 {
+    if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || !g) return KGMA_E_ARG;
     if (ctx->last_mode < 0) return fail(ctx, KGMA_E_STATE, "no scan has been run");
     TieResolver tr{ctx, g, {}, {}, {}, nullptr, {}, {}};
@@ -4285,6 +4393,7 @@ void aligned_cb(void *user, int32_t contig, int32_t kfv, int64_t lo, int64_t hi,
 int kgma_scan_aligned(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64_t buff, int64_t genome_pos0, uint32_t flags,
                       const uint8_t *const *consensus, const int64_t *consensus_len, int32_t gap_open_score, int32_t gap_extend_score)
 {
+    if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || !g) return KGMA_E_ARG;
     if (!consensus || !consensus_len) return fail(ctx, KGMA_E_ARG, "null consensus");
     if (buff < 0) return fail(ctx, KGMA_E_ARG, "buff < 0");
@@ -4385,6 +4494,232 @@ int kgma_scan_aligned(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64_t
     return KGMA_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// The strobemer engine's host half (StrobeGenomeMiner.jl:46-91, Alignment.jl:83-111).  The hit state machine is the single
+// engine's over the dips, with CMI = the best window's step i (virtual window start - 1) and with the score gate of process_hit!
+// applied AFTER the machine has run: the gate returns before append_hit!, but goal_ind and currminim are updated by the caller
+// whether or not the hit was kept, so alignment never feeds back.  Candidates first, one alignment batch, then the gate.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// The reference's sequential Float64 loop over one record (KGMA_F_CHAIN_REPLAY): residues -> randstrobe bins -> first window summed
+// left to right -> the running update in the reference's operation order.  The exact integer D is carried along for kgma_hit.D.
+// This file is compiled with -ffp-contract=off: every rounding below is the reference's.
+void strobe_float_record(const kgma_ctx *ctx, const uint8_t *res, int64_t L, int64_t c, int64_t buff, int64_t genome_pos, std::vector<kgma_hit> &out)
+{
+    const KfvInfo &f = ctx->kfv[0];
+    const int s = ctx->st_s, w_min = ctx->st_wmin, w_max = ctx->st_wmax, k = ctx->k;
+    const int64_t q = ctx->st_q, W = f.W, N = f.N;
+    const int64_t NB = (int64_t)1 << (4 * s);
+    const int64_t n_items = std::max<int64_t>(W - k + 1, L - k - 1);  // strobemers the loop reads
+    std::vector<uint8_t> code((size_t)L);
+    for (int64_t i = 0; i < L; i++) { const int cd = res_code(res[i]); code[(size_t)i] = (uint8_t)(cd < 0 ? 0 : cd); }   // (a residue the reference never looks up)
+    const int64_t n_s = L - s + 1;
+    std::vector<uint32_t> smer((size_t)n_s);
+    for (int64_t i = 0; i < n_s; i++) {
+        uint32_t v = 0;
+        for (int j = 0; j < s; j++) v = (v << 2) | code[(size_t)(i + j)];
+        smer[(size_t)i] = v;
+    }
+    std::vector<uint32_t> bin((size_t)n_items);
+    for (int64_t p = 0; p < n_items; p++) {
+        const uint32_t first = smer[(size_t)p];
+        uint32_t second = smer[(size_t)(p + w_min - 1)];
+        for (int o = w_min; o <= w_max; o++) {                         // Strobemers.jl:52-60: the last offset of score 0, else w_min
+            const uint32_t cand = smer[(size_t)(p + o - 1)];
+            if ((int64_t)(first + cand) % q == 0) second = cand;
+        }
+        bin[(size_t)p] = (first << (2 * s)) | second;
+    }
+    std::vector<double> cur((size_t)NB, 0.0);
+    std::vector<int64_t> ci((size_t)NB, 0);
+    for (int64_t p = 0; p <= W - k; p++) { cur[bin[(size_t)p]] += 1.0; ci[bin[(size_t)p]] += 1; }
+    double acc = 0.0;
+    int64_t D = 0;
+    for (int64_t x = 0; x < NB; x++) {
+        const double d = f.ref[(size_t)x] - cur[(size_t)x];
+        acc += d * d;
+        const int64_t e = f.S[(size_t)x] - N * ci[(size_t)x];
+        D += e * e;
+    }
+    double kd = (1.0 / (double)(2 * k)) * acc;                          // StrobeGenomeMiner.jl:43
+    const double SF = 1.0 / (double)k;                                  // :137
+    const double thr = f.thr;
+    int64_t CMI = 2, goal_ind = 0, curD = D;
+    bool stop = true;
+    double currminim = kd;
+    for (int64_t i = 1; i <= L - W - 1; i++) {
+        const uint32_t l = bin[(size_t)(i - 1)], r = bin[(size_t)(i - 1 + W - k)];
+        if (l != r) {
+            double t = 1.0 + cur[r];                                   // :60-62, left to right
+            t = t + f.ref[l];
+            t = t - f.ref[r];
+            t = t - cur[l];
+            kd += SF * t;
+            D += 2 * N * (f.S[l] - f.S[r] - N * (ci[l] - 1 - ci[r]));
+            cur[l] -= 1.0; cur[r] += 1.0;
+            ci[l] -= 1; ci[r] += 1;
+        }
+        if (kd < thr) {
+            if (kd < currminim) { currminim = kd; curD = D; CMI = i; stop = false; }
+        } else if (!stop) {
+            stop = true;
+            CMI += 1;
+            if (CMI > goal_ind) {
+                goal_ind = CMI + W - 1;
+                kgma_hit h;
+                memset(&h, 0, sizeof h);
+                h.contig = (int32_t)c; h.kfv = 0; h.cmi = CMI;
+                h.lo = std::max<int64_t>(CMI - buff, 1); h.hi = std::min<int64_t>(CMI + W - 1 + buff, L);
+                h.genome_pos = genome_pos; h.D = curD; h.dist = currminim; h.flags = KGMA_HIT_CHAIN;
+                out.push_back(h);
+                currminim = kd; curD = D;
+            }
+        }
+    }
+}
+
+// candidates of every record: the dip machine on exact integers, or (chain) the Float64 replay for the records that need it
+int strobe_candidates(kgma_ctx *ctx, const kgma_genome *g, int64_t buff, uint32_t flags)
+{
+    const bool chain = (flags & KGMA_F_CHAIN_REPLAY) && !(flags & KGMA_F_NO_TIE_RESOLVE);
+    const double t0 = now_ms();
+    const KfvInfo &f = ctx->kfv[0];
+    const int64_t W = f.W;
+    const double scale = 2.0 * (double)ctx->k * (double)f.N * (double)f.N;
+    const int64_t nc = (int64_t)ctx->contig_len.size();
+    reset_chain_stats(ctx);
+    ctx->stats.chain_band_log2 = ctx->band_log2; ctx->stats.chain_rescans = 0;
+    ctx->hits.clear();
+    size_t di = 0, ai = 0;
+    int64_t genome_pos = 0;                                            // StrobeGenomeMiner.jl:24
+    std::vector<kgma_hit> rec_hits;
+    std::vector<uint8_t> res;
+    double chain_ms = 0;
+    for (int64_t c = 0; c < nc; c++) {
+        const int64_t L = ctx->contig_len[(size_t)c];
+        if (ctx->contig_nwin[(size_t)c] == 0) continue;                // L < W: :36 (genome_pos does not advance)
+        const int64_t D1 = ctx->firstD[(size_t)c];
+        int64_t CMI = 2, goal_ind = 0, currmin = D1;                   // :46
+        bool stop = true, flagged = false;
+        uint32_t cur_flags = 0;
+        rec_hits.clear();
+        while (di < ctx->dips.size() && ctx->dips[di].contig < c) di++;
+        for (; di < ctx->dips.size() && ctx->dips[di].contig == c; di++) {
+            kgma_dip &d = ctx->dips[di];
+            const bool improved = d.D_min < currmin;                   // :73-77 (strict running minimum)
+            if (!improved && d.D_min == currmin) d.flags |= KGMA_HIT_TIE;   // equal to the stale running minimum: rounding decides in the reference
+            if (d.flags & (KGMA_HIT_TIE | KGMA_HIT_AT_THRESHOLD)) flagged = true;
+            if (improved) {
+                currmin = d.D_min;
+                CMI = d.argmin - 1;                                    // the step i whose window starts at i + 1
+                stop = false;
+                cur_flags = d.flags;
+            }
+            if (d.exit_pos == 0) continue;                             // dip still open at the record end
+            if (!stop) {                                               // :80-90
+                stop = true;
+                CMI += 1;
+                if (CMI > goal_ind) {
+                    goal_ind = CMI + W - 1;
+                    kgma_hit h;
+                    memset(&h, 0, sizeof h);
+                    h.contig = (int32_t)c; h.kfv = 0; h.cmi = CMI;
+                    h.lo = std::max<int64_t>(CMI - buff, 1); h.hi = std::min<int64_t>(CMI + W - 1 + buff, L);
+                    h.genome_pos = genome_pos; h.D = currmin; h.dist = (double)currmin / scale;
+                    h.flags = cur_flags | (d.flags & KGMA_HIT_AT_THRESHOLD);
+                    rec_hits.push_back(h);
+                    currmin = d.D_exit;                                // :88
+                }
+            }
+        }
+        while (ai < ctx->att.size() && ctx->att[ai].contig < c) ai++;
+        if (ai < ctx->att.size() && ctx->att[ai].contig == c) flagged = true;   // a tested window inside the threshold band
+        if (chain && flagged && g) {
+            const double t1 = now_ms();
+            res.resize((size_t)L);
+            const int frc = kgma_genome_fetch(ctx, g, c, 1, L, res.data());
+            if (frc) return frc;
+            rec_hits.clear();
+            strobe_float_record(ctx, res.data(), L, c, buff, genome_pos, rec_hits);
+            ctx->stats.n_chain_pairs++;
+            ctx->stats.chain_windows += std::max<int64_t>(L - W, 1);
+            chain_ms += now_ms() - t1;
+        }
+        ctx->hits.insert(ctx->hits.end(), rec_hits.begin(), rec_hits.end());
+        genome_pos += L;                                               // :92
+    }
+    ctx->stats.chain_ms = chain_ms;
+    ctx->stats.n_tie_flagged = 0;
+    for (const kgma_dip &dd : ctx->dips) ctx->stats.n_tie_flagged += (dd.flags & KGMA_HIT_TIE) ? 1 : 0;
+    ctx->stats.replay_ms = now_ms() - t0 - chain_ms;
+    return KGMA_OK;
+}
+
+}  // namespace
+
+int kgma_strobe_scan(kgma_ctx *ctx, const kgma_genome *g, int64_t buff, uint32_t flags, const uint8_t *consensus, int64_t consensus_len,
+                     int32_t gap_open_score, int32_t gap_extend_score, int64_t score_threshold)
+{
+    if (!ctx || !g) return KGMA_E_ARG;
+    if (buff < 0) return fail(ctx, KGMA_E_ARG, "buff < 0");
+    if (consensus && (consensus_len < 0 || consensus_len > KGMA_ALIGN_MAX_CONSENSUS))
+        return fail(ctx, KGMA_E_UNSUPPORTED, "consensus: %lld residues", (long long)consensus_len);
+    ctx->aligns.clear();
+    ctx->n_align_device = ctx->n_align_host = 0;
+    int rc = kgma_scan_device(ctx, g, KGMA_MODE_STROBE, flags);
+    if (rc) return rc;
+    rc = strobe_candidates(ctx, g, buff, flags);
+    if (rc) return rc;
+    const int64_t nh = (int64_t)ctx->hits.size();
+    if (consensus && nh > 0) {
+        // process_hit! (Alignment.jl:91-106): pairalign against consensus[1:windowsize], the score gate, cigar_to_UnitRange
+        const int64_t cl = std::min<int64_t>(consensus_len, ctx->kfv[0].W);
+        if (cl < 1) return fail(ctx, KGMA_E_UNSUPPORTED, "the consensus is empty and %lld candidates are to be aligned against it", (long long)nh);
+        std::vector<int32_t> hc;
+        std::vector<int64_t> lo, hi, which, first((size_t)nh), last((size_t)nh), score((size_t)nh);
+        int64_t n_host = 0;
+        for (int64_t i = 0; i < nh; i++) {
+            const kgma_hit &h = ctx->hits[(size_t)i];
+            const int64_t n = h.hi - h.lo + 1;
+            if (n >= 1 && n <= KGMA_ALIGN_MAX_SEGMENT) { hc.push_back(h.contig); lo.push_back(h.lo); hi.push_back(h.hi); which.push_back(i); continue; }
+            // (segments beyond the device aligner's rows: the host restatement)
+            std::vector<uint8_t> seg((size_t)std::max<int64_t>(n, 1));
+            std::vector<char> cig((size_t)(2 * (cl + std::max<int64_t>(n, 0)) + 16));
+            int64_t sc = 0, f1 = 1, l1 = n;
+            if (n < 1 || hipMemcpy(seg.data(), g->d_ascii + g->cd[(size_t)h.contig].ascii_off + (h.lo - 1), (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+                kgma_host_semiglobal_cigar(consensus, cl, seg.data(), n, gap_open_score, gap_extend_score, cig.data(), (int64_t)cig.size(), &sc) != KGMA_OK)
+                return fail(ctx, KGMA_E_HIP, "host alignment of candidate %lld failed", (long long)i);
+            cigar_range(cig.data(), &f1, &l1);
+            first[(size_t)i] = f1; last[(size_t)i] = l1; score[(size_t)i] = sc;
+            n_host++;
+        }
+        if (!which.empty()) {
+            std::vector<int64_t> f2(which.size()), l2(which.size()), s2(which.size());
+            rc = kgma_align_hits_device(ctx, g, consensus, cl, gap_open_score, gap_extend_score, (int64_t)which.size(), hc.data(), lo.data(), hi.data(),
+                                        f2.data(), l2.data(), s2.data());
+            if (rc) return rc;
+            for (size_t u = 0; u < which.size(); u++) { first[(size_t)which[u]] = f2[u]; last[(size_t)which[u]] = l2[u]; score[(size_t)which[u]] = s2[u]; }
+        }
+        ctx->n_align_host = n_host;
+        ctx->n_align_device = nh - n_host;
+        std::vector<kgma_hit> kept;
+        for (int64_t i = 0; i < nh; i++) {
+            kgma_hit h = ctx->hits[(size_t)i];
+            if (score[(size_t)i] < score_threshold) continue;          // Alignment.jl:96-98
+            const int64_t L = ctx->contig_len[(size_t)h.contig];
+            ctx->aligns.push_back(kgma_alignment{h.contig, 0, h.lo, h.hi, first[(size_t)i], last[(size_t)i]});
+            const int64_t l0 = h.lo;
+            h.lo = std::max<int64_t>(1, l0 + first[(size_t)i] - 1);
+            h.hi = std::min<int64_t>(l0 + last[(size_t)i] - 1, L);
+            kept.push_back(h);
+        }
+        ctx->hits.swap(kept);
+    }
+    ctx->stats.n_hits = (int64_t)ctx->hits.size();
+    return KGMA_OK;
+}
+
 int kgma_get_alignments(kgma_ctx *ctx, kgma_alignment *out, int64_t cap, int64_t *n, int64_t *n_device, int64_t *n_host)
 {
     if (!ctx || !n) return KGMA_E_ARG;
@@ -4421,6 +4756,7 @@ int kgma_replay_dips(kgma_ctx *ctx, int32_t mode, int64_t buff, int64_t genome_p
                      const int64_t *record_len, const int64_t *first_D, const kgma_dip *dips, const int64_t *dip_last_min,
                      int64_t n_dips, kgma_align_fn align, void *align_user)
 {
+    if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || n_records < 0 || n_dips < 0 || (n_records && (!record_len || !first_D)) || (n_dips && (!dips || !dip_last_min)))
         return KGMA_E_ARG;
     if (ctx->m == 0) return fail(ctx, KGMA_E_STATE, "kgma_set_refs has not been called");
@@ -4510,6 +4846,7 @@ int kgma_set_att(kgma_ctx *ctx, const int32_t *contig, const int32_t *kfv, const
 int kgma_chain_export(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32_t kfv, int64_t last_window, const int64_t *win_lo,
                       const int64_t *win_hi, int64_t n_intervals, int64_t *n_streams, int64_t *n_chunks, int64_t *pool_units, double *first)
 {
+    if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || !g || !n_streams || !n_chunks || !pool_units || !first || n_intervals < 0 || (n_intervals && (!win_lo || !win_hi))) return KGMA_E_ARG;
     if (ctx->m == 0) return fail(ctx, KGMA_E_STATE, "kgma_set_refs has not been called");
     if (kfv < 1 || kfv > ctx->m || contig < 0 || contig >= g->n_contigs) return fail(ctx, KGMA_E_ARG, "no such record / KFV");

@@ -201,6 +201,24 @@ constexpr int KGMA_WIDE_LDS_MAX_NK = 2048;
 constexpr int KGMA_WIDE_LDS_NK_CAP = 8192 - 64 - 1024 - 512;   // ... the most an LDS table can serve: 8192 entries, 128 KiB (one wave per CU)
 constexpr uint32_t KGMA_SP_EMPTY = 0xFFFFFFFFu;
 
+// Parameters of one launch of the strobemer kernel (kgma_strobe.hip): the integer form of the generic kernel with a randstrobe
+// bin (4^(2s) of them) in the place of the k-mer.  nk is the number of strobemers that slide (W - k); every window holds one more,
+// the record's strobemer W - k + 1, which never leaves (StrobeGenomeMiner.jl:50-57 re-enters the window's own last strobemer).
+struct StrobeParams {
+    int32_t s, w_min, w_max;             // randstrobe parameters (Strobemers.jl:45-65); k = w_max + s - 1 <= 16 residues per strobemer
+    int32_t nk;                          // strobemers that slide per window: W - k
+    int32_t N;                           // reference count
+    int32_t kfv_id;                      // 1-based KFV index reported in records (1)
+    int32_t n_slots;                     // wave slots of the launch
+    int32_t pad;
+    int64_t T, T_hi, sumS2;              // as GenParams
+    double inv_scale;                    // 2 k N^2
+    const int32_t *S;                    // the KFV's S table, 4^(2s) entries, natural bin order (first * 4^s + second)
+    uint32_t zero[4];                    // bit v: v % q == 0, for the sums of two s-mer values (< 2 * 4^s <= 128)
+};
+constexpr int KGMA_STROBE_MAX_S = 3;                           // 4^(2s) 16-bit counters per wave and the S table fit the LDS; sums fit `zero`
+constexpr int KGMA_STROBE_MAX_K = 16;                          // a strobemer's residues are one dword of the 2-bit genome copy
+
 // Count-table stream kernel (kgma_stream.hip): one wave per stream of consecutive window starts.
 constexpr int KGMA_STREAM_MIN_WINDOWS = 2048;                  // shorter streams waste their warm-up (n k-mers)
 constexpr int KGMA_STREAM_MAX_WINDOWS = 1 << 19;               // longer genomes take more rounds (100 Gb, one KFV: 24 rounds of 509 k windows

@@ -37,6 +37,7 @@ end
 
 const KGMA_MODE_SINGLE = Int32(0)
 const KGMA_MODE_OMN = Int32(1)
+const KGMA_MODE_STROBE = Int32(2)
 const KGMA_F_RETURN_DISTS = UInt32(1)
 const KGMA_F_CHAIN_REPLAY = UInt32(4)   # ties decided by the reference's running Float64 distance (kgma.h)
 const KGMA_E_BADBASE = 4
@@ -327,6 +328,73 @@ function Omn_KmerGMA!(; genome_path::String, refVecs::Vector{Vector{Float64}}, w
     return nothing
 end
 
-export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, Context
+struct KgmaAlignment
+    contig::Int32
+    kfv::Int32
+    lo::Int64
+    hi::Int64
+    first::Int64
+    last::Int64
+end
+
+"""
+    StrobeGMA!(; kwargs...)   -- same keywords as KmerGMA.StrobeGMA! (src/StrobemerGMA/StrobeGenomeMiner.jl:5-24)
+plus `n_refs` and `float_chain`.  The scan, the re-alignment of process_hit! (src/Alignment.jl:83-111: EDNAFULL with the gap
+scores of `score_model`) and its `score_threshold` gate run on the device (kgma_set_strobe_ref + kgma_strobe_scan); with
+`do_return_align` the kept candidates are aligned once more on the host, only to hand BioAlignments objects back.
+"""
+function StrobeGMA!(; genome_path::String, refVec, consensus_refseq::KmerGMA.Seq,
+    s::Int = 2, w_min::Int = 3, w_max::Int = 5, q::Int = 5, windowsize::Int64 = 289,
+    thr::Union{Int64, Float64} = 33.5, ScaleFactor::Float64 = 0.166666666666666666666666666667, buff::Int64 = 50,
+    do_align::Bool = true,
+    score_model::AffineGapScoreModel{Int64} = AffineGapScoreModel(EDNAFULL, gap_open = -69, gap_extend = -5),
+    score_threshold::Int = 0, do_return_dists::Bool = false, do_return_align::Bool = false, get_hit_loci::Bool = false,
+    dist_vec = Float64[], result_align_vec = [], hit_loci_vec = Int[], genome_pos::Int = 0,
+    resultVec::Vector{FASTA.Record} = FASTA.Record[], n_refs::Union{Nothing, Int} = nothing,
+    float_chain::Bool = true, ctx::Context = default_context())
+
+    genome_pos == 0 || error("StrobeGMA! starts genome_pos at 0 (StrobeGenomeMiner.jl:147)")
+    check(ctx, ccall((:kgma_set_strobe_ref, libkgma), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Ptr{Float64}, Int64, Float64, Int64),
+        ctx.h, s, w_min, w_max, q, collect(Float64, refVec), windowsize, Float64(thr), n_refs === nothing ? 0 : n_refs))
+    g = genome_from_fasta(ctx, genome_path)
+    try
+        cons = do_align ? Vector{UInt8}(string(consensus_refseq)) : UInt8[]
+        check(ctx, ccall((:kgma_strobe_scan, libkgma), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Int64, UInt32, Ptr{UInt8}, Int64, Int32, Int32, Int64),
+            ctx.h, g.h, buff, scan_flags(do_return_dists, float_chain), do_align ? pointer(cons) : C_NULL, length(cons),
+            score_model.gap_open, score_model.gap_extend, score_threshold))
+        hits = fetch_hits(ctx)
+        bodies = hit_bodies(g, hits)
+        for (h, body) in zip(hits, bodies)
+            seq_UnitRange = Int(h.lo):Int(h.hi)
+            header = identifier(g, h.contig) *                         # append_hit! (src/Alignment.jl:69-80), do_overlap = false
+                " | dist = " * string(round(h.dist, digits = 2)) *
+                " | MatchPos = $seq_UnitRange" *
+                " | GenomePos = $(h.genome_pos)" *
+                " | Len = " * string(last(seq_UnitRange) - first(seq_UnitRange) + 1)
+            push!(resultVec, FASTA.Record(header, body))
+            get_hit_loci && push!(hit_loci_vec, h.lo + h.genome_pos)
+        end
+        if do_align && do_return_align
+            n = Ref{Int64}(0)
+            check(ctx, ccall((:kgma_get_alignments, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaAlignment}, Int64, Ref{Int64}, Ptr{Int64}, Ptr{Int64}),
+                             ctx.h, C_NULL, 0, n, C_NULL, C_NULL))
+            al = Vector{KgmaAlignment}(undef, n[])
+            check(ctx, ccall((:kgma_get_alignments, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaAlignment}, Int64, Ref{Int64}, Ptr{Int64}, Ptr{Int64}),
+                             ctx.h, al, n[], n, C_NULL, C_NULL))
+            for a in al
+                push!(result_align_vec, pairalign(SemiGlobalAlignment(), view(consensus_refseq, 1:windowsize),
+                                                  subseq(g, a.contig, a.lo, a.hi), score_model))
+            end
+        end
+        do_return_dists && fetch_dists!(ctx, 1, dist_vec)
+    finally
+        free!(g)
+    end
+    return nothing
+end
+
+export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, Context
 
 end # module

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("KGMA_LIB") or os.path.join(_PKG_DIR, "libkgma.so")
 KGMA_OK = 0
 KGMA_E_ARG, KGMA_E_NODEVICE, KGMA_E_HIP, KGMA_E_BADBASE, KGMA_E_BOUNDS = 1, 2, 3, 4, 5
 KGMA_E_UNSUPPORTED, KGMA_E_OVERFLOW, KGMA_E_NOMEM, KGMA_E_STATE = 6, 7, 8, 9
-MODE_SINGLE, MODE_OMN = 0, 1
+MODE_SINGLE, MODE_OMN, MODE_STROBE = 0, 1, 2
 F_RETURN_DISTS, F_NO_TIE_RESOLVE, F_CHAIN_REPLAY = 1, 2, 4
 HIT_TIE, HIT_AT_THRESHOLD, HIT_TIE_RESOLVED, HIT_CHAIN = 1, 2, 4, 8
 
@@ -34,6 +34,7 @@ EXPORTS = [
     "kgma_scan_aligned", "kgma_get_alignments", "kgma_set_residue_source", "kgma_host_chain_values",
     "kgma_chain_values", "kgma_host_chain_walk", "kgma_chain_chunk_steps", "kgma_set_chain_source", "kgma_get_att", "kgma_set_att",
     "kgma_chain_export", "kgma_chain_export_copy", "kgma_kfv_scale", "kgma_kfv_is_float",
+    "kgma_set_strobe_ref", "kgma_strobe_scan",
 ]
 
 
@@ -118,6 +119,8 @@ def load():
     L.kgma_set_refs.argtypes = [vp, i32, i32, P(dbl), P(i64), P(dbl), P(i64)]
     L.kgma_set_refs_sparse.argtypes = [vp, i32, i32, P(i64), P(C.c_uint32), P(dbl), P(i64), P(dbl), P(i64)]
     L.kgma_set_thresholds.argtypes = [vp, P(dbl)]
+    L.kgma_set_strobe_ref.argtypes = [vp, i32, i32, i32, i64, P(dbl), i64, dbl, i64]
+    L.kgma_strobe_scan.argtypes = [vp, vp, i64, u32, C.c_char_p, i64, i32, i32, i64]
     L.kgma_genome_from_host.argtypes = [vp, P(C.c_char_p), P(i64), i64, P(vp)]
     L.kgma_genome_from_fasta.argtypes = [vp, vp, i64, P(vp)]
     L.kgma_genome_from_fasta_file.argtypes = [vp, C.c_char_p, P(vp)]
@@ -383,6 +386,26 @@ class Context:
                                                 None if nr is None else _np_ptr(nr, C.c_int64)))
         self.k, self.m = k, m
         self.ws = [int(w) for w in ws]
+
+    def set_strobe_ref(self, s: int, w_min: int, w_max: int, q: int, ref: np.ndarray, windowsize: int, thr: float,
+                       n_refs: Optional[int] = None) -> None:
+        """kgma_set_strobe_ref: the strobemer method's reference (4^(2s) bins, natural bin order); replaces the context's
+        references.  n_refs=None: N is inferred from the entries."""
+        R = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).ravel())
+        if not 1 <= int(s) <= 7 or R.size != 4 ** (2 * int(s)):
+            raise ValueError(f"KFV length {R.size} != 4^(2*{s})")
+        self._check(load().kgma_set_strobe_ref(self._h, int(s), int(w_min), int(w_max), int(q), _np_ptr(R, C.c_double),
+                                               int(windowsize), float(thr), 0 if n_refs is None else int(n_refs)))
+        self.k, self.m = int(w_max) + int(s) - 1, 1
+        self.ws = [int(windowsize)]
+
+    def strobe_scan(self, genome: Genome, buff: int = 50, flags: int = 0, consensus: Optional[bytes] = None,
+                    gap_open: int = -69, gap_extend: int = -5, score_threshold: int = 0) -> None:
+        """kgma_strobe_scan: StrobeGMA! over every record; consensus=None is do_align = false, otherwise the candidates are
+        aligned on the device and those scoring below score_threshold dropped (process_hit!)."""
+        cons = None if consensus is None else bytes(consensus)
+        self._check(load().kgma_strobe_scan(self._h, genome._h, int(buff), int(flags), cons, 0 if cons is None else len(cons),
+                                            int(gap_open), int(gap_extend), int(score_threshold)))
 
     def set_thresholds(self, thr: Sequence[float]) -> None:
         th = np.asarray(list(thr)[:self.m], dtype=np.float64)

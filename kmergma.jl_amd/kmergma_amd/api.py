@@ -8,6 +8,8 @@ Same names, keyword arguments, mutation-of-caller-vectors behaviour and error be
     findGenes              src/API.jl:60-104
     findGenes_cluster_mode src/API.jl:161-226
     write_results          src/API.jl:234-241
+    StrobeGMA!             src/StrobemerGMA/StrobeGenomeMiner.jl:5-95
+    Strobemer_findGenes    src/StrobemerGMA/StrobeGenomeMiner.jl:119-158
 
 but the per-record scan runs on the MI355X through libkgma's C ABI (include/kgma.h).  The host
 keeps what the reference keeps on the host: FASTA parsing, reference preparation, optional
@@ -339,6 +341,75 @@ def findGenes_cluster_mode(*, genome_path: str, ref_path: str, cluster_cutoffs=(
     if verbose:
         log.info(info)
         log.info("To write the results, use `KmerGMA.write_results`")
+    return out
+
+
+def StrobeGMA(*, genome_path, refVec, consensus_refseq: bytes = b"", s: int = 2, w_min: int = 3, w_max: int = 5, q: int = 5,
+              windowsize: int = 289, thr: float = 33.5, ScaleFactor=None, buff: int = 50, do_align: bool = True,
+              gap_open_score: int = -69, gap_extend_score: int = -5, score_threshold: int = 0,
+              do_return_dists: bool = False, do_return_align: bool = False, get_hit_loci: bool = False,
+              dist_vec: Optional[list] = None, result_align_vec: Optional[list] = None, hit_loci_vec: Optional[list] = None,
+              resultVec: Optional[list] = None, n_refs: Optional[int] = None, ctx: Optional["_lib.Context"] = None,
+              float_chain: bool = True) -> None:
+    """`StrobeGMA!` (src/StrobemerGMA/StrobeGenomeMiner.jl:5-95): mutates resultVec / hit_loci_vec / dist_vec /
+    result_align_vec.  The scan, the re-alignment of process_hit! (src/Alignment.jl:83-111; the reference's score model
+    defaults to gap_open = -69, gap_extend = -5) and its score gate run on the device (kgma_strobe_scan).
+    float_chain (default on): KGMA_F_CHAIN_REPLAY -- records whose decisions hang on the rounding of the reference's
+    running Float64 distance are decided by a host replay of that loop (kgma.h)."""
+    k = int(w_max) + int(s) - 1
+    if ScaleFactor is not None and abs(float(ScaleFactor) - 1.0 / k) > 1e-12:
+        raise ValueError(f"ScaleFactor = {ScaleFactor} is not 1/(w_max + s - 1) = 1/{k}")
+    resultVec = resultVec if resultVec is not None else []
+    ctx = ctx or default_context()
+    ctx.set_strobe_ref(s, w_min, w_max, q, np.asarray(refVec, dtype=np.float64), int(windowsize), float(thr), n_refs)
+    view = _GenomeView(ctx, genome_path)
+    try:
+        flags = (_lib.F_RETURN_DISTS if do_return_dists else 0) | (_lib.F_CHAIN_REPLAY if float_chain else 0)
+        ctx.strobe_scan(view.genome, int(buff), flags, bytes(consensus_refseq) if do_align else None,
+                        gap_open_score, gap_extend_score, int(score_threshold))
+        if do_align and do_return_align and result_align_vec is not None:
+            result_align_vec.extend((a["contig"], 0, a["lo"], a["hi"], a["first"], a["last"]) for a in ctx.alignments()[0])
+        hits = ctx.hits()
+        bodies = view.subseqs((h["contig"], h["lo"], h["hi"]) for h in hits)
+        for h, body in zip(hits, bodies):
+            hdr = headers.single_header(view.identifier(h["contig"]), h["dist"], h["lo"], h["hi"], h["genome_pos"])
+            resultVec.append(Record(hdr, body))
+            if get_hit_loci and hit_loci_vec is not None:
+                hit_loci_vec.append(h["lo"] + h["genome_pos"])
+        if do_return_dists and dist_vec is not None:
+            dist_vec.extend(ctx.dists(1).tolist())
+    finally:
+        view.free()
+
+
+def Strobemer_findGenes(*, genome_path: str, ref_path: str, s: int = 2, w_min: int = 3, w_max: int = 5, q: int = 5,
+                        KmerDistThr=30, buffer: int = 50, do_align: bool = True, align_score_thr: int = 0,
+                        do_return_dists: bool = False, do_return_hit_loci: bool = False, do_return_align: bool = False,
+                        verbose: bool = True, ctx=None, float_chain: bool = True) -> list:
+    """`Strobemer_findGenes` (src/StrobemerGMA/StrobeGenomeMiner.jl:119-158).  Returns [hits, (loci), (aligns), (dists)]."""
+    RV, windowsize, consensus_refseq, (_S, N) = refprep.gen_ref_ws_cons_strobe(ref_path, s, w_min, w_max, q, return_int=True)
+    hit_vector: list = []
+    dist_vec: list = []
+    hit_loci_vec: list = []
+    alignment_vec: list = []
+    if verbose:
+        log.info("initializing iteration...")
+    StrobeGMA(genome_path=genome_path, refVec=RV, consensus_refseq=consensus_refseq, s=s, w_min=w_min, w_max=w_max, q=q,
+              windowsize=windowsize, thr=KmerDistThr, ScaleFactor=1 / (w_max + s - 1), buff=buffer,
+              score_threshold=align_score_thr, do_align=do_align, do_return_dists=do_return_dists,
+              do_return_align=do_return_align, get_hit_loci=do_return_hit_loci, dist_vec=dist_vec,
+              result_align_vec=alignment_vec, hit_loci_vec=hit_loci_vec, resultVec=hit_vector, n_refs=N, ctx=ctx,
+              float_chain=float_chain)
+    info = "genome mining completed successfully, returning vector of: vector of hits"
+    out = [hit_vector]
+    if do_return_hit_loci:
+        out.append(hit_loci_vec); info += ", vector of hit locations"
+    if do_return_align:
+        out.append(alignment_vec); info += ", vector of alignments"
+    if do_return_dists:
+        out.append(dist_vec); info += ", vector of kmer distances along the genome"
+    if verbose:
+        log.info(info)
     return out
 
 

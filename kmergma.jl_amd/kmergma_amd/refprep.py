@@ -162,6 +162,90 @@ def gen_ref_ws_cons(reference_seqs, k: int, get_maxlen: bool = False, return_int
     return tuple(out)
 
 
+# ---- strobemer method (src/StrobemerGMA/Strobemers.jl, StrobeRefGen.jl) ----------------------------------------------
+
+def _check_strobe(s: int, w_min: int, w_max: int, q: int) -> None:
+    # where the reference throws or has no meaning: an empty s-mer, an offset before the sequence, an empty offset
+    # range (min_ind stays w_min, beyond the k = w_max + s - 1 residues), a modulus of 0 (DivideError) or below
+    if s < 1 or w_min < 1 or w_min > w_max or q < 1:
+        raise ValueError(f"invalid randstrobe parameters: s = {s}, w_min = {w_min}, w_max = {w_max}, q = {q}")
+
+
+def randstrobe_score(s1: bytes, s2: bytes, q: int) -> int:
+    """src/StrobemerGMA/Strobemers.jl:12-14."""
+    return (as_UInt(s1) + as_UInt(s2)) % q
+
+
+def _strobe_offset(seq: bytes, s: int, w_min: int, w_max: int, q: int) -> int:
+    # Strobemers.jl:51-60: `min_score::Int = 2 << 63` is 0 and the test is `<=`: the LAST offset whose score is 0
+    # wins, w_min if there is none
+    first = seq[:s]
+    min_score, min_ind = (2 << 63) & 0xFFFFFFFFFFFFFFFF, w_min
+    for i in range(w_min, w_max + 1):
+        score = randstrobe_score(first, seq[i - 1:i - 1 + s], q)
+        if score <= min_score:
+            min_score, min_ind = score, i
+    return min_ind
+
+
+def get_strobe_2_mer(seq: bytes, s: int = 2, w_min: int = 3, w_max: int = 5, q: int = 5, withGap: bool = True) -> bytes:
+    """src/StrobemerGMA/Strobemers.jl:45-65: the randstrobe of `seq` (its first w_max + s - 1 residues are read)."""
+    _check_strobe(s, w_min, w_max, q)
+    ind = _strobe_offset(seq, s, w_min, w_max, q)
+    first, second = seq[:s], seq[ind - 1:ind - 1 + s]
+    if not withGap:
+        return first + second
+    return first + b"-" * (ind - s - 1) + second + b"-" * (len(seq) - ind - s + 1)
+
+
+def strobe_indices(seq: bytes, s: int = 2, w_min: int = 3, w_max: int = 5, q: int = 5) -> np.ndarray:
+    """0-based bin (first * 4^s + second, natural values) of the randstrobe at every position with k = w_max + s - 1
+    residues left: what ungapped_strobe_2_mer_count! counts (Strobemers.jl:104-114)."""
+    _check_strobe(s, w_min, w_max, q)
+    k = w_max + s - 1
+    smers = kmer_indices(seq, s)
+    n = len(seq) - k + 1
+    if n <= 0:
+        return np.zeros(0, dtype=np.int64)
+    first = smers[:n]
+    chosen = np.full(n, w_min, dtype=np.int64)
+    for i in range(w_min, w_max + 1):
+        chosen[(first + smers[i - 1:i - 1 + n]) % q == 0] = i
+    return first * 4 ** s + smers[chosen - 1 + np.arange(n)]
+
+
+def ungapped_strobe_2_mer_count(seq: bytes, s: int = 2, w_min: int = 3, w_max: int = 5, q: int = 5) -> np.ndarray:
+    """src/StrobemerGMA/Strobemers.jl:90-102: Float64 histogram of length 4^(2s)."""
+    return np.bincount(strobe_indices(seq, s, w_min, w_max, q), minlength=4 ** (2 * s)).astype(np.float64)
+
+
+def gen_ref_ws_cons_strobe(reference_seqs, s: int = 2, w_min: int = 3, w_max: int = 5, q: int = 5,
+                           get_maxlen: bool = False, return_int: bool = False):
+    """The strobemer method of gen_ref_ws_cons (src/StrobemerGMA/StrobeRefGen.jl:4-43).
+
+    Returns (KFV, windowsize, consensus[, maxlen]); with return_int=True additionally (S:int64[4^(2s)], N) such that
+    KFV == S * (1/N) elementwise."""
+    _check_strobe(s, w_min, w_max, q)
+    recs = _records(reference_seqs)
+    answer = np.zeros(4 ** (2 * s), dtype=np.float64)
+    n, cumulative, maxlen = 0, 0, 0
+    prof = Profile(1)
+    for rec in recs:
+        n += 1
+        cumulative += len(rec.sequence)
+        maxlen = max(maxlen, len(rec.sequence))
+        answer += ungapped_strobe_2_mer_count(rec.sequence, s, w_min, w_max, q)
+        prof.lengthen(len(rec.sequence))
+        prof.add(rec.sequence)
+    inv = 1.0 / n
+    out = [answer * inv, _julia_round_int(cumulative * inv), prof.consensus()]
+    if get_maxlen:
+        out.append(maxlen)
+    if return_int:
+        out.append((answer.astype(np.int64), n))
+    return tuple(out)
+
+
 def get_cluster_index(inp, cutoffs: Sequence) -> int:
     """src/ReferenceGeneration.jl:50-57 (1-based)."""
     answer = 1

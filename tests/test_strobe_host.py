@@ -1,0 +1,124 @@
+"""Strobemer method without a GPU: the reference's own expected values (tests/golden/strobe.json) hold for the CPU oracle
+(tests/strobe_oracle.py) and for the refprep mirror, the "W - k sliding strobemers plus one permanent copy" identity the
+device formulation rests on holds by direct recount, and the reference preparation on the alpaca fixture is S/N bit for bit."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from tests import strobe_oracle as so
+from kmergma_amd import fasta, refprep
+
+from tests.conftest import DATA, GOLDEN
+
+PARAMS = [(2, 3, 5, 5), (3, 4, 7, 5), (1, 2, 4, 5), (2, 3, 5, 7), (2, 3, 5, 1)]
+
+
+@pytest.fixture(scope="module")
+def gold():
+    with open(os.path.join(GOLDEN, "strobe.json")) as fh:
+        return json.load(fh)
+
+
+def test_golden_randstrobe_score(gold):
+    for g in gold["randstrobe_score"]:
+        assert refprep.randstrobe_score(g["s1"].encode(), g["s2"].encode(), g["q"]) == g["value"]
+
+
+@pytest.mark.parametrize("impl", [so.get_strobe_2_mer, refprep.get_strobe_2_mer])
+def test_golden_get_strobe_2_mer(gold, impl):
+    for g in gold["get_strobe_2_mer"]:
+        assert impl(g["seq"].encode(), withGap=g["withGap"]) == g["value"].encode()
+    # (a true minimum over the offsets would give ATAT here; read literally no offset scores 0 and w_min is kept)
+    assert impl(b"ATGCATGC", withGap=False) != b"ATAT"
+
+
+@pytest.mark.parametrize("impl", [lambda *a: so.strobe_count(*a).astype(np.float64), refprep.ungapped_strobe_2_mer_count])
+def test_golden_count(gold, impl):
+    g = gold["ungapped_strobe_2_mer_count"]
+    counts = impl(g["seq"].encode(), g["s"], g["w_min"], g["w_max"], g["q"])
+    assert counts.size == 4 ** (2 * g["s"])
+    assert round(float(np.mean(counts)), 4) == g["mean_rounded_4"]
+    for idx, v in g["entries_1_based"].items():
+        assert counts[int(idx) - 1] == v
+
+
+@pytest.mark.parametrize("s,w_min,w_max,q", PARAMS)
+def test_bins_agree_with_per_position_definition(s, w_min, w_max, q):
+    rng = np.random.default_rng(7 + s + q)
+    seq = bytes(rng.choice(np.frombuffer(b"ACGTN", dtype=np.uint8), size=400, p=[.24, .24, .24, .24, .04]))
+    k = w_max + s - 1
+    a = so.strobe_bins(seq, s, w_min, w_max, q)
+    b = refprep.strobe_indices(seq, s, w_min, w_max, q)
+    c = [refprep.as_UInt(refprep.get_strobe_2_mer(seq[i:i + k], s, w_min, w_max, q, withGap=False)) for i in range(len(seq) - k + 1)]
+    assert a.tolist() == b.tolist() == c
+
+
+@pytest.mark.parametrize("s,w_min,w_max,q", PARAMS)
+def test_window_is_sliding_items_plus_permanent_copy(s, w_min, w_max, q):
+    """After step i the reference's count vector is the W - k strobemers starting at i+1 .. i+W-k (1-based) plus one copy of
+    the record's strobemer W-k+1 -- for every step of a record, the last one included."""
+    rng = np.random.default_rng(11)
+    W = 67
+    k = w_max + s - 1
+    seq = bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=700)])
+    bins = so.strobe_bins(seq, s, w_min, w_max, q)
+    NB = 4 ** (2 * s)
+    L = len(seq)
+    for i in list(range(0, 80)) + [L - W - 2, L - W - 1]:
+        direct = so.window_counts_direct(seq, s, w_min, w_max, q, W, i)
+        want = np.bincount(bins[i:i + W - k], minlength=NB)          # 0-based items i .. i+W-k-1 = strobemers i+1 .. i+W-k
+        want[bins[W - k]] += 1                                       # the permanent copy: strobemer W-k+1
+        assert direct.tolist() == want.tolist(), i
+
+
+def test_gen_ref_on_alpaca_fixture():
+    path = os.path.join(DATA, "Alp_V_ref.fasta")
+    RV, W, cons, (S, N) = refprep.gen_ref_ws_cons_strobe(path, 2, 3, 5, 5, return_int=True)
+    assert N == 84 and W == 289 and RV.size == 256 and len(cons) >= W
+    assert np.array_equal(RV, S.astype(np.float64) * (1.0 / N))      # S/N bit for bit
+    seqs = [r.sequence for r in fasta.read_fasta(path)]
+    oRV, oW, oS, oN = so.gen_ref(seqs, 2, 3, 5, 5)
+    assert oN == N and oW == W and np.array_equal(oS, S) and np.array_equal(oRV, RV)
+    # the k-mer method builds the same consensus
+    assert cons == refprep.gen_ref_ws_cons(path, 6)[2]
+    assert refprep.gen_ref_ws_cons_strobe(path, 2, 3, 5, 5, get_maxlen=True)[3] == max(len(x) for x in seqs)
+
+
+def test_oracles_agree_on_a_planted_record():
+    """exact and float results of the oracle agree where no decision hangs on rounding; the first dip a window
+    that overlaps the plant opens pre-empts the later ones for a window's length (goal_ind), so the hit lies within W of it."""
+    path = os.path.join(DATA, "Alp_V_ref.fasta")
+    RV, W, cons, (S, N) = refprep.gen_ref_ws_cons_strobe(path, 2, 3, 5, 5, return_int=True)
+    rng = np.random.default_rng(3)
+    gene = fasta.read_fasta(path)[0].sequence.upper()
+    a = bytearray(np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=6000)].tobytes())
+    a[2000:2000 + len(gene)] = gene
+    r = so.scan([bytes(a), b"ACGT" * 10], RV, S, N, 2, 3, 5, 5, W, 30.0, 50, return_dists=True)
+    key = lambda h: (h["contig"], h["cmi"], h["lo"], h["hi"], h["genome_pos"], h["D"])
+    assert [key(h) for h in r["exact"]] == [key(h) for h in r["float"]]
+    assert len(r["exact"]) >= 1 and any(abs(h["cmi"] - 2001) <= W for h in r["exact"])
+    assert r["first_D"][1] == -1 and len(r["dists_exact"]) == 6000 - W - 1
+    scale = 2 * 6 * N * N
+    rel = max(abs(f - e / scale) / (e / scale) for e, f in zip(r["dists_exact"], r["dists_float"]))
+    assert rel < 1e-11
+
+
+@pytest.mark.parametrize("kw", [dict(s=0), dict(w_min=0), dict(w_min=6, w_max=5), dict(q=0), dict(q=-3)])
+def test_argument_errors(kw):
+    args = dict(s=2, w_min=3, w_max=5, q=5)
+    args.update(kw)
+    with pytest.raises(ValueError):
+        refprep.get_strobe_2_mer(b"ACGTACGTACGT", **args)
+    with pytest.raises(ValueError):
+        refprep.ungapped_strobe_2_mer_count(b"ACGTACGTACGT", **args)
+    with pytest.raises(ValueError):
+        so.strobe_bins(b"ACGTACGTACGT", args["s"], args["w_min"], args["w_max"], args["q"])
+
+
+def test_bad_residue_is_a_key_error():
+    with pytest.raises(KeyError):
+        refprep.ungapped_strobe_2_mer_count(b"ACGTACXTACGTAC")
+    with pytest.raises(KeyError):
+        so.strobe_bins(b"ACGTACXTACGTAC", 2, 3, 5, 5)
