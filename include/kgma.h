@@ -478,6 +478,33 @@ int kgma_set_strobe_ref(kgma_ctx *ctx, int32_t s, int32_t w_min, int32_t w_max, 
 int kgma_strobe_scan(kgma_ctx *ctx, const kgma_genome *g, int64_t buff, uint32_t flags, const uint8_t *consensus, int64_t consensus_len,
                      int32_t gap_open_score, int32_t gap_extend_score, int64_t score_threshold);
 
+/* ---- exact sequence search: exactMatch (src/ExactMatch.jl:89-121) ------------------------------------------------------------------
+ * Every occurrence of every query in every record of `g`.  queries[offsets[i] .. offsets[i+1]) is query i: DNA symbols, either
+ * case.  Comparison is symbol equality after case folding -- BioSequences' ExactSearchQuery with isequal on DNAAlphabet{4}
+ * (convert_to_search_query, src/ExactMatch.jl:46-58): N matches only N, each of M R W S Y K V H D B and '-' only itself; a genome N
+ * does NOT match a query T, although the scans' 2-bit code stores N as T.  A match of a query of length m at 1-based start s covers
+ * s : s+m-1 and lies inside one record; a query longer than a record has no match there.  overlap != 0: every occurrence
+ * (FindAllOverlap, src/ExactMatch.jl:33-43); overlap == 0: the leftmost occurrence, then the leftmost one starting behind its end,
+ * and so on (FindAll, src/ExactMatch.jl:20-30).  All queries are served in one pass over the genome: the number of kernel launches
+ * does not depend on n_queries (queries of A/C/G/T only are filtered on the 2-bit copy of the genome and verified against the
+ * residue text, the others -- and every query when a record holds a symbol outside A/C/G/T/N, or under the testing switch
+ * KGMA_EXACT_ASCII=1 -- are compared on the residue text: at most one launch of each kind, repeated once when the matches outgrow
+ * the device buffer; KGMA_E_OVERFLOW if they do so again).
+ * KGMA_E_ARG: an empty query, or a query symbol outside the 16-symbol alphabet.  KGMA_E_BADBASE: a genome residue outside it, in any
+ * record (the reference decodes every record before it searches, getSeq at src/ExactMatch.jl:109); kgma_last_error names the first
+ * such record and position.
+ * The call needs no references and leaves the KFVs and the hits, dips and distances of the last scan as they are; of kgma_stats it
+ * sets bases_scanned, scan_ms (hipEvents around the launches) and n_launches.  kgma_get_matches returns the matches of the last
+ * call sorted by (query, contig, start), with the two-call pattern of kgma_get_hits. */
+typedef struct {
+    int32_t query;       /* 0-based index of the query                                         */
+    int32_t contig;      /* 0-based index of the record                                        */
+    int64_t start;       /* 1-based position of the match's first symbol                       */
+} kgma_match;
+int kgma_exact_match(kgma_ctx *ctx, const kgma_genome *g, const uint8_t *queries, const int64_t *offsets /* n_queries + 1 */,
+                     int32_t n_queries, int32_t overlap);
+int kgma_get_matches(kgma_ctx *ctx, kgma_match *out, int64_t cap, int64_t *n);
+
 /* kgma_repack_scan_hits in two halves, for step loops that have other work to queue while the GPU scans
  * (bench.py with several ranks: the hit exchange of step i overlaps the scan of step i+1).  kgma_step_begin
  * hands the step to a helper thread owned by the context and returns at once; kgma_step_end waits for it

@@ -79,6 +79,8 @@ hipError_t launch_fasta_scatter(const uint8_t *raw, int64_t n, const int64_t *bl
                                 const ContigDesc *cd, int n_rec, uint8_t *ascii, hipStream_t st);
 int scan_tile_stride_words(int nk);
 int scan_nblocks(int nk);
+int64_t exact_tile_starts(bool two_bit);
+hipError_t launch_exact(const ExactArgs &a, int kind, int64_t n_tiles, hipStream_t st);
 int kdist_grid(int k, int64_t n_seqs);
 hipError_t launch_kdist(int mode, const uint8_t *seqs, const int64_t *off, int64_t n_seqs, int k, const double *ref,
                         uint32_t *scratch, double scale, double *out, unsigned long long *first_bad, hipStream_t st);
@@ -341,6 +343,13 @@ struct kgma_ctx {
     std::vector<ChainStream> cx_streams; std::vector<ChainChunk> cx_chunks, cx_pool; double cx_first = 0;
     std::vector<kgma_alignment> aligns;      // alignments the hit state machine consumed (kgma_scan_aligned), in order
     int64_t n_align_device = 0, n_align_host = 0;
+    // exact search (kgma_exact_match): device buffers kept between calls, and the matches of the last call
+    ExactQuery *d_xq = nullptr; int64_t xq_cap = 0;
+    uint8_t *d_xtext = nullptr; int64_t xtext_cap = 0;
+    int64_t *d_xprefix = nullptr; int64_t xprefix_cap = 0;
+    ExactMatch *d_xout = nullptr; int64_t xout_cap = 0;
+    unsigned long long *d_xctl = nullptr; int64_t xctl_cap = 0;
+    std::vector<kgma_match> matches;
     std::vector<int64_t> contig_len;
     int64_t n_dists_per_kfv = 0;
     int64_t tile_windows = KGMA_TILE_WINDOWS;
@@ -760,6 +769,11 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->h_cpin) (void)hipHostFree(ctx->h_cpin);
     if (ctx->h_cpin2) (void)hipHostFree(ctx->h_cpin2);
     if (ctx->d_gath) (void)hipFree(ctx->d_gath);
+    if (ctx->d_xq) (void)hipFree(ctx->d_xq);
+    if (ctx->d_xtext) (void)hipFree(ctx->d_xtext);
+    if (ctx->d_xprefix) (void)hipFree(ctx->d_xprefix);
+    if (ctx->d_xout) (void)hipFree(ctx->d_xout);
+    if (ctx->d_xctl) (void)hipFree(ctx->d_xctl);
     if (ctx->evp0) (void)hipEventDestroy(ctx->evp0);
     if (ctx->evp1) (void)hipEventDestroy(ctx->evp1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -4889,6 +4903,168 @@ int kgma_chain_export_copy(kgma_ctx *ctx, int64_t *win0, int32_t *n_valid, int64
     }
     if (!ctx->cx_chunks.empty()) memcpy(chunks, ctx->cx_chunks.data(), ctx->cx_chunks.size() * sizeof(ChainChunk));
     if (pool && !ctx->cx_pool.empty()) memcpy(pool, ctx->cx_pool.data(), ctx->cx_pool.size() * sizeof(ChainChunk));
+    return KGMA_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// exact sequence search (exactMatch, src/ExactMatch.jl:89-121; kernels: kgma_exact.hip)
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(kgma_match) == sizeof(ExactMatch), "kgma_match is the device record");
+
+// the 16 symbols of DNAAlphabet{4}, either case
+static bool exact_symbol(uint8_t ch)
+{
+    static const char sym[] = "ACGTMRWSYKVHDBN";
+    if (ch == '-') return true;
+    const uint8_t u = (uint8_t)(ch & 0xDFu);
+    return u >= 'A' && u <= 'Z' && strchr(sym, (int)u) != nullptr;
+}
+
+// One launch over the whole genome for the queries `qs` (kind: kgma_exact.hip, launch_exact); appends the matches to `found`.
+// A launch whose matches do not fit the device buffer is repeated once with a buffer of the size it counted.
+static int exact_launch(kgma_ctx *ctx, const kgma_genome *g, int kind, const std::vector<ExactQuery> &qs, std::vector<kgma_match> &found,
+                        unsigned long long *bad_out, int *n_launches)
+{
+    const int64_t nc = g->n_contigs;
+    const int64_t per_tile = exact_tile_starts(kind == 2);
+    std::vector<int64_t> prefix((size_t)nc + 1, 0);
+    for (int64_t c = 0; c < nc; c++) prefix[(size_t)c + 1] = prefix[(size_t)c] + (g->cd[(size_t)c].len + per_tile - 1) / per_tile;
+    const int64_t n_tiles = prefix[(size_t)nc];
+    if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_exact_match: %lld tiles exceed one launch", (long long)n_tiles);
+    int rc;
+    if ((rc = dev_reserve(ctx, ctx->d_xq, ctx->xq_cap, (int64_t)qs.size()))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_xprefix, ctx->xprefix_cap, nc + 1))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_xctl, ctx->xctl_cap, 2))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_xout, ctx->xout_cap, (int64_t)1 << 16))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xq, qs.data(), qs.size() * sizeof(ExactQuery), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xprefix, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    unsigned long long ctl[2] = {0, 0};
+    for (int attempt = 0;; attempt++) {
+        ExactArgs a{};
+        a.ascii = g->d_ascii; a.inter = g->d_inter; a.cd = g->d_cd; a.tile_prefix = ctx->d_xprefix;
+        a.n_contigs = (int32_t)nc; a.n_queries = (int32_t)qs.size();
+        a.queries = ctx->d_xq; a.qtext = ctx->d_xtext; a.out = ctx->d_xout; a.ctl = ctx->d_xctl; a.cap = (unsigned long long)ctx->xout_cap;
+        const unsigned long long init[2] = {0ull, NO_BAD};
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xctl, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, launch_exact(a, kind, n_tiles, ctx->stream));
+        (*n_launches)++;
+        HIP_TRY(ctx, hipMemcpyAsync(ctl, ctx->d_xctl, sizeof ctl, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctl[1] != NO_BAD) { *bad_out = ctl[1]; return KGMA_OK; }     // (the caller reports it; the matches are not wanted)
+        if (ctl[0] <= (unsigned long long)ctx->xout_cap) break;
+        if (attempt == 1) return fail(ctx, KGMA_E_OVERFLOW, "kgma_exact_match: %llu matches overflowed the regrown buffer", ctl[0]);
+        if (ctl[0] > (1ull << 40)) return fail(ctx, KGMA_E_NOMEM, "kgma_exact_match: %llu matches", ctl[0]);
+        if ((rc = dev_reserve(ctx, ctx->d_xout, ctx->xout_cap, (int64_t)ctl[0]))) return rc;
+    }
+    const size_t n0 = found.size();
+    found.resize(n0 + (size_t)ctl[0]);
+    if (ctl[0]) HIP_TRY(ctx, hipMemcpy(found.data() + n0, ctx->d_xout, (size_t)ctl[0] * sizeof(kgma_match), hipMemcpyDeviceToHost));
+    return KGMA_OK;
+}
+
+int kgma_exact_match(kgma_ctx *ctx, const kgma_genome *gc, const uint8_t *queries, const int64_t *offsets, int32_t n_queries, int32_t overlap)
+{
+    if (!ctx || !gc) return KGMA_E_ARG;
+    if (n_queries < 0 || (n_queries > 0 && (!queries || !offsets))) return fail(ctx, KGMA_E_ARG, "kgma_exact_match: no queries");
+    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping is updated
+    std::vector<uint8_t> text;
+    std::vector<ExactQuery> q_ascii, q_2bit;
+    std::vector<int64_t> qlen((size_t)n_queries);
+    for (int32_t i = 0; i < n_queries; i++) {
+        const int64_t b = offsets[i], m = offsets[i + 1] - b;
+        if (m < 1) return fail(ctx, KGMA_E_ARG, "kgma_exact_match: query %d is empty", i);
+        qlen[(size_t)i] = m;
+        ExactQuery Q{};
+        Q.text_off = (int64_t)text.size(); Q.len = m; Q.id = i;
+        bool acgt = true;
+        for (int64_t j = 0; j < m; j++) {
+            const uint8_t ch = queries[b + j];
+            if (!exact_symbol(ch)) return fail(ctx, KGMA_E_ARG, "kgma_exact_match: query %d, symbol %lld (0x%02x) is outside the DNA alphabet", i, (long long)j + 1, ch);
+            const uint8_t u = (uint8_t)(ch & 0xDFu);
+            acgt = acgt && (u == 'A' || u == 'C' || u == 'G' || u == 'T');
+            text.push_back(u);
+        }
+        ExactQuery P = Q;      // the same query for the 2-bit kernel
+        for (int64_t j = 0; j < std::min<int64_t>(m, 8); j++) {
+            Q.pat[j >> 2] |= (uint32_t)text[(size_t)(Q.text_off + j)] << (8 * (j & 3));
+            Q.mask[j >> 2] |= 0xFFu << (8 * (j & 3));
+        }
+        if (acgt)
+            for (int64_t j = 0; j < std::min<int64_t>(m, 16); j++) {
+                const uint8_t u = text[(size_t)(Q.text_off + j)];
+                P.pat[0] |= (u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : 3u) << (2 * j);
+                P.mask[0] |= 3u << (2 * j);
+            }
+        q_ascii.push_back(Q);
+        if (acgt) q_2bit.push_back(P);
+        else { P.len = 0; q_2bit.push_back(P); }       // len 0: not a 2-bit query
+    }
+    (void)hipSetDevice(ctx->device);
+    // what the pack kernel knows about the residues (first_bad) and the 2-bit copy must be current: a pack that is deferred, or never
+    // queued since the text changed, runs now
+    if (g->repack_deferred || g->text_dirty) {
+        g->repack_deferred = false;
+        const int prc = kgma_genome_repack(ctx, g);
+        if (prc) return prc;
+    }
+    int rc = genome_sync(ctx, g);
+    if (rc) return rc;
+    bool clean = true;                       // no residue outside A/C/G/T/N anywhere: nothing to check, and the 2-bit copy is faithful up to N
+    for (int64_t c = 0; c < g->n_contigs; c++) clean = clean && g->first_bad[(size_t)c] == NO_BAD;
+    const char *sw = getenv("KGMA_EXACT_ASCII");     // testing only: every query through the residue-text kernel
+    const bool allow_2bit = clean && !(sw && atoi(sw) != 0);
+    std::vector<ExactQuery> la, lb;
+    for (int32_t i = 0; i < n_queries; i++) {
+        if (allow_2bit && q_2bit[(size_t)i].len > 0) lb.push_back(q_2bit[(size_t)i]);
+        else la.push_back(q_ascii[(size_t)i]);
+    }
+    if ((rc = dev_reserve(ctx, ctx->d_xtext, ctx->xtext_cap, (int64_t)text.size() + 8))) return rc;
+    if (!text.empty()) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xtext, text.data(), text.size(), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<kgma_match> found;
+    unsigned long long bad = NO_BAD;
+    int n_launches = 0;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (!la.empty() && (rc = exact_launch(ctx, g, clean ? 0 : 1, la, found, &bad, &n_launches))) return rc;
+    if (bad == NO_BAD && !lb.empty() && (rc = exact_launch(ctx, g, 2, lb, found, &bad, &n_launches))) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    ctx->stats.bases_scanned = g->total_bases;
+    ctx->stats.scan_ms = ms;
+    ctx->stats.n_launches = n_launches;
+    if (bad != NO_BAD) {
+        ctx->matches.clear();
+        return fail(ctx, KGMA_E_BADBASE, "record %lld: residue %lld is outside the DNA alphabet", (long long)(bad >> 40),
+                    (long long)(bad & ((1ull << 40) - 1)) + 1);
+    }
+    std::sort(found.begin(), found.end(), [](const kgma_match &x, const kgma_match &y) {
+        return x.query != y.query ? x.query < y.query : x.contig != y.contig ? x.contig < y.contig : x.start < y.start;
+    });
+    if (!overlap) {
+        // FindAll (src/ExactMatch.jl:20-30): the leftmost match, then the leftmost one that starts behind its end
+        size_t w = 0;
+        int64_t last_end = 0;
+        for (size_t i = 0; i < found.size(); i++) {
+            const kgma_match &mt = found[i];
+            const bool fresh = w == 0 || found[w - 1].query != mt.query || found[w - 1].contig != mt.contig;
+            if (!fresh && mt.start <= last_end) continue;
+            last_end = mt.start + qlen[(size_t)mt.query] - 1;
+            found[w++] = mt;
+        }
+        found.resize(w);
+    }
+    ctx->matches.swap(found);
+    return KGMA_OK;
+}
+
+int kgma_get_matches(kgma_ctx *ctx, kgma_match *out, int64_t cap, int64_t *n)
+{
+    if (!ctx || !n) return KGMA_E_ARG;
+    *n = (int64_t)ctx->matches.size();
+    if (!out) return KGMA_OK;
+    if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_matches: capacity %lld < %lld", (long long)cap, (long long)*n);
+    if (*n) memcpy(out, ctx->matches.data(), (size_t)*n * sizeof(kgma_match));
     return KGMA_OK;
 }
 

@@ -246,4 +246,38 @@ struct ContigDesc {
     int64_t len;          // residues
 };
 
+
+// Exact sequence search (kgma_exact.hip; exactMatch, src/ExactMatch.jl:89-121).  One query of a launch: its case-folded text
+// (byte & 0xDF: letters to upper case, '-' to 0x0D) at qtext + text_off, and the leading symbols the kernel tests in registers --
+// ASCII kernel: the first min(len, 8) folded bytes, little endian, in pat[0..1] with a byte mask in mask[0..1]; 2-bit kernel: the
+// codes of the first min(len, 16) symbols (first symbol = bits 0-1, as the interleaved genome copy) in pat[0] with mask[0].
+struct ExactQuery {
+    int64_t text_off, len;
+    uint32_t pat[2], mask[2];
+    int32_t id;           // 0-based query index reported in the matches
+    int32_t pad;
+};
+struct ExactMatch {       // = kgma_match
+    int32_t query, contig;
+    int64_t start;        // 1-based
+};
+static_assert(sizeof(ExactMatch) == 16, "matches are 16 bytes");
+constexpr int KGMA_EXACT_THREADS = 256;
+constexpr int KGMA_EXACT_ITERS = 4;                            // runs of start positions a lane takes per tile
+constexpr int KGMA_EXACT_RUN_ASCII = 16;                       // start positions per run: one 16-byte load (+ 8 bytes of the next run)
+constexpr int KGMA_EXACT_RUN_2BIT = 32;                        // ... two dwords of the interleaved copy (+ one of the next run)
+struct ExactArgs {
+    const uint8_t *ascii;
+    const uint32_t *inter;
+    const ContigDesc *cd;
+    const int64_t *tile_prefix;   // [n_contigs + 1]: tiles of the records before record c (a tile never spans two records)
+    int32_t n_contigs, n_queries;
+    const ExactQuery *queries;
+    const uint8_t *qtext;
+    ExactMatch *out;
+    unsigned long long *ctl;      // [0]: matches found (keeps counting past cap), [1]: smallest (record << 40 | 0-based offset) of a
+                                  // residue outside the 16-symbol alphabet (checking launches only)
+    unsigned long long cap;
+};
+
 }  // namespace kgma

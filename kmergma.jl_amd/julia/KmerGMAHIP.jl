@@ -395,6 +395,57 @@ function StrobeGMA!(; genome_path::String, refVec, consensus_refseq::KmerGMA.Seq
     return nothing
 end
 
-export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, Context
+struct KgmaMatch          # kgma_match: 0-based query and contig, 1-based start
+    query::Int32
+    contig::Int32
+    start::Int64
+end
+
+query_text(q::FASTA.Record) = FASTA.sequence(String, q)        # convert_to_search_query, src/ExactMatch.jl:46-58
+query_text(q) = string(q)
+
+# kgma_exact_match + kgma_get_matches: every occurrence of every query in every record, sorted by (query, contig, start)
+function exact_matches(g::DeviceGenome, queries::Vector{String}, overlap::Bool)
+    ctx = g.ctx
+    text = Vector{UInt8}(join(queries))
+    offsets = Int64[0; cumsum(Int64[ncodeunits(q) for q in queries])]
+    check(ctx, ccall((:kgma_exact_match, libkgma), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int64}, Int32, Int32),
+                     ctx.h, g.h, text, offsets, length(queries), overlap ? 1 : 0))
+    n = Ref{Int64}(0)
+    check(ctx, ccall((:kgma_get_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaMatch}, Int64, Ref{Int64}), ctx.h, C_NULL, 0, n))
+    out = Vector{KgmaMatch}(undef, n[])
+    check(ctx, ccall((:kgma_get_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaMatch}, Int64, Ref{Int64}), ctx.h, out, n[], n))
+    return out
+end
+
+"""
+    exactMatch_batch(queries, genome; overlap = true)   -- `genome`: a FASTA path or an open DeviceGenome
+exactMatch (src/ExactMatch.jl:100-121) for all queries in one pass over the genome: per query the Dict of record identifier =>
+match ranges, or "no match".
+"""
+function exactMatch_batch(queries::Vector, genome::Union{String, DeviceGenome}; overlap::Bool = true, ctx::Context = default_context())
+    g = genome isa String ? genome_from_fasta(ctx, genome) : genome
+    try
+        qs = String[query_text(q) for q in queries]
+        dicts = [Dict{String, Vector{UnitRange{Int64}}}() for _ in qs]
+        last_contig = fill(Int32(-1), length(qs))
+        for m in exact_matches(g, qs, overlap)
+            d, id = dicts[m.query + 1], identifier(g, m.contig)
+            m.contig == last_contig[m.query + 1] || (d[id] = UnitRange{Int64}[]; last_contig[m.query + 1] = m.contig)
+            push!(d[id], m.start:m.start + ncodeunits(qs[m.query + 1]) - 1)
+        end
+        return Any[isempty(d) ? "no match" : d for d in dicts]
+    finally
+        genome isa String && free!(g)
+    end
+end
+
+"""
+    exactMatch(query, genome; overlap = true)   -- KmerGMA.exactMatch's reader method (src/ExactMatch.jl:100-121) on the device
+"""
+exactMatch(query, genome::Union{String, DeviceGenome}; overlap::Bool = true, ctx::Context = default_context()) =
+    exactMatch_batch([query], genome; overlap = overlap, ctx = ctx)[1]
+
+export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, Context
 
 end # module

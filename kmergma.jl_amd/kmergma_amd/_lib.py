@@ -34,7 +34,7 @@ EXPORTS = [
     "kgma_scan_aligned", "kgma_get_alignments", "kgma_set_residue_source", "kgma_host_chain_values",
     "kgma_chain_values", "kgma_host_chain_walk", "kgma_chain_chunk_steps", "kgma_set_chain_source", "kgma_get_att", "kgma_set_att",
     "kgma_chain_export", "kgma_chain_export_copy", "kgma_kfv_scale", "kgma_kfv_is_float",
-    "kgma_set_strobe_ref", "kgma_strobe_scan",
+    "kgma_set_strobe_ref", "kgma_strobe_scan", "kgma_exact_match", "kgma_get_matches",
 ]
 
 
@@ -55,6 +55,10 @@ class KgmaAlignment(C.Structure):
                 ("first", C.c_int64), ("last", C.c_int64)]
 
 
+class KgmaMatch(C.Structure):
+    _fields_ = [("query", C.c_int32), ("contig", C.c_int32), ("start", C.c_int64)]
+
+
 class KgmaStats(C.Structure):
     _fields_ = [("bases_scanned", C.c_int64), ("windows_scanned", C.c_int64), ("n_dips", C.c_int64),
                 ("n_hits", C.c_int64), ("n_tie_flagged", C.c_int64), ("n_at_threshold", C.c_int64),
@@ -71,6 +75,8 @@ HIT_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("cmi", "<i8"), ("lo", 
 
 DIP_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("start", "<i8"), ("end", "<i8"), ("argmin", "<i8"),
                       ("D_min", "<i8"), ("exit_pos", "<i8"), ("D_exit", "<i8"), ("flags", "<u4"), ("reserved", "<u4")])
+
+MATCH_DTYPE = np.dtype([("query", "<i4"), ("contig", "<i4"), ("start", "<i8")])
 
 ALIGN_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                        C.POINTER(C.c_int64), C.POINTER(C.c_int64))
@@ -121,6 +127,8 @@ def load():
     L.kgma_set_thresholds.argtypes = [vp, P(dbl)]
     L.kgma_set_strobe_ref.argtypes = [vp, i32, i32, i32, i64, P(dbl), i64, dbl, i64]
     L.kgma_strobe_scan.argtypes = [vp, vp, i64, u32, C.c_char_p, i64, i32, i32, i64]
+    L.kgma_exact_match.argtypes = [vp, vp, C.c_char_p, P(i64), i32, i32]
+    L.kgma_get_matches.argtypes = [vp, P(KgmaMatch), i64, P(i64)]
     L.kgma_genome_from_host.argtypes = [vp, P(C.c_char_p), P(i64), i64, P(vp)]
     L.kgma_genome_from_fasta.argtypes = [vp, vp, i64, P(vp)]
     L.kgma_genome_from_fasta_file.argtypes = [vp, C.c_char_p, P(vp)]
@@ -406,6 +414,22 @@ class Context:
         cons = None if consensus is None else bytes(consensus)
         self._check(load().kgma_strobe_scan(self._h, genome._h, int(buff), int(flags), cons, 0 if cons is None else len(cons),
                                             int(gap_open), int(gap_extend), int(score_threshold)))
+
+    def exact_match(self, genome: Genome, queries: Sequence[bytes], overlap: bool = True) -> None:
+        """kgma_exact_match: every occurrence of every query (DNA symbols, either case) in every record of `genome`, one
+        pass over the genome for the whole batch; overlap=False keeps FindAll's non-overlapping leftmost matches.
+        Needs no references.  matches() afterwards."""
+        text, off = self._concat(queries)
+        self._check(load().kgma_exact_match(self._h, genome._h, text, _np_ptr(off, C.c_int64), off.size - 1, 1 if overlap else 0))
+
+    def matches(self) -> np.ndarray:
+        """Matches of the last exact_match as a structured array (MATCH_DTYPE: 0-based query and contig, 1-based start),
+        sorted by (query, contig, start)."""
+        n = C.c_int64(0)
+        self._check(load().kgma_get_matches(self._h, None, 0, C.byref(n)))
+        arr = np.zeros(max(n.value, 1), dtype=MATCH_DTYPE)
+        self._check(load().kgma_get_matches(self._h, arr.ctypes.data_as(C.POINTER(KgmaMatch)), n.value, C.byref(n)))
+        return arr[:n.value]
 
     def set_thresholds(self, thr: Sequence[float]) -> None:
         th = np.asarray(list(thr)[:self.m], dtype=np.float64)

@@ -10,6 +10,8 @@ Same names, keyword arguments, mutation-of-caller-vectors behaviour and error be
     write_results          src/API.jl:234-241
     StrobeGMA!             src/StrobemerGMA/StrobeGenomeMiner.jl:5-95
     Strobemer_findGenes    src/StrobemerGMA/StrobeGenomeMiner.jl:119-158
+    exactMatch             src/ExactMatch.jl:89-121
+    fasta_id_to_cumulative_len_dict  src/ExactMatch.jl:146-158
 
 but the per-record scan runs on the MI355X through libkgma's C ABI (include/kgma.h).  The host
 keeps what the reference keeps on the host: FASTA parsing, reference preparation, optional
@@ -410,6 +412,111 @@ def Strobemer_findGenes(*, genome_path: str, ref_path: str, s: int = 2, w_min: i
         out.append(dist_vec); info += ", vector of kmer distances along the genome"
     if verbose:
         log.info(info)
+    return out
+
+
+_DNA_SYMBOLS = frozenset(b"ACGTMRWSYKVHDBNacgtmrwsykvhdbn-")
+
+
+def _query_bytes(query) -> bytes:
+    """convert_to_search_query (src/ExactMatch.jl:46-58): a Record, a str or bytes of DNA symbols."""
+    if isinstance(query, Record):
+        q = bytes(query.sequence)
+    elif isinstance(query, str):
+        q = query.encode()
+    elif isinstance(query, (bytes, bytearray, memoryview)):
+        q = bytes(query)
+    else:
+        raise TypeError("Invalid query sequence type")
+    if not q:
+        raise ValueError("empty query")
+    if not _DNA_SYMBOLS.issuperset(q):
+        i = next(i for i, ch in enumerate(q) if ch not in _DNA_SYMBOLS)
+        raise ValueError(f"query symbol {i + 1} ({q[i:i + 1]!r}) is outside the DNA alphabet")
+    return q
+
+
+def _open_subject(ctx, subject):
+    """(device genome, per-record identifier lookup, owned) for a FASTA path, an open device genome or a _GenomeView."""
+    if isinstance(subject, str):
+        g = ctx.genome_from_fasta(subject)
+        return g, g, True
+    if isinstance(subject, _GenomeView):
+        return subject.genome, subject, False
+    return subject, subject, False
+
+
+def _identifier(src, c: int) -> str:
+    if isinstance(src, _GenomeView):
+        return src.identifier(c)
+    parts = src.header(c).split(None, 1)       # FASTA.identifier: the header up to the first whitespace
+    return parts[0] if parts else ""
+
+
+def exactMatch_batch(queries, genome_or_path, *, overlap: bool = True, ctx=None) -> list:
+    """exactMatch (src/ExactMatch.jl:100-121) for many queries in ONE pass over the genome (kgma_exact_match): per query
+    the dict {identifier: [(lo, hi), ...]} over the records with at least one match, or the string "no match".
+    `genome_or_path`: a FASTA path, or a device genome that is already open (it stays open)."""
+    qs = [_query_bytes(q) for q in queries]
+    if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
+        raise TypeError("Invalid subject sequence type")
+    ctx = ctx or default_context()
+    g, src, owned = _open_subject(ctx, genome_or_path)
+    try:
+        ctx.exact_match(g, qs, overlap)
+        mt = ctx.matches()
+        ids = {int(c): _identifier(src, int(c)) for c in np.unique(mt["contig"])}
+    finally:
+        if owned:
+            g.free()
+    out = [dict() for _ in qs]
+    # (sorted by query, record, start: one run per (query, record); a later record with the same identifier replaces the
+    #  earlier one's entry, as the reference's Dict assignment does)
+    bounds = np.flatnonzero(np.diff(mt["query"]) | np.diff(mt["contig"])) + 1
+    for run in np.split(mt, bounds) if mt.size else []:
+        qi, m = int(run["query"][0]), len(qs[int(run["query"][0])])
+        out[qi][ids[int(run["contig"][0])]] = [(s, s + m - 1) for s in run["start"].tolist()]
+    return [d if d else "no match" for d in out]
+
+
+def exactMatch(query, subject_seq, *, overlap: bool = True, ctx=None):
+    """exactMatch (src/ExactMatch.jl:89-121).  `query`: bytes / str / Record.  A `subject_seq` of residues (bytes, or a
+    Record) returns the list of 1-based inclusive (lo, hi) matches, or None when there is none (:89-98); a str is a FASTA
+    path, as in the reference (:100-107), and it or an open device genome returns {identifier: [(lo, hi), ...]} over the
+    records with a match, or the string "no match".  overlap=False keeps FindAll's non-overlapping matches (:20-30).
+    Symbols compare as BioSequences' isequal does: N only matches N, an IUPAC code only itself."""
+    q = _query_bytes(query)
+    if isinstance(subject_seq, (Record, bytes, bytearray, memoryview)):
+        seq = bytes(subject_seq.sequence if isinstance(subject_seq, Record) else subject_seq)
+        ctx = ctx or default_context()
+        g = ctx.genome_from_host([seq])
+        try:
+            ctx.exact_match(g, [q], overlap)
+            starts = ctx.matches()["start"].tolist()
+        finally:
+            g.free()
+        return [(s, s + len(q) - 1) for s in starts] or None
+    return exactMatch_batch([q], subject_seq, overlap=overlap, ctx=ctx)[0]
+
+
+def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
+    """src/ExactMatch.jl:146-158: the full description line of every record -> the summed length of the records BEFORE it
+    (what the scan reports as GenomePos).  Given an open device genome the headers and lengths come from its handle;
+    given a path the file is read on the host, as the reference does."""
+    if isinstance(fasta_file_path, _GenomeView):
+        g = fasta_file_path.genome
+        pairs = [(fasta_file_path.descriptions[c], g.contig_len(c)) for c in range(g.n_contigs)]
+    elif isinstance(fasta_file_path, _lib.Genome):
+        g = fasta_file_path
+        pairs = [(g.header(c), g.contig_len(c)) for c in range(g.n_contigs)]
+    elif isinstance(fasta_file_path, str):
+        pairs = [(r.description, len(r.sequence)) for r in read_fasta(fasta_file_path)]
+    else:
+        raise TypeError("expected a FASTA path or an open device genome")
+    out, total = {}, 0
+    for desc, n in pairs:
+        out[desc] = total
+        total += n
     return out
 
 
