@@ -299,6 +299,33 @@ int kgma_get_dists(kgma_ctx *ctx, int32_t kfv, double *out, int64_t cap, int64_t
 
 int kgma_get_stats(kgma_ctx *ctx, kgma_stats *out);
 
+/* Distance-bound prefilter of the last scan (one integer KFV, k = 5 or 6, 8-bit count-table kernel, no distance output).
+ * A window's distance has the exact lower bound D >= sumS2 - 2N sumS + N^2 n (sumS: the sum of S over the window's k-mer
+ * positions), so a cheap pass over the genome names the GRANULES (16 consecutive window starts of a record, granule g =
+ * windows 16g + 1 ... 16g + 16) that may hold a window at or below the threshold band; the exact scan then runs over
+ * streams built around them instead of over every window.  Results are those of the full scan.  The scan falls back to
+ * the full scan (same results) when the candidate list overflows, when the candidate streams outnumber the regular ones
+ * or when they cover too large a part of the windows; a fallback is remembered for the (genome, references, thresholds)
+ * triple and later scans of it skip the filter.  KGMA_FILTER=0 switches the filter off. */
+enum { KGMA_FILTER_OK = 0, KGMA_FILTER_OVERFLOW = 1, KGMA_FILTER_STREAMS = 2, KGMA_FILTER_FRACTION = 3, KGMA_FILTER_REMEMBERED = 4 };
+typedef struct kgma_filter_stats {
+    int32_t ran;             /* the filter kernel ran in the last scan */
+    int32_t fell_back;       /* the full scan ran although the filter applies */
+    int32_t reason;          /* KGMA_FILTER_*: why it fell back */
+    int32_t reserved;
+    int64_t granules;        /* candidate granules */
+    int64_t regions;         /* merged, padded regions (every record's first windows included) */
+    int64_t streams;         /* candidate streams the exact kernel walked */
+    int64_t windows;         /* windows in candidate streams */
+    int64_t positions;       /* ... plus the streams' warm-up positions */
+    int64_t total_windows;   /* windows of the records */
+    int64_t bound;           /* U: a granule is a candidate when its sum of S reaches it */
+    double filter_ms;        /* filter kernel time */
+} kgma_filter_stats;
+int kgma_get_filter_stats(kgma_ctx *ctx, kgma_filter_stats *out);
+/* The last scan's candidate granules (0-based record, 0-based granule), sorted; two-call pattern as kgma_get_hits. */
+int kgma_get_filter_candidates(kgma_ctx *ctx, int32_t *contig, int64_t *granule, int64_t cap, int64_t *n);
+
 /* HOST-side helper (not on the device path; a Julia host keeps using BioAlignments.jl): semi-global
  * affine-gap alignment of `a` (global; the consensus) against `b` (leading/trailing residues of b
  * free), EDNAFULL scores, gap of length L scoring gap_open_score + L*gap_extend_score

@@ -45,6 +45,8 @@ hipError_t launch_synth(uint8_t *ascii, const ContigDesc *cd, int n_contigs, int
                         uint64_t seed, hipStream_t st);
 hipError_t launch_scan(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
 hipError_t launch_stream(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
+bool filter_applies(int k, int64_t s_max);
+hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, hipStream_t st);
 int stream_waves(int k, int nk, int n_kfv, int n_sizes);
 int stream_slots_per_cu(int k, int nk, int nk_min, int n_longer, int n_kfv, int n_sizes, bool s16, int64_t n_ref, bool u8, int n_plus2, bool need_wide);
 bool stream8_derive_applies(int k, int nk_min, int nk_max, int n_kfv, int64_t n_ref, bool s16);
@@ -319,6 +321,20 @@ struct kgma_ctx {
     int last_mode = -1;
     std::vector<TileDesc> tiles;
     std::vector<int64_t> contig_tile_base;   // per contig: index of its first tile or -1
+    // Distance-bound prefilter (kgma_filter.hip; filter_candidate_table): the candidate stream table of the last scan beside the
+    // regular one above, which stays cached -- the fallback, the filter kernel itself and the chain path use it
+    bool scan_filtered = false;              // the last scan ran over ftiles: stitch_dips and the first-window D read that table
+    std::vector<TileDesc> ftiles;            // sorted by (record, first window)
+    std::vector<int64_t> fcontig_tile_base;  // per contig: index of its first candidate stream or -1
+    TileDesc *d_ftiles = nullptr; int64_t ftiles_cap = 0;
+    unsigned int *d_fctl = nullptr;          // entries the filter kernel appended (left at zero by its publish kernel)
+    uint8_t *h_fpin = nullptr, *h_fpin_dev = nullptr; size_t fpin_cap = 0;   // pinned: [count u32, pad][FilterEntry list]: the kernel writes it directly
+    hipEvent_t evf0 = nullptr, evf1 = nullptr;
+    std::vector<FilterEntry> fentries;       // the last scan's entries, sorted (kgma_get_filter_candidates)
+    std::vector<int64_t> fnwin;              // ... and the records' window counts then (the granules past a record's end are never set)
+    kgma_filter_stats fstats{};
+    uint64_t refs_version = 0;
+    struct FilterMemo { uint64_t uid = 0, refs = 0; int64_t T = 0, T_hi = 0; bool valid = false; } fmemo;   // the last fallback
     std::vector<int64_t> contig_nwin;        // evaluated windows per contig (0 = skipped)
     std::vector<int64_t> contig_looked;      // last residue the reference looks up (-1: BoundsError)
     int64_t tk_bases = 0, tk_windows = 0;
@@ -741,6 +757,11 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_Wtab) (void)hipFree(ctx->d_Wtab);
     if (ctx->d_diff) (void)hipFree(ctx->d_diff);
     if (ctx->d_tiles) (void)hipFree(ctx->d_tiles);
+    if (ctx->d_ftiles) (void)hipFree(ctx->d_ftiles);
+    if (ctx->d_fctl) (void)hipFree(ctx->d_fctl);
+    if (ctx->h_fpin) (void)hipHostFree(ctx->h_fpin);
+    if (ctx->evf0) (void)hipEventDestroy(ctx->evf0);
+    if (ctx->evf1) (void)hipEventDestroy(ctx->evf1);
     if (ctx->d_res) (void)hipFree(ctx->d_res);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_done) (void)hipFree(ctx->d_done);
@@ -1177,6 +1198,7 @@ static int set_refs_sparse_core(kgma_ctx *ctx, int32_t k, int32_t m, std::vector
     ctx->m = m;
     ctx->strobe = false;
     ctx->kfv.swap(kv);
+    ctx->refs_version++;                                              // (the prefilter remembers its fallbacks per reference set)
     for (double *p : ctx->d_dist) if (p) (void)hipFree(p);
     ctx->d_dist.assign((size_t)m, nullptr);
     ctx->dist_cap.assign((size_t)m, 0);
@@ -1274,6 +1296,7 @@ int kgma_set_refs(kgma_ctx *ctx, int32_t k, int32_t m, const double *ref, const 
     ctx->m = m;
     ctx->strobe = false;
     ctx->kfv.swap(kv);
+    ctx->refs_version++;                                              // (the prefilter remembers its fallbacks per reference set)
     for (double *p : ctx->d_dist) if (p) (void)hipFree(p);
     ctx->d_dist.assign((size_t)m, nullptr);
     ctx->dist_cap.assign((size_t)m, 0);
@@ -1376,6 +1399,7 @@ int kgma_set_strobe_ref(kgma_ctx *ctx, int32_t s, int32_t w_min, int32_t w_max, 
     ctx->strobe = true;
     ctx->st_s = s; ctx->st_wmin = w_min; ctx->st_wmax = w_max; ctx->st_q = q;
     ctx->kfv.swap(kv);
+    ctx->refs_version++;                                              // (the prefilter remembers its fallbacks per reference set)
     for (double *p : ctx->d_dist) if (p) (void)hipFree(p);
     ctx->d_dist.assign(1, nullptr);
     ctx->dist_cap.assign(1, 0);
@@ -1944,13 +1968,15 @@ struct Frag {             // one device record in global coordinates
 
 int stitch_dips(kgma_ctx *ctx, const std::vector<DevRecord> &recs)
 {
-    const int64_t n_tiles = (int64_t)ctx->tiles.size();
+    // (a filtered scan ran over the candidate stream table: streams of any length at 64-window boundaries, sorted by record and window)
+    const std::vector<TileDesc> &tiles = ctx->scan_filtered ? ctx->ftiles : ctx->tiles;
+    const int64_t n_tiles = (int64_t)tiles.size();
     const int64_t P = ctx->tile_windows;
     std::vector<Frag> fr;
     fr.reserve(recs.size());
     for (const DevRecord &r : recs) {
         if (r.tile < 0 || r.tile >= n_tiles) return fail(ctx, KGMA_E_HIP, "corrupt device record (tile %d)", r.tile);
-        const TileDesc &td = ctx->tiles[(size_t)r.tile];
+        const TileDesc &td = tiles[(size_t)r.tile];
         const int kfv = (r.kind_kfv >> 8) - 1;
         if (kfv < 0 || kfv >= ctx->m) return fail(ctx, KGMA_E_HIP, "corrupt device record (kfv %d)", kfv + 1);
         const int64_t D0 = ctx->D0[(size_t)kfv * (size_t)n_tiles + (size_t)r.tile];
@@ -2047,8 +2073,18 @@ int stitch_dips(kgma_ctx *ctx, const std::vector<DevRecord> &recs)
             for (size_t u = i; u < n && fr[u].contig == cur.contig && fr[u].kfv == cur.kfv && fr[u].start <= e; u++)
                 if (fr[u].kind == REC_EXIT && fr[u].start == e) { d.exit_pos = e; d.D_exit = fr[u].exitD; found = true; break; }
             if (!found) {
-                if ((e - 1) % P != 0) return fail(ctx, KGMA_E_HIP, "internal: dip exit at window %lld of record %d not found", (long long)e, cur.contig);
-                const int64_t t = ctx->contig_tile_base[(size_t)cur.contig] + (e - 1) / P;
+                int64_t t = -1;
+                if (ctx->scan_filtered) {
+                    // the candidate stream that starts at the exit window: a region cut into consecutive streams (every dip
+                    // closes inside its region)
+                    const auto it = std::lower_bound(tiles.begin(), tiles.end(), std::make_pair((int32_t)cur.contig, e), [](const TileDesc &a, const std::pair<int32_t, int64_t> &b) {
+                        return a.contig != b.first ? a.contig < b.first : a.win0 < b.second;
+                    });
+                    if (it != tiles.end() && it->contig == cur.contig && it->win0 == e) t = (int64_t)(it - tiles.begin());
+                } else if ((e - 1) % P == 0) {
+                    t = ctx->contig_tile_base[(size_t)cur.contig] + (e - 1) / P;
+                }
+                if (t < 0) return fail(ctx, KGMA_E_HIP, "internal: dip exit at window %lld of record %d not found", (long long)e, cur.contig);
                 d.exit_pos = e;
                 d.D_exit = ctx->D0[(size_t)cur.kfv * (size_t)n_tiles + (size_t)t];
             }
@@ -2227,6 +2263,175 @@ static int sinter_tables(kgma_ctx *ctx, const std::vector<int> &kfvs, int nv, co
 
 extern "C" {
 
+// ---- distance-bound prefilter of the one-KFV scan (kgma_filter.hip) -------------------------------------------------------------
+// D >= sumS2 - 2N sumS + N^2 n for every window (c^2 >= c, sum c = n), so only windows whose sum of S over their k-mer positions
+// reaches U = ceil((sumS2 + N^2 n - Dmax) / 2N) can have D <= Dmax = max(T - 1, T_hi): the largest D anything reacts to (dips and
+// their minima are below T, guard-band windows up to T_hi -- the band kgma_scan widens for a drift rescan arrives here in T / T_hi).
+// The filter kernel walks the regular stream table and names the candidate GRANULES (16 window starts); the host merges them into
+// regions and builds a second stream table for the exact kernel, which takes any (word_base, win0, n_valid, first_test, contig)
+// streams and forms every stream's own D0:
+//   * a region starts and ends on 64-window boundaries (streams start on plane words) with at least 64 windows in front of its
+//     first and behind its last candidate window, clipped to the record: every dip closes inside its region, exit window
+//     included, and candidate windows sit in steady steps (a stream's warm-up steps hold windows 0 ... 63 at most);
+//   * regions closer than a stream's warm-up (n k-mers) are merged: walking the gap costs less than starting again;
+//   * every record with windows has a region at its first window (first_test = 1): its D is kgma_get_first_window's and the
+//     anchor of the chain's drift check;
+//   * a region longer than the regular stream length is cut into consecutive streams (a dip across the cut is joined by
+//     stitch_dips like one across two regular streams).
+// Fallback to the regular table (same results): the list overflowed, more candidate streams than regular ones, or the candidate
+// streams' positions (windows + warm-ups) exceed FILTER_MAX_FRACTION of the windows.  A fallback is remembered for the (genome,
+// references, thresholds) triple: later scans of it skip the filter.
+// FILTER_MAX_FRACTION: break-even is 1 - filter time / scan time per window, less a margin for the short streams' warm-ups and
+// uneven lengths.  FILTER_MIN_WINDOWS: small genomes keep the plain scan -- the filter adds a launch and a host round trip to a step
+// of a fraction of a millisecond (KGMA_FILTER_MIN_WINDOWS overrides it: tests run the filter on small genomes).  Both values and
+// what they rest on: EXPERIMENTS.md section 12.
+constexpr double FILTER_MAX_FRACTION = 0.5;
+constexpr int64_t FILTER_MIN_WINDOWS = 1000000000ll;
+static int64_t filter_min_windows()
+{
+    if (const char *e = getenv("KGMA_FILTER_MIN_WINDOWS")) return std::max<int64_t>(1, atoll(e));
+    return FILTER_MIN_WINDOWS;
+}
+
+static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t n_tiles, bool *filtered)
+{
+    *filtered = false;
+    kgma_filter_stats &fs = ctx->fstats;
+    const KfvInfo &f = ctx->kfv[0];
+    const int64_t nc = g->n_contigs;
+    int64_t total_nwin = 0;
+    for (int64_t c = 0; c < nc; c++) total_nwin += ctx->contig_nwin[(size_t)c];
+    fs.total_windows = total_nwin;
+    if (total_nwin < filter_min_windows()) return KGMA_OK;
+    if (*std::min_element(f.S.begin(), f.S.end()) < 0) return KGMA_OK;   // (the granule sums bound sumS only for S >= 0: sums of counts are)
+    const int64_t Dmax = std::max(f.T - 1, f.T_hi);
+    const __int128 num = (__int128)f.sumS2 + (__int128)f.N * (__int128)f.N * (__int128)nk - (__int128)Dmax;
+    if (num <= 0) return KGMA_OK;                                       // U <= 0: every window is a candidate
+    const __int128 twoN = 2 * (__int128)f.N;
+    const __int128 U128 = (num + twoN - 1) / twoN;
+    const uint32_t U = U128 > 0x7FFFFFFF ? 0x7FFFFFFFu : (uint32_t)U128;   // (a granule's sum stays below 2^26: no candidates)
+    fs.bound = (int64_t)U;
+    const bool geom_debug = getenv("KGMA_GEOM_DEBUG") != nullptr;
+    auto &memo = ctx->fmemo;
+    if (memo.valid && memo.uid == g->uid && memo.refs == ctx->refs_version && memo.T == f.T && memo.T_hi == f.T_hi) {
+        fs.fell_back = 1; fs.reason = KGMA_FILTER_REMEMBERED;
+        if (geom_debug) fprintf(stderr, "scan filter: skipped, this genome fell back before\n");
+        return KGMA_OK;
+    }
+    // ---- buffers: the list lives in pinned host memory (the kernel appends a few thousand 16-byte entries), its counter on the device
+    int64_t cap = 1 << 18;
+    if (const char *e = getenv("KGMA_FILTER_CAP")) cap = std::min<int64_t>(std::max<int64_t>(1, atoll(e)), 1 << 24);
+    const size_t pin_need = 16 + (size_t)cap * sizeof(FilterEntry);
+    if (pin_need > ctx->fpin_cap) {
+        if (ctx->h_fpin) (void)hipHostFree(ctx->h_fpin);
+        ctx->h_fpin = nullptr; ctx->fpin_cap = 0;
+        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_fpin), pin_need, hipHostMallocDefault));
+        ctx->fpin_cap = pin_need;
+        HIP_TRY(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_fpin_dev), ctx->h_fpin, 0));
+    }
+    if (!ctx->d_fctl) {
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_fctl), 16));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_fctl, 0, 16, ctx->stream));
+    }
+    if (!ctx->evf0) { HIP_TRY(ctx, hipEventCreate(&ctx->evf0)); HIP_TRY(ctx, hipEventCreate(&ctx->evf1)); }
+    FilterArgs a;
+    memset(&a, 0, sizeof a);
+    a.inter = g->d_inter; a.n_dwords = 2 * g->total_words;
+    a.tiles = ctx->d_tiles; a.n_tiles = (int32_t)n_tiles;
+    a.nblk = (nk + 14) / 16 + 1;
+    a.cd = g->d_cd;
+    a.S = ctx->d_Stab;
+    a.U = U;
+    a.cap = (unsigned int)cap;
+    a.list = reinterpret_cast<FilterEntry *>(ctx->h_fpin_dev + 16);
+    a.ctl = ctx->d_fctl;
+    HIP_TRY(ctx, hipEventRecord(ctx->evf0, ctx->stream));
+    HIP_TRY(ctx, launch_filter(a, ctx->k, f.Smax, ctx->n_cus, reinterpret_cast<unsigned int *>(ctx->h_fpin_dev), ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->evf1, ctx->stream));
+    HIP_TRY(ctx, sync_spin(ctx->stream));
+    fs.ran = 1;
+    {
+        float fms = 0;
+        (void)hipEventElapsedTime(&fms, ctx->evf0, ctx->evf1);
+        fs.filter_ms = fms;
+    }
+    const unsigned int count = *reinterpret_cast<const unsigned int *>(ctx->h_fpin);
+    const size_t n_e = (size_t)std::min<int64_t>(count, cap);
+    const FilterEntry *he = reinterpret_cast<const FilterEntry *>(ctx->h_fpin + 16);
+    ctx->fentries.assign(he, he + n_e);
+    std::sort(ctx->fentries.begin(), ctx->fentries.end(), [](const FilterEntry &x, const FilterEntry &y) {
+        // (by first candidate granule: the entries of two neighbouring streams may share a base, their bits never overlap)
+        return x.contig != y.contig ? x.contig < y.contig : (int64_t)x.gbase + __builtin_ctzll(x.mask) < (int64_t)y.gbase + __builtin_ctzll(y.mask);
+    });
+    ctx->fnwin = ctx->contig_nwin;
+    for (const FilterEntry &e : ctx->fentries) fs.granules += __builtin_popcountll(e.mask);
+
+    const int64_t P = ctx->tile_windows;
+    const int64_t merge_gap = (((int64_t)nk + 63) / 64) * 64;
+    int reason = (int64_t)count > cap ? KGMA_FILTER_OVERFLOW : KGMA_FILTER_OK;
+    ctx->ftiles.clear();
+    ctx->fcontig_tile_base.assign((size_t)nc, -1);
+    size_t ei = 0;
+    for (int64_t c = 0; c < nc && reason == KGMA_FILTER_OK; c++) {
+        const int64_t nwin = ctx->contig_nwin[(size_t)c];
+        while (ei < ctx->fentries.size() && ctx->fentries[ei].contig < c) ei++;
+        if (nwin <= 0) continue;
+        ctx->fcontig_tile_base[(size_t)c] = (int64_t)ctx->ftiles.size();
+        int64_t rs = 0, re = std::min<int64_t>(nwin, 64);               // the region being grown (0-based windows [rs, re))
+        auto flush = [&]() {
+            fs.regions++;
+            for (int64_t t = rs; t < re; t += P) {
+                TileDesc td;
+                td.word_base = g->cd[(size_t)c].word_off + t / 32;
+                td.win0 = t + 1;
+                td.dist_base = -1;
+                td.n_valid = (int32_t)std::min<int64_t>(P, re - t);
+                td.first_test = t == 0 ? 1 : 0;
+                td.contig = (int32_t)c;
+                td.pad = 0;
+                ctx->ftiles.push_back(td);
+                fs.windows += td.n_valid;
+                fs.positions += (int64_t)td.n_valid + nk - 1;
+            }
+        };
+        for (; ei < ctx->fentries.size() && ctx->fentries[ei].contig == c; ei++) {
+            const FilterEntry &e = ctx->fentries[ei];
+            uint64_t m = e.mask;
+            while (m) {
+                const int b0 = __builtin_ctzll(m);
+                const uint64_t inv = ~(m >> b0);
+                const int len = inv ? __builtin_ctzll(inv) : 64 - b0;    // run of set bits b0 ... b0 + len - 1
+                m = b0 + len >= 64 ? 0 : m & (~(uint64_t)0 << (b0 + len));
+                const int64_t wa = 16 * ((int64_t)e.gbase + b0), wb = std::min<int64_t>(16 * ((int64_t)e.gbase + b0 + len) - 1, nwin - 1);
+                if (wa < 0 || wa >= nwin) return fail(ctx, KGMA_E_HIP, "internal: filter candidate outside record %lld", (long long)c);
+                const int64_t s = std::max<int64_t>(0, (wa / 64) * 64 - 64), en = std::min<int64_t>(nwin, ((wb + 1 + 63) / 64) * 64 + 64);
+                if (s <= re + merge_gap) { rs = std::min(rs, s); re = std::max(re, en); }
+                else { flush(); rs = s; re = en; }
+            }
+        }
+        flush();
+        // (the walk ends as soon as the candidate streams cover too much: that also bounds the table; where both limits are passed
+        //  the fraction is the reason reported)
+        if ((double)fs.positions > FILTER_MAX_FRACTION * (double)total_nwin) reason = KGMA_FILTER_FRACTION;
+    }
+    fs.streams = (int64_t)ctx->ftiles.size();
+    if (reason == KGMA_FILTER_OK && fs.streams > n_tiles) reason = KGMA_FILTER_STREAMS;
+    if (geom_debug)
+        fprintf(stderr, "scan filter: U %u, %lld granules, %lld regions, %lld candidate streams, %lld of %lld windows, %.3f ms%s%s\n", U, (long long)fs.granules,
+                (long long)fs.regions, (long long)fs.streams, (long long)fs.windows, (long long)total_nwin, fs.filter_ms, reason ? ", fallback: " : "",
+                reason == KGMA_FILTER_OVERFLOW ? "list overflow" : reason == KGMA_FILTER_STREAMS ? "too many streams" : reason == KGMA_FILTER_FRACTION ? "too many windows" : "");
+    if (reason != KGMA_FILTER_OK) {
+        fs.fell_back = 1; fs.reason = reason;
+        memo.valid = true; memo.uid = g->uid; memo.refs = ctx->refs_version; memo.T = f.T; memo.T_hi = f.T_hi;
+        return KGMA_OK;
+    }
+    int rc = dev_reserve(ctx, ctx->d_ftiles, ctx->ftiles_cap, (int64_t)ctx->ftiles.size());
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ftiles, ctx->ftiles.data(), ctx->ftiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice, ctx->stream));
+    *filtered = true;
+    return KGMA_OK;
+}
+
 int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_t flags)
 {
     if (!ctx || !gc) return KGMA_E_ARG;
@@ -2384,6 +2589,9 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     ctx->hits.clear();
     ctx->have_dists = false;
     ctx->last_mode = -1;
+    ctx->scan_filtered = false;
+    memset(&ctx->fstats, 0, sizeof ctx->fstats);
+    ctx->fentries.clear();
     {
         // every kernel but the 8-bit stream kernel reads the bit-plane copy of the genome
         bool planes_needed = !use_stream;
@@ -2594,6 +2802,24 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         ctx->tk_uid = g->uid; ctx->tk_mode = mode; ctx->tk_maxws = maxws; ctx->tk_k = k; ctx->tk_version = geom_version;
     }
 
+    // ---- distance-bound prefilter: one integer KFV on the 8-bit count-table kernel at k = 5, 6, no distance output -- the exact
+    //      kernel then walks the candidate stream table instead of the regular one (filter_candidate_table)
+    bool filtered = false;
+    {
+        const char *fe = getenv("KGMA_FILTER"), *ds = getenv("KGMA_DEBUG_SKIP");
+        const KfvInfo &f0 = ctx->kfv[0];
+        const int nk0 = (int)(f0.W - k + 1);
+        if (!(fe && atoi(fe) == 0) && use_stream && !generic_all && m_used == 1 && groups.size() == 1 && groups[0].kfvs.size() == 1 && groups[0].kfvs[0] == 0 &&
+            !want_dists && !overlap && !(ds && atoi(ds) != 0) && !f0.fp && f0.fits32 && !f0.S.empty() && stream8_applies(k, nk0, 1, f0.N, f0.Smax <= 32767) &&
+            !stream8_c16_applies(k, nk0, 1, f0.N, f0.Smax <= 32767, false) && filter_applies(k, f0.Smax)) {
+            rc = filter_candidate_table(ctx, g, nk0, n_tiles, &filtered);
+            if (rc) return rc;
+        }
+    }
+    // the table the exact kernel walks: its streams, D0 slots and records
+    const int64_t n_scan = filtered ? (int64_t)ctx->ftiles.size() : n_tiles;
+    const TileDesc *d_scan_tiles = filtered ? ctx->d_ftiles : ctx->d_tiles;
+
     unsigned int n_recs = 0;
     for (int attempt = 0;; attempt++) {
         if (attempt > 0) ctx->ov_groups = 0;                          // (a repeated scan is one plain launch)
@@ -2641,7 +2867,7 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
             }
             a.planes = g->d_planes;
             a.inter = g->d_inter;
-            a.tiles = ctx->d_tiles;
+            a.tiles = d_scan_tiles;
             if (strobe) {
                 const KfvInfo &f = ctx->kfv[0];
                 StrobeParams sp;
@@ -2714,11 +2940,11 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
             a.recs = d_recs;
             a.rec_count = reinterpret_cast<unsigned int *>(d_cnt);
             a.rec_cap = ctx->rec_cap;
-            a.n_tiles = (int32_t)n_tiles;
+            a.n_tiles = (int32_t)n_scan;
             a.n_att = reinterpret_cast<unsigned long long *>(d_cnt + 8);
             a.n_cold = reinterpret_cast<unsigned long long *>(d_cnt + 16);
             a.tile0 = 0;
-            a.n_chunk_tiles = (int32_t)n_tiles;
+            a.n_chunk_tiles = (int32_t)n_scan;
             a.tile_windows = ctx->tile_windows;
             // several KFVs, k <= 7: two kernels (match loop -> per-window differences; window pass with the S
             // tables in LDS), in chunks of tiles so that the difference buffer stays bounded (kgma_pos.hip)
@@ -2764,9 +2990,9 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         // afterwards, which only happens for dip-dense inputs) and the counters are reset: ONE synchronisation,
         // no copy-engine launch, no memset before the next scan
         (void)d_aux; (void)d_D0;
-        HIP_TRY(ctx, launch_export(ctx->d_res, ctx->h_pin_dev, ctx->res_d0_slots, n_tiles * (int64_t)ctx->m, ctx->rec_cap,
+        HIP_TRY(ctx, launch_export(ctx->d_res, ctx->h_pin_dev, ctx->res_d0_slots, n_scan * (int64_t)ctx->m, ctx->rec_cap,
                                    (unsigned int)std::min<size_t>(INLINE_RECS, ctx->rec_cap), ((flags & KGMA_F_NO_TIE_RESOLVE) || strobe) ? 0 : 1,
-                                   ctx->d_tiles, g->d_cd, g->d_ascii, ctx->d_Wtab, ctx->d_done, ctx->stream));
+                                   d_scan_tiles, g->d_cd, g->d_ascii, ctx->d_Wtab, ctx->d_done, ctx->stream));
         HIP_TRY(ctx, sync_spin(ctx->stream));
         ctx->counters_clean = true;
         if (g->pack_pending) {
@@ -2786,7 +3012,8 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         if (rc) return rc;
     }
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    // (a scan whose filter ran: from the filter's launch to the end of the exact kernel -- filter, read-back, table, exact launch)
+    (void)hipEventElapsedTime(&ms, ctx->fstats.ran ? ctx->evf0 : ctx->ev0, ctx->ev1);
     ctx->stats.overlap_ms = 0;
     if (ctx->ov_groups > 0) {
         // overlapped step: scan_ms = the sum of the scan launches' times (what the roofline is computed from), overlap_ms = the
@@ -2807,28 +3034,29 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         HIP_TRY(ctx, hipMemcpy(recs.data() + n_inline,
                                reinterpret_cast<DevRecord *>(ctx->d_res + KGMA_RES_HDR + ctx->res_d0_slots * 8 + KGMA_AUX_BYTES) + n_inline,
                                ((size_t)n_recs - n_inline) * sizeof(DevRecord), hipMemcpyDeviceToHost));
-    ctx->D0.assign(h_D0, h_D0 + (size_t)n_tiles * (size_t)ctx->m);
+    ctx->D0.assign(h_D0, h_D0 + (size_t)n_scan * (size_t)ctx->m);
     for (int j = 0; j < m_used; j++) {
         // (Float64 KFV: the kernel wrote each stream's first distance as a double; the host works on the lattice)
         const KfvInfo &kf = ctx->kfv[(size_t)j];
         if (!kf.fp) continue;
-        for (int64_t t = 0; t < n_tiles; t++) {
+        for (int64_t t = 0; t < n_scan; t++) {
             double dv;
-            memcpy(&dv, &ctx->D0[(size_t)j * (size_t)n_tiles + (size_t)t], sizeof dv);
-            ctx->D0[(size_t)j * (size_t)n_tiles + (size_t)t] = lattice_of(kf, k, dv);
+            memcpy(&dv, &ctx->D0[(size_t)j * (size_t)n_scan + (size_t)t], sizeof dv);
+            ctx->D0[(size_t)j * (size_t)n_scan + (size_t)t] = lattice_of(kf, k, dv);
         }
     }
     ctx->firstD.assign((size_t)ctx->m * (size_t)nc, -1);
     for (int j = 0; j < ctx->m; j++)
         for (int64_t c = 0; c < nc; c++) {
-            const int64_t tb = ctx->contig_tile_base[(size_t)c];
-            if (tb >= 0) ctx->firstD[(size_t)j * (size_t)nc + (size_t)c] = ctx->D0[(size_t)j * (size_t)n_tiles + (size_t)tb];
+            const int64_t tb = filtered ? ctx->fcontig_tile_base[(size_t)c] : ctx->contig_tile_base[(size_t)c];   // (the record's first stream starts at its first window)
+            if (tb >= 0) ctx->firstD[(size_t)j * (size_t)nc + (size_t)c] = ctx->D0[(size_t)j * (size_t)n_scan + (size_t)tb];
         }
     ctx->stats.n_at_threshold = (int64_t)*h_natt;
     if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "scan cold steps: %llu\n", *h_ncold);
     ctx->aux_host = h_aux;
     ctx->aux_used = *reinterpret_cast<const unsigned int *>(ctx->h_pin + 4);
     ctx->have_dists = want_dists;
+    ctx->scan_filtered = filtered;
     rc = stitch_dips(ctx, recs);
     if (rc) return rc;
     ctx->last_mode = mode;
@@ -4796,6 +5024,7 @@ int kgma_replay_dips(kgma_ctx *ctx, int32_t mode, int64_t buff, int64_t genome_p
         if (dips[i].contig < 0 || dips[i].contig >= n_records || dips[i].kfv < 1 || dips[i].kfv > ctx->m)
             return fail(ctx, KGMA_E_ARG, "kgma_replay_dips: dip %lld refers to record %d / KFV %d", (long long)i, dips[i].contig, dips[i].kfv);
     ctx->tiles.clear();
+    ctx->scan_filtered = false;
     ctx->contig_tile_base.assign((size_t)n_records, -1);
     ctx->tk_uid = 0;            // the scan's cached tile geometry is gone: the next scan rebuilds it
     ctx->have_dists = false;
@@ -5116,6 +5345,27 @@ int kgma_get_dists(kgma_ctx *ctx, int32_t kfv, double *out, int64_t cap, int64_t
     if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_dists: capacity too small");
     (void)hipSetDevice(ctx->device);
     if (*n) HIP_TRY(ctx, hipMemcpy(out, ctx->d_dist[(size_t)(kfv - 1)], (size_t)*n * sizeof(double), hipMemcpyDeviceToHost));
+    return KGMA_OK;
+}
+
+int kgma_get_filter_stats(kgma_ctx *ctx, kgma_filter_stats *out)
+{
+    if (!ctx || !out) return KGMA_E_ARG;
+    *out = ctx->fstats;
+    return KGMA_OK;
+}
+
+int kgma_get_filter_candidates(kgma_ctx *ctx, int32_t *contig, int64_t *granule, int64_t cap, int64_t *n)
+{
+    if (!ctx || !n) return KGMA_E_ARG;
+    int64_t need = 0;
+    for (const FilterEntry &e : ctx->fentries) need += __builtin_popcountll(e.mask);
+    *n = need;
+    if (!contig || !granule) return KGMA_OK;
+    if (cap < need) return KGMA_E_ARG;
+    int64_t i = 0;
+    for (const FilterEntry &e : ctx->fentries)
+        for (uint64_t m = e.mask; m; m &= m - 1) { contig[i] = e.contig; granule[i] = (int64_t)e.gbase + __builtin_ctzll(m); i++; }
     return KGMA_OK;
 }
 

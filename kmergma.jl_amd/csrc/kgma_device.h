@@ -225,6 +225,29 @@ constexpr int KGMA_STREAM_MAX_WINDOWS = 1 << 19;               // longer genomes
                                                                // 155.1 ms, 12 rounds of 1 M windows 157.3 ms, 48 rounds 154.5 ms)
 constexpr int KGMA_STREAM_MAX_K = 7;                           // 4^k 16-bit counters per wave must fit the LDS
 
+// Distance-bound prefilter of the one-KFV scan at k = 5, 6 (kgma_filter.hip).  A GRANULE is 16 consecutive window starts of a
+// record; an entry names the granules of one wave iteration that may hold a window with D <= Dmax.
+struct FilterEntry {
+    int32_t contig;
+    int32_t gbase;        // granule of bit 0 of the mask (negative at a record's start: those bits are never set)
+    uint64_t mask;
+};
+static_assert(sizeof(FilterEntry) == 16, "filter entries are 16 bytes");
+struct ContigDesc;
+struct FilterArgs {
+    const uint32_t *inter;        // the 2-bit genome copy the scan reads
+    int64_t n_dwords;             // its length
+    const TileDesc *tiles;        // the scan's regular stream table: one wave walks one stream's granules
+    int32_t n_tiles;
+    int32_t nblk;                 // blocks of 16 positions a granule's windows use: floor((n + 14) / 16) + 1
+    const ContigDesc *cd;
+    const int32_t *S;             // the KFV's S table (4^k int32, the 2-bit copy's index order); every entry in 0 ... 65535
+    uint32_t U;                   // candidate: the granule's sum of S reaches U
+    unsigned int cap;             // entries the list holds
+    FilterEntry *list;
+    unsigned int *ctl;            // entries appended (keeps counting past cap)
+};
+
 // Aux region of the result block: residues under tied minima, gathered on the device (export_kernel)
 constexpr int KGMA_AUX_BYTES = 64 << 10;
 constexpr int KGMA_RES_HDR = 32;                               // counters at the head of a scan's result block (kgma_api.cpp)

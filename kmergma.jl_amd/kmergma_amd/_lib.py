@@ -35,7 +35,9 @@ EXPORTS = [
     "kgma_chain_values", "kgma_host_chain_walk", "kgma_chain_chunk_steps", "kgma_set_chain_source", "kgma_get_att", "kgma_set_att",
     "kgma_chain_export", "kgma_chain_export_copy", "kgma_kfv_scale", "kgma_kfv_is_float",
     "kgma_set_strobe_ref", "kgma_strobe_scan", "kgma_exact_match", "kgma_get_matches",
+    "kgma_get_filter_stats", "kgma_get_filter_candidates",
 ]
+FILTER_OK, FILTER_OVERFLOW, FILTER_STREAMS, FILTER_FRACTION, FILTER_REMEMBERED = 0, 1, 2, 3, 4
 
 
 class KgmaHit(C.Structure):
@@ -68,6 +70,12 @@ class KgmaStats(C.Structure):
                 ("chain_device_pairs", C.c_int64), ("chain_device_ms", C.c_double), ("chain_raw_steps", C.c_int64),
                 ("chain_max_drift", C.c_double), ("chain_band_log2", C.c_int32), ("chain_rescans", C.c_int32),
                 ("overlap_ms", C.c_double)]
+
+
+class KgmaFilterStats(C.Structure):
+    _fields_ = [("ran", C.c_int32), ("fell_back", C.c_int32), ("reason", C.c_int32), ("reserved", C.c_int32),
+                ("granules", C.c_int64), ("regions", C.c_int64), ("streams", C.c_int64), ("windows", C.c_int64),
+                ("positions", C.c_int64), ("total_windows", C.c_int64), ("bound", C.c_int64), ("filter_ms", C.c_double)]
 
 
 HIT_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("cmi", "<i8"), ("lo", "<i8"), ("hi", "<i8"),
@@ -153,6 +161,8 @@ def load():
     L.kgma_get_first_window.argtypes = [vp, i32, P(i64), i64, P(i64)]
     L.kgma_get_dists.argtypes = [vp, i32, P(dbl), i64, P(i64)]
     L.kgma_get_stats.argtypes = [vp, P(KgmaStats)]
+    L.kgma_get_filter_stats.argtypes = [vp, P(KgmaFilterStats)]
+    L.kgma_get_filter_candidates.argtypes = [vp, P(i32), P(i64), i64, P(i64)]
     L.kgma_resolve_ties_local.argtypes = [vp, vp]
     L.kgma_repack_scan_hits.argtypes = [vp, vp, i32, i64, i64, C.c_uint32, P(KgmaHit), i64, P(i64)]
     L.kgma_align_hits_device.argtypes = [vp, vp, C.c_char_p, i64, i32, i32, i64, P(i32), P(i64), P(i64), P(i64), P(i64), P(i64)]
@@ -759,6 +769,21 @@ class Context:
         s = KgmaStats()
         self._check(load().kgma_get_stats(self._h, C.byref(s)))
         return {f: getattr(s, f) for f, _ in KgmaStats._fields_}
+
+    def filter_stats(self) -> dict:
+        """kgma_get_filter_stats: what the distance-bound prefilter did in the last scan."""
+        s = KgmaFilterStats()
+        self._check(load().kgma_get_filter_stats(self._h, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in KgmaFilterStats._fields_ if f != "reserved"}
+
+    def filter_candidates(self) -> np.ndarray:
+        """kgma_get_filter_candidates: the last scan's candidate granules as an (n, 2) int64 array (record, granule), sorted."""
+        n = C.c_int64(0)
+        self._check(load().kgma_get_filter_candidates(self._h, None, None, 0, C.byref(n)))
+        c = np.zeros(max(n.value, 1), dtype=np.int32); g = np.zeros(max(n.value, 1), dtype=np.int64)
+        if n.value:
+            self._check(load().kgma_get_filter_candidates(self._h, _np_ptr(c, C.c_int32), _np_ptr(g, C.c_int64), n.value, C.byref(n)))
+        return np.stack([c[:n.value].astype(np.int64), g[:n.value]], axis=1) if n.value else np.zeros((0, 2), dtype=np.int64)
 
     @property
     def stream(self) -> int:
