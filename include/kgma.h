@@ -312,7 +312,7 @@ typedef struct kgma_filter_stats {
     int32_t ran;             /* the filter kernel ran in the last scan */
     int32_t fell_back;       /* the full scan ran although the filter applies */
     int32_t reason;          /* KGMA_FILTER_*: why it fell back */
-    int32_t reserved;
+    int32_t form;            /* the filter kernel's form: S entry bytes (1, 2) | table copies (1, 32) << 8; 0: it did not run */
     int64_t granules;        /* candidate granules */
     int64_t regions;         /* merged, padded regions (every record's first windows included) */
     int64_t streams;         /* candidate streams the exact kernel walked */

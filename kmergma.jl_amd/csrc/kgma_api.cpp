@@ -46,7 +46,7 @@ hipError_t launch_synth(uint8_t *ascii, const ContigDesc *cd, int n_contigs, int
 hipError_t launch_scan(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
 hipError_t launch_stream(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
 bool filter_applies(int k, int64_t s_max);
-hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, hipStream_t st);
+hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, int32_t *form, hipStream_t st);
 int stream_waves(int k, int nk, int n_kfv, int n_sizes);
 int stream_slots_per_cu(int k, int nk, int nk_min, int n_longer, int n_kfv, int n_sizes, bool s16, int64_t n_ref, bool u8, int n_plus2, bool need_wide);
 bool stream8_derive_applies(int k, int nk_min, int nk_max, int n_kfv, int64_t n_ref, bool s16);
@@ -2346,10 +2346,12 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
     a.list = reinterpret_cast<FilterEntry *>(ctx->h_fpin_dev + 16);
     a.ctl = ctx->d_fctl;
     HIP_TRY(ctx, hipEventRecord(ctx->evf0, ctx->stream));
-    HIP_TRY(ctx, launch_filter(a, ctx->k, f.Smax, ctx->n_cus, reinterpret_cast<unsigned int *>(ctx->h_fpin_dev), ctx->stream));
+    int32_t form = 0;
+    HIP_TRY(ctx, launch_filter(a, ctx->k, f.Smax, ctx->n_cus, reinterpret_cast<unsigned int *>(ctx->h_fpin_dev), &form, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->evf1, ctx->stream));
     HIP_TRY(ctx, sync_spin(ctx->stream));
     fs.ran = 1;
+    fs.form = form;
     {
         float fms = 0;
         (void)hipEventElapsedTime(&fms, ctx->evf0, ctx->evf1);

@@ -157,13 +157,16 @@ static hipError_t filter_launch(const FilterArgs &a, int n_cus, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, hipStream_t st)
+// *form: the instantiation launched, S entry bytes | table copies << 8 (kgma_filter_stats::form)
+hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, int32_t *form, hipStream_t st)
 {
     if (!filter_applies(k, s_max) || a.nblk < 1 || a.nblk > 63) return hipErrorInvalidValue;
+    const int es = s_max < 256 ? 1 : 2, copies = k == 6 && es == 2 ? 1 : 32;
     hipError_t e;
-    if (k == 5) e = s_max < 256 ? filter_launch<5, 1, 32>(a, n_cus, st) : filter_launch<5, 2, 32>(a, n_cus, st);
-    else e = s_max < 256 ? filter_launch<6, 1, 32>(a, n_cus, st) : filter_launch<6, 2, 1>(a, n_cus, st);
+    if (k == 5) e = es == 1 ? filter_launch<5, 1, 32>(a, n_cus, st) : filter_launch<5, 2, 32>(a, n_cus, st);
+    else e = es == 1 ? filter_launch<6, 1, 32>(a, n_cus, st) : filter_launch<6, 2, 1>(a, n_cus, st);
     if (e != hipSuccess) return e;
+    *form = es | (copies << 8);
     hipLaunchKernelGGL(filter_publish_kernel, dim3(1), dim3(64), 0, st, a.ctl, host_count);
     return hipGetLastError();
 }

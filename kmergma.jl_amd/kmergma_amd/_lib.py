@@ -73,7 +73,7 @@ class KgmaStats(C.Structure):
 
 
 class KgmaFilterStats(C.Structure):
-    _fields_ = [("ran", C.c_int32), ("fell_back", C.c_int32), ("reason", C.c_int32), ("reserved", C.c_int32),
+    _fields_ = [("ran", C.c_int32), ("fell_back", C.c_int32), ("reason", C.c_int32), ("form", C.c_int32),
                 ("granules", C.c_int64), ("regions", C.c_int64), ("streams", C.c_int64), ("windows", C.c_int64),
                 ("positions", C.c_int64), ("total_windows", C.c_int64), ("bound", C.c_int64), ("filter_ms", C.c_double)]
 
@@ -774,7 +774,7 @@ class Context:
         """kgma_get_filter_stats: what the distance-bound prefilter did in the last scan."""
         s = KgmaFilterStats()
         self._check(load().kgma_get_filter_stats(self._h, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in KgmaFilterStats._fields_ if f != "reserved"}
+        return {f: getattr(s, f) for f, _ in KgmaFilterStats._fields_}
 
     def filter_candidates(self) -> np.ndarray:
         """kgma_get_filter_candidates: the last scan's candidate granules as an (n, 2) int64 array (record, granule), sorted."""

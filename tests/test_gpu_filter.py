@@ -9,8 +9,9 @@ import pytest
 
 from kmergma_amd import _lib
 from oracle import oracle as orc
+from tests import filter_cases as fc
 from tests import filter_ref
-from tests.helpers import hit_key, make_genome, mutate, random_dna
+from tests.helpers import hit_key, kmer_values, make_genome, mutate, random_dna
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +29,14 @@ def _small_genomes(monkeypatch):
     monkeypatch.setenv("KGMA_FILTER_MIN_WINDOWS", "1")
 
 
-def _scan(monkeypatch, contigs, ref, thr, flags, filter_on=True, env=None, repeat=1):
+def _scan(monkeypatch, contigs, ref, thr, flags, filter_on=True, env=None, repeat=1, k=K):
     """One fresh context, `repeat` scans of the same genome; returns the last scan's results and every scan's filter stats."""
     monkeypatch.setenv("KGMA_FILTER", "1" if filter_on else "0")
     for name, val in (env or {}).items():
         monkeypatch.setenv(name, val)
     ctx = _lib.Context(0)
     try:
-        ctx.set_refs(K, [ref["RV"]], [ref["ws"]], [thr], [ref["N"]])
+        ctx.set_refs(k, [ref["RV"]], [ref["ws"]], [thr], [ref["N"]])
         g = ctx.genome_from_host(contigs)
         fstats = []
         for _ in range(repeat):
@@ -62,15 +63,15 @@ def _same(a, b):
     assert a["windows"] == b["windows"]
 
 
-def _on_off_oracle(monkeypatch, contigs, ref, thr, expect_ran=True):
+def _on_off_oracle(monkeypatch, contigs, ref, thr, expect_ran=True, k=K, W=W, all_flags=(0, _lib.F_CHAIN_REPLAY)):
     """Filter on against filter off, without and with the chain replay, and against the oracles; returns the filtered exact scan."""
-    T = orc.int_threshold(thr, K, ref["N"])
-    _, _, oD1 = orc.single_scan_int(contigs, ref["S"], ref["N"], K, W, T, BUFF)
-    ohits, _ = orc.single_scan(contigs, ref["RV"], K, W, thr, BUFF)
+    T = orc.int_threshold(thr, k, ref["N"])
+    _, _, oD1 = orc.single_scan_int(contigs, ref["S"], ref["N"], k, W, T, BUFF)
+    ohits, _ = orc.single_scan(contigs, ref["RV"], k, W, thr, BUFF)
     first = None
-    for flags in (0, _lib.F_CHAIN_REPLAY):
-        on = _scan(monkeypatch, contigs, ref, thr, flags, True)
-        off = _scan(monkeypatch, contigs, ref, thr, flags, False)
+    for flags in all_flags:
+        on = _scan(monkeypatch, contigs, ref, thr, flags, True, k=k)
+        off = _scan(monkeypatch, contigs, ref, thr, flags, False, k=k)
         assert on["kernel"].startswith("stream8_kernel")
         _same(on, off)
         fs = on["fstats"][0]
@@ -78,6 +79,8 @@ def _on_off_oracle(monkeypatch, contigs, ref, thr, expect_ran=True):
         if expect_ran:
             assert fs["ran"] == 1 and fs["fell_back"] == 0 and fs["reason"] == _lib.FILTER_OK, fs
             assert 0 < fs["windows"] <= fs["total_windows"] and fs["streams"] >= fs["regions"] >= len(contigs) - 1
+        else:
+            assert fs["ran"] == 0 and fs["fell_back"] == 0 and fs["form"] == 0, fs
         has = np.asarray([len(c) >= W for c in contigs])
         assert np.array_equal(on["D1"][has], oD1[has])
         if flags & _lib.F_CHAIN_REPLAY:
@@ -192,3 +195,155 @@ def test_other_launch_shapes_do_not_filter(monkeypatch, alp_ref, alp_clusters, g
         g.free()
     finally:
         ctx.close()
+
+
+# ---- the shape matrix (tests/filter_cases.py): every kernel form, nblk = 2 ... 25, the switch points -----------------------------
+
+def _check_cell(monkeypatch, k, contigs, ref, thr, chain):
+    """What test_matrix asserts of one (references, genome, threshold): on == off == oracles, the device's candidates are numpy's,
+    the bound and the kernel form are the expected ones, the filter ran and did not fall back."""
+    N, W = ref["N"], ref["ws"]
+    on, ohits = _on_off_oracle(monkeypatch, contigs, ref, thr, k=k, W=W, all_flags=(0, _lib.F_CHAIN_REPLAY) if chain else (0,))
+    T, T_hi = filter_ref.threshold_band(thr, k, N)
+    U = filter_ref.bound_U(ref["S"], N, k, W, T, T_hi)
+    want = filter_ref.candidates(contigs, ref["S"], k, W, U)
+    fs = on["fstats"][0]
+    print("k %d N %d nk %d thr %.2f U %d Smax %d: form %#x granules %d regions %d streams %d windows %d of %d, %d hits" % (
+        k, N, W - k + 1, thr, U, int(np.max(ref["S"])), fs["form"], fs["granules"], fs["regions"], fs["streams"], fs["windows"],
+        fs["total_windows"], len(on["hits"])))
+    assert fs["bound"] == U > 0
+    assert fs["form"] == fc.form_of(k, int(np.max(ref["S"])))
+    assert np.array_equal(on["cand"], want)
+    assert fs["granules"] == len(want) > 0
+    return on, ohits
+
+
+@pytest.mark.parametrize("cell", fc.MATRIX, ids=fc.cell_id)
+def test_matrix(monkeypatch, cell):
+    """k = 5, 6 x one- and two-byte S entries x nblk = 2, 2, 2, 3, 4, 8, 19, 25: the long record with its plants and its tandem
+    run (>= 128 candidate granules in a row: lo_cur and lo_prev) and the short records whose last granule is a candidate (lim)."""
+    k, N, nk = cell
+    c = fc.cell(k, N, nk)
+    assert (int(c["ref"]["S"].max()) < 256) == (N == 7) and fc.longest_run(c["want"]) >= 128
+    on, ohits = _check_cell(monkeypatch, k, c["contigs"], c["ref"], c["thr"], chain=nk == fc.CHAIN_NK)
+    assert np.array_equal(on["cand"], c["want"]) and on["fstats"][0]["bound"] == c["U"]
+    assert on["fstats"][0]["form"] == {(5, 7): 0x2001, (5, 300): 0x2002, (6, 7): 0x2001, (6, 300): 0x0102}[(k, N)]
+    assert len(on["hits"]) > 0 and len(on["dips"]) >= 10                # (the plants of the long record at least)
+
+
+def _edge_ref(k, value):
+    """The k = 5 / 6, nk = 100, N = 300 family with the S entry of a k-mer of the base that every plant holds overwritten (255 and 256: the others
+    clipped to 255), the matrix genome, and a threshold: the largest planted distance under the new S plus the matrix cell's margin (a
+    quarter of the largest planted distance under the family's own S, + 0.05).  The margin is kept absolute because one entry of
+    65535 puts (65535 - N c)^2 into every planted window's distance: a quarter of that would put Dmax above sumS2 + N^2 n, U <= 0."""
+    c = fc.cell(k, 300, 100)
+    base, W = c["ref"]["base"], c["W"]
+    km = kmer_values(base, k)
+    planted = [set(kmer_values(c["contigs"][r][s:s + W], k).tolist()) for r, s in c["plants"]]
+    x = next(int(v) for v in km if np.count_nonzero(km == v) == 1 and all(int(v) in p for p in planted))   # in every plant, once in the base
+    S = c["ref"]["S"].copy()
+    if value in (255, 256):
+        S = np.minimum(S, 255)
+    S[x] = value
+    ref = fc.ref_from_S(S, 300, k, W, base)
+    D = fc.exact_D(c["contigs"], S, 300, k, W)
+    thr = round(fc.planted_max(D, c["plants"], k, 300) + 0.25 * fc.planted_max(c["D"], c["plants"], k, 300) + 0.05, 2)
+    return c, ref, thr
+
+
+@pytest.mark.parametrize("k", [5, 6])
+@pytest.mark.parametrize("value", [255, 256, 65535, 65536])
+def test_entry_width_edges(monkeypatch, k, value):
+    """Smax 255 | 256 selects the entry width, 65535 is the last value the two-byte table holds (read without sign extension: the
+    plants hold that k-mer), 65536 keeps the filter off."""
+    c, ref, thr = _edge_ref(k, value)
+    assert int(ref["S"].max()) == value
+    if value == 65536:
+        on, ohits = _on_off_oracle(monkeypatch, c["contigs"], ref, thr, expect_ran=False, k=k, W=c["W"])
+        assert len(ohits) >= 10 and len(on["cand"]) == 0
+        return
+    on, ohits = _check_cell(monkeypatch, k, c["contigs"], ref, thr, chain=True)
+    assert on["fstats"][0]["form"] & 0xFF == (1 if value == 255 else 2)
+    assert len(ohits) >= 10
+    have = set(map(tuple, on["cand"].tolist()))
+    assert all((r, s // 16) in have for r, s in c["plants"])            # found through the overwritten entry
+
+
+@pytest.mark.parametrize("nk,N", [(17, 7), (17, 300), (383, 7), (383, 300)])
+def test_threshold_on_a_windows_distance_k5(monkeypatch, nk, N):
+    """test_threshold_on_a_windows_distance at k = 5 with nblk = 2 and 25."""
+    k, W = 5, nk + 4
+    ref = fc.family(k, N, nk)
+    rng = np.random.default_rng([6203, nk, N])
+    contigs = [random_dna(rng, 5_000) + mutate(rng, ref["base"], 0.04) + random_dna(rng, 5_000) + ref["base"] + random_dna(rng, 3_000)]
+    D = fc.exact_D(contigs, ref["S"], N, k, W)[0]
+    scale = 2.0 * k * N * N
+    above = np.nonzero(D > D[10_000 + W])[0]
+    s = int(above[np.argmin(np.abs(D[above] - 1.15 * D[10_000 + W]))])   # the window nearest above the exact copy's distance
+    thr = float(D[s]) / scale
+    T, T_hi = filter_ref.threshold_band(thr, k, N)
+    assert T == D[s] <= T_hi and D[10_000 + W] < T
+    on, _ = _on_off_oracle(monkeypatch, contigs, ref, thr, k=k, W=W)
+    assert on["counts"][2] > 0 and [s + 1] in on["att"][:, 2:].tolist()
+    fs = on["fstats"][0]
+    assert fs["bound"] == filter_ref.bound_U(ref["S"], N, k, W, T, T_hi) and fs["form"] == fc.form_of(k, int(ref["S"].max()))
+    assert np.array_equal(on["cand"], filter_ref.candidates(contigs, ref["S"], k, W, fs["bound"]))
+    assert len(on["dips"]) > 0
+
+
+@pytest.mark.parametrize("k,N,nk", [(5, 300, 16), (6, 7, 284), (6, 300, 100)])   # (cells whose numpy set is empty)
+def test_no_candidates(monkeypatch, k, N, nk):
+    """Plants mutated at 4 % and a threshold no window meets: the filter runs, names nothing, and the scan walks one region per
+    record with a window (its first windows) and finds nothing."""
+    ref = fc.family(k, N, nk)
+    W = ref["ws"]
+    contigs, _ = fc.genome(k, nk, ref["base"], plant_rate=0.04)
+    contigs[0] = contigs[0][:fc.TANDEM_AT] + contigs[0][:fc.PLANT_EVERY][-10_000:] + contigs[0][fc.TANDEM_AT + 10_000:]   # no exact copy
+    assert len(contigs[0]) == fc.LONG
+    T, T_hi = filter_ref.threshold_band(0.01, k, N)
+    U = filter_ref.bound_U(ref["S"], N, k, W, T, T_hi)
+    assert U > 0 and len(filter_ref.candidates(contigs, ref["S"], k, W, U)) == 0
+    on, ohits = _on_off_oracle(monkeypatch, contigs, ref, 0.01, k=k, W=W, all_flags=(0,))
+    fs = on["fstats"][0]
+    assert fs["bound"] == U and fs["form"] == fc.form_of(k, int(ref["S"].max()))
+    assert len(on["cand"]) == 0 and fs["granules"] == 0
+    assert fs["regions"] == sum(len(c) >= W for c in contigs) == len(contigs) - 1
+    assert len(on["hits"]) == 0 and len(ohits) == 0 and len(on["dips"]) == 0
+
+
+@pytest.mark.parametrize("k,N", [(5, 300), (6, 7)])
+def test_bound_not_positive(monkeypatch, k, N):
+    """A threshold above every window's distance: U <= 0, every window would be a candidate and the filter is skipped (no
+    fallback, the bound stays 0); every record with a window is one long dip."""
+    c = fc.cell(k, N, 34)
+    ref, W, contigs = c["ref"], c["W"], c["contigs"]
+    thr = float(np.ceil(max(int(d.max()) for d in c["D"] if d.size) / (2.0 * k * N * N))) + 1.0
+    T, T_hi = filter_ref.threshold_band(thr, k, N)
+    assert filter_ref.bound_U(ref["S"], N, k, W, T, T_hi) <= 0
+    on, _ = _on_off_oracle(monkeypatch, contigs, ref, thr, expect_ran=False, k=k, W=W, all_flags=(0,))
+    assert on["fstats"][0]["bound"] == 0 and len(on["cand"]) == 0
+    # (a record's first window is never tested: records of one window have no dip; the dip is open at the record's end)
+    assert sorted(d["contig"] for d in on["dips"]) == [r for r, seq in enumerate(contigs) if len(seq) > W]
+    assert all(d["end"] == len(contigs[d["contig"]]) - W + 1 for d in on["dips"])
+
+
+def test_fallback_reports_the_device_set(monkeypatch):
+    """A threshold at which more than half of the granules are candidates: the scan falls back (FILTER_FRACTION), the results
+    are the unfiltered scan's and kgma_get_filter_candidates still serves the kernel's set -- the numpy set."""
+    k, N, nk = 5, 7, 34
+    c = fc.cell(k, N, nk)
+    ref, W, contigs = c["ref"], c["W"], c["contigs"]
+    n_gran = sum((len(seq) - W + 16) // 16 for seq in contigs if len(seq) >= W)
+    Dall = np.sort(np.concatenate(c["D"]))
+    thr = round(float(Dall[int(0.4 * Dall.size)]) / (2.0 * k * N * N), 2)       # four windows in ten are below it
+    T, T_hi = filter_ref.threshold_band(thr, k, N)
+    U = filter_ref.bound_U(ref["S"], N, k, W, T, T_hi)
+    want = filter_ref.candidates(contigs, ref["S"], k, W, U)
+    assert U > 0 and len(want) > 0.6 * n_gran                            # (candidate windows alone pass FILTER_MAX_FRACTION = 0.5)
+    on = _scan(monkeypatch, contigs, ref, thr, 0, True, k=k)
+    off = _scan(monkeypatch, contigs, ref, thr, 0, False, k=k)
+    _same(on, off)
+    fs = on["fstats"][0]
+    assert (fs["ran"], fs["fell_back"], fs["reason"]) == (1, 1, _lib.FILTER_FRACTION), fs
+    assert fs["bound"] == U and fs["form"] == fc.form_of(k, int(ref["S"].max()))
+    assert np.array_equal(on["cand"], want) and fs["granules"] == len(want)
