@@ -269,6 +269,27 @@ int kgma_genome_poke(kgma_ctx *ctx, kgma_genome *g, int64_t contig, int64_t pos,
  * benchmarks that time pack + scan). */
 int kgma_genome_repack(kgma_ctx *ctx, kgma_genome *g);
 
+/* A new device-resident genome whose record c is the reverse complement of record c of `g` (same number of
+ * records, same lengths, same header lines).  Made on the device from the resident residue text: no host copy
+ * (one kernel, 1 byte read and 1 written per base, then the pack kernel as in kgma_genome_from_host).  No counterpart
+ * in the reference, whose engines read every record left to right only: scanning the new genome finds the genes of
+ * the reverse strand.  The complement keeps the case: A<->T, C<->G, M<->K, R<->Y, V<->B, H<->D; W, S, N and '-' are
+ * their own complements; any other byte is copied, so a residue outside the alphabet is reported (KGMA_E_BADBASE) by
+ * the same scans as on `g`, at its mirrored position.
+ * COORDINATES of every result on the new genome (hits, dips, matches, alignments, kgma_genome_fetch) are those of the
+ * REVERSED records: position p there is position L - p + 1 of the source record (L its length), so a range lo:hi there
+ * is (L - hi + 1):(L - lo + 1) on `g`, and its residues are the reverse complement of that source range.  genome_pos
+ * keeps its meaning (the records' order and lengths are the source's).
+ * `g` is left untouched; it may have no records, and records of length 0.  The result is an ordinary genome (its own
+ * device memory, about the size of `g`'s; a fresh identity for the scan caches) and is freed with kgma_genome_free.
+ * KGMA_E_ARG for null arguments; KGMA_E_HIP / KGMA_E_NOMEM as kgma_genome_from_host (nothing is left allocated). */
+int kgma_genome_revcomp(kgma_ctx *ctx, const kgma_genome *g, kgma_genome **out);
+/* The kernel of kgma_genome_revcomp alone: overwrites the residue text of `rc` -- a genome with the record lengths of `g`,
+ * such as an earlier kgma_genome_revcomp(g) -- with the reverse complement of `g`'s current text (after kgma_genome_poke on
+ * `g`; benchmarks time this call).  Queued on the context's stream; call kgma_genome_repack(rc) afterwards, as after
+ * kgma_genome_poke.  KGMA_E_ARG when the record lengths differ or g == rc. */
+int kgma_genome_revcomp_into(kgma_ctx *ctx, const kgma_genome *g, kgma_genome *rc);
+
 /* Scan every record of `g`.  mode: KGMA_MODE_*.  buff: `buff`.
  * (What "identical to the reference" means: every window's distance is the exact value; the hit list is the one
  * the reference's Float64 arithmetic produces wherever that does not hang on rounding noise.  Where it does -- dips

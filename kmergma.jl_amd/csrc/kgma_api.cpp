@@ -83,6 +83,8 @@ int scan_tile_stride_words(int nk);
 int scan_nblocks(int nk);
 int64_t exact_tile_starts(bool two_bit);
 hipError_t launch_exact(const ExactArgs &a, int kind, int64_t n_tiles, hipStream_t st);
+int64_t revcomp_tile_bytes();
+hipError_t launch_revcomp(const RevcompArgs &a, int64_t n_tiles, hipStream_t st);
 int kdist_grid(int k, int64_t n_seqs);
 hipError_t launch_kdist(int mode, const uint8_t *seqs, const int64_t *off, int64_t n_seqs, int k, const double *ref,
                         uint32_t *scratch, double scale, double *out, unsigned long long *first_bad, hipStream_t st);
@@ -366,6 +368,9 @@ struct kgma_ctx {
     ExactMatch *d_xout = nullptr; int64_t xout_cap = 0;
     unsigned long long *d_xctl = nullptr; int64_t xctl_cap = 0;
     std::vector<kgma_match> matches;
+    // reverse complement (kgma_genome_revcomp): the tile table of the last call, on the device and as uploaded
+    int64_t *d_rcprefix = nullptr; int64_t rcprefix_cap = 0;
+    std::vector<int64_t> rcprefix;
     std::vector<int64_t> contig_len;
     int64_t n_dists_per_kfv = 0;
     int64_t tile_windows = KGMA_TILE_WINDOWS;
@@ -795,6 +800,7 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_xprefix) (void)hipFree(ctx->d_xprefix);
     if (ctx->d_xout) (void)hipFree(ctx->d_xout);
     if (ctx->d_xctl) (void)hipFree(ctx->d_xctl);
+    if (ctx->d_rcprefix) (void)hipFree(ctx->d_rcprefix);
     if (ctx->evp0) (void)hipEventDestroy(ctx->evp0);
     if (ctx->evp1) (void)hipEventDestroy(ctx->evp1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1609,6 +1615,65 @@ int kgma_genome_synthetic(kgma_ctx *ctx, const int64_t *contig_len, int64_t n_co
         return fail(ctx, KGMA_E_HIP, "synthetic genome generation failed: %s", hipGetErrorString(he));
     }
     rc = kgma_genome_repack(ctx, g);
+    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
+    *out = g;
+    return KGMA_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// reverse complement of a resident genome (kgma_revcomp.hip)
+// ------------------------------------------------------------------------------------------
+int kgma_genome_revcomp_into(kgma_ctx *ctx, const kgma_genome *g, kgma_genome *rc)
+{
+    if (!ctx) return KGMA_E_ARG;
+    if (!g || !rc) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: null argument");
+    if (g == rc) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: source and destination are the same genome");
+    const int64_t nc = g->n_contigs;
+    bool same = rc->n_contigs == nc && rc->ascii_bytes == g->ascii_bytes;
+    for (int64_t c = 0; c < nc && same; c++) same = rc->cd[(size_t)c].len == g->cd[(size_t)c].len;
+    if (!same) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: the genomes' record lengths differ");
+    (void)hipSetDevice(ctx->device);
+    // a record's slot in the text: its residues rounded up to 32 bytes + 32 (genome_layout); the kernel writes all of it
+    const int64_t per_tile = revcomp_tile_bytes();
+    std::vector<int64_t> prefix((size_t)nc + 1, 0);
+    for (int64_t c = 0; c < nc; c++) {
+        const int64_t slot = ((g->cd[(size_t)c].len + 31) & ~31ll) + 32;
+        prefix[(size_t)c + 1] = prefix[(size_t)c] + (slot + per_tile - 1) / per_tile;
+    }
+    const int64_t n_tiles = prefix[(size_t)nc];
+    if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_genome_revcomp: %lld tiles exceed one launch", (long long)n_tiles);
+    if (!ctx->d_rcprefix || prefix != ctx->rcprefix) {
+        // (a launch of an earlier call may still be reading the table it was given)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->rcprefix.clear();
+        int rc_ = dev_reserve(ctx, ctx->d_rcprefix, ctx->rcprefix_cap, nc + 1);
+        if (rc_) return rc_;
+        HIP_TRY(ctx, hipMemcpy(ctx->d_rcprefix, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        ctx->rcprefix = prefix;
+    }
+    RevcompArgs a{};
+    a.src = g->d_ascii; a.dst = rc->d_ascii; a.cd = rc->d_cd; a.tile_prefix = ctx->d_rcprefix; a.n_contigs = (int32_t)nc;
+    HIP_TRY(ctx, launch_revcomp(a, n_tiles, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(rc->d_ascii + (rc->ascii_bytes - 64), 0, 64, ctx->stream));      // the text's 64 tail bytes
+    rc->text_dirty = true;
+    return KGMA_OK;
+}
+
+int kgma_genome_revcomp(kgma_ctx *ctx, const kgma_genome *src, kgma_genome **out)
+{
+    if (!ctx) return KGMA_E_ARG;
+    if (!src || !out) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp: null argument");
+    *out = nullptr;
+    kgma_genome *g = new (std::nothrow) kgma_genome();
+    if (!g) return fail(ctx, KGMA_E_NOMEM, "out of host memory");
+    std::vector<int64_t> lens((size_t)src->n_contigs);
+    for (int64_t c = 0; c < src->n_contigs; c++) lens[(size_t)c] = src->cd[(size_t)c].len;
+    int rc = genome_layout(ctx, g, lens.data(), src->n_contigs);
+    if (rc == KGMA_OK) {
+        g->headers = src->headers;
+        rc = kgma_genome_revcomp_into(ctx, src, g);
+    }
+    if (rc == KGMA_OK) rc = kgma_genome_repack(ctx, g);
     if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
     *out = g;
     return KGMA_OK;

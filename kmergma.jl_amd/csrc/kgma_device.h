@@ -303,4 +303,16 @@ struct ExactArgs {
     unsigned long long cap;
 };
 
+// Reverse complement of the residue text (kgma_revcomp.hip; kgma_genome_revcomp).  Source and destination have the same layout.
+constexpr int KGMA_REVCOMP_THREADS = 256;
+constexpr int KGMA_REVCOMP_ITERS = 4;                          // 16-byte chunks a lane takes per tile (a tile: 16 KiB of a record's slot)
+struct RevcompArgs {
+    const uint8_t *src;           // the source genome's residue text
+    uint8_t *dst;                 // the destination's: every byte of every record's slot is written
+    const ContigDesc *cd;
+    const int64_t *tile_prefix;   // [n_contigs + 1]: tiles of the records before record c (a tile never spans two records)
+    int32_t n_contigs;
+    int32_t pad;
+};
+
 }  // namespace kgma

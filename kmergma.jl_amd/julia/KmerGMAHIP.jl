@@ -93,6 +93,36 @@ function genome_from_record(ctx::Context, record::FASTA.Record)
     return DeviceGenome(ctx, g[])
 end
 
+# the records of `g` reverse-complemented on the device (kgma_genome_revcomp): a new genome with the same record lengths and
+# header lines.  Results on it are in the reversed records' coordinates: position p there is L - p + 1 on `g`.
+function genome_revcomp(g::DeviceGenome)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(g.ctx, ccall((:kgma_genome_revcomp, libkgma), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), g.ctx.h, g.h, r))
+    return DeviceGenome(g.ctx, r[])
+end
+
+contig_len(g::DeviceGenome, contig::Integer) = ccall((:kgma_genome_contig_len, libkgma), Int64, (Ptr{Cvoid}, Int64), g.h, contig)
+
+# lo:hi of a record of length L in the coordinates of its reverse complement (its own inverse)
+strand_range(L::Integer, r::UnitRange) = (L - last(r) + 1):(L - first(r) + 1)
+
+check_strand(strand::String) = strand in ("+", "-", "both") || throw(ArgumentError("strand must be \"+\", \"-\" or \"both\""))
+
+# run(genome, minus::Bool) on `g` and / or on its reverse complement; with "both" the reversed genome is made after the
+# forward results have been taken and freed before returning (two genomes on the device at the peak)
+function for_strands(run::Function, g::DeviceGenome, strand::String)
+    strand != "-" && run(g, false)
+    if strand != "+"
+        rc = genome_revcomp(g)
+        try
+            run(rc, true)
+        finally
+            free!(rc)
+        end
+    end
+    return nothing
+end
+
 free!(g::DeviceGenome) = (g.h == C_NULL || ccall((:kgma_genome_free, libkgma), Cvoid, (Ptr{Cvoid}, Ptr{Cvoid}), g.ctx.h, g.h); g.h = C_NULL; nothing)
 
 function identifier(g::DeviceGenome, contig::Integer)
@@ -187,11 +217,16 @@ scan_flags(do_return_dists::Bool, float_chain::Bool) =
 # the body shared by ac_gma_testing! and record_KmerGMA!: scan `g` with the single engine and build the records
 function single_engine!(ctx::Context, g::DeviceGenome, ident::Function; refVec, consensus_refseq, k, windowsize, thr, buff,
                         do_align, result_align_vec, gap_open_score, gap_extend_score, do_return_dists, dist_vec,
-                        do_return_align, get_hit_loci, hit_loci_vec, resultVec, n_refs, with_genome_pos::Bool, float_chain::Bool)
-    nref = n_refs === nothing ? C_NULL : Int64[n_refs]
-    check(ctx, ccall((:kgma_set_refs, libkgma), Cint,
-        (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
-        ctx.h, k, 1, collect(Float64, refVec), Int64[windowsize], Float64[thr], nref))
+                        do_return_align, get_hit_loci, hit_loci_vec, resultVec, n_refs, with_genome_pos::Bool, float_chain::Bool,
+                        minus::Bool = false, set_refs::Bool = true)
+    # (minus: `g` is the reverse complement of the caller's genome -- hits come back in its coordinates and are reported in
+    #  forward coordinates with " | Strand = -"; the body stays the reversed genome's lo:hi, the gene in reference orientation)
+    if set_refs
+        nref = n_refs === nothing ? C_NULL : Int64[n_refs]
+        check(ctx, ccall((:kgma_set_refs, libkgma), Cint,
+            (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+            ctx.h, k, 1, collect(Float64, refVec), Int64[windowsize], Float64[thr], nref))
+    end
     st = AlignState(g, [consensus_refseq], windowsize,
         AffineGapScoreModel(EDNAFULL, gap_open = gap_open_score, gap_extend = gap_extend_score),
         do_return_align, result_align_vec)
@@ -206,15 +241,17 @@ function single_engine!(ctx::Context, g::DeviceGenome, ident::Function; refVec, 
     bodies = hit_bodies(g, hits)
     for (h, body) in zip(hits, bodies)
         seq_UnitRange = Int(h.lo):Int(h.hi)
+        minus && (seq_UnitRange = strand_range(contig_len(g, h.contig), seq_UnitRange))
         # the reference's record format: src/Alignment.jl:69-80 (append_hit!, do_overlap = false);
         # record_KmerGMA! omits GenomePos (src/MultiThread/GenomeMiner.jl:87-93)
         header = ident(h.contig) *
             " | dist = " * string(round(h.dist, digits = 2)) *
             " | MatchPos = $seq_UnitRange" *
             (with_genome_pos ? " | GenomePos = $(h.genome_pos)" : "") *
-            " | Len = " * string(last(seq_UnitRange) - first(seq_UnitRange) + 1)
+            " | Len = " * string(last(seq_UnitRange) - first(seq_UnitRange) + 1) *
+            (minus ? " | Strand = -" : "")
         push!(resultVec, FASTA.Record(header, body))
-        get_hit_loci && push!(hit_loci_vec, h.lo + h.genome_pos)
+        get_hit_loci && push!(hit_loci_vec, first(seq_UnitRange) + h.genome_pos)
     end
     do_return_dists && fetch_dists!(ctx, 1, dist_vec)
     return nothing
@@ -223,7 +260,12 @@ end
 """
     ac_gma_testing!(; kwargs...)   -- same keywords as KmerGMA.ac_gma_testing! (src/GenomeMiner.jl:4-23)
 plus `n_refs` (number of reference sequences averaged into refVec; inferred when omitted) and `float_chain`
-(default true: rounding-dependent ties decided by the reference's running Float64 distance, KGMA_F_CHAIN_REPLAY).
+(default true: rounding-dependent ties decided by the reference's running Float64 distance, KGMA_F_CHAIN_REPLAY), and
+`strand`: "+" (default, the reference's scan), "-" (the same scan over the reverse complement of every record, made on the
+device; hits reported in forward coordinates, lo:hi -> (L - hi + 1):(L - lo + 1), with " | Strand = -" appended to the header
+and the gene in reference orientation as the body) or "both" (the plus results, then the minus results; not de-duplicated,
+a palindromic region may be reported twice).  With `do_return_align` the BioAlignments objects of minus hits are those of the
+gene-oriented segments.
 """
 function ac_gma_testing!(; genome_path::String, refVec::Vector{Float64}, consensus_refseq::KmerGMA.Seq,
     k::Int64 = 6, windowsize::Int64 = 289, thr::Union{Int64, Float64} = 33.5, buff::Int64 = 50,
@@ -232,14 +274,18 @@ function ac_gma_testing!(; genome_path::String, refVec::Vector{Float64}, consens
     do_return_dists::Bool = false, dist_vec = Float64[], do_return_align::Bool = false,
     get_hit_loci::Bool = false, hit_loci_vec::Vector{Int} = Int[],
     resultVec::Vector{FASTA.Record} = FASTA.Record[], n_refs::Union{Nothing, Int} = nothing,
-    float_chain::Bool = true, ctx::Context = default_context())
+    float_chain::Bool = true, strand::String = "+", ctx::Context = default_context())
 
+    check_strand(strand)
     mask == unsigned(4^k - 1) || error("mask must be 4^k - 1")
     g = genome_from_fasta(ctx, genome_path)
     try
-        single_engine!(ctx, g, c -> identifier(g, c); refVec, consensus_refseq, k, windowsize, thr, buff, do_align,
-            result_align_vec, gap_open_score, gap_extend_score, do_return_dists, dist_vec, do_return_align,
-            get_hit_loci, hit_loci_vec, resultVec, n_refs, with_genome_pos = true, float_chain)
+        for_strands(g, strand) do gs, minus
+            single_engine!(ctx, gs, c -> identifier(gs, c); refVec, consensus_refseq, k, windowsize, thr, buff, do_align,
+                result_align_vec, gap_open_score, gap_extend_score, do_return_dists, dist_vec, do_return_align,
+                get_hit_loci, hit_loci_vec, resultVec, n_refs, with_genome_pos = true, float_chain, minus,
+                set_refs = !(minus && strand == "both"))
+        end
     finally
         free!(g)
     end
@@ -274,7 +320,8 @@ end
 
 """
     Omn_KmerGMA!(; kwargs...)   -- same keywords as KmerGMA.Omn_KmerGMA! (src/OmnGenomeMiner.jl:7-30)
-plus `n_refs::Vector{Int}` (reference count per cluster) and `float_chain`.
+plus `n_refs::Vector{Int}` (reference count per cluster), `float_chain` and `strand` ("+", "-" or "both": as
+ac_gma_testing!; with "both" every KFV's distances are its plus vector followed by its minus vector).
 """
 function Omn_KmerGMA!(; genome_path::String, refVecs::Vector{Vector{Float64}}, windowsizes::Vector{Int64},
     consensus_seqs::Vector{KmerGMA.Seq}, resultVec::Vector{FASTA.Record}, k::Int64 = 6, ScaleFactor::Real = 1/6,
@@ -283,47 +330,53 @@ function Omn_KmerGMA!(; genome_path::String, refVecs::Vector{Vector{Float64}}, w
     gap_extend_score::Int = -1, genome_pos::Int64 = 0, get_hit_loci::Bool = false,
     hit_loci_vec::Vector{Int} = Int[], get_aligns::Bool = false, do_return_dists::Bool = false,
     dist_vec_vec::Vector{Vector{Float64}} = [Float64[] for _ in 1:6],
-    n_refs::Union{Nothing, Vector{Int}} = nothing, float_chain::Bool = true, ctx::Context = default_context())
+    n_refs::Union{Nothing, Vector{Int}} = nothing, float_chain::Bool = true, strand::String = "+",
+    ctx::Context = default_context())
 
+    check_strand(strand)
     m = length(windowsizes)
     refmat = reduce(vcat, refVecs[1:m])                  # m x 4^k, row-major as the C side expects
     nref = n_refs === nothing ? C_NULL : Int64.(n_refs)
     check(ctx, ccall((:kgma_set_refs, libkgma), Cint,
         (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
         ctx.h, k, m, refmat, Int64.(windowsizes), Float64.(thr_vec[1:m]), nref))
-    g = genome_from_fasta(ctx, genome_path)
+    g0 = genome_from_fasta(ctx, genome_path)
     try
-        st = AlignState(g, consensus_seqs, 0,
-            AffineGapScoreModel(EDNAFULL, gap_open = gap_open_score, gap_extend = gap_extend_score),
-            get_aligns, align_vec)
-        cb = align_hits ? @cfunction(align_trampoline, Cvoid,
-            (Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64})) : C_NULL
-        GC.@preserve st begin
-            check(ctx, ccall((:kgma_scan, libkgma), Cint,
-                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Int64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
-                ctx.h, g.h, KGMA_MODE_OMN, buff, genome_pos, scan_flags(do_return_dists, float_chain),
-                cb, pointer_from_objref(st)))
-        end
-        hits = fetch_hits(ctx)
-        bodies = hit_bodies(g, hits)
-        for (h, body) in zip(hits, bodies)
-            seq_UnitRange = Int(h.lo):Int(h.hi)
-            # record construction as in src/OmnGenomeMiner.jl:141-149
-            push!(resultVec, FASTA.Record(
-                identifier(g, h.contig) *
-                    " | Dist = " * string(round(h.dist, digits = 2)) *
-                    " | KFV = $(h.kfv)" *
-                    " | MatchPos = $seq_UnitRange" *
-                    " | GenomePos = $(h.genome_pos)" *
-                    " | Len = " * string(last(seq_UnitRange) - first(seq_UnitRange) + 1),
-                body))
-            get_hit_loci && push!(hit_loci_vec, first(seq_UnitRange) + h.genome_pos)
-        end
-        if do_return_dists
-            for j in 1:m; fetch_dists!(ctx, j, dist_vec_vec[j]) end
+        for_strands(g0, strand) do g, minus
+            st = AlignState(g, consensus_seqs, 0,
+                AffineGapScoreModel(EDNAFULL, gap_open = gap_open_score, gap_extend = gap_extend_score),
+                get_aligns, align_vec)
+            cb = align_hits ? @cfunction(align_trampoline, Cvoid,
+                (Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64})) : C_NULL
+            GC.@preserve st begin
+                check(ctx, ccall((:kgma_scan, libkgma), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Int64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
+                    ctx.h, g.h, KGMA_MODE_OMN, buff, genome_pos, scan_flags(do_return_dists, float_chain),
+                    cb, pointer_from_objref(st)))
+            end
+            hits = fetch_hits(ctx)
+            bodies = hit_bodies(g, hits)
+            for (h, body) in zip(hits, bodies)
+                seq_UnitRange = Int(h.lo):Int(h.hi)
+                minus && (seq_UnitRange = strand_range(contig_len(g, h.contig), seq_UnitRange))
+                # record construction as in src/OmnGenomeMiner.jl:141-149
+                push!(resultVec, FASTA.Record(
+                    identifier(g, h.contig) *
+                        " | Dist = " * string(round(h.dist, digits = 2)) *
+                        " | KFV = $(h.kfv)" *
+                        " | MatchPos = $seq_UnitRange" *
+                        " | GenomePos = $(h.genome_pos)" *
+                        " | Len = " * string(last(seq_UnitRange) - first(seq_UnitRange) + 1) *
+                        (minus ? " | Strand = -" : ""),
+                    body))
+                get_hit_loci && push!(hit_loci_vec, first(seq_UnitRange) + h.genome_pos)
+            end
+            if do_return_dists
+                for j in 1:m; fetch_dists!(ctx, j, dist_vec_vec[j]) end
+            end
         end
     finally
-        free!(g)
+        free!(g0)
     end
     return nothing
 end

@@ -35,7 +35,7 @@ EXPORTS = [
     "kgma_chain_values", "kgma_host_chain_walk", "kgma_chain_chunk_steps", "kgma_set_chain_source", "kgma_get_att", "kgma_set_att",
     "kgma_chain_export", "kgma_chain_export_copy", "kgma_kfv_scale", "kgma_kfv_is_float",
     "kgma_set_strobe_ref", "kgma_strobe_scan", "kgma_exact_match", "kgma_get_matches",
-    "kgma_get_filter_stats", "kgma_get_filter_candidates",
+    "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
 ]
 FILTER_OK, FILTER_OVERFLOW, FILTER_STREAMS, FILTER_FRACTION, FILTER_REMEMBERED = 0, 1, 2, 3, 4
 
@@ -154,6 +154,8 @@ def load():
     L.kgma_genome_free.restype = None
     L.kgma_genome_repack.argtypes = [vp, vp]
     L.kgma_genome_poke.argtypes = [vp, vp, i64, i64, i64, C.c_char_p]
+    L.kgma_genome_revcomp.argtypes = [vp, vp, P(vp)]
+    L.kgma_genome_revcomp_into.argtypes = [vp, vp, vp]
     L.kgma_scan.argtypes = [vp, vp, i32, i64, i64, u32, ALIGN_FN, vp]
     L.kgma_scan_device.argtypes = [vp, vp, i32, u32]
     L.kgma_get_hits.argtypes = [vp, P(KgmaHit), i64, P(i64)]
@@ -317,6 +319,18 @@ class Genome:
 
     def repack(self) -> None:
         self._ctx._check(load().kgma_genome_repack(self._ctx._h, self._h))
+
+    def revcomp(self) -> "Genome":
+        """kgma_genome_revcomp: a new device genome whose record c is the reverse complement of this genome's record c
+        (same lengths and headers), made on the device.  Results on it are in the reversed records' coordinates: position
+        p there is L - p + 1 here.  This genome is left as it is; free the new one like any other."""
+        h = C.c_void_p()
+        self._ctx._check(load().kgma_genome_revcomp(self._ctx._h, self._h, C.byref(h)))
+        return Genome(self._ctx, h)
+
+    def revcomp_into(self, rc: "Genome") -> None:
+        """kgma_genome_revcomp_into: the kernel alone, into a genome of the same record lengths (repack() it afterwards)."""
+        self._ctx._check(load().kgma_genome_revcomp_into(self._ctx._h, self._h, rc._h))
 
     def free(self) -> None:
         if self._h is not None:

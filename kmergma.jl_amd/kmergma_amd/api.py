@@ -25,6 +25,10 @@ Differences a caller can observe (all documented in DESIGN.md):
     thresholds reproduce the reference bit for bit).
   * `do_align=True` needs an `aligner` callable (see `kmergma_amd.align`); the default is the
     package's restatement of BioAlignments' semi-global affine alignment.
+  * `strand=` (no counterpart in the reference, which reads every record left to right only): "+" (default) is the
+    reference's scan; "-" scans the reverse complement of every record, made on the device from the resident text
+    (kgma_genome_revcomp), and reports the hits in FORWARD coordinates with ` | Strand = -` in the header and the gene in
+    reference orientation as the body; "both" returns the plus results followed by the minus results (`strand_range`).
 """
 from __future__ import annotations
 
@@ -83,8 +87,67 @@ class _GenomeView:
             return [self._recs[c].sequence[lo - 1:hi] if hi >= lo else b"" for c, lo, hi in ranges]
         return self.genome.fetch_batch([(c, lo, max(hi - lo + 1, 0)) for c, lo, hi in ranges])
 
+    def reversed(self) -> "_GenomeView":
+        """The same records reverse-complemented ON THE DEVICE (kgma_genome_revcomp): same headers, same lengths.  Its
+        subsequences -- bodies of minus-strand hits, segments for an aligner -- always come from the reversed device genome,
+        also when this view was built from host records.  The caller frees it."""
+        v = object.__new__(_GenomeView)
+        v.genome = self.genome.revcomp()
+        v.descriptions = self.descriptions
+        v._recs = None
+        return v
+
     def free(self):
         self.genome.free()
+
+
+STRANDS = ("+", "-", "both")
+
+
+def _check_strand(strand) -> None:
+    if strand not in STRANDS:
+        raise ValueError(f"strand must be one of '+', '-', 'both', not {strand!r}")
+
+
+def strand_range(L: int, lo: int, hi: int):
+    """lo:hi (1-based, inclusive) of a record of length L in the coordinates of its reverse complement: position p is
+    L - p + 1 there, so the range is (L - hi + 1):(L - lo + 1).  The map is its own inverse."""
+    return L - hi + 1, L - lo + 1
+
+
+def _for_strands(view: _GenomeView, strand: str, run) -> None:
+    """run(view, "+") and / or run(reversed view, "-").  With "both" the reversed genome is made after the forward scan's
+    results have been taken, and freed before returning: two genomes on the device at the peak."""
+    if strand != "-":
+        run(view, "+")
+    if strand != "+":
+        rc = view.reversed()
+        try:
+            run(rc, "-")
+        finally:
+            rc.free()
+
+
+def _emit_hits(view, strand, hits, header_of, resultVec, hit_loci_vec) -> None:
+    """The FASTA records of a scan's hits.  Minus strand: `view` is the reversed genome and the hits are in its coordinates;
+    the body is the reversed genome's lo:hi (the gene in reference orientation), header and locus use the forward range."""
+    bodies = view.subseqs((h["contig"], h["lo"], h["hi"]) for h in hits)
+    for h, body in zip(hits, bodies):
+        lo, hi = h["lo"], h["hi"]
+        if strand == "-":
+            lo, hi = strand_range(view.genome.contig_len(h["contig"]), lo, hi)
+        resultVec.append(Record(header_of(h, lo, hi), body))
+        if hit_loci_vec is not None:
+            hit_loci_vec.append(lo + h["genome_pos"])
+
+
+def _emit_aligns(view, strand, aligns, out) -> None:
+    """Alignment tuples (contig, kfv, lo, hi, first, last): lo:hi in forward coordinates; first / last stay relative to the
+    aligned segment, which is gene-oriented on either strand."""
+    for c, kfv, lo, hi, first, last in aligns:
+        if strand == "-":
+            lo, hi = strand_range(view.genome.contig_len(c), lo, hi)
+        out.append((c, kfv, lo, hi, first, last))
 
 
 def _check_derived(k: int, mask, ScaleFactor) -> None:
@@ -118,44 +181,55 @@ def ac_gma_testing(*, genome_path, refVec, consensus_refseq: bytes = b"", k: int
                    do_return_align: bool = False, get_hit_loci: bool = False,
                    hit_loci_vec: Optional[list] = None, resultVec: Optional[list] = None,
                    n_refs: Optional[int] = None, aligner: Optional[Callable] = None,
-                   with_genome_pos: bool = True, ctx: Optional["_lib.Context"] = None, float_chain: bool = True) -> None:
+                   with_genome_pos: bool = True, ctx: Optional["_lib.Context"] = None, float_chain: bool = True,
+                   strand: str = "+") -> None:
     """`ac_gma_testing!` (src/GenomeMiner.jl:4-109): mutates resultVec / hit_loci_vec / dist_vec.
     float_chain (default on): KGMA_F_CHAIN_REPLAY -- every decision that hangs on the rounding of the reference's
-    running Float64 distance is taken from a host replay of that value (kgma.h)."""
+    running Float64 distance is taken from a host replay of that value (kgma.h).
+    strand: "+" (default) is the reference's scan.  "-" is the same scan over the reverse complement of every record (same
+    headers, same order; made on the device), each hit then rewritten to forward coordinates: lo:hi ->
+    (L - hi + 1):(L - lo + 1), header from that range with ` | Strand = -` appended, locus = forward lo + GenomePos, body =
+    the gene in reference orientation (the reverse complement of the forward range); alignment tuples get the same range
+    map, their first / last stay relative to the gene-oriented segment.  "both": the plus results, then the minus results
+    in the order the engine emitted them (distances: the plus vector, then the minus vector).  Hits are NOT de-duplicated
+    between the strands: a palindromic region may be reported twice."""
+    _check_strand(strand)
     _check_derived(k, mask, ScaleFactor)
     resultVec = resultVec if resultVec is not None else []
     ctx = ctx or default_context()
     ctx.set_refs(k, [np.asarray(refVec, dtype=np.float64)], [int(windowsize)], [float(thr)],
                  None if n_refs is None else [int(n_refs)])
     view = _GenomeView(ctx, genome_path)
-    genome = view.genome
-    try:
-        cb = None
-        device_align = do_align and aligner is None and int(windowsize) + 2 * int(buff) <= 8191
-        if do_align and not device_align:
-            if aligner is None:
-                from .align import align_range as aligner  # noqa: N813
-            cb = _make_align_cb(aligner, view, lambda kfv: consensus_refseq, lambda kfv: int(windowsize),
-                                gap_open_score, gap_extend_score, result_align_vec if do_return_align else None)
-        flags = (_lib.F_RETURN_DISTS if do_return_dists else 0) | (_lib.F_CHAIN_REPLAY if float_chain else 0)
+    device_align = do_align and aligner is None and int(windowsize) + 2 * int(buff) <= 8191
+    if do_align and not device_align and aligner is None:
+        from .align import align_range as aligner  # noqa: N813
+    flags = (_lib.F_RETURN_DISTS if do_return_dists else 0) | (_lib.F_CHAIN_REPLAY if float_chain else 0)
+
+    def run(v, sd):
+        aligns: list = []
         if device_align:
             # the single engine's alignment does not feed back into the hit state machine
             # (GenomeMiner.jl:96-99): all hits of the scan are re-aligned in one device batch
-            ctx.scan_aligned(genome, _lib.MODE_SINGLE, int(buff), 0, flags, [consensus_refseq], gap_open_score, gap_extend_score)
-            if do_return_align and result_align_vec is not None:
-                result_align_vec.extend((a["contig"], 0, a["lo"], a["hi"], a["first"], a["last"]) for a in ctx.alignments()[0])
+            ctx.scan_aligned(v.genome, _lib.MODE_SINGLE, int(buff), 0, flags, [consensus_refseq], gap_open_score, gap_extend_score)
+            if do_return_align:
+                aligns.extend((a["contig"], 0, a["lo"], a["hi"], a["first"], a["last"]) for a in ctx.alignments()[0])
         else:
-            ctx.scan(genome, _lib.MODE_SINGLE, int(buff), 0, flags, cb)
-        hits = ctx.hits()
-        bodies = view.subseqs((h["contig"], h["lo"], h["hi"]) for h in hits)
-        for h, body in zip(hits, bodies):
-            c = h["contig"]
-            hdr = headers.single_header(view.identifier(c), h["dist"], h["lo"], h["hi"], h["genome_pos"], with_genome_pos)
-            resultVec.append(Record(hdr, body))
-            if get_hit_loci and hit_loci_vec is not None:
-                hit_loci_vec.append(h["lo"] + h["genome_pos"])
+            cb = None
+            if do_align:
+                cb = _make_align_cb(aligner, v, lambda kfv: consensus_refseq, lambda kfv: int(windowsize),
+                                    gap_open_score, gap_extend_score, aligns if do_return_align else None)
+            ctx.scan(v.genome, _lib.MODE_SINGLE, int(buff), 0, flags, cb)
+        if result_align_vec is not None:
+            _emit_aligns(v, sd, aligns, result_align_vec)
+        _emit_hits(v, sd, ctx.hits(),
+                   lambda h, lo, hi: headers.single_header(v.identifier(h["contig"]), h["dist"], lo, hi, h["genome_pos"],
+                                                           with_genome_pos, strand=sd),
+                   resultVec, hit_loci_vec if get_hit_loci else None)
         if do_return_dists and dist_vec is not None:
             dist_vec.extend(ctx.dists(1).tolist())
+
+    try:
+        _for_strands(view, strand, run)
     finally:
         view.free()
 
@@ -163,12 +237,13 @@ def ac_gma_testing(*, genome_path, refVec, consensus_refseq: bytes = b"", k: int
 def record_KmerGMA(*, record: Record, refVec, consensus_refseq: bytes = b"", resultVec_vec: List[list],
                    k: int = 6, windowsize: int = 289, thr: float = 30, buff: int = 50, do_align: bool = True,
                    gap_open_score: int = -69, gap_extend_score: int = -1, n_refs: Optional[int] = None,
-                   aligner: Optional[Callable] = None, ctx=None) -> None:
-    """`record_KmerGMA!` (src/MultiThread/GenomeMiner.jl:8-98): one record, header without GenomePos."""
+                   aligner: Optional[Callable] = None, ctx=None, strand: str = "+") -> None:
+    """`record_KmerGMA!` (src/MultiThread/GenomeMiner.jl:8-98): one record, header without GenomePos.
+    strand: as ac_gma_testing."""
     ac_gma_testing(genome_path=[record], refVec=refVec, consensus_refseq=consensus_refseq, k=k,
                    windowsize=windowsize, thr=thr, buff=buff, do_align=do_align, gap_open_score=gap_open_score,
                    gap_extend_score=gap_extend_score, resultVec=resultVec_vec[0], n_refs=n_refs, aligner=aligner,
-                   with_genome_pos=False, ctx=ctx)
+                   with_genome_pos=False, ctx=ctx, strand=strand)
 
 
 def Omn_KmerGMA(*, genome_path, refVecs: Sequence, windowsizes: Sequence[int], consensus_seqs: Sequence[bytes] = (),
@@ -178,45 +253,50 @@ def Omn_KmerGMA(*, genome_path, refVecs: Sequence, windowsizes: Sequence[int], c
                 gap_extend_score: int = -1, genome_pos: int = 0, get_hit_loci: bool = False,
                 hit_loci_vec: Optional[list] = None, get_aligns: bool = False, do_return_dists: bool = False,
                 dist_vec_vec: Optional[List[list]] = None, n_refs: Optional[Sequence[int]] = None,
-                aligner: Optional[Callable] = None, ctx=None, float_chain: bool = True) -> None:
+                aligner: Optional[Callable] = None, ctx=None, float_chain: bool = True, strand: str = "+") -> None:
     """`Omn_KmerGMA!` (src/OmnGenomeMiner.jl:7-162).  Without a caller-supplied `aligner` the hits are re-aligned on the
-    device: every dip's candidate range in one batch per KFV, looked up by the hit state machine (kgma_scan_aligned)."""
+    device: every dip's candidate range in one batch per KFV, looked up by the hit state machine (kgma_scan_aligned).
+    strand: "+", "-" or "both", as ac_gma_testing (with "both" every KFV's distances are its plus vector followed by its
+    minus vector; hits are not de-duplicated between the strands)."""
+    _check_strand(strand)
     _check_derived(k, mask, ScaleFactor)
     m = len(windowsizes)
     ctx = ctx or default_context()
     ctx.set_refs(k, [np.asarray(r, dtype=np.float64) for r in refVecs], [int(w) for w in windowsizes],
                  [float(t) for t in list(thr_vec)[:m]], None if n_refs is None else [int(n) for n in n_refs])
     view = _GenomeView(ctx, genome_path)
-    genome = view.genome
-    try:
-        cb = None
-        flags = (_lib.F_RETURN_DISTS if do_return_dists else 0) | (_lib.F_CHAIN_REPLAY if float_chain else 0)
-        device_align = (align_hits and aligner is None and len(consensus_seqs) >= m
-                        and max(int(w) for w in windowsizes) + 2 * int(buff) <= 8191)
+    flags = (_lib.F_RETURN_DISTS if do_return_dists else 0) | (_lib.F_CHAIN_REPLAY if float_chain else 0)
+    device_align = (align_hits and aligner is None and len(consensus_seqs) >= m
+                    and max(int(w) for w in windowsizes) + 2 * int(buff) <= 8191)
+    if align_hits and not device_align and aligner is None:
+        from .align import align_range as aligner  # noqa: N813
+
+    def run(v, sd):
+        aligns: list = []
         if device_align:
             # the cluster engine aligns against the whole consensus_seqs[ind] (OmnGenomeMiner.jl:131)
-            ctx.scan_aligned(genome, _lib.MODE_OMN, int(buff), int(genome_pos), flags, list(consensus_seqs)[:m],
+            ctx.scan_aligned(v.genome, _lib.MODE_OMN, int(buff), int(genome_pos), flags, list(consensus_seqs)[:m],
                              gap_open_score, gap_extend_score)
-            if get_aligns and align_vec is not None:
-                align_vec.extend((a["contig"], a["kfv"], a["lo"], a["hi"], a["first"], a["last"]) for a in ctx.alignments()[0])
+            if get_aligns:
+                aligns.extend((a["contig"], a["kfv"], a["lo"], a["hi"], a["first"], a["last"]) for a in ctx.alignments()[0])
         else:
+            cb = None
             if align_hits:
-                if aligner is None:
-                    from .align import align_range as aligner  # noqa: N813
-                cb = _make_align_cb(aligner, view, lambda kfv: consensus_seqs[kfv - 1], lambda kfv: None,
-                                    gap_open_score, gap_extend_score, align_vec if get_aligns else None)
-            ctx.scan(genome, _lib.MODE_OMN, int(buff), int(genome_pos), flags, cb)
-        hits = ctx.hits()
-        bodies = view.subseqs((h["contig"], h["lo"], h["hi"]) for h in hits)
-        for h, body in zip(hits, bodies):
-            c = h["contig"]
-            hdr = headers.omn_header(view.identifier(c), h["dist"], h["kfv"], h["lo"], h["hi"], h["genome_pos"])
-            resultVec.append(Record(hdr, body))
-            if get_hit_loci and hit_loci_vec is not None:
-                hit_loci_vec.append(h["lo"] + h["genome_pos"])
+                cb = _make_align_cb(aligner, v, lambda kfv: consensus_seqs[kfv - 1], lambda kfv: None,
+                                    gap_open_score, gap_extend_score, aligns if get_aligns else None)
+            ctx.scan(v.genome, _lib.MODE_OMN, int(buff), int(genome_pos), flags, cb)
+        if align_vec is not None:
+            _emit_aligns(v, sd, aligns, align_vec)
+        _emit_hits(v, sd, ctx.hits(),
+                   lambda h, lo, hi: headers.omn_header(v.identifier(h["contig"]), h["dist"], h["kfv"], lo, hi, h["genome_pos"],
+                                                        strand=sd),
+                   resultVec, hit_loci_vec if get_hit_loci else None)
         if do_return_dists and dist_vec_vec is not None:
             for j in range(m):
                 dist_vec_vec[j].extend(ctx.dists(j + 1).tolist())
+
+    try:
+        _for_strands(view, strand, run)
     finally:
         view.free()
 
@@ -243,12 +323,17 @@ def findGenes(*, genome_path: str, ref_path: str, k: int = 6, KmerDistThr=0, buf
               do_align: bool = True, gap_open_score: int = -69, gap_extend_score: int = -1,
               do_return_dists: bool = False, do_return_hit_loci: bool = False, do_return_align: bool = False,
               verbose: bool = True, KmerDist_threshold_buffer: float = 8.0, aligner: Optional[Callable] = None,
-              ctx=None) -> list:
+              ctx=None, strand: str = "+") -> list:
     """`findGenes` (src/API.jl:60-104). Returns [hits, (loci), (aligns), (dists)].
+
+    strand: "+" (default: the reference's scan), "-" (genes on the reverse strand, reported in forward coordinates with
+    ` | Strand = -` in the header and the gene in reference orientation as the body) or "both" (the plus results followed by
+    the minus results; not de-duplicated, a palindromic region may be reported twice): see ac_gma_testing.
 
     Every 1 <= k <= 15 is served.  Reference preparation runs its k-mer counting and kmer_dist batches on the device for
     k <= 10; for k >= 11 it uses the host restatement in refprep (the device refprep entry points stop at k = 10), and the scan
     itself runs on the device at every k."""
+    _check_strand(strand)
     if verbose:
         log.info("pre-processing references and parameters...")
     warn_helper(k, do_return_dists)
@@ -276,7 +361,7 @@ def findGenes(*, genome_path: str, ref_path: str, k: int = 6, KmerDistThr=0, buf
                    do_align=do_align, gap_open_score=gap_open_score, gap_extend_score=gap_extend_score,
                    do_return_dists=do_return_dists, do_return_align=do_return_align,
                    get_hit_loci=do_return_hit_loci, dist_vec=dist_vec, result_align_vec=alignment_vec,
-                   hit_loci_vec=hit_loci_vec, resultVec=hit_vector, n_refs=N, aligner=aligner, ctx=ctx)
+                   hit_loci_vec=hit_loci_vec, resultVec=hit_vector, n_refs=N, aligner=aligner, ctx=ctx, strand=strand)
     info = "genome mining completed successfully, returning vector of: vector of hits"
     out = [hit_vector]
     if do_return_hit_loci:
@@ -294,11 +379,16 @@ def findGenes_cluster_mode(*, genome_path: str, ref_path: str, cluster_cutoffs=(
                            KmerDistThrs: Sequence[float] = (0.0,), buffer: int = 100, do_align: bool = True,
                            gap_open_score: int = -200, gap_extend_score: int = -1, do_return_dists: bool = False,
                            do_return_hit_loci: bool = False, do_return_align: bool = False, verbose: bool = True,
-                           kmerDist_threshold_buffer: float = 7, aligner: Optional[Callable] = None, ctx=None) -> list:
+                           kmerDist_threshold_buffer: float = 7, aligner: Optional[Callable] = None, ctx=None,
+                           strand: str = "+") -> list:
     """`findGenes_cluster_mode` (src/API.jl:161-226).
+
+    strand: "+", "-" or "both", as findGenes (with "both" every KFV's distance vector is its plus vector followed by its
+    minus vector; hits are not de-duplicated between the strands).
 
     Every 1 <= k <= 15 is served; for k >= 11 reference preparation uses the host restatement in refprep (the device refprep
     entry points stop at k = 10), as in findGenes."""
+    _check_strand(strand)
     if verbose:
         log.info("pre-processing references and parameters...")
     warn_helper(k, do_return_dists)
@@ -331,7 +421,7 @@ def findGenes_cluster_mode(*, genome_path: str, ref_path: str, cluster_cutoffs=(
                 align_hits=do_align, gap_open_score=gap_open_score, gap_extend_score=gap_extend_score,
                 get_aligns=do_return_align, get_hit_loci=do_return_hit_loci, hit_loci_vec=hit_loci_vec,
                 align_vec=alignment_vec, do_return_dists=do_return_dists, dist_vec_vec=dist_vec_vec,
-                n_refs=[n for _, n in ints], aligner=aligner, ctx=ctx)
+                n_refs=[n for _, n in ints], aligner=aligner, ctx=ctx, strand=strand)
     info = "genome mining completed successfully, returning vector of: vector of hits"
     out = [hit_vector]
     if do_return_hit_loci:
@@ -352,12 +442,14 @@ def StrobeGMA(*, genome_path, refVec, consensus_refseq: bytes = b"", s: int = 2,
               do_return_dists: bool = False, do_return_align: bool = False, get_hit_loci: bool = False,
               dist_vec: Optional[list] = None, result_align_vec: Optional[list] = None, hit_loci_vec: Optional[list] = None,
               resultVec: Optional[list] = None, n_refs: Optional[int] = None, ctx: Optional["_lib.Context"] = None,
-              float_chain: bool = True) -> None:
+              float_chain: bool = True, strand: str = "+") -> None:
     """`StrobeGMA!` (src/StrobemerGMA/StrobeGenomeMiner.jl:5-95): mutates resultVec / hit_loci_vec / dist_vec /
     result_align_vec.  The scan, the re-alignment of process_hit! (src/Alignment.jl:83-111; the reference's score model
     defaults to gap_open = -69, gap_extend = -5) and its score gate run on the device (kgma_strobe_scan).
     float_chain (default on): KGMA_F_CHAIN_REPLAY -- records whose decisions hang on the rounding of the reference's
-    running Float64 distance are decided by a host replay of that loop (kgma.h)."""
+    running Float64 distance are decided by a host replay of that loop (kgma.h).
+    strand: "+", "-" or "both", as ac_gma_testing (hits are not de-duplicated between the strands)."""
+    _check_strand(strand)
     k = int(w_max) + int(s) - 1
     if ScaleFactor is not None and abs(float(ScaleFactor) - 1.0 / k) > 1e-12:
         raise ValueError(f"ScaleFactor = {ScaleFactor} is not 1/(w_max + s - 1) = 1/{k}")
@@ -365,21 +457,22 @@ def StrobeGMA(*, genome_path, refVec, consensus_refseq: bytes = b"", s: int = 2,
     ctx = ctx or default_context()
     ctx.set_strobe_ref(s, w_min, w_max, q, np.asarray(refVec, dtype=np.float64), int(windowsize), float(thr), n_refs)
     view = _GenomeView(ctx, genome_path)
-    try:
-        flags = (_lib.F_RETURN_DISTS if do_return_dists else 0) | (_lib.F_CHAIN_REPLAY if float_chain else 0)
-        ctx.strobe_scan(view.genome, int(buff), flags, bytes(consensus_refseq) if do_align else None,
+    flags = (_lib.F_RETURN_DISTS if do_return_dists else 0) | (_lib.F_CHAIN_REPLAY if float_chain else 0)
+
+    def run(v, sd):
+        ctx.strobe_scan(v.genome, int(buff), flags, bytes(consensus_refseq) if do_align else None,
                         gap_open_score, gap_extend_score, int(score_threshold))
         if do_align and do_return_align and result_align_vec is not None:
-            result_align_vec.extend((a["contig"], 0, a["lo"], a["hi"], a["first"], a["last"]) for a in ctx.alignments()[0])
-        hits = ctx.hits()
-        bodies = view.subseqs((h["contig"], h["lo"], h["hi"]) for h in hits)
-        for h, body in zip(hits, bodies):
-            hdr = headers.single_header(view.identifier(h["contig"]), h["dist"], h["lo"], h["hi"], h["genome_pos"])
-            resultVec.append(Record(hdr, body))
-            if get_hit_loci and hit_loci_vec is not None:
-                hit_loci_vec.append(h["lo"] + h["genome_pos"])
+            _emit_aligns(v, sd, [(a["contig"], 0, a["lo"], a["hi"], a["first"], a["last"]) for a in ctx.alignments()[0]],
+                         result_align_vec)
+        _emit_hits(v, sd, ctx.hits(),
+                   lambda h, lo, hi: headers.single_header(v.identifier(h["contig"]), h["dist"], lo, hi, h["genome_pos"], strand=sd),
+                   resultVec, hit_loci_vec if get_hit_loci else None)
         if do_return_dists and dist_vec is not None:
             dist_vec.extend(ctx.dists(1).tolist())
+
+    try:
+        _for_strands(view, strand, run)
     finally:
         view.free()
 
@@ -387,8 +480,10 @@ def StrobeGMA(*, genome_path, refVec, consensus_refseq: bytes = b"", s: int = 2,
 def Strobemer_findGenes(*, genome_path: str, ref_path: str, s: int = 2, w_min: int = 3, w_max: int = 5, q: int = 5,
                         KmerDistThr=30, buffer: int = 50, do_align: bool = True, align_score_thr: int = 0,
                         do_return_dists: bool = False, do_return_hit_loci: bool = False, do_return_align: bool = False,
-                        verbose: bool = True, ctx=None, float_chain: bool = True) -> list:
-    """`Strobemer_findGenes` (src/StrobemerGMA/StrobeGenomeMiner.jl:119-158).  Returns [hits, (loci), (aligns), (dists)]."""
+                        verbose: bool = True, ctx=None, float_chain: bool = True, strand: str = "+") -> list:
+    """`Strobemer_findGenes` (src/StrobemerGMA/StrobeGenomeMiner.jl:119-158).  Returns [hits, (loci), (aligns), (dists)].
+    strand: "+", "-" or "both", as findGenes (hits are not de-duplicated between the strands)."""
+    _check_strand(strand)
     RV, windowsize, consensus_refseq, (_S, N) = refprep.gen_ref_ws_cons_strobe(ref_path, s, w_min, w_max, q, return_int=True)
     hit_vector: list = []
     dist_vec: list = []
@@ -401,7 +496,7 @@ def Strobemer_findGenes(*, genome_path: str, ref_path: str, s: int = 2, w_min: i
               score_threshold=align_score_thr, do_align=do_align, do_return_dists=do_return_dists,
               do_return_align=do_return_align, get_hit_loci=do_return_hit_loci, dist_vec=dist_vec,
               result_align_vec=alignment_vec, hit_loci_vec=hit_loci_vec, resultVec=hit_vector, n_refs=N, ctx=ctx,
-              float_chain=float_chain)
+              float_chain=float_chain, strand=strand)
     info = "genome mining completed successfully, returning vector of: vector of hits"
     out = [hit_vector]
     if do_return_hit_loci:

@@ -32,6 +32,17 @@ class Record:
                 and self.sequence.upper() == other.sequence.upper())
 
 
+# The complement of the 16-symbol DNA alphabet, case kept; W, S, N and '-' are their own complements and every other byte
+# maps to itself.  This is the map revcomp_kernel applies on the device (csrc/kgma_revcomp.hip).
+_COMPLEMENT = bytes.maketrans(b"ATCGMKRYVBHDatcgmkryvbhd", b"TAGCKMYRBVDHtagckmyrbvdh")
+
+
+def reverse_complement(seq: bytes) -> bytes:
+    """The reverse complement of residue bytes: A<->T, C<->G, M<->K, R<->Y, V<->B, H<->D in either case; W, S, N, '-'
+    and any byte outside the alphabet are kept as they are (at their mirrored position)."""
+    return bytes(seq).translate(_COMPLEMENT)[::-1]
+
+
 def read_fasta(path: str) -> List[Record]:
     """Parse a FASTA file: multi-line records, blank lines and CR/LF tolerated."""
     records: List[Record] = []

@@ -2,6 +2,9 @@
 
 src/Alignment.jl:57-81 (append_hit!: `dist`), src/OmnGenomeMiner.jl:141-149 (`Dist` + `KFV`),
 src/MultiThread/GenomeMiner.jl:87-93 (no GenomePos).
+
+`strand="-"` (a hit found on the reverse-complemented records, which the reference cannot report) appends
+` | Strand = -` as the last field; `strand="+"` is the reference's header, unchanged.
 """
 from __future__ import annotations
 
@@ -31,13 +34,20 @@ def julia_float_str(x: float) -> str:
     return r
 
 
-def single_header(identifier: str, dist: float, lo: int, hi: int, genome_pos, with_genome_pos: bool = True) -> str:
+def _strand_field(strand: str) -> str:
+    if strand not in ("+", "-"):
+        raise ValueError(f"strand must be '+' or '-', not {strand!r}")
+    return " | Strand = -" if strand == "-" else ""
+
+
+def single_header(identifier: str, dist: float, lo: int, hi: int, genome_pos, with_genome_pos: bool = True,
+                  strand: str = "+") -> str:
     s = f"{identifier} | dist = {julia_float_str(julia_round2(dist))} | MatchPos = {lo}:{hi}"
     if with_genome_pos:
         s += f" | GenomePos = {genome_pos}"
-    return s + f" | Len = {hi - lo + 1}"
+    return s + f" | Len = {hi - lo + 1}" + _strand_field(strand)
 
 
-def omn_header(identifier: str, dist: float, kfv: int, lo: int, hi: int, genome_pos: int) -> str:
+def omn_header(identifier: str, dist: float, kfv: int, lo: int, hi: int, genome_pos: int, strand: str = "+") -> str:
     return (f"{identifier} | Dist = {julia_float_str(julia_round2(dist))} | KFV = {kfv}"
-            f" | MatchPos = {lo}:{hi} | GenomePos = {genome_pos} | Len = {hi - lo + 1}")
+            f" | MatchPos = {lo}:{hi} | GenomePos = {genome_pos} | Len = {hi - lo + 1}" + _strand_field(strand))
