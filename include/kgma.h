@@ -333,7 +333,9 @@ typedef struct kgma_filter_stats {
     int32_t ran;             /* the filter kernel ran in the last scan */
     int32_t fell_back;       /* the full scan ran although the filter applies */
     int32_t reason;          /* KGMA_FILTER_*: why it fell back */
-    int32_t form;            /* the filter kernel's form: S entry bytes (1, 2) | table copies (1, 32) << 8; 0: it did not run */
+    int32_t form;            /* the filter kernel's form: S entry bytes (1, 2) | table copies (1, 32) << 8; 0: it did not run.
+                              * Bit 16: it read the block sums that the step's pack wrote (kgma_repack_scan_hits / kgma_step_begin
+                              * with KGMA_FUSE_SUMS != 0) instead of cutting and looking up the k-mers itself */
     int64_t granules;        /* candidate granules */
     int64_t regions;         /* merged, padded regions (every record's first windows included) */
     int64_t streams;         /* candidate streams the exact kernel walked */
@@ -346,6 +348,10 @@ typedef struct kgma_filter_stats {
 int kgma_get_filter_stats(kgma_ctx *ctx, kgma_filter_stats *out);
 /* The last scan's candidate granules (0-based record, 0-based granule), sorted; two-call pattern as kgma_get_hits. */
 int kgma_get_filter_candidates(kgma_ctx *ctx, int32_t *contig, int64_t *granule, int64_t cap, int64_t *n);
+/* Block sums of record `contig` as the last step whose pack computed them left them (bit 16 of kgma_filter_stats.form): out[i] =
+ * the sum of S over the k-mers that start at 0-based positions 16 b ... 16 b + 15 of the record, b = first_block + i, and do not
+ * pass the record's last k-mer.  A record has 2 * ceil(len / 32) blocks.  KGMA_E_STATE: no such step has run on this genome. */
+int kgma_get_block_sums(kgma_ctx *ctx, const kgma_genome *genome, int64_t contig, int64_t first_block, int64_t n, uint32_t *out);
 
 /* HOST-side helper (not on the device path; a Julia host keeps using BioAlignments.jl): semi-global
  * affine-gap alignment of `a` (global; the consensus) against `b` (leading/trailing residues of b

@@ -47,6 +47,8 @@ hipError_t launch_scan(const ScanArgs &a, const GroupParams &gp, hipStream_t st)
 hipError_t launch_stream(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
 bool filter_applies(int k, int64_t s_max);
 hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, int32_t *form, hipStream_t st);
+bool pack_sums_applies(int k, int64_t s_max);
+hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, hipStream_t st);
 int stream_waves(int k, int nk, int n_kfv, int n_sizes);
 int stream_slots_per_cu(int k, int nk, int nk_min, int n_longer, int n_kfv, int n_sizes, bool s16, int64_t n_ref, bool u8, int n_plus2, bool need_wide);
 bool stream8_derive_applies(int k, int nk_min, int nk_max, int n_kfv, int64_t n_ref, bool s16);
@@ -179,6 +181,12 @@ struct kgma_genome {
     ContigDesc *d_cd = nullptr;
     unsigned long long *d_first_bad = nullptr;
     int32_t *d_block_contig = nullptr;       // record of the first word of every pack block (pack_kernel)
+    // the prefilter's block sums (pack_sums_kernel): one uint16 per dword of d_inter, allocated by the first step that fuses them into
+    // its pack.  bsum_fresh: written by the pack of the scan that is running (only that scan's filter reads them); bsum_k: the k of
+    // the last step that wrote them (0: none; kgma_get_block_sums); bsum_failed: the allocation failed once, plain path from then on
+    uint16_t *d_bsum = nullptr;
+    bool bsum_fresh = false, bsum_failed = false;
+    int bsum_k = 0;
     int64_t device_bytes = 0;
 };
 
@@ -929,6 +937,7 @@ int kgma_kmer_count_batch(kgma_ctx *ctx, int32_t k, const uint8_t *seqs, const i
 // One findGenes step in one call: re-encode the resident residues (Consts.jl:22-28), scan, replay, and
 // copy the hits out (two-call pattern collapsed: `cap` hits fit or KGMA_E_ARG with *n = needed).
 static bool overlap_setup(kgma_ctx *ctx);
+static bool fuse_sums_possible(const kgma_ctx *ctx, int32_t mode);
 static int64_t overlap_min_bases()                                   // (KGMA_OVERLAP_MIN_BASES: tests force the overlapped step on small genomes)
 {
     if (const char *e = getenv("KGMA_OVERLAP_MIN_BASES")) return std::max<int64_t>(1, atoll(e));
@@ -942,7 +951,9 @@ int kgma_repack_scan_hits(kgma_ctx *ctx, kgma_genome *g, int32_t mode, int64_t b
     if (!ctx || !g || !n) return KGMA_E_ARG;
     // a large genome's re-encoding is left to the scan, which may run it beside its own launches (launch_overlapped)
     int rc = KGMA_OK;
+    // ... or put the prefilter's block sums into it (pack_sums_kernel), which only the scan can decide
     if (mode == KGMA_MODE_SINGLE && g->n_contigs >= 4 && g->total_bases >= overlap_min_bases() && overlap_setup(ctx)) g->repack_deferred = true;
+    else if (fuse_sums_possible(ctx, mode)) g->repack_deferred = true;
     else rc = kgma_genome_repack(ctx, g);
     if (rc) return rc;
     rc = kgma_scan(ctx, g, mode, buff, genome_pos0, flags, nullptr, nullptr);
@@ -973,6 +984,7 @@ static void step_worker_main(kgma_ctx *ctx)
         if (st == -1) return;
         int rc = KGMA_OK;
         if (w->mode == KGMA_MODE_SINGLE && w->g->n_contigs >= 4 && w->g->total_bases >= overlap_min_bases() && overlap_setup(ctx)) w->g->repack_deferred = true;
+        else if (fuse_sums_possible(ctx, w->mode)) w->g->repack_deferred = true;
         else rc = kgma_genome_repack(ctx, w->g);
         if (!rc) rc = kgma_scan(ctx, w->g, w->mode, w->buff, w->genome_pos0, w->flags, nullptr, nullptr);
         w->rc = rc;
@@ -1497,9 +1509,10 @@ static int ensure_planes(kgma_ctx *ctx, kgma_genome *g)
     return KGMA_OK;
 }
 
-int kgma_genome_repack(kgma_ctx *ctx, kgma_genome *g)
+// sums: the step's pack with the prefilter's block sums of KFV 0 (pack_sums_kernel; the caller has checked that it applies and
+// that g->d_bsum exists)
+static int genome_repack(kgma_ctx *ctx, kgma_genome *g, bool sums)
 {
-    if (!ctx || !g) return KGMA_E_ARG;
     (void)hipSetDevice(ctx->device);
     // first_bad (smallest position of a residue outside A/C/G/T/N per record) is a function of the residue
     // text: re-encoding unchanged text finds the same minima, so the reset and the download of the table
@@ -1507,7 +1520,18 @@ int kgma_genome_repack(kgma_ctx *ctx, kgma_genome *g)
     const bool dirty = g->text_dirty;
     if (dirty) HIP_TRY(ctx, hipMemsetAsync(g->d_first_bad, 0xFF, std::max<size_t>(1, (size_t)g->n_contigs) * 8, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->evp0, ctx->stream));
-    if (g->n_contigs > 0)
+    if (g->n_contigs > 0 && sums) {
+        PackSumsArgs a;
+        memset(&a, 0, sizeof a);
+        a.ascii = g->d_ascii; a.planes = g->d_planes; a.inter = g->d_inter; a.bsum = g->d_bsum;
+        a.cd = g->d_cd; a.total_words = g->total_words; a.block_contig = g->d_block_contig; a.first_bad = g->d_first_bad;
+        a.S = ctx->d_Stab; a.n_contigs = (int32_t)g->n_contigs;
+        const int bw = pack_block_words();
+        a.block_shift = (bw & (bw - 1)) == 0 ? __builtin_ctz((unsigned)bw) : -1;
+        HIP_TRY(ctx, launch_pack_sums(a, ctx->k, ctx->kfv[0].Smax, ctx->n_cus, ctx->stream));
+        g->bsum_fresh = true;
+        g->bsum_k = ctx->k;
+    } else if (g->n_contigs > 0)
         HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream));
     else
     {
@@ -1519,6 +1543,12 @@ int kgma_genome_repack(kgma_ctx *ctx, kgma_genome *g)
     g->text_dirty = false;
     g->pack_pending = true;     // completed by the next scan's single synchronisation (or genome_sync)
     return KGMA_OK;
+}
+
+int kgma_genome_repack(kgma_ctx *ctx, kgma_genome *g)
+{
+    if (!ctx || !g) return KGMA_E_ARG;
+    return genome_repack(ctx, g, false);
 }
 
 int kgma_genome_from_host(kgma_ctx *ctx, const uint8_t *const *contig_ascii, const int64_t *contig_len,
@@ -1996,6 +2026,7 @@ void kgma_genome_free(kgma_ctx *ctx, kgma_genome *g)
     if (g->d_cd) (void)hipFree(g->d_cd);
     if (g->d_first_bad) (void)hipFree(g->d_first_bad);
     if (g->d_block_contig) (void)hipFree(g->d_block_contig);
+    if (g->d_bsum) (void)hipFree(g->d_bsum);
     if (g->first_bad) (void)hipHostFree(g->first_bad);
     if (ctx && ctx->tk_uid == g->uid) ctx->tk_uid = 0;
     delete g;
@@ -2358,6 +2389,37 @@ static int64_t filter_min_windows()
     return FILTER_MIN_WINDOWS;
 }
 
+// The filter's threshold U on a granule's sum of S for KFV 0; false: the filter does not run (a genome below the size limit, a
+// negative S entry, or U <= 0).
+static bool filter_bound(const kgma_ctx *ctx, int nk, int64_t total_nwin, uint32_t *U)
+{
+    const KfvInfo &f = ctx->kfv[0];
+    if (total_nwin < filter_min_windows()) return false;
+    if (*std::min_element(f.S.begin(), f.S.end()) < 0) return false;    // (the granule sums bound sumS only for S >= 0: sums of counts are)
+    const int64_t Dmax = std::max(f.T - 1, f.T_hi);
+    const __int128 num = (__int128)f.sumS2 + (__int128)f.N * (__int128)f.N * (__int128)nk - (__int128)Dmax;
+    if (num <= 0) return false;                                         // U <= 0: every window is a candidate
+    const __int128 twoN = 2 * (__int128)f.N;
+    const __int128 U128 = (num + twoN - 1) / twoN;
+    *U = U128 > 0x7FFFFFFF ? 0x7FFFFFFFu : (uint32_t)U128;              // (a granule's sum stays below 2^26: no candidates)
+    return true;
+}
+static bool filter_remembered(const kgma_ctx *ctx, const kgma_genome *g)
+{
+    const KfvInfo &f = ctx->kfv[0];
+    const auto &memo = ctx->fmemo;
+    return memo.valid && memo.uid == g->uid && memo.refs == ctx->refs_version && memo.T == f.T && memo.T_hi == f.T_hi;
+}
+
+// The step's pack may carry the prefilter's block sums (pack_sums_kernel; KGMA_FUSE_SUMS=0: never): what the step entry points can
+// tell before the scan -- they then leave the pack to it, which knows whether the filter will run (kgma_scan_device).
+static bool fuse_sums_possible(const kgma_ctx *ctx, int32_t mode)
+{
+    const char *e = getenv("KGMA_FUSE_SUMS"), *fe = getenv("KGMA_FILTER"), *ov = getenv("KGMA_OVERLAP");
+    if ((e && atoi(e) == 0) || (fe && atoi(fe) == 0) || (ov && atoi(ov) == 1)) return false;
+    return mode == KGMA_MODE_SINGLE && !ctx->strobe && ctx->m >= 1 && !ctx->kfv[0].fp && pack_sums_applies(ctx->k, ctx->kfv[0].Smax);
+}
+
 static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t n_tiles, bool *filtered)
 {
     *filtered = false;
@@ -2367,18 +2429,12 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
     int64_t total_nwin = 0;
     for (int64_t c = 0; c < nc; c++) total_nwin += ctx->contig_nwin[(size_t)c];
     fs.total_windows = total_nwin;
-    if (total_nwin < filter_min_windows()) return KGMA_OK;
-    if (*std::min_element(f.S.begin(), f.S.end()) < 0) return KGMA_OK;   // (the granule sums bound sumS only for S >= 0: sums of counts are)
-    const int64_t Dmax = std::max(f.T - 1, f.T_hi);
-    const __int128 num = (__int128)f.sumS2 + (__int128)f.N * (__int128)f.N * (__int128)nk - (__int128)Dmax;
-    if (num <= 0) return KGMA_OK;                                       // U <= 0: every window is a candidate
-    const __int128 twoN = 2 * (__int128)f.N;
-    const __int128 U128 = (num + twoN - 1) / twoN;
-    const uint32_t U = U128 > 0x7FFFFFFF ? 0x7FFFFFFFu : (uint32_t)U128;   // (a granule's sum stays below 2^26: no candidates)
+    uint32_t U = 0;
+    if (!filter_bound(ctx, nk, total_nwin, &U)) return KGMA_OK;
     fs.bound = (int64_t)U;
     const bool geom_debug = getenv("KGMA_GEOM_DEBUG") != nullptr;
     auto &memo = ctx->fmemo;
-    if (memo.valid && memo.uid == g->uid && memo.refs == ctx->refs_version && memo.T == f.T && memo.T_hi == f.T_hi) {
+    if (filter_remembered(ctx, g)) {
         fs.fell_back = 1; fs.reason = KGMA_FILTER_REMEMBERED;
         if (geom_debug) fprintf(stderr, "scan filter: skipped, this genome fell back before\n");
         return KGMA_OK;
@@ -2410,6 +2466,7 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
     a.cap = (unsigned int)cap;
     a.list = reinterpret_cast<FilterEntry *>(ctx->h_fpin_dev + 16);
     a.ctl = ctx->d_fctl;
+    a.bsum = g->bsum_fresh ? g->d_bsum : nullptr;                       // (this scan's pack wrote the block sums: the PRESUMMED form)
     HIP_TRY(ctx, hipEventRecord(ctx->evf0, ctx->stream));
     int32_t form = 0;
     HIP_TRY(ctx, launch_filter(a, ctx->k, f.Smax, ctx->n_cus, reinterpret_cast<unsigned int *>(ctx->h_fpin_dev), &form, ctx->stream));
@@ -2577,13 +2634,40 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     if (generic_all) use_stream = true;                // (a stream kernel: same stream table, same records)
     // a re-encoding left to this scan (kgma_repack_scan_hits): beside the scan's launches when it is ONE stream8 launch of one KFV
     // (launch_overlapped), else one launch in front of it
+    // The distance-bound prefilter applies: one integer KFV on the 8-bit count-table kernel at k = 5, 6, no distance output
+    // (filter_candidate_table decides whether it runs)
+    auto filter_wanted = [&](bool ovl) {
+        const char *fe = getenv("KGMA_FILTER"), *ds = getenv("KGMA_DEBUG_SKIP");
+        const KfvInfo &f0 = ctx->kfv[0];
+        const int nk0 = (int)(f0.W - k + 1);
+        return !(fe && atoi(fe) == 0) && use_stream && !generic_all && m_used == 1 && groups.size() == 1 && groups[0].kfvs.size() == 1 && groups[0].kfvs[0] == 0 &&
+               !(flags & KGMA_F_RETURN_DISTS) && !ovl && !(ds && atoi(ds) != 0) && !f0.fp && f0.fits32 && !f0.S.empty() && stream8_applies(k, nk0, 1, f0.N, f0.Smax <= 32767) &&
+               !stream8_c16_applies(k, nk0, 1, f0.N, f0.Smax <= 32767, false) && filter_applies(k, f0.Smax);
+    };
     bool overlap = false;
+    g->bsum_fresh = false;                                             // (block sums are only good inside the scan whose pack wrote them)
     if (g->repack_deferred) {
         overlap = use_stream && !generic_all && groups.size() == 1 && groups[0].kfvs.size() == 1 && m_used == 1 && group_s8(groups[0]) &&
                   g->d_planes == nullptr && overlap_setup(ctx);
         if (!overlap) {
             g->repack_deferred = false;
-            const int prc = kgma_genome_repack(ctx, g);
+            // the pack carries the filter's block sums when the filter is going to run on byte entries (else: the plain pack, and
+            // the filter, if it runs after all, cuts its k-mers itself)
+            bool sums = false;
+            if (fuse_sums_possible(ctx, mode) && !g->bsum_failed && filter_wanted(false) && !filter_remembered(ctx, g)) {
+                const int64_t W0 = ctx->kfv[0].W;
+                int64_t total_nwin = 0;
+                for (const ContigDesc &d : g->cd) total_nwin += d.len >= W0 ? d.len - W0 + 1 : 0;
+                uint32_t U = 0;
+                sums = filter_bound(ctx, (int)(W0 - k + 1), total_nwin, &U);
+            }
+            if (sums && !g->d_bsum) {
+                if (hipMalloc(reinterpret_cast<void **>(&g->d_bsum), (size_t)g->total_words * 4) != hipSuccess) {
+                    (void)hipGetLastError();
+                    g->d_bsum = nullptr; g->bsum_failed = true; sums = false;
+                } else g->device_bytes += g->total_words * 4;
+            }
+            const int prc = genome_repack(ctx, g, sums);
             if (prc) return prc;
         }
     }
@@ -2872,16 +2956,9 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     // ---- distance-bound prefilter: one integer KFV on the 8-bit count-table kernel at k = 5, 6, no distance output -- the exact
     //      kernel then walks the candidate stream table instead of the regular one (filter_candidate_table)
     bool filtered = false;
-    {
-        const char *fe = getenv("KGMA_FILTER"), *ds = getenv("KGMA_DEBUG_SKIP");
-        const KfvInfo &f0 = ctx->kfv[0];
-        const int nk0 = (int)(f0.W - k + 1);
-        if (!(fe && atoi(fe) == 0) && use_stream && !generic_all && m_used == 1 && groups.size() == 1 && groups[0].kfvs.size() == 1 && groups[0].kfvs[0] == 0 &&
-            !want_dists && !overlap && !(ds && atoi(ds) != 0) && !f0.fp && f0.fits32 && !f0.S.empty() && stream8_applies(k, nk0, 1, f0.N, f0.Smax <= 32767) &&
-            !stream8_c16_applies(k, nk0, 1, f0.N, f0.Smax <= 32767, false) && filter_applies(k, f0.Smax)) {
-            rc = filter_candidate_table(ctx, g, nk0, n_tiles, &filtered);
-            if (rc) return rc;
-        }
+    if (filter_wanted(overlap)) {
+        rc = filter_candidate_table(ctx, g, (int)(ctx->kfv[0].W - k + 1), n_tiles, &filtered);
+        if (rc) return rc;
     }
     // the table the exact kernel walks: its streams, D0 slots and records
     const int64_t n_scan = filtered ? (int64_t)ctx->ftiles.size() : n_tiles;
@@ -5419,6 +5496,22 @@ int kgma_get_filter_stats(kgma_ctx *ctx, kgma_filter_stats *out)
 {
     if (!ctx || !out) return KGMA_E_ARG;
     *out = ctx->fstats;
+    return KGMA_OK;
+}
+
+int kgma_get_block_sums(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int64_t first_block, int64_t n, uint32_t *out)
+{
+    if (!ctx || !g) return KGMA_E_ARG;
+    if (!g->d_bsum || g->bsum_k == 0) return fail(ctx, KGMA_E_STATE, "kgma_get_block_sums: no step has put block sums into this genome's pack");
+    if (contig < 0 || contig >= g->n_contigs || first_block < 0 || n < 0 || (!out && n > 0)) return fail(ctx, KGMA_E_ARG, "kgma_get_block_sums: bad argument");
+    const ContigDesc &d = g->cd[(size_t)contig];
+    if (first_block + n > 2 * ((d.len + 31) / 32)) return fail(ctx, KGMA_E_ARG, "kgma_get_block_sums: blocks outside the record");
+    if (n == 0) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint16_t> tmp((size_t)n);
+    HIP_TRY(ctx, hipMemcpy(tmp.data(), g->d_bsum + 2 * d.word_off + first_block, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; i++) out[i] = tmp[(size_t)i];
     return KGMA_OK;
 }
 

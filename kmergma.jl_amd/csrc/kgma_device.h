@@ -246,6 +246,23 @@ struct FilterArgs {
     unsigned int cap;             // entries the list holds
     FilterEntry *list;
     unsigned int *ctl;            // entries appended (keeps counting past cap)
+    const uint16_t *bsum;         // PRESUMMED form: the block sums pack_sums_kernel wrote beside `inter` in this step (else unused)
+};
+
+// The step's pack with the prefilter's block sums (kgma_filter.hip: pack_sums_kernel): what pack_kernel writes, plus per dword J of
+// `inter` the sum of S over the k-mers that start in it and belong to its record (0 for padding) -- bsum[J], 16 x 255 at most.
+struct PackSumsArgs {
+    const uint8_t *ascii;
+    uint32_t *planes;             // may be null, as for pack_kernel
+    uint32_t *inter;
+    uint16_t *bsum;               // [2 * total_words]
+    const ContigDesc *cd;
+    int64_t total_words;
+    const int32_t *block_contig;  // record of the first word of every block of 2^block_shift words (pack_kernel's table)
+    unsigned long long *first_bad;
+    const int32_t *S;             // the KFV's S table as FilterArgs::S, every entry below 256
+    int32_t n_contigs;
+    int32_t block_shift;
 };
 
 // Aux region of the result block: residues under tied minima, gathered on the device (export_kernel)

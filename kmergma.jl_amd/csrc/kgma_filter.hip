@@ -16,11 +16,15 @@
 // The S table is kept as 32 interleaved copies where they fit the LDS (4^k bytes or int16 each): lane l reads copy l % 32, which
 // lives in bank l % 32, so the 64 random reads of a wave never collide (2 LDS cycles instead of ~7 for one copy).
 // Output: per wave iteration with a candidate, ONE entry {record, granule of bit 0, 64-bit mask} appended with one atomic.
+// In a step (kgma_repack_scan_hits) whose S entries are bytes the block sums come from the step's pack instead: pack_sums_kernel
+// (below) writes them beside the 2-bit copy, and filter_kernel<..., PRESUMMED> loads one uint16 where it would do the 16 lookups.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "kgma_device.h"
+#include "kgma_pack.h"
 
 namespace kgma {
 
@@ -40,23 +44,33 @@ __device__ __forceinline__ uint32_t f_incl_scan(uint32_t x)
 
 }  // namespace
 
-// ES: bytes per S entry (1: every S < 256, 2: < 65536); COPIES: 32 bank-interleaved copies, or 1
+// The S table in LDS: dword (x / EPD) of copy c is LDS dword (x / EPD) * COPIES + c (EPD = 4 / ES entries per dword)
 template <int K, int ES, int COPIES>
+__device__ __forceinline__ void f_stage_table(uint32_t *fsm, const int32_t *S)
+{
+    constexpr int NB = 1 << (2 * K);
+    constexpr int EPD = 4 / ES;
+    for (int t = (int)threadIdx.x; t < NB / EPD * COPIES; t += (int)blockDim.x) {
+        const int d = t / COPIES;
+        uint32_t v = 0;
+#pragma unroll
+        for (int e = 0; e < EPD; e++) v |= (uint32_t)S[d * EPD + e] << (8 * ES * e);
+        fsm[t] = v;
+    }
+    __syncthreads();
+}
+
+// ES: bytes per S entry (1: every S < 256, 2: < 65536); COPIES: 32 bank-interleaved copies, or 1
+// PRESUMMED: the block sums come from a.bsum (pack_sums_kernel wrote them in this step) -- one 2-byte load in the place of the 16
+// lookups, no S table in LDS; everything from the prefix sum on is the same code
+template <int K, int ES, int COPIES, bool PRESUMMED = false>
 __global__ __launch_bounds__(1024) void filter_kernel(FilterArgs a)
 {
     constexpr int NB = 1 << (2 * K);
     constexpr uint32_t KM = (uint32_t)NB - 1u;
     constexpr int EPD = 4 / ES;                                        // entries per dword
     extern __shared__ uint32_t fsm[];
-    // dword (x / EPD) of copy c is LDS dword (x / EPD) * COPIES + c
-    for (int t = (int)threadIdx.x; t < NB / EPD * COPIES; t += (int)blockDim.x) {
-        const int d = t / COPIES;
-        uint32_t v = 0;
-#pragma unroll
-        for (int e = 0; e < EPD; e++) v |= (uint32_t)a.S[d * EPD + e] << (8 * ES * e);
-        fsm[t] = v;
-    }
-    __syncthreads();
+    if constexpr (!PRESUMMED) f_stage_table<K, ES, COPIES>(fsm, a.S);
     const uint8_t *tab = reinterpret_cast<const uint8_t *>(fsm);
     const int lane = (int)(threadIdx.x & 63);
     const uint32_t coff = COPIES > 1 ? 4u * (uint32_t)(lane & (COPIES - 1)) : 0u;
@@ -83,8 +97,13 @@ __global__ __launch_bounds__(1024) void filter_kernel(FilterArgs a)
         const int iters = (nb + 63) >> 6;
         auto load = [&](const int it, uint32_t &d0, uint32_t &d1) {
             const int64_t j = dw0 + ((int64_t)it << 6) + lane;
-            d0 = j < a.n_dwords ? a.inter[j] : 0u;
-            d1 = j + 1 < a.n_dwords ? a.inter[j + 1] : 0u;
+            if constexpr (PRESUMMED) {
+                d0 = j < a.n_dwords ? (uint32_t)a.bsum[j] : 0u;
+                d1 = 0u;
+            } else {
+                d0 = j < a.n_dwords ? a.inter[j] : 0u;
+                d1 = j + 1 < a.n_dwords ? a.inter[j + 1] : 0u;
+            }
         };
         uint32_t carry = 0, prevI = 0, n0, n1;
         load(0, n0, n1);
@@ -93,7 +112,10 @@ __global__ __launch_bounds__(1024) void filter_kernel(FilterArgs a)
             if (it + 1 < iters) load(it + 1, n0, n1);
             const int jb = (it << 6) + lane;                           // block, local to the stream
             uint32_t sum = 0;
-            if (rem - (((it << 6) + 63) << 4) >= 15) {                 // (wave-uniform) every position of the iteration is a k-mer of the record
+            if constexpr (PRESUMMED) {
+                // (the record's partial last block is masked in bsum; a block behind it may belong to the next record)
+                sum = rem - (jb << 4) >= 0 ? d0 : 0u;
+            } else if (rem - (((it << 6) + 63) << 4) >= 15) {          // (wave-uniform) every position of the iteration is a k-mer of the record
 #pragma unroll
                 for (int i = 0; i < 16; i++) {
                     const uint32_t x = (i == 0 ? d0 : __builtin_amdgcn_alignbit(d1, d0, 2 * i)) & KM;
@@ -130,6 +152,173 @@ __global__ __launch_bounds__(1024) void filter_kernel(FilterArgs a)
     }
 }
 
+// ---- the step's pack with the block sums -------------------------------------------------------------------------------------
+// pack_sums_kernel writes what pack_kernel writes (kgma_kernels.hip: planes, interleaved copy, first_bad) and, per dword J of the
+// interleaved copy, bsum[J] = the sum of S over the k-mers that start in the dword and are k-mers of its record (position <= len - K);
+// 0 for padding.  filter_kernel<..., PRESUMMED> then loads one sum where it would cut and look up 16 k-mers: the codes are in
+// registers here anyway, and the pack waits for HBM while the filter waits for the vector unit.
+// Persistent waves, the S table in LDS as filter_kernel<K, 1, 32> keeps it.  A wave takes UNITS of 128 consecutive plane words (two
+// chunks of 64: lane l packs words l and 64 + l) and has the next unit's four 16-byte loads per lane in flight while it encodes the
+// current one (64 KiB per CU at 16 waves).  A word's second dword needs the first dword of the next word: lane l + 1's, the other
+// chunk's lane 0 for lane 63 of the first chunk, and for the unit's last word K - 1 residues encoded by lane 0 on the side.
+// Fast path: the unit lies in one record, every word is full and of accepted letters, and K - 1 residues of the record follow it --
+// no position needs the mask.  Everything else (record ends, partial words, padding, several records in a unit, a residue to
+// report) goes word by word like pack_kernel's slow path, with the mask; keeping pack_word's one-residue-at-a-time branch out of
+// the fast path is also what keeps the kernel inside the 128 VGPRs of a 16-wave workgroup (113, no scratch).
+constexpr int PS_UNIT = 128;
+
+__device__ __forceinline__ uint32_t ps_code(uint32_t ch)               // the code pack_word gives a residue (one it reports: 0)
+{
+    ch &= 0xDFu;
+    return (ch == 'C' ? 1u : 0u) | (ch == 'G' ? 2u : 0u) | ((ch == 'T' || ch == 'N') ? 3u : 0u);
+}
+template <int K>
+__device__ __forceinline__ uint32_t ps_halo(const uint2 b)             // 2-bit codes of the first K - 1 of 8 residues
+{
+    uint32_t r = 0;
+#pragma unroll
+    for (int i = 0; i < K - 1; i++) r |= ps_code(((i < 4 ? b.x : b.y) >> (8 * (i & 3))) & 0xFFu) << (2 * i);
+    return r;
+}
+// sum of S over the first nv of the 16 k-mers that start in d0 (d1: the dword behind it); tab: the lane's copy of the 32 copies of
+// byte entries (byte x % 4 of dword (x / 4) * 32)
+template <int K, bool MASKED>
+__device__ __forceinline__ uint32_t ps_sum16(const uint32_t d0, const uint32_t d1, const uint8_t *tab, const int nv)
+{
+    constexpr uint32_t KM = (1u << (2 * K)) - 1u;
+    uint32_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const uint32_t y = i == 0 ? d0 : __builtin_amdgcn_alignbit(d1, d0, 2 * i);
+        // byte (x % 4) of dword (x / 4) * 32 + copy: the three fields do not overlap
+        const uint32_t v = tab[((y & (KM & ~3u)) << 5) + (y & 3u)];
+        sum += (!MASKED || i < nv) ? v : 0u;
+    }
+    return sum;
+}
+
+template <int K>
+__global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
+{
+    extern __shared__ uint32_t fsm[];
+    f_stage_table<K, 1, 32>(fsm, a.S);
+    const int lane = (int)(threadIdx.x & 63);
+    const uint8_t *tab = reinterpret_cast<const uint8_t *>(fsm) + 4 * (lane & 31);   // the lane's copy
+    const int waves_per_wg = (int)(blockDim.x >> 6);
+    const int64_t wave0 = (int64_t)blockIdx.x * waves_per_wg + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t n_waves = (int64_t)gridDim.x * waves_per_wg;
+    const int64_t n_units = (a.total_words + PS_UNIT - 1) / PS_UNIT;
+    const int next_idx = ((lane + 1) & 63) << 2;                       // (bpermute takes byte addresses)
+    uint2 *out = reinterpret_cast<uint2 *>(a.planes);
+    uint2 *out2 = reinterpret_cast<uint2 *>(a.inter);
+    uint32_t *outs = reinterpret_cast<uint32_t *>(a.bsum);             // one dword per plane word: its two sums
+
+    // a unit's record and path (wave-uniform), and on the fast path its loads
+    struct Unit { int c; int64_t w0; bool fast; u32x4_t v[4]; uint2 halo; };
+    auto prepare = [&](const int64_t u, Unit &n) {
+        const int64_t g0 = u * PS_UNIT;
+        int c = a.block_contig[g0 >> a.block_shift];
+        while (c + 1 < a.n_contigs && a.cd[c + 1].word_off <= g0) c++;
+        const ContigDesc d = a.cd[c];
+        n.c = c;
+        n.w0 = g0 - d.word_off;
+        n.fast = n.w0 >= 0 && g0 + PS_UNIT <= a.total_words && (n.w0 + PS_UNIT) * 32 + (K - 1) <= d.len;
+        if (n.fast) {
+            const uint8_t *base = a.ascii + d.ascii_off + n.w0 * 32;
+            const u32x4_t *p = reinterpret_cast<const u32x4_t *>(base) + 2 * lane;
+            n.v[0] = __builtin_nontemporal_load(p);
+            n.v[1] = __builtin_nontemporal_load(p + 1);
+            n.v[2] = __builtin_nontemporal_load(p + 128);
+            n.v[3] = __builtin_nontemporal_load(p + 129);
+            n.halo = make_uint2(0u, 0u);
+            if (lane == 0) n.halo = *reinterpret_cast<const uint2 *>(base + PS_UNIT * 32);
+        }
+    };
+    // (gb: a wave-uniform word index, so that the addresses are a scalar base plus the lane's offset)
+    auto store = [&](const int64_t gb, const int l, const uint2 r, const uint2 iw, const uint32_t s0, const uint32_t s1) {
+        if (a.planes != nullptr) {
+            u32x2_t rv; rv.x = r.x; rv.y = r.y;
+            __builtin_nontemporal_store(rv, reinterpret_cast<u32x2_t *>(out + gb) + l);
+        }
+        u32x2_t iv; iv.x = iw.x; iv.y = iw.y;
+        __builtin_nontemporal_store(iv, reinterpret_cast<u32x2_t *>(out2 + gb) + l);
+        __builtin_nontemporal_store(s0 | (s1 << 16), outs + gb + l);
+    };
+
+    auto process = [&](const Unit &cu, const int64_t u) {
+        const int64_t g0 = u * PS_UNIT;
+        bool clean = false;
+        uint2 r0 = make_uint2(0u, 0u), r1 = r0, i0, i1;
+        if (cu.fast) {
+            uint32_t bad0, bad1;
+            const uint4 a0 = make_uint4(cu.v[0].x, cu.v[0].y, cu.v[0].z, cu.v[0].w), b0 = make_uint4(cu.v[1].x, cu.v[1].y, cu.v[1].z, cu.v[1].w);
+            const uint4 a1 = make_uint4(cu.v[2].x, cu.v[2].y, cu.v[2].z, cu.v[2].w), b1 = make_uint4(cu.v[3].x, cu.v[3].y, cu.v[3].z, cu.v[3].w);
+            if (a.planes == nullptr) {                                 // (no planes kept: straight to the 2-bit codes)
+                i0 = pack_word_2bit(a0, b0, &bad0);
+                i1 = pack_word_2bit(a1, b1, &bad1);
+            } else {
+                r0 = pack_word<true>(a0, b0, 32, &bad0);
+                r1 = pack_word<true>(a1, b1, 32, &bad1);
+                i0 = interleave_word(r0); i1 = interleave_word(r1);
+            }
+            clean = __ballot((bad0 | bad1) != 0) == 0;                 // (a residue to report: the unit goes word by word)
+        }
+        if (clean) {
+            // the first dword of the next word: lane l + 1's; lane 63 reads lane 0, which offers the other chunk's / the halo's
+            const uint32_t h = ps_halo<K>(cu.halo);
+            const uint32_t n0 = (uint32_t)__builtin_amdgcn_ds_bpermute(next_idx, (int)(lane == 0 ? i1.x : i0.x));
+            const uint32_t n1 = (uint32_t)__builtin_amdgcn_ds_bpermute(next_idx, (int)(lane == 0 ? h : i1.x));
+            // (one sum's 16 lookups at a time: the other waves of the SIMD cover their latency, interleaving all 64 only costs registers)
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t s00 = ps_sum16<K, false>(i0.x, i0.y, tab, 16);
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t s01 = ps_sum16<K, false>(i0.y, n0, tab, 16);
+            store(g0, lane, r0, i0, s00, s01);
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t s10 = ps_sum16<K, false>(i1.x, i1.y, tab, 16);
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t s11 = ps_sum16<K, false>(i1.y, n1, tab, 16);
+            store(g0 + 64, lane, r1, i1, s10, s11);
+            return;
+        }
+#pragma unroll 1
+        for (int q = 0; q < PS_UNIT / 64; q++) {
+            const int64_t g = g0 + q * 64 + lane;
+            if (g >= a.total_words) continue;
+            int c = cu.c;
+            while (c + 1 < a.n_contigs && a.cd[c + 1].word_off <= g) c++;
+            const ContigDesc d = a.cd[c];
+            const int64_t w = g - d.word_off, L = d.len, base0 = w * 32;
+            uint2 r = make_uint2(0u, 0u), iw = make_uint2(0u, 0u);
+            uint32_t s0 = 0, s1 = 0;
+            if (w >= 0 && base0 < L) {
+                const uint8_t *src = a.ascii + d.ascii_off + base0;
+                const uint4 *p = reinterpret_cast<const uint4 *>(src);
+                const int nvalid = (L - base0) < 32 ? (int)(L - base0) : 32;
+                uint32_t bad;
+                r = pack_word(p[0], p[1], nvalid, &bad);
+                if (bad) atomicMin(&a.first_bad[c], (unsigned long long)(base0 + __builtin_ctz(bad) + 1));
+                iw = interleave_word(r);
+                // (a k-mer that reaches into the next word lies in the record: so does what it reads of that word)
+                const uint32_t h = base0 + 32 < L ? ps_halo<K>(*reinterpret_cast<const uint2 *>(src + 32)) : 0u;
+                const int64_t nk = L - K + 1 - base0;                  // k-mers of the record from the word's first position on
+                const int nv0 = nk < 0 ? 0 : nk > 16 ? 16 : (int)nk, nv1 = nk < 16 ? 0 : nk > 32 ? 16 : (int)(nk - 16);
+                s0 = ps_sum16<K, true>(iw.x, iw.y, tab, nv0);
+                s1 = ps_sum16<K, true>(iw.y, h, tab, nv1);
+            }
+            store(g0 + q * 64, lane, r, iw, s0, s1);
+        }
+    };
+
+    Unit nx;
+    if (wave0 < n_units) prepare(wave0, nx);
+    for (int64_t u = wave0; u < n_units; u += n_waves) {
+        const Unit cu = nx;
+        if (u + n_waves < n_units) prepare(u + n_waves, nx);
+        process(cu, u);
+    }
+}
+
 // count of entries (it keeps counting past the capacity) to the pinned mirror; the device counter is left at zero for the next scan
 __global__ void filter_publish_kernel(unsigned int *ctl, unsigned int *host)
 {
@@ -141,32 +330,61 @@ __global__ void filter_publish_kernel(unsigned int *ctl, unsigned int *host)
 
 bool filter_applies(int k, int64_t s_max) { return (k == 5 || k == 6) && s_max >= 0 && s_max <= 65535; }
 
-template <int K, int ES, int COPIES>
+template <int K, int ES, int COPIES, bool PRESUMMED = false>
 static hipError_t filter_launch(const FilterArgs &a, int n_cus, hipStream_t st)
 {
-    constexpr size_t lds = ((size_t)1 << (2 * K)) * ES * COPIES;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&filter_kernel<K, ES, COPIES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    constexpr size_t lds = PRESUMMED ? 0 : ((size_t)1 << (2 * K)) * ES * COPIES;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&filter_kernel<K, ES, COPIES, PRESUMMED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     // persistent waves: every CU's wave slots once (one 16-wave workgroup where the copies fill the LDS, else two)
-    const int per_cu = lds > (64u << 10) ? 1 : 2;
+    int per_cu = lds > (64u << 10) ? 1 : 2;
+    if (PRESUMMED)
+        if (const char *w = getenv("KGMA_FILTER_WGS")) per_cu = atoi(w) == 1 ? 1 : 2;   // experiments (EXPERIMENTS.md section 14)
     int64_t grid = (int64_t)n_cus * per_cu;
     const int64_t need = ((int64_t)a.n_tiles + 15) / 16;
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((filter_kernel<K, ES, COPIES>), dim3((unsigned)grid), dim3(1024), lds, st, a);
+    hipLaunchKernelGGL((filter_kernel<K, ES, COPIES, PRESUMMED>), dim3((unsigned)grid), dim3(1024), lds, st, a);
     return hipGetLastError();
 }
 
-// *form: the instantiation launched, S entry bytes | table copies << 8 (kgma_filter_stats::form)
+bool pack_sums_applies(int k, int64_t s_max) { return (k == 5 || k == 6) && s_max >= 0 && s_max < 256; }
+
+template <int K>
+static hipError_t pack_sums_launch(const PackSumsArgs &a, int n_cus, hipStream_t st)
+{
+    constexpr size_t lds = ((size_t)1 << (2 * K)) * 32;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&pack_sums_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    // persistent waves, as filter_launch
+    int64_t grid = (int64_t)n_cus * (lds > (64u << 10) ? 1 : 2);
+    const int64_t need = ((a.total_words + PS_UNIT - 1) / PS_UNIT + 15) / 16;
+    if (grid > need) grid = need;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL((pack_sums_kernel<K>), dim3((unsigned)grid), dim3(1024), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, hipStream_t st)
+{
+    if (!pack_sums_applies(k, s_max) || a.total_words <= 0 || a.block_shift < 0 || ((int64_t)1 << a.block_shift) % PS_UNIT != 0) return hipErrorInvalidValue;
+    return k == 5 ? pack_sums_launch<5>(a, n_cus, st) : pack_sums_launch<6>(a, n_cus, st);
+}
+
+// *form: the instantiation launched, S entry bytes | table copies << 8 (kgma_filter_stats::form); bit 16: the PRESUMMED form, on the
+// block sums a.bsum that pack_sums_kernel wrote (byte entries only)
 hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, int32_t *form, hipStream_t st)
 {
     if (!filter_applies(k, s_max) || a.nblk < 1 || a.nblk > 63) return hipErrorInvalidValue;
     const int es = s_max < 256 ? 1 : 2, copies = k == 6 && es == 2 ? 1 : 32;
+    const bool presummed = a.bsum != nullptr;
+    if (presummed && es != 1) return hipErrorInvalidValue;
     hipError_t e;
-    if (k == 5) e = es == 1 ? filter_launch<5, 1, 32>(a, n_cus, st) : filter_launch<5, 2, 32>(a, n_cus, st);
+    if (presummed) e = k == 5 ? filter_launch<5, 1, 32, true>(a, n_cus, st) : filter_launch<6, 1, 32, true>(a, n_cus, st);
+    else if (k == 5) e = es == 1 ? filter_launch<5, 1, 32>(a, n_cus, st) : filter_launch<5, 2, 32>(a, n_cus, st);
     else e = es == 1 ? filter_launch<6, 1, 32>(a, n_cus, st) : filter_launch<6, 2, 1>(a, n_cus, st);
     if (e != hipSuccess) return e;
-    *form = es | (copies << 8);
+    *form = es | (copies << 8) | (presummed ? 1 << 16 : 0);
     hipLaunchKernelGGL(filter_publish_kernel, dim3(1), dim3(64), 0, st, a.ctl, host_count);
     return hipGetLastError();
 }

@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "kgma_device.h"
+#include "kgma_pack.h"
 
 namespace kgma {
 
@@ -50,77 +51,6 @@ __device__ __forceinline__ int find_contig(const ContigDesc *cd, int n_contigs, 
     return lo;
 }
 
-// One lane packs 32 residues (two 16-byte loads) into one {hi,lo} word pair.
-__device__ __forceinline__ uint2 pack_word(const uint4 a, const uint4 b, const int nvalid, uint32_t *bad_out)
-{
-    uint32_t h = 0, l = 0, bad = 0;
-    const uint32_t x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    // Four residues per 32-bit word at a time.  After folding case, (ch >> 1) & 7 is distinct for the five
-    // accepted letters (A 0, C 1, T 2, G 3, N 7): v_perm_b32 uses it as an index into two 8-byte tables,
-    // one giving the letter back (any difference = a residue outside A/C/G/T/N) and one giving the code
-    // as 0x00 / 0x0F / 0xF0 / 0xFF (low nibble = code bit 0, high nibble = code bit 1; N -> T's code 3).
-    // ANDing with one bit per byte and summing the bytes (v_sad_u8) collects four residues' plane bits.
-    uint32_t diff = 0, hw[8], lw[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const uint32_t v = x[j] & 0xDFDFDFDFu;                       // fold case
-        const uint32_t sel = (v >> 1) & 0x07070707u;
-        const uint32_t letter = __builtin_amdgcn_perm(0x4E000000u, 0x47544341u, sel);   // idx 7 'N' | 3 'G' 2 'T' 1 'C' 0 'A'
-        const uint32_t code = __builtin_amdgcn_perm(0xFF000000u, 0xF0FF0F00u, sel);     // idx 7 -> 3 | G 2, T 3, C 1, A 0
-        diff |= v ^ letter;
-        // residue t of word j goes to bit 4*(j&1)+t of the plane byte: pick that bit out of the nibble that
-        // carries the plane's indicator
-        if (j & 1) {
-            lw[j] = (code << 4) & 0x80402010u;
-            hw[j] = code & 0x80402010u;
-        } else {
-            lw[j] = code & 0x08040201u;
-            hw[j] = (code >> 4) & 0x08040201u;
-        }
-    }
-    if (diff == 0 && nvalid == 32) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {                                // 8 residues -> one byte of each plane
-            const uint32_t lb = __builtin_amdgcn_sad_u8(lw[2 * q + 1], 0u, __builtin_amdgcn_sad_u8(lw[2 * q], 0u, 0u));
-            const uint32_t hb = __builtin_amdgcn_sad_u8(hw[2 * q + 1], 0u, __builtin_amdgcn_sad_u8(hw[2 * q], 0u, 0u));
-            l |= lb << (8 * q);
-            h |= hb << (8 * q);
-        }
-    } else {
-        // a record's last (partial) word, or a residue to report: one residue at a time
-#pragma unroll
-        for (int i = 0; i < 32; i++) {
-            const uint32_t ch = ((x[i >> 2] >> (8 * (i & 3))) & 0xFFu) & 0xDFu;  // fold case
-            const uint32_t isA = ch == 'A', isC = ch == 'C', isG = ch == 'G';
-            const uint32_t isT = (ch == 'T') | (ch == 'N');
-            const uint32_t in = i < nvalid;
-            h |= ((isG | isT) & in) << i;
-            l |= ((isC | isT) & in) << i;
-            bad |= ((1u ^ (isA | isC | isG | isT)) & in) << i;
-        }
-    }
-    *bad_out = bad;
-    return make_uint2(h, l);
-}
-
-// 2-bit interleaved copy of a plane word pair (stream8_kernel cuts a k-mer out of it with ONE funnel shift):
-// base t of the word -> bits 2t (code bit 0 = lo plane) and 2t+1 (code bit 1 = hi plane) of a 64-bit value.
-__device__ __forceinline__ uint32_t spread16(uint32_t x)             // bit j of the low half -> bit 2j
-{
-    x &= 0xFFFFu;
-    x = (x | (x << 8)) & 0x00FF00FFu;
-    x = (x | (x << 4)) & 0x0F0F0F0Fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    x = (x | (x << 1)) & 0x55555555u;
-    return x;
-}
-__device__ __forceinline__ uint2 interleave_word(const uint2 hl)     // hl = {hi plane, lo plane}
-{
-    const uint32_t i0 = spread16(hl.y & 0xFFFFu) | (spread16(hl.x & 0xFFFFu) << 1);
-    const uint32_t i1 = spread16(hl.y >> 16) | (spread16(hl.x >> 16) << 1);
-    return make_uint2(i0, i1);
-}
-
 // A workgroup packs PACK_U x 256 consecutive plane words (32 KiB of residues at PACK_U = 4).  The record of
 // the block's first word comes from a host-built table (one entry per block: no per-word binary search in
 // front of the loads); when the whole block lies inside that record -- all but a few blocks per record -- the
@@ -129,8 +59,6 @@ __device__ __forceinline__ uint2 interleave_word(const uint2 hl)     // hl = {hi
 // text is read once and the planes are next read by another kernel, neither should displace L2 lines.
 constexpr int PACK_U = 4;
 constexpr int PACK_BLOCK_WORDS = 256 * PACK_U;
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
 // `planes` may be null: the bit-plane copy is only kept for genomes that a kernel reading it has scanned (the 8-bit
 // stream kernel reads the interleaved copy alone), which saves a quarter byte per base of writes and of memory.

@@ -36,7 +36,9 @@ EXPORTS = [
     "kgma_chain_export", "kgma_chain_export_copy", "kgma_kfv_scale", "kgma_kfv_is_float",
     "kgma_set_strobe_ref", "kgma_strobe_scan", "kgma_exact_match", "kgma_get_matches",
     "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
+    "kgma_get_block_sums",
 ]
+FILTER_FORM_PRESUMMED = 1 << 16      # kgma_filter_stats.form: the filter read the block sums the step's pack wrote (KGMA_FUSE_SUMS)
 FILTER_OK, FILTER_OVERFLOW, FILTER_STREAMS, FILTER_FRACTION, FILTER_REMEMBERED = 0, 1, 2, 3, 4
 
 
@@ -165,6 +167,7 @@ def load():
     L.kgma_get_stats.argtypes = [vp, P(KgmaStats)]
     L.kgma_get_filter_stats.argtypes = [vp, P(KgmaFilterStats)]
     L.kgma_get_filter_candidates.argtypes = [vp, P(i32), P(i64), i64, P(i64)]
+    L.kgma_get_block_sums.argtypes = [vp, vp, i64, i64, i64, P(C.c_uint32)]
     L.kgma_resolve_ties_local.argtypes = [vp, vp]
     L.kgma_repack_scan_hits.argtypes = [vp, vp, i32, i64, i64, C.c_uint32, P(KgmaHit), i64, P(i64)]
     L.kgma_align_hits_device.argtypes = [vp, vp, C.c_char_p, i64, i32, i32, i64, P(i32), P(i64), P(i64), P(i64), P(i64), P(i64)]
@@ -789,6 +792,14 @@ class Context:
         s = KgmaFilterStats()
         self._check(load().kgma_get_filter_stats(self._h, C.byref(s)))
         return {f: getattr(s, f) for f, _ in KgmaFilterStats._fields_}
+
+    def get_block_sums(self, genome: "Genome", contig: int, first_block: int = 0, n: int = -1) -> np.ndarray:
+        """kgma_get_block_sums: record `contig`'s block sums (one per 16 positions) of the last step whose pack computed them."""
+        if n < 0:
+            n = 2 * ((genome.contig_len(contig) + 31) // 32) - first_block
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(load().kgma_get_block_sums(self._h, genome._h, contig, first_block, n, _np_ptr(out, C.c_uint32)))
+        return out[:n]
 
     def filter_candidates(self) -> np.ndarray:
         """kgma_get_filter_candidates: the last scan's candidate granules as an (n, 2) int64 array (record, granule), sorted."""
