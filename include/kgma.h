@@ -559,6 +559,36 @@ int kgma_exact_match(kgma_ctx *ctx, const kgma_genome *g, const uint8_t *queries
                      int32_t n_queries, int32_t overlap);
 int kgma_get_matches(kgma_ctx *ctx, kgma_match *out, int64_t cap, int64_t *n);
 
+/* IUPAC motif search with mismatches on a resident genome (the working form of the reference's src/RSS.jl, whose RSS_dist counts
+ * every N of a spacer as a mismatch).  Motif i is motifs[offsets[i] .. offsets[i+1]), 1 ... 64 symbols of ACGTRYSWKMBDHVN in either
+ * case; each symbol stands for a set of bases, N for all four.  Laid at 1-based start s of a record of length L (s + m - 1 <= L; no
+ * match spans two records), position j of the motif MATCHES when the set of the genome residue (case folded; N = all four) is a
+ * subset of the symbol's set: a base A/C/G/T matches a symbol that contains it, a genome N matches only a motif N.  mism(s) is the
+ * number of non-matching positions, and every s with mism(s) <= max_mismatch[i] is reported, overlapping ones included.
+ * 0 <= max_mismatch[i] <= 15, and it must be smaller than the number of informative (non-N) positions of the motif -- otherwise
+ * every start would match (an all-N motif is refused the same way).  The minus strand is served by passing the reverse-complemented
+ * motif: it is searched on the same genome and its matches are in forward coordinates.
+ * All motifs are served by ONE kernel launch over the bit-plane copy of the genome (made on first use, 0.25 byte per base; each
+ * 32-bit operation serves 32 starts, candidates are verified and counted on the residue text), repeated once when the hits outgrow
+ * the device buffer (KGMA_E_NOMEM, context still usable, if the larger buffer cannot be had; KGMA_E_OVERFLOW if it overflows again).
+ * KGMA_E_ARG: an empty motif or one of more than 64 symbols, a symbol outside the 15 codes, a max_mismatch out of range;
+ * kgma_last_error names motif and position.  KGMA_E_BADBASE: a genome residue outside A/C/G/T/N, in any record (the 2-bit copies
+ * are not faithful there); kgma_last_error names the first such record and position.
+ * The call needs no references and leaves the KFVs, the hits, dips and distances of the last scan and the matches of the last
+ * kgma_exact_match as they are; of kgma_stats it sets bases_scanned, scan_ms (hipEvents around the launches) and n_launches.
+ * kgma_get_motif_matches returns the hits of the last call sorted by (motif, contig, start), with the two-call pattern of
+ * kgma_get_hits; after a call that failed, for whatever reason, it returns none. */
+typedef struct {
+    int32_t motif;       /* 0-based index of the motif                                         */
+    int32_t contig;      /* 0-based index of the record                                        */
+    int64_t start;       /* 1-based position of the motif's first symbol                       */
+    int32_t mismatches;  /* non-matching positions, <= max_mismatch of the motif               */
+    int32_t reserved;
+} kgma_motif_hit;
+int kgma_motif_match(kgma_ctx *ctx, const kgma_genome *g, const uint8_t *motifs, const int64_t *offsets /* n_motifs + 1 */,
+                     int32_t n_motifs, const int32_t *max_mismatch /* n_motifs */);
+int kgma_get_motif_matches(kgma_ctx *ctx, kgma_motif_hit *out, int64_t cap, int64_t *n);
+
 /* kgma_repack_scan_hits in two halves, for step loops that have other work to queue while the GPU scans
  * (bench.py with several ranks: the hit exchange of step i overlaps the scan of step i+1).  kgma_step_begin
  * hands the step to a helper thread owned by the context and returns at once; kgma_step_end waits for it

@@ -85,6 +85,9 @@ int scan_tile_stride_words(int nk);
 int scan_nblocks(int nk);
 int64_t exact_tile_starts(bool two_bit);
 hipError_t launch_exact(const ExactArgs &a, int kind, int64_t n_tiles, hipStream_t st);
+int64_t motif_tile_starts();
+int motif_planes(int max_mm);
+hipError_t launch_motif(const MotifArgs &a, int P, int64_t n_tiles, hipStream_t st);
 int64_t revcomp_tile_bytes();
 hipError_t launch_revcomp(const RevcompArgs &a, int64_t n_tiles, hipStream_t st);
 int kdist_grid(int k, int64_t n_seqs);
@@ -376,6 +379,13 @@ struct kgma_ctx {
     ExactMatch *d_xout = nullptr; int64_t xout_cap = 0;
     unsigned long long *d_xctl = nullptr; int64_t xctl_cap = 0;
     std::vector<kgma_match> matches;
+    // motif search (kgma_motif_match): likewise
+    MotifDesc *d_mq = nullptr; int64_t mq_cap = 0;
+    uint32_t *d_minfo = nullptr; int64_t minfo_cap = 0;
+    int64_t *d_mprefix = nullptr; int64_t mprefix_cap = 0;
+    MotifHit *d_mout = nullptr; int64_t mout_cap = 0;
+    unsigned long long *d_mctl = nullptr; int64_t mctl_cap = 0;
+    std::vector<kgma_motif_hit> motif_hits;
     // reverse complement (kgma_genome_revcomp): the tile table of the last call, on the device and as uploaded
     int64_t *d_rcprefix = nullptr; int64_t rcprefix_cap = 0;
     std::vector<int64_t> rcprefix;
@@ -808,6 +818,11 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_xprefix) (void)hipFree(ctx->d_xprefix);
     if (ctx->d_xout) (void)hipFree(ctx->d_xout);
     if (ctx->d_xctl) (void)hipFree(ctx->d_xctl);
+    if (ctx->d_mq) (void)hipFree(ctx->d_mq);
+    if (ctx->d_minfo) (void)hipFree(ctx->d_minfo);
+    if (ctx->d_mprefix) (void)hipFree(ctx->d_mprefix);
+    if (ctx->d_mout) (void)hipFree(ctx->d_mout);
+    if (ctx->d_mctl) (void)hipFree(ctx->d_mctl);
     if (ctx->d_rcprefix) (void)hipFree(ctx->d_rcprefix);
     if (ctx->evp0) (void)hipEventDestroy(ctx->evp0);
     if (ctx->evp1) (void)hipEventDestroy(ctx->evp1);
@@ -5438,6 +5453,139 @@ int kgma_get_matches(kgma_ctx *ctx, kgma_match *out, int64_t cap, int64_t *n)
     if (!out) return KGMA_OK;
     if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_matches: capacity %lld < %lld", (long long)cap, (long long)*n);
     if (*n) memcpy(out, ctx->matches.data(), (size_t)*n * sizeof(kgma_match));
+    return KGMA_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// IUPAC motif search with mismatches (the working form of src/RSS.jl; kernel: kgma_motif.hip)
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(kgma_motif_hit) == sizeof(MotifHit), "kgma_motif_hit is the device record");
+
+// base set of an IUPAC symbol (bit 0 A, 1 C, 2 G, 3 T), either case; 0: not one of the 15 symbols
+static uint32_t iupac_set(uint8_t ch)
+{
+    switch (ch & 0xDFu) {
+    case 'A': return 1;  case 'C': return 2;  case 'G': return 4;  case 'T': return 8;
+    case 'R': return 5;  case 'Y': return 10; case 'S': return 6;  case 'W': return 9;
+    case 'K': return 12; case 'M': return 3;  case 'B': return 14; case 'D': return 13;
+    case 'H': return 11; case 'V': return 7;  case 'N': return 15;
+    default: return 0;
+    }
+}
+
+int kgma_motif_match(kgma_ctx *ctx, const kgma_genome *gc, const uint8_t *motifs, const int64_t *offsets, int32_t n_motifs,
+                     const int32_t *max_mismatch)
+{
+    if (!ctx || !gc) return KGMA_E_ARG;
+    ctx->motif_hits.clear();                           // (whatever happens below: a failed call leaves no hits of an earlier one behind)
+    if (n_motifs < 0 || (n_motifs > 0 && (!motifs || !offsets || !max_mismatch))) return fail(ctx, KGMA_E_ARG, "kgma_motif_match: no motifs");
+    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping and its lazily made plane copy are updated
+    std::vector<MotifDesc> descs;
+    std::vector<uint32_t> info;
+    int P = 0;
+    for (int32_t i = 0; i < n_motifs; i++) {
+        const int64_t b = offsets[i], m = offsets[i + 1] - b;
+        if (m < 1 || m > 64) return fail(ctx, KGMA_E_ARG, "kgma_motif_match: motif %d has %lld symbols (1 ... 64)", i, (long long)m);
+        const int32_t d = max_mismatch[i];
+        if (d < 0 || d > 15) return fail(ctx, KGMA_E_ARG, "kgma_motif_match: motif %d: max_mismatch %d (0 ... 15)", i, d);
+        MotifDesc M{};
+        M.info_off = (int32_t)info.size(); M.len = (int32_t)m; M.max_mm = d; M.id = i;
+        for (int64_t j = 0; j < m; j++) {
+            const uint32_t set = iupac_set(motifs[b + j]);
+            if (!set) return fail(ctx, KGMA_E_ARG, "kgma_motif_match: motif %d, symbol %lld (0x%02x) is not an IUPAC nucleotide code", i, (long long)j + 1, motifs[b + j]);
+            if (set == 15u) continue;
+            info.push_back((uint32_t)j | (set << 8));          // (offsets ascend: those below 32 come first)
+            if (j < 32) M.n_lo++; else M.n_hi++;
+        }
+        if (d >= M.n_lo + M.n_hi)
+            return fail(ctx, KGMA_E_ARG, "kgma_motif_match: motif %d: max_mismatch %d is not smaller than its %d informative (non-N) positions: every start would match",
+                        i, d, M.n_lo + M.n_hi);
+        info.push_back(0x0F00u);                               // the spare entry the kernel's read-ahead touches
+        P = std::max(P, motif_planes(d));
+        descs.push_back(M);
+    }
+    (void)hipSetDevice(ctx->device);
+    // what the pack kernel knows about the residues (first_bad) and the plane copy must be current: a pack that is deferred, or never
+    // queued since the text changed, runs now
+    if (g->repack_deferred || g->text_dirty) {
+        g->repack_deferred = false;
+        const int prc = kgma_genome_repack(ctx, g);
+        if (prc) return prc;
+    }
+    int rc = ensure_planes(ctx, g);
+    if (rc) return rc;
+    if ((rc = genome_sync(ctx, g))) return rc;
+    ctx->stats.bases_scanned = g->total_bases;
+    ctx->stats.scan_ms = 0;
+    ctx->stats.n_launches = 0;
+    for (int64_t c = 0; c < g->n_contigs; c++)
+        if (g->first_bad[(size_t)c] != NO_BAD) {
+            return fail(ctx, KGMA_E_BADBASE, "record %lld: residue %llu is not one of A/C/G/T/N", (long long)c, g->first_bad[(size_t)c]);   // (first_bad is 1-based)
+        }
+    const int64_t nc = g->n_contigs, per_tile = motif_tile_starts();
+    std::vector<int64_t> prefix((size_t)nc + 1, 0);
+    for (int64_t c = 0; c < nc; c++) prefix[(size_t)c + 1] = prefix[(size_t)c] + (g->cd[(size_t)c].len + per_tile - 1) / per_tile;
+    const int64_t n_tiles = prefix[(size_t)nc];
+    if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_motif_match: %lld tiles exceed one launch", (long long)n_tiles);
+    std::vector<kgma_motif_hit> found;
+    if (n_motifs > 0 && n_tiles > 0) {
+        if ((rc = dev_reserve(ctx, ctx->d_mq, ctx->mq_cap, (int64_t)descs.size()))) return rc;
+        if ((rc = dev_reserve(ctx, ctx->d_minfo, ctx->minfo_cap, (int64_t)info.size()))) return rc;
+        if ((rc = dev_reserve(ctx, ctx->d_mprefix, ctx->mprefix_cap, nc + 1))) return rc;
+        if ((rc = dev_reserve(ctx, ctx->d_mctl, ctx->mctl_cap, 2))) return rc;
+        if ((rc = dev_reserve(ctx, ctx->d_mout, ctx->mout_cap, (int64_t)1 << 16))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mq, descs.data(), descs.size() * sizeof(MotifDesc), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_minfo, info.data(), info.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mprefix, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        unsigned long long ctl[2] = {0, 0};
+        int n_launches = 0;
+        // one launch for the whole batch; hits that do not fit the device buffer: once more with a buffer of the size it counted
+        for (int attempt = 0;; attempt++) {
+            MotifArgs a{};
+            a.planes = reinterpret_cast<const uint32_t *>(g->d_planes); a.ascii = g->d_ascii; a.cd = g->d_cd; a.tile_prefix = ctx->d_mprefix;
+            a.n_contigs = (int32_t)nc; a.n_motifs = (int32_t)descs.size();
+            a.motifs = ctx->d_mq; a.info = ctx->d_minfo; a.out = ctx->d_mout; a.ctl = ctx->d_mctl; a.cap = (unsigned long long)ctx->mout_cap;
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_mctl, 0, 2 * sizeof(unsigned long long), ctx->stream));
+            HIP_TRY(ctx, launch_motif(a, P, n_tiles, ctx->stream));
+            n_launches++;
+            HIP_TRY(ctx, hipMemcpyAsync(ctl, ctx->d_mctl, sizeof ctl, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (ctl[0] <= (unsigned long long)ctx->mout_cap) break;
+            if (attempt == 1) return fail(ctx, KGMA_E_OVERFLOW, "kgma_motif_match: %llu hits overflowed the regrown buffer", ctl[0]);
+            // the larger buffer is taken before the old one is given up: without room for it the context stays as it was
+            MotifHit *fresh = nullptr;
+            if (ctl[0] > (1ull << 40) || hipMalloc(reinterpret_cast<void **>(&fresh), (size_t)ctl[0] * sizeof(MotifHit)) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ctx, KGMA_E_NOMEM, "kgma_motif_match: no device memory for %llu hits", ctl[0]);
+            }
+            (void)hipFree(ctx->d_mout);
+            ctx->device_bytes += ((int64_t)ctl[0] - ctx->mout_cap) * (int64_t)sizeof(MotifHit);
+            ctx->d_mout = fresh; ctx->mout_cap = (int64_t)ctl[0];
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+        ctx->stats.scan_ms = ms;
+        ctx->stats.n_launches = n_launches;
+        found.resize((size_t)ctl[0]);
+        if (ctl[0]) HIP_TRY(ctx, hipMemcpy(found.data(), ctx->d_mout, (size_t)ctl[0] * sizeof(kgma_motif_hit), hipMemcpyDeviceToHost));
+        std::sort(found.begin(), found.end(), [](const kgma_motif_hit &x, const kgma_motif_hit &y) {
+            return x.motif != y.motif ? x.motif < y.motif : x.contig != y.contig ? x.contig < y.contig : x.start < y.start;
+        });
+    }
+    ctx->motif_hits.swap(found);
+    return KGMA_OK;
+}
+
+int kgma_get_motif_matches(kgma_ctx *ctx, kgma_motif_hit *out, int64_t cap, int64_t *n)
+{
+    if (!ctx || !n) return KGMA_E_ARG;
+    *n = (int64_t)ctx->motif_hits.size();
+    if (!out) return KGMA_OK;
+    if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_motif_matches: capacity %lld < %lld", (long long)cap, (long long)*n);
+    if (*n) memcpy(out, ctx->motif_hits.data(), (size_t)*n * sizeof(kgma_motif_hit));
     return KGMA_OK;
 }
 

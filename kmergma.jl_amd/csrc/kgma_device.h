@@ -320,6 +320,39 @@ struct ExactArgs {
     unsigned long long cap;
 };
 
+// IUPAC motif search with mismatches (kgma_motif.hip; kgma_motif_match).  One motif of a launch: its INFORMATIVE (non-N) positions
+// only, as entries `offset | set << 8` (offset 0 ... 63 in the motif, set: bit 0 A, 1 C, 2 G, 3 T of the bases the symbol stands
+// for) at info + info_off -- first the n_lo entries with offset < 32, then the n_hi entries with offset >= 32, then one spare entry
+// (the kernel reads one entry ahead).
+struct MotifDesc {
+    int32_t info_off;
+    int32_t n_lo, n_hi;
+    int32_t len;          // symbols, 1 ... 64
+    int32_t max_mm;       // mismatches allowed, 0 ... 15 and < n_lo + n_hi
+    int32_t id;           // 0-based motif index reported in the hits
+    int32_t pad[2];
+};
+struct MotifHit {         // = kgma_motif_hit
+    int32_t motif, contig;
+    int64_t start;        // 1-based
+    int32_t mismatches, reserved;
+};
+static_assert(sizeof(MotifHit) == 24, "motif hits are 24 bytes");
+constexpr int KGMA_MOTIF_THREADS = 256;
+constexpr int KGMA_MOTIF_ITERS = 4;                            // plane words (32 start positions each) a lane takes per tile
+struct MotifArgs {
+    const uint32_t *planes;       // the plane copy: a {hi, lo} word pair per 32 bases (N stored as T)
+    const uint8_t *ascii;
+    const ContigDesc *cd;
+    const int64_t *tile_prefix;   // [n_contigs + 1]: tiles of the records before record c (a tile never spans two records)
+    int32_t n_contigs, n_motifs;
+    const MotifDesc *motifs;
+    const uint32_t *info;
+    MotifHit *out;
+    unsigned long long *ctl;      // [0]: hits found (keeps counting past cap)
+    unsigned long long cap;
+};
+
 // Reverse complement of the residue text (kgma_revcomp.hip; kgma_genome_revcomp).  Source and destination have the same layout.
 constexpr int KGMA_REVCOMP_THREADS = 256;
 constexpr int KGMA_REVCOMP_ITERS = 4;                          // 16-byte chunks a lane takes per tile (a tile: 16 KiB of a record's slot)

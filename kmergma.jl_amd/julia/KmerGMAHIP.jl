@@ -499,6 +499,49 @@ end
 exactMatch(query, genome::Union{String, DeviceGenome}; overlap::Bool = true, ctx::Context = default_context()) =
     exactMatch_batch([query], genome; overlap = overlap, ctx = ctx)[1]
 
-export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, Context
+struct KgmaMotifHit       # kgma_motif_hit: 0-based motif and contig, 1-based start
+    motif::Int32
+    contig::Int32
+    start::Int64
+    mismatches::Int32
+    reserved::Int32
+end
+
+const HumanRSSV = "CACAGTG" * "N"^12 * "ACAAAAACC"            # src/RSS.jl:14-15
+const HumanRSSD = "CACAGTG" * "N"^23 * "ACAAAAACC"
+
+"""
+    motifMatch(motifs, genome; max_mismatch = 0)   -- `genome`: a FASTA path or an open DeviceGenome
+IUPAC motifs (1 ... 64 symbols) with at most `max_mismatch` (one number, or one per motif) non-matching positions, all in one
+pass over the genome (kgma_motif_match): per motif the vector of (record identifier, range, mismatches).  A genome base matches
+a symbol whose set holds it; a genome N matches only a motif N.  For the minus strand pass the reverse complement of the motif:
+its matches are in forward coordinates.
+"""
+function motifMatch(motifs::Vector, genome::Union{String, DeviceGenome}; max_mismatch = 0, ctx::Context = default_context())
+    g = genome isa String ? genome_from_fasta(ctx, genome) : genome
+    try
+        ms = String[query_text(m) for m in motifs]
+        text = Vector{UInt8}(join(ms))
+        offsets = Int64[0; cumsum(Int64[ncodeunits(m) for m in ms])]
+        ds = max_mismatch isa Integer ? fill(Int32(max_mismatch), length(ms)) : Int32.(max_mismatch)
+        check(ctx, ccall((:kgma_motif_match, libkgma), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int64}, Int32, Ptr{Int32}),
+                         ctx.h, g.h, text, offsets, length(ms), ds))
+        n = Ref{Int64}(0)
+        check(ctx, ccall((:kgma_get_motif_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaMotifHit}, Int64, Ref{Int64}), ctx.h, C_NULL, 0, n))
+        hits = Vector{KgmaMotifHit}(undef, n[])
+        check(ctx, ccall((:kgma_get_motif_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaMotifHit}, Int64, Ref{Int64}), ctx.h, hits, n[], n))
+        out = [Tuple{String, UnitRange{Int64}, Int}[] for _ in ms]
+        for h in hits
+            push!(out[h.motif + 1], (identifier(g, h.contig), h.start:h.start + ncodeunits(ms[h.motif + 1]) - 1, Int(h.mismatches)))
+        end
+        return out
+    finally
+        genome isa String && free!(g)
+    end
+end
+motifMatch(motif, genome::Union{String, DeviceGenome}; max_mismatch::Integer = 0, ctx::Context = default_context()) =
+    motifMatch([motif], genome; max_mismatch = max_mismatch, ctx = ctx)[1]
+
+export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, HumanRSSV, HumanRSSD, Context
 
 end # module

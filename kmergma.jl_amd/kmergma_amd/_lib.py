@@ -35,6 +35,7 @@ EXPORTS = [
     "kgma_chain_values", "kgma_host_chain_walk", "kgma_chain_chunk_steps", "kgma_set_chain_source", "kgma_get_att", "kgma_set_att",
     "kgma_chain_export", "kgma_chain_export_copy", "kgma_kfv_scale", "kgma_kfv_is_float",
     "kgma_set_strobe_ref", "kgma_strobe_scan", "kgma_exact_match", "kgma_get_matches",
+    "kgma_motif_match", "kgma_get_motif_matches",
     "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
     "kgma_get_block_sums",
 ]
@@ -63,6 +64,11 @@ class KgmaMatch(C.Structure):
     _fields_ = [("query", C.c_int32), ("contig", C.c_int32), ("start", C.c_int64)]
 
 
+class KgmaMotifHit(C.Structure):
+    _fields_ = [("motif", C.c_int32), ("contig", C.c_int32), ("start", C.c_int64), ("mismatches", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class KgmaStats(C.Structure):
     _fields_ = [("bases_scanned", C.c_int64), ("windows_scanned", C.c_int64), ("n_dips", C.c_int64),
                 ("n_hits", C.c_int64), ("n_tie_flagged", C.c_int64), ("n_at_threshold", C.c_int64),
@@ -87,6 +93,8 @@ DIP_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("start", "<i8"), ("end
                       ("D_min", "<i8"), ("exit_pos", "<i8"), ("D_exit", "<i8"), ("flags", "<u4"), ("reserved", "<u4")])
 
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("contig", "<i4"), ("start", "<i8")])
+
+MOTIF_HIT_DTYPE = np.dtype([("motif", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("mismatches", "<i4"), ("reserved", "<i4")])
 
 ALIGN_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                        C.POINTER(C.c_int64), C.POINTER(C.c_int64))
@@ -139,6 +147,8 @@ def load():
     L.kgma_strobe_scan.argtypes = [vp, vp, i64, u32, C.c_char_p, i64, i32, i32, i64]
     L.kgma_exact_match.argtypes = [vp, vp, C.c_char_p, P(i64), i32, i32]
     L.kgma_get_matches.argtypes = [vp, P(KgmaMatch), i64, P(i64)]
+    L.kgma_motif_match.argtypes = [vp, vp, C.c_char_p, P(i64), i32, P(i32)]
+    L.kgma_get_motif_matches.argtypes = [vp, P(KgmaMotifHit), i64, P(i64)]
     L.kgma_genome_from_host.argtypes = [vp, P(C.c_char_p), P(i64), i64, P(vp)]
     L.kgma_genome_from_fasta.argtypes = [vp, vp, i64, P(vp)]
     L.kgma_genome_from_fasta_file.argtypes = [vp, C.c_char_p, P(vp)]
@@ -456,6 +466,26 @@ class Context:
         self._check(load().kgma_get_matches(self._h, None, 0, C.byref(n)))
         arr = np.zeros(max(n.value, 1), dtype=MATCH_DTYPE)
         self._check(load().kgma_get_matches(self._h, arr.ctypes.data_as(C.POINTER(KgmaMatch)), n.value, C.byref(n)))
+        return arr[:n.value]
+
+    def motif_match(self, genome: Genome, motifs: Sequence[bytes], max_mismatch: Sequence[int]) -> None:
+        """kgma_motif_match: every start in every record of `genome` at which motif i (1 ... 64 IUPAC symbols, either case)
+        lies with at most max_mismatch[i] non-matching positions; one pass over the genome for the whole batch.  Needs no
+        references.  motif_matches() afterwards."""
+        text, off = self._concat(motifs)
+        mm = np.ascontiguousarray(np.asarray(list(max_mismatch), dtype=np.int32).ravel())
+        if mm.size != off.size - 1:
+            raise ValueError("need one max_mismatch per motif")
+        mm = np.concatenate([mm, np.zeros(1, np.int32)])          # (never empty: a pointer to take)
+        self._check(load().kgma_motif_match(self._h, genome._h, text, _np_ptr(off, C.c_int64), off.size - 1, _np_ptr(mm, C.c_int32)))
+
+    def motif_matches(self) -> np.ndarray:
+        """Hits of the last motif_match as a structured array (MOTIF_HIT_DTYPE: 0-based motif and contig, 1-based start,
+        mismatches), sorted by (motif, contig, start)."""
+        n = C.c_int64(0)
+        self._check(load().kgma_get_motif_matches(self._h, None, 0, C.byref(n)))
+        arr = np.zeros(max(n.value, 1), dtype=MOTIF_HIT_DTYPE)
+        self._check(load().kgma_get_motif_matches(self._h, arr.ctypes.data_as(C.POINTER(KgmaMotifHit)), n.value, C.byref(n)))
         return arr[:n.value]
 
     def set_thresholds(self, thr: Sequence[float]) -> None:

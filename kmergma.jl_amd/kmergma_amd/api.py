@@ -12,6 +12,7 @@ Same names, keyword arguments, mutation-of-caller-vectors behaviour and error be
     Strobemer_findGenes    src/StrobemerGMA/StrobeGenomeMiner.jl:119-158
     exactMatch             src/ExactMatch.jl:89-121
     fasta_id_to_cumulative_len_dict  src/ExactMatch.jl:146-158
+    HumanRSSV, HumanRSSD, RSS_dist   src/RSS.jl:11-28 (and motifMatch / findRSS: the search that file is after)
 
 but the per-record scan runs on the MI355X through libkgma's C ABI (include/kgma.h).  The host
 keeps what the reference keeps on the host: FASTA parsing, reference preparation, optional
@@ -38,7 +39,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib, headers, refprep
-from .fasta import Record, read_fasta, write_fasta
+from .fasta import Record, read_fasta, reverse_complement, write_fasta
 
 log = logging.getLogger("KmerGMA")
 
@@ -592,6 +593,135 @@ def exactMatch(query, subject_seq, *, overlap: bool = True, ctx=None):
             g.free()
         return [(s, s + len(q) - 1) for s in starts] or None
     return exactMatch_batch([q], subject_seq, overlap=overlap, ctx=ctx)[0]
+
+
+# ---- IUPAC motif search with mismatches (kgma_motif_match): the working form of src/RSS.jl ----------------------------------
+
+# The recombination signal sequence heptamer - spacer - nonamer, as src/RSS.jl:11-15 defines it and under the reference's
+# names: HumanRSSV has the 12-nt spacer, HumanRSSD the 23-nt one.  The names are the reference's; which gene segment carries
+# which spacer depends on the locus, and IGHV genes carry the 23-nt form: on tests/data/Loci.fasta it is HumanRSSD that lies
+# behind each of the seven V genes the scan finds.
+HumanRSSV = b"CACAGTG" + b"N" * 12 + b"ACAAAAACC"
+HumanRSSD = b"CACAGTG" + b"N" * 23 + b"ACAAAAACC"
+
+_IUPAC_SYMBOLS = frozenset(b"ACGTRYSWKMBDHVNacgtryswkmbdhvn")
+MOTIF_MAX_LEN, MOTIF_MAX_MISMATCH = 64, 15
+
+
+def RSS_dist(RSS1, RSS2=HumanRSSV) -> int:
+    """RSS_dist (src/RSS.jl:22-28), literally: the number of positions i of RSS1 at which RSS1[i] != RSS2[i], symbols
+    compared for inequality after case folding.  The quirk is the reference's: an `N` of RSS2 is unequal to every base, so
+    against HumanRSSV every sequence has a distance of at least 12 and `is_RSS(..., thr = 1)` can never hold.  Use motifMatch
+    / findRSS for the search the file is after.  An RSS2 shorter than RSS1 raises IndexError (the reference: BoundsError)."""
+    a, b = _query_bytes(RSS1).upper(), _query_bytes(RSS2).upper()
+    if len(b) < len(a):
+        raise IndexError(f"RSS2 has {len(b)} symbols, RSS1 {len(a)} (BoundsError, src/RSS.jl:25)")
+    return sum(1 for i in range(len(a)) if a[i] != b[i])
+
+
+def _motif_bytes(motif, max_mismatch, which: str = "motif") -> bytes:
+    """The checks of kgma_motif_match, made before any device call."""
+    if isinstance(motif, Record):
+        m = bytes(motif.sequence)
+    elif isinstance(motif, str):
+        m = motif.encode()
+    elif isinstance(motif, (bytes, bytearray, memoryview)):
+        m = bytes(motif)
+    else:
+        raise TypeError("Invalid motif type")
+    if not 1 <= len(m) <= MOTIF_MAX_LEN:
+        raise ValueError(f"{which} has {len(m)} symbols (1 ... {MOTIF_MAX_LEN})")
+    for i, ch in enumerate(m):
+        if ch not in _IUPAC_SYMBOLS:
+            raise ValueError(f"{which}, symbol {i + 1} ({m[i:i + 1]!r}) is not an IUPAC nucleotide code")
+    d = int(max_mismatch)
+    if not 0 <= d <= MOTIF_MAX_MISMATCH:
+        raise ValueError(f"{which}: max_mismatch {d} (0 ... {MOTIF_MAX_MISMATCH})")
+    informative = sum(1 for ch in m.upper() if ch != ord("N"))
+    if d >= informative:
+        raise ValueError(f"{which}: max_mismatch {d} is not smaller than its {informative} informative (non-N) positions: "
+                         "every start would match")
+    return m
+
+
+def _motif_args(motifs, max_mismatch, strand):
+    _check_strand(strand)
+    motifs = list(motifs)
+    if isinstance(max_mismatch, (int, np.integer)):
+        ds = [int(max_mismatch)] * len(motifs)
+    else:
+        ds = [int(d) for d in max_mismatch]
+        if len(ds) != len(motifs):
+            raise ValueError("need one max_mismatch per motif")
+    ms = [_motif_bytes(m, d, f"motif {i}") for i, (m, d) in enumerate(zip(motifs, ds))]
+    # the minus strand: the reverse-complemented motif on the SAME genome, in the same pass
+    sent, tags = [], []
+    for i, (m, d) in enumerate(zip(ms, ds)):
+        if strand != "-":
+            sent.append((m, d)); tags.append((i, "+"))
+        if strand != "+":
+            sent.append((reverse_complement(m), d)); tags.append((i, "-"))
+    return ms, sent, tags
+
+
+def _motif_run(ctx, g, ms, sent, tags) -> list:
+    """Per motif the hits (record, lo, hi, strand, mismatches), sorted by (record, lo, strand)."""
+    ctx.motif_match(g, [m for m, _ in sent], [d for _, d in sent])
+    out = [[] for _ in ms]
+    for h in ctx.motif_matches().tolist():
+        i, st = tags[h[0]]
+        out[i].append((h[1], h[2], h[2] + len(ms[i]) - 1, st, h[3]))
+    for lst in out:
+        lst.sort(key=lambda t: (t[0], t[1], t[3]))              # ("+" sorts before "-")
+    return out
+
+
+def motifMatch_batch(motifs, genome_or_path, *, max_mismatch=0, strand: str = "+", ctx=None) -> list:
+    """Many IUPAC motifs in ONE pass over the genome (kgma_motif_match): per motif the list of
+    (record_index, identifier, lo, hi, strand, mismatches) -- 0-based record, 1-based inclusive lo:hi in forward coordinates --
+    sorted by (record, lo, strand).  `max_mismatch`: one number for all motifs or one per motif.  Semantics: motifMatch.
+    `genome_or_path`: a FASTA path, or a device genome that is already open (it stays open)."""
+    ms, sent, tags = _motif_args(motifs, max_mismatch, strand)
+    if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
+        raise TypeError("Invalid subject sequence type")
+    ctx = ctx or default_context()
+    g, src, owned = _open_subject(ctx, genome_or_path)
+    try:
+        res = _motif_run(ctx, g, ms, sent, tags)
+        ids = {c: _identifier(src, c) for c in {t[0] for lst in res for t in lst}}
+    finally:
+        if owned:
+            g.free()
+    return [[(c, ids[c], lo, hi, st, mm) for c, lo, hi, st, mm in lst] for lst in res]
+
+
+def motifMatch(motif, subject_seq, *, max_mismatch: int = 0, strand: str = "+", ctx=None):
+    """Every place at which `motif` -- 1 ... 64 IUPAC symbols (ACGTRYSWKMBDHVN, either case; bytes / str / Record) -- lies on
+    the subject with at most `max_mismatch` (0 ... 15) non-matching positions; overlapping places included, none spanning two
+    records.  A genome base matches a symbol whose set contains it; a genome N matches only a motif N (assembly gaps never
+    match informative positions).  `max_mismatch` must be smaller than the number of non-N symbols of the motif.  The subject
+    may hold A/C/G/T/N only (KgmaError KGMA_E_BADBASE otherwise).
+    strand: "+" the motif as given; "-" its reverse complement, searched on the same genome and reported at the forward
+    lo:hi it covers; "both" the two together (a motif equal to its own reverse complement is reported on both strands).
+    A `subject_seq` of residues (bytes, or a Record) returns [(lo, hi, strand, mismatches)] sorted by (lo, strand); a FASTA
+    path or an open device genome returns motifMatch_batch(...)[0].  An empty list when there is no match."""
+    if isinstance(subject_seq, (Record, bytes, bytearray, memoryview)):
+        ms, sent, tags = _motif_args([motif], max_mismatch, strand)
+        seq = bytes(subject_seq.sequence if isinstance(subject_seq, Record) else subject_seq)
+        ctx = ctx or default_context()
+        g = ctx.genome_from_host([seq])
+        try:
+            res = _motif_run(ctx, g, ms, sent, tags)[0]
+        finally:
+            g.free()
+        return [(lo, hi, st, mm) for _, lo, hi, st, mm in res]
+    return motifMatch_batch([motif], subject_seq, max_mismatch=max_mismatch, strand=strand, ctx=ctx)[0]
+
+
+def findRSS(genome_or_path, rss=HumanRSSD, max_mismatch: int = 1, strand: str = "both", ctx=None):
+    """Recombination signal sequences on a genome: motifMatch with the 23-nt-spacer RSS, one mismatch and both strands as the
+    defaults.  (The reference's Align_RSS / is_RSS are not mirrored: DESIGN.md, section 8.)"""
+    return motifMatch(rss, genome_or_path, max_mismatch=max_mismatch, strand=strand, ctx=ctx)
 
 
 def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
