@@ -17,6 +17,7 @@
 // from what it fetched one step earlier.  Trace bytes are stored wavefront-major (coalesced 64-byte
 // rows).  Lane 0 then walks the traceback and reduces the CIGAR to what cigar_to_UnitRange needs:
 // the length of its first run and the sum of all runs but the last.
+// The model itself (codes, scores, free end gaps) is defined on its own in tests/align_ref.py, which the tests hold this kernel to.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

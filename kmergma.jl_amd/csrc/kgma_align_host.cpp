@@ -12,6 +12,7 @@
 // length L scoring gap_open + L*gap_extend, EDNAFULL substitution scores, traceback preferring
 // match, then deletion, then insertion.  Pinned by the reference's own expectations that go
 // through the aligner (test/test_folder/test-KmerGMA.jl:128-145,179-193,214-250,257-271).
+// The model itself (codes, scores, free end gaps) is defined on its own in tests/align_ref.py, which the tests hold this file to.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
