@@ -246,7 +246,7 @@ struct FilterArgs {
     unsigned int cap;             // entries the list holds
     FilterEntry *list;
     unsigned int *ctl;            // entries appended (keeps counting past cap)
-    const uint16_t *bsum;         // PRESUMMED form: the block sums pack_sums_kernel wrote beside `inter` in this step (else unused)
+    const uint16_t *bsum;         // filter_sums_kernel: the block sums pack_sums_kernel wrote beside `inter` in this step (else null)
 };
 
 // The step's pack with the prefilter's block sums (kgma_filter.hip: pack_sums_kernel): what pack_kernel writes, plus per dword J of

@@ -17,7 +17,7 @@
 // lives in bank l % 32, so the 64 random reads of a wave never collide (2 LDS cycles instead of ~7 for one copy).
 // Output: per wave iteration with a candidate, ONE entry {record, granule of bit 0, 64-bit mask} appended with one atomic.
 // In a step (kgma_repack_scan_hits) whose S entries are bytes the block sums come from the step's pack instead: pack_sums_kernel
-// (below) writes them beside the 2-bit copy, and filter_kernel<..., PRESUMMED> loads one uint16 where it would do the 16 lookups.
+// (below) writes them beside the 2-bit copy, and filter_sums_kernel walks the streams on those sums, four blocks per lane.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,16 +61,14 @@ __device__ __forceinline__ void f_stage_table(uint32_t *fsm, const int32_t *S)
 }
 
 // ES: bytes per S entry (1: every S < 256, 2: < 65536); COPIES: 32 bank-interleaved copies, or 1
-// PRESUMMED: the block sums come from a.bsum (pack_sums_kernel wrote them in this step) -- one 2-byte load in the place of the 16
-// lookups, no S table in LDS; everything from the prefix sum on is the same code
-template <int K, int ES, int COPIES, bool PRESUMMED = false>
+template <int K, int ES, int COPIES>
 __global__ __launch_bounds__(1024) void filter_kernel(FilterArgs a)
 {
     constexpr int NB = 1 << (2 * K);
     constexpr uint32_t KM = (uint32_t)NB - 1u;
     constexpr int EPD = 4 / ES;                                        // entries per dword
     extern __shared__ uint32_t fsm[];
-    if constexpr (!PRESUMMED) f_stage_table<K, ES, COPIES>(fsm, a.S);
+    f_stage_table<K, ES, COPIES>(fsm, a.S);
     const uint8_t *tab = reinterpret_cast<const uint8_t *>(fsm);
     const int lane = (int)(threadIdx.x & 63);
     const uint32_t coff = COPIES > 1 ? 4u * (uint32_t)(lane & (COPIES - 1)) : 0u;
@@ -97,13 +95,8 @@ __global__ __launch_bounds__(1024) void filter_kernel(FilterArgs a)
         const int iters = (nb + 63) >> 6;
         auto load = [&](const int it, uint32_t &d0, uint32_t &d1) {
             const int64_t j = dw0 + ((int64_t)it << 6) + lane;
-            if constexpr (PRESUMMED) {
-                d0 = j < a.n_dwords ? (uint32_t)a.bsum[j] : 0u;
-                d1 = 0u;
-            } else {
-                d0 = j < a.n_dwords ? a.inter[j] : 0u;
-                d1 = j + 1 < a.n_dwords ? a.inter[j + 1] : 0u;
-            }
+            d0 = j < a.n_dwords ? a.inter[j] : 0u;
+            d1 = j + 1 < a.n_dwords ? a.inter[j + 1] : 0u;
         };
         uint32_t carry = 0, prevI = 0, n0, n1;
         load(0, n0, n1);
@@ -112,10 +105,7 @@ __global__ __launch_bounds__(1024) void filter_kernel(FilterArgs a)
             if (it + 1 < iters) load(it + 1, n0, n1);
             const int jb = (it << 6) + lane;                           // block, local to the stream
             uint32_t sum = 0;
-            if constexpr (PRESUMMED) {
-                // (the record's partial last block is masked in bsum; a block behind it may belong to the next record)
-                sum = rem - (jb << 4) >= 0 ? d0 : 0u;
-            } else if (rem - (((it << 6) + 63) << 4) >= 15) {          // (wave-uniform) every position of the iteration is a k-mer of the record
+            if (rem - (((it << 6) + 63) << 4) >= 15) {                 // (wave-uniform) every position of the iteration is a k-mer of the record
 #pragma unroll
                 for (int i = 0; i < 16; i++) {
                     const uint32_t x = (i == 0 ? d0 : __builtin_amdgcn_alignbit(d1, d0, 2 * i)) & KM;
@@ -152,12 +142,114 @@ __global__ __launch_bounds__(1024) void filter_kernel(FilterArgs a)
     }
 }
 
+// The form on the block sums a.bsum that pack_sums_kernel wrote in this step (kgma_filter_stats::form bit 16): no k-mers, no S
+// table.  A wave iteration covers 256 blocks, lane l the blocks 4l ... 4l + 3 -- one 8-byte load (bsum + 2 * word_base is 4-byte
+// aligned whatever the record's word offset, and an 8-byte global load needs no more) -- so that the DPP scan, the carry, the loop
+// and the ballots' bookkeeping run once per 256 blocks: a serial prefix over the lane's four sums, one scan over the lane totals.
+// With nblk = 4 qa + QB the lower end of element q of lane l is element (q - QB) & 3 of lane l - qa - [q < QB], of this iteration
+// or, for the first lanes, of the one before.  Every source lane is read by exactly one destination per q, so the SOURCE chooses
+// which iteration's value it offers: one ds_bpermute per element.
+// The list keeps its format (64 consecutive granules per entry): the four ballots hold block 4l + q at bit l and are transposed,
+// with four more ballots, only when one of them is non-zero.
+// QB: nblk % 4 (which element of the source lane an element reads is then fixed at compile time)
+template <int QB>
+__global__ __launch_bounds__(1024) void filter_sums_kernel(FilterArgs a, int K)
+{
+    const int lane = (int)(threadIdx.x & 63);
+    const int waves_per_wg = (int)(blockDim.x >> 6);
+    const int wave0 = (int)blockIdx.x * waves_per_wg + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int n_waves = (int)gridDim.x * waves_per_wg;
+    const int nblk = a.nblk;
+    const int qa = nblk >> 2;
+    int lo_idx[4];                                                     // (bpermute takes byte addresses)
+    bool offer_cur[4];                                                 // the lane's reader is in this iteration (else in the next)
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int back = qa + (q < QB ? 1 : 0);
+        lo_idx[q] = ((lane - back) & 63) << 2;
+        offer_cur[q] = lane + back < 64;
+    }
+    const uint32_t *pairs = reinterpret_cast<const uint32_t *>(a.bsum);   // a plane word's two sums
+    const int64_t n_pairs = a.n_dwords >> 1;
+
+    for (int t = wave0; t < a.n_tiles; t += n_waves) {
+        const TileDesc td = a.tiles[t];
+        const int64_t g0 = (td.win0 - 1) >> 4;                         // first granule of the stream (streams start on 64-window boundaries)
+        const int ng = (td.n_valid + 15) >> 4;
+        const int nb = ng + nblk - 1;                                  // blocks the stream's granules use
+        // blocks of the stream that hold a k-mer of the record (its last k-mer is at len - K): the partial last one is masked in
+        // bsum, a block behind it may belong to the next record
+        const int64_t rem64 = a.cd[td.contig].len - K - (g0 << 4);
+        const int nvb = __builtin_amdgcn_readfirstlane(rem64 < 0 ? 0 : (int)((rem64 > 0x3FFFFFFF ? 0x3FFFFFFF : rem64) >> 4) + 1);
+        const int iters = (nb + 255) >> 8;
+        auto load = [&](const int it, uint32_t &x, uint32_t &y) {
+            const int64_t j = td.word_base + ((int64_t)it << 7) + 2 * lane;
+            x = 0u; y = 0u;
+            if (j + 1 < n_pairs) {
+                u32x2_t v;
+                __builtin_memcpy(&v, pairs + j, 8);
+                x = v.x; y = v.y;
+            } else if (j < n_pairs) {
+                x = pairs[j];
+            }
+        };
+        uint32_t carry = 0, prevR[4] = {0u, 0u, 0u, 0u}, nx, ny;
+        load(0, nx, ny);
+        for (int it = 0; it < iters; it++) {
+            const uint32_t x = nx, y = ny;
+            if (it + 1 < iters) load(it + 1, nx, ny);
+            const int jb = (it << 8) + 4 * lane;                       // the lane's first block, local to the stream
+            uint32_t s[4] = {x & 0xFFFFu, x >> 16, y & 0xFFFFu, y >> 16};
+            if ((it << 8) + 256 > nvb) {                               // (wave-uniform) the record ends in this iteration
+#pragma unroll
+                for (int q = 0; q < 4; q++) s[q] = jb + q < nvb ? s[q] : 0u;
+            }
+            uint32_t I[4], R[4];
+            const uint32_t p1 = s[0] + s[1], p2 = p1 + s[2], p3 = p2 + s[3];
+            I[3] = f_incl_scan(p3) + carry;                            // (mod 2^32: only differences nblk blocks apart are used)
+            carry = (uint32_t)__builtin_amdgcn_readlane((int)I[3], 63);
+            const uint32_t base = I[3] - p3;
+            I[0] = base + s[0]; I[1] = base + p1; I[2] = base + p2;
+#pragma unroll
+            for (int q = 0; q < 4; q++) R[q] = I[(q - QB) & 3];
+            uint64_t m[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(lo_idx[q], (int)(offer_cur[q] ? R[q] : prevR[q]));
+                prevR[q] = R[q];
+                const int gl = jb + q - (nblk - 1);                    // the granule whose last block this is
+                m[q] = __ballot(((uint32_t)gl < (uint32_t)ng) & (I[q] - lo >= a.U));
+            }
+            if ((m[0] | m[1] | m[2] | m[3]) != 0) {                    // rare: entry e holds the blocks 64 e ... 64 e + 63 of the iteration
+                const uint64_t mine = (lane & 3) == 0 ? m[0] : (lane & 3) == 1 ? m[1] : (lane & 3) == 2 ? m[2] : m[3];
+#pragma unroll 1
+                for (int e = 0; e < 4; e++) {
+                    const uint64_t me = __ballot(((mine >> (16 * e + (lane >> 2))) & 1u) != 0);
+                    if (me != 0 && lane == 0) {
+                        const unsigned int idx = atomicAdd(a.ctl, 1u);
+                        if (idx < a.cap) {
+                            FilterEntry fe;
+                            fe.contig = td.contig;
+                            fe.gbase = (int32_t)(g0 + (it << 8) + 64 * e - (nblk - 1));
+                            fe.mask = me;
+                            a.list[idx] = fe;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
 // ---- the step's pack with the block sums -------------------------------------------------------------------------------------
 // pack_sums_kernel writes what pack_kernel writes (kgma_kernels.hip: planes, interleaved copy, first_bad) and, per dword J of the
 // interleaved copy, bsum[J] = the sum of S over the k-mers that start in the dword and are k-mers of its record (position <= len - K);
-// 0 for padding.  filter_kernel<..., PRESUMMED> then loads one sum where it would cut and look up 16 k-mers: the codes are in
+// 0 for padding.  filter_sums_kernel then loads one sum where filter_kernel cuts and looks up 16 k-mers: the codes are in
 // registers here anyway, and the pack waits for HBM while the filter waits for the vector unit.
-// Persistent waves, the S table in LDS as filter_kernel<K, 1, 32> keeps it.  A wave takes UNITS of 128 consecutive plane words (two
+// Persistent waves.  In LDS: the PAIR table P[y] = S[y & KM] + S[(y >> 2) & KM] over the (K + 1)-mers y (uint16: every S < 256, so
+// P <= 510 and a block sum <= 4080), one copy, and behind it S itself as bytes.  On the fast path a dword's sum is eight reads of
+// P at the even positions -- the address is the (K + 1)-mer cut out one bit low, i.e. already times two: a shift or v_alignbit and
+// one AND per two positions; the word-by-word path looks single positions up in the byte table.  A wave takes UNITS of 128 consecutive plane words (two
 // chunks of 64: lane l packs words l and 64 + l) and has the next unit's four 16-byte loads per lane in flight while it encodes the
 // current one (64 KiB per CU at 16 waves).  A word's second dword needs the first dword of the next word: lane l + 1's, the other
 // chunk's lane 0 for lane 63 of the first chunk, and for the unit's last word K - 1 residues encoded by lane 0 on the side.
@@ -180,30 +272,72 @@ __device__ __forceinline__ uint32_t ps_halo(const uint2 b)             // 2-bit 
     for (int i = 0; i < K - 1; i++) r |= ps_code(((i < 4 ? b.x : b.y) >> (8 * (i & 3))) & 0xFFu) << (2 * i);
     return r;
 }
-// sum of S over the first nv of the 16 k-mers that start in d0 (d1: the dword behind it); tab: the lane's copy of the 32 copies of
-// byte entries (byte x % 4 of dword (x / 4) * 32)
-template <int K, bool MASKED>
-__device__ __forceinline__ uint32_t ps_sum16(const uint32_t d0, const uint32_t d1, const uint8_t *tab, const int nv)
+// the same of residues that are all accepted letters, in either case (a unit with another one is reported and its sums are void)
+template <int K>
+__device__ __forceinline__ uint32_t ps_halo_clean(const uint2 b)
+{
+    const uint32_t c0 = __builtin_amdgcn_perm(0x03000000u, 0x02030100u, (b.x >> 1) & 0x07070707u);   // (as pack_word_2bit)
+    uint32_t r = __builtin_amdgcn_udot4(c0, 0x40100401u, 0u, false);
+    if (K > 5) {
+        const uint32_t c1 = __builtin_amdgcn_perm(0x03000000u, 0x02030100u, (b.y >> 1) & 0x07070707u);
+        r = __builtin_amdgcn_udot4(c1, 0x40100401u, 0u, false) << 8 | r;
+    }
+    return r & ((1u << (2 * (K - 1))) - 1u);
+}
+// sum of S over the first nv of the 16 k-mers that start in d0 (d1: the dword behind it); tab: S as bytes
+template <int K>
+__device__ __forceinline__ uint32_t ps_sum16_masked(const uint32_t d0, const uint32_t d1, const uint8_t *tab, const int nv)
 {
     constexpr uint32_t KM = (1u << (2 * K)) - 1u;
     uint32_t sum = 0;
 #pragma unroll
     for (int i = 0; i < 16; i++) {
-        const uint32_t y = i == 0 ? d0 : __builtin_amdgcn_alignbit(d1, d0, 2 * i);
-        // byte (x % 4) of dword (x / 4) * 32 + copy: the three fields do not overlap
-        const uint32_t v = tab[((y & (KM & ~3u)) << 5) + (y & 3u)];
-        sum += (!MASKED || i < nv) ? v : 0u;
+        const uint32_t v = tab[(i == 0 ? d0 : __builtin_amdgcn_alignbit(d1, d0, 2 * i)) & KM];
+        sum += i < nv ? v : 0u;
     }
     return sum;
+}
+// sum of S over all 16 k-mers that start in d0: eight pair sums.  ptab: the pair table; the byte offset of the pair at positions
+// i, i + 1 is the (K + 1)-mer at i times 2.  A pair that lies inside d0 takes a plain shift (two-operand forms issue at twice
+// v_alignbit's rate, profiles/r01_valu_issue_rates.txt)
+template <int K>
+__device__ __forceinline__ uint32_t ps_sum16_pairs(const uint32_t d0, const uint32_t d1, const uint8_t *ptab)
+{
+    constexpr uint32_t M2 = ((1u << (2 * (K + 1))) - 1u) << 1;
+    uint32_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i += 2) {
+        const uint32_t y2 = i == 0 ? d0 << 1 : 2 * i + 2 * (K + 1) <= 32 ? d0 >> (2 * i - 1) : __builtin_amdgcn_alignbit(d1, d0, 2 * i - 1);
+        sum += *reinterpret_cast<const uint16_t *>(ptab + (y2 & M2));
+    }
+    return sum;
+}
+// the pair table (4^(K+1) uint16) at fsm, S as bytes (4^K) behind it
+template <int K>
+__device__ __forceinline__ void ps_stage_tables(uint32_t *fsm, const int32_t *S)
+{
+    constexpr int NB = 1 << (2 * K), NP = 4 * NB;
+    constexpr uint32_t KM = (uint32_t)NB - 1u;
+    uint32_t *bytes = fsm + NP / 2;
+    for (int t = (int)threadIdx.x; t < NB / 4; t += (int)blockDim.x)
+        bytes[t] = (uint32_t)S[4 * t] | (uint32_t)S[4 * t + 1] << 8 | (uint32_t)S[4 * t + 2] << 16 | (uint32_t)S[4 * t + 3] << 24;
+    __syncthreads();
+    const uint8_t *tab = reinterpret_cast<const uint8_t *>(bytes);
+    for (int t = (int)threadIdx.x; t < NP / 2; t += (int)blockDim.x) {
+        const uint32_t y = 2u * (uint32_t)t, hi = tab[(y >> 2) & KM];    // (y and y + 1 share their second k-mer)
+        fsm[t] = ((uint32_t)tab[y & KM] + hi) | ((uint32_t)tab[(y + 1u) & KM] + hi) << 16;
+    }
+    __syncthreads();
 }
 
 template <int K>
 __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
 {
     extern __shared__ uint32_t fsm[];
-    f_stage_table<K, 1, 32>(fsm, a.S);
+    ps_stage_tables<K>(fsm, a.S);
     const int lane = (int)(threadIdx.x & 63);
-    const uint8_t *tab = reinterpret_cast<const uint8_t *>(fsm) + 4 * (lane & 31);   // the lane's copy
+    const uint8_t *ptab = reinterpret_cast<const uint8_t *>(fsm);      // pair sums
+    const uint8_t *tab = ptab + (8u << (2 * K));                       // S as bytes
     const int waves_per_wg = (int)(blockDim.x >> 6);
     const int64_t wave0 = (int64_t)blockIdx.x * waves_per_wg + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t n_waves = (int64_t)gridDim.x * waves_per_wg;
@@ -265,19 +399,19 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
         }
         if (clean) {
             // the first dword of the next word: lane l + 1's; lane 63 reads lane 0, which offers the other chunk's / the halo's
-            const uint32_t h = ps_halo<K>(cu.halo);
+            const uint32_t h = ps_halo_clean<K>(cu.halo);
             const uint32_t n0 = (uint32_t)__builtin_amdgcn_ds_bpermute(next_idx, (int)(lane == 0 ? i1.x : i0.x));
             const uint32_t n1 = (uint32_t)__builtin_amdgcn_ds_bpermute(next_idx, (int)(lane == 0 ? h : i1.x));
             // (one sum's 16 lookups at a time: the other waves of the SIMD cover their latency, interleaving all 64 only costs registers)
             __builtin_amdgcn_sched_barrier(0);
-            const uint32_t s00 = ps_sum16<K, false>(i0.x, i0.y, tab, 16);
+            const uint32_t s00 = ps_sum16_pairs<K>(i0.x, i0.y, ptab);
             __builtin_amdgcn_sched_barrier(0);
-            const uint32_t s01 = ps_sum16<K, false>(i0.y, n0, tab, 16);
+            const uint32_t s01 = ps_sum16_pairs<K>(i0.y, n0, ptab);
             store(g0, lane, r0, i0, s00, s01);
             __builtin_amdgcn_sched_barrier(0);
-            const uint32_t s10 = ps_sum16<K, false>(i1.x, i1.y, tab, 16);
+            const uint32_t s10 = ps_sum16_pairs<K>(i1.x, i1.y, ptab);
             __builtin_amdgcn_sched_barrier(0);
-            const uint32_t s11 = ps_sum16<K, false>(i1.y, n1, tab, 16);
+            const uint32_t s11 = ps_sum16_pairs<K>(i1.y, n1, ptab);
             store(g0 + 64, lane, r1, i1, s10, s11);
             return;
         }
@@ -303,8 +437,8 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
                 const uint32_t h = base0 + 32 < L ? ps_halo<K>(*reinterpret_cast<const uint2 *>(src + 32)) : 0u;
                 const int64_t nk = L - K + 1 - base0;                  // k-mers of the record from the word's first position on
                 const int nv0 = nk < 0 ? 0 : nk > 16 ? 16 : (int)nk, nv1 = nk < 16 ? 0 : nk > 32 ? 16 : (int)(nk - 16);
-                s0 = ps_sum16<K, true>(iw.x, iw.y, tab, nv0);
-                s1 = ps_sum16<K, true>(iw.y, h, tab, nv1);
+                s0 = ps_sum16_masked<K>(iw.x, iw.y, tab, nv0);
+                s1 = ps_sum16_masked<K>(iw.y, h, tab, nv1);
             }
             store(g0 + q * 64, lane, r, iw, s0, s1);
         }
@@ -330,21 +464,36 @@ __global__ void filter_publish_kernel(unsigned int *ctl, unsigned int *host)
 
 bool filter_applies(int k, int64_t s_max) { return (k == 5 || k == 6) && s_max >= 0 && s_max <= 65535; }
 
-template <int K, int ES, int COPIES, bool PRESUMMED = false>
-static hipError_t filter_launch(const FilterArgs &a, int n_cus, hipStream_t st)
+static int64_t filter_grid(const FilterArgs &a, int n_cus, int per_cu)
 {
-    constexpr size_t lds = PRESUMMED ? 0 : ((size_t)1 << (2 * K)) * ES * COPIES;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&filter_kernel<K, ES, COPIES, PRESUMMED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    // persistent waves: every CU's wave slots once (one 16-wave workgroup where the copies fill the LDS, else two)
-    int per_cu = lds > (64u << 10) ? 1 : 2;
-    if (PRESUMMED)
-        if (const char *w = getenv("KGMA_FILTER_WGS")) per_cu = atoi(w) == 1 ? 1 : 2;   // experiments (EXPERIMENTS.md section 14)
     int64_t grid = (int64_t)n_cus * per_cu;
     const int64_t need = ((int64_t)a.n_tiles + 15) / 16;
     if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((filter_kernel<K, ES, COPIES, PRESUMMED>), dim3((unsigned)grid), dim3(1024), lds, st, a);
+    return grid < 1 ? 1 : grid;
+}
+
+template <int K, int ES, int COPIES>
+static hipError_t filter_launch(const FilterArgs &a, int n_cus, hipStream_t st)
+{
+    constexpr size_t lds = ((size_t)1 << (2 * K)) * ES * COPIES;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&filter_kernel<K, ES, COPIES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    // persistent waves: every CU's wave slots once (one 16-wave workgroup where the copies fill the LDS, else two)
+    hipLaunchKernelGGL((filter_kernel<K, ES, COPIES>), dim3((unsigned)filter_grid(a, n_cus, lds > (64u << 10) ? 1 : 2)), dim3(1024), lds, st, a);
+    return hipGetLastError();
+}
+
+static hipError_t filter_sums_launch(const FilterArgs &a, int k, int n_cus, hipStream_t st)
+{
+    int per_cu = 2;
+    if (const char *w = getenv("KGMA_FILTER_WGS")) per_cu = atoi(w) == 1 ? 1 : 2;       // experiments (EXPERIMENTS.md section 14)
+    const dim3 grid((unsigned)filter_grid(a, n_cus, per_cu));
+    switch (a.nblk & 3) {
+    case 0: hipLaunchKernelGGL(filter_sums_kernel<0>, grid, dim3(1024), 0, st, a, k); break;
+    case 1: hipLaunchKernelGGL(filter_sums_kernel<1>, grid, dim3(1024), 0, st, a, k); break;
+    case 2: hipLaunchKernelGGL(filter_sums_kernel<2>, grid, dim3(1024), 0, st, a, k); break;
+    default: hipLaunchKernelGGL(filter_sums_kernel<3>, grid, dim3(1024), 0, st, a, k); break;
+    }
     return hipGetLastError();
 }
 
@@ -353,11 +502,11 @@ bool pack_sums_applies(int k, int64_t s_max) { return (k == 5 || k == 6) && s_ma
 template <int K>
 static hipError_t pack_sums_launch(const PackSumsArgs &a, int n_cus, hipStream_t st)
 {
-    constexpr size_t lds = ((size_t)1 << (2 * K)) * 32;
+    constexpr size_t lds = ((size_t)1 << (2 * K)) * 9;                 // 4^(K+1) uint16 + 4^K bytes
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&pack_sums_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    // persistent waves, as filter_launch
-    int64_t grid = (int64_t)n_cus * (lds > (64u << 10) ? 1 : 2);
+    // persistent waves: one 16-wave workgroup per CU (at up to 128 VGPRs a second one would not be resident beside it)
+    int64_t grid = n_cus;
     const int64_t need = ((a.total_words + PS_UNIT - 1) / PS_UNIT + 15) / 16;
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
@@ -371,7 +520,7 @@ hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_c
     return k == 5 ? pack_sums_launch<5>(a, n_cus, st) : pack_sums_launch<6>(a, n_cus, st);
 }
 
-// *form: the instantiation launched, S entry bytes | table copies << 8 (kgma_filter_stats::form); bit 16: the PRESUMMED form, on the
+// *form: the instantiation launched, S entry bytes | table copies << 8 (kgma_filter_stats::form); bit 16: filter_sums_kernel, on the
 // block sums a.bsum that pack_sums_kernel wrote (byte entries only)
 hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, int32_t *form, hipStream_t st)
 {
@@ -380,7 +529,7 @@ hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, u
     const bool presummed = a.bsum != nullptr;
     if (presummed && es != 1) return hipErrorInvalidValue;
     hipError_t e;
-    if (presummed) e = k == 5 ? filter_launch<5, 1, 32, true>(a, n_cus, st) : filter_launch<6, 1, 32, true>(a, n_cus, st);
+    if (presummed) e = filter_sums_launch(a, k, n_cus, st);
     else if (k == 5) e = es == 1 ? filter_launch<5, 1, 32>(a, n_cus, st) : filter_launch<5, 2, 32>(a, n_cus, st);
     else e = es == 1 ? filter_launch<6, 1, 32>(a, n_cus, st) : filter_launch<6, 2, 1>(a, n_cus, st);
     if (e != hipSuccess) return e;

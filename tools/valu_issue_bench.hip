@@ -1,6 +1,7 @@
 // valu_issue_bench.hip -- measures the VALU issue rate of the bit operations the scan kernel is built from
 // (build: hipcc --offload-arch=gfx950 -O3 -o valu_issue_bench tools/valu_issue_bench.hip). Output of one run is
-// kept in profiles/r01_valu_issue_rates.txt; DESIGN.md section 4 uses it for the VALU roofline.
+// kept in profiles/r01_valu_issue_rates.txt; DESIGN.md section 4 uses it for the VALU roofline.  The rows from v_dot4_u32_u8 on
+// are the forms of the fused pack's encoder and pair lookups (EXPERIMENTS.md section 15).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -32,6 +33,11 @@ __global__ void __launch_bounds__(256) kern(uint32_t *out, uint64_t *cyc, int it
                 else if (OP == 5) d = __builtin_amdgcn_alignbit(a, b, 7); // v_alignbit imm
                 else if (OP == 6) d = (a >> 3) | b;                       // lshr + or  (2 ops)
                 else if (OP == 7) d = (a & c) | b;                        // v_and_or_b32
+                else if (OP == 8) d = __builtin_amdgcn_udot4(a, b, c, false);   // v_dot4_u32_u8
+                else if (OP == 9) d = __builtin_amdgcn_perm(a, b, c & 0x07070707u) ^ c;   // v_and + v_perm_b32 + v_xor (3 ops)
+                else if (OP == 10) d = a + b + c;                         // v_add3_u32
+                else if (OP == 11) d = (a << 8) | b;                      // v_lshl_or_b32
+                else if (OP == 12) d = (a >> 3) & b;                      // lshr + and  (2 ops)
                 else d = a + b;
                 asm volatile("" : "+v"(d));
                 r[i] = d;
@@ -86,6 +92,11 @@ int main()
         run<4>("bitop3 xor3", w);
         run<7>("v_and_or", w);
         run<6>("lshr+or (2 ops)", w);
+        run<8>("v_dot4_u32_u8", w);
+        run<9>("and+v_perm+xor (3 ops)", w);
+        run<10>("v_add3_u32", w);
+        run<11>("v_lshl_or", w);
+        run<12>("lshr+and (2 ops)", w);
     }
     return 0;
 }
