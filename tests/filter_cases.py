@@ -17,7 +17,7 @@ KS = (5, 6)
 NS = (7, 300)
 NKS = (2, 16, 17, 18, 34, 100, 284, 383)
 MATRIX = [(k, N, nk) for k in KS for N in NS for nk in NKS]
-CHAIN_NK = 100                          # the one nk per instantiation that also runs the chain replay
+CHAIN_NK = 100                          # the chain replay runs too at every nk up to this one
 BUFF = 50
 LONG, PLANT_EVERY, TANDEM_AT, TANDEM_WINDOWS = 200_000, 20_000, 110_000, 2_400
 SEED = 6200

@@ -72,3 +72,38 @@ def test_walk_checks_drift_and_ties(alp_ref):
     with pytest.raises(_lib.KgmaError):
         _lib.host_chain_walk(first * (1 + 2.0 ** -28), scale, nk, em["win0"], em["n_valid"], em["chunk_base"], em["D0"], em["chunks"], em["pool"],
                              [(nwin, nwin)])
+
+
+@pytest.mark.parametrize("nk", [2, 3, 17, 33, 63, 64, 65])
+@pytest.mark.parametrize("T", [1024, 4096])
+def test_walk_short_windows(nk, T):
+    """Windows of fewer k-mers than a 64-position step (and 64, 65): a stream's n_valid + nk - 1 positions end inside the step that
+    holds its last window, and the window a step starts on is clamped to the stream's first.  Every window (raw steps only) and a
+    few sampled ones (regular chunks in between), bit for bit against the oracle's running value."""
+    from tests import filter_cases as fc
+    k = 6
+    ref = fc.family(k, 7, nk)
+    W, RV, S, N = ref["ws"], ref["RV"], ref["S"], ref["N"]
+    rng = np.random.default_rng([13, nk])
+    a = bytearray(random_dna(rng, 9_000))
+    a[1000:1300] = b"A" * 300
+    a[2000:2200] = b"N" * 100 + b"n" * 100
+    a[3000:3300] = b"AC" * 150
+    a[5000:5000 + W] = ref["base"]
+    a[6000 + 63 - nk:6000 + 63 - nk + W] = ref["base"]
+    seq = bytes(a)
+    first, inc, D = chain_emul.increments(seq, RV, S, N, k, W)
+    _, od = orc.single_scan([seq], RV, k, W, 30.0, 50, return_dists=True)
+    chain = np.concatenate([[first], od])
+    nwin = len(D)
+    assert nwin == len(seq) - W + 1 and first == orc.kmer_dist_kfv(seq[:W], RV, k)
+    scale = 2.0 * k * N * N
+    em = chain_emul.emulate(inc, D, nk, T, scale, hot_windows=range(1, nwin + 1))
+    v, _ = _lib.host_chain_walk(first, scale, nk, em["win0"], em["n_valid"], em["chunk_base"], em["D0"], em["chunks"], em["pool"], [(1, nwin)])
+    assert np.array_equal(v, chain), "first mismatch at window %d" % (int(np.argmax(v != chain)) + 1)
+    iv = [(1, 1), (2, 3), (63, 66), (T, T + 2), (5001, 5001), (nwin - 1, nwin)]
+    hot = [w for lo, hi in iv for w in range(lo, hi + 1)]
+    em = chain_emul.emulate(inc, D, nk, T, scale, hot_windows=hot)
+    v, drift = _lib.host_chain_walk(first, scale, nk, em["win0"], em["n_valid"], em["chunk_base"], em["D0"], em["chunks"], em["pool"], iv)
+    assert np.array_equal(v, np.concatenate([chain[lo - 1:hi] for lo, hi in iv]))
+    assert drift < 2.0 ** -40

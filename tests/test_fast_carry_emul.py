@@ -95,7 +95,9 @@ def _S(rng, k, N=7):
     return rng.integers(0, N + 1, size=1 << (2 * k)).astype(np.int64), N
 
 
-@pytest.mark.parametrize("k,nk", [(6, 284), (5, 120), (2, 200)])
+# (nk < 64: a lane's leaving k-mer entered by lane p - nk of the same step -- it is not in the start-of-step counts, so nearly every
+#  lane is pending; the step total and the prefix margin hold all the same)
+@pytest.mark.parametrize("k,nk", [(6, 284), (5, 120), (2, 200), (6, 2), (6, 17), (6, 63), (5, 33), (2, 3)])
 def test_random_sequence(k, nk):
     rng = np.random.default_rng(1000 + k)
     S, N = _S(rng, k)
@@ -121,6 +123,23 @@ def test_tandem_repeats(period):
     seq = np.concatenate([rng.integers(0, 4, size=350), rep, rng.integers(0, 4, size=500)])
     worst = _run(seq, k, nk, S, N, rng)
     assert max(worst) > 0 or period == 1, "a repeat without pending lanes"
+
+
+@pytest.mark.parametrize("nk", [17, 63])
+def test_short_windows_tandem_and_homopolymer(nk):
+    """Windows of fewer k-mers than a step has lanes, over a tandem repeat (period 3 and 7) and a homopolymer next to random sequence."""
+    k = 6
+    for period in (3, 7):
+        rng = np.random.default_rng(200 + 10 * nk + period)
+        S, N = _S(rng, k)
+        unit = rng.integers(0, 4, size=period)
+        rep = np.tile(unit, 700 // period + 1)[:700]
+        worst = _run(np.concatenate([rng.integers(0, 4, size=350), rep, rng.integers(0, 4, size=500)]), k, nk, S, N, rng)
+        assert max(worst) > 0, "a repeat without pending lanes"
+    rng = np.random.default_rng(300 + nk)
+    S, N = _S(rng, k)
+    worst = _run(np.concatenate([rng.integers(0, 4, size=400), np.full(500, 2), rng.integers(0, 4, size=600)]), k, nk, S, N, rng)
+    assert max(worst) > 0
 
 
 def test_many_collisions():
