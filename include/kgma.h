@@ -238,6 +238,37 @@ int kgma_genome_from_fasta(kgma_ctx *ctx, const uint8_t *text, int64_t n, kgma_g
 int kgma_genome_from_fasta_file(kgma_ctx *ctx, const char *path, kgma_genome **out);
 int kgma_genome_header(const kgma_genome *g, int64_t contig, const char **text, int64_t *len);
 
+/* Build a device-resident genome from a UCSC .2bit file (the form assemblies are distributed in: hg38.2bit).  The file is 2 bits
+ * per base on disk, with its runs of N and its soft-masked runs as interval lists; the packed bytes and the lists are shipped as
+ * they are (0.25 byte per base over the link instead of the 1 byte of FASTA text) and expanded to the ordinary resident text by
+ * one kernel (twobit_unpack_kernel: one pass, 0.25 B read + 1 B written per base), then packed as in kgma_genome_from_host.
+ * Residue i of a record is N inside an N block, else the letter of its 2-bit code, and lower case inside a mask block (an N
+ * there is `n`): what twoBitToFa writes.  The result is an ordinary genome; kgma_genome_header returns a record's name.
+ * flags: KGMA_2BIT_NOMASK ignores the mask blocks (all upper case: twoBitToFa -noMask).
+ * The whole file is validated on the host before any device work.  KGMA_E_UNSUPPORTED: a byte-swapped file, a version above 1
+ * (0: 32-bit record offsets, 1: 64-bit), more tiles than one launch of the kernel takes.  KGMA_E_ARG: a wrong signature; an index,
+ * a table or packed data that run past the end of the file; a block that ends behind its record; sums that leave 64 bits; more
+ * records than a genome holds; a path that cannot be opened as a regular file.  kgma_last_error names record and field.  Block
+ * lists need not be sorted or disjoint: they are normalised (empty blocks dropped, sorted, overlapping and adjacent ones merged).
+ * KGMA_E_HIP / KGMA_E_NOMEM as kgma_genome_from_host (nothing is left allocated). */
+enum { KGMA_2BIT_NOMASK = 1u << 0 };
+int kgma_genome_from_2bit_file(kgma_ctx *ctx, const char *path, uint32_t flags, kgma_genome **out);
+/* Device time of twobit_unpack_kernel in the last kgma_genome_from_2bit_file of the context (hipEvents around the launch), in
+ * milliseconds; 0 if the file had no records.  KGMA_E_STATE before the first such call. */
+int kgma_get_2bit_unpack_ms(kgma_ctx *ctx, double *ms);
+/* HOST-side (no device, no context): what the parser of kgma_genome_from_2bit_file makes of a file -- the same validation, status
+ * codes and messages (`err`, NUL-terminated, may be NULL).  Block counts are those of the normalised lists. */
+typedef struct {
+    int32_t version;
+    int32_t reserved;
+    int64_t n_records;
+    int64_t total_bases;
+    int64_t n_blocks;       /* N blocks, all records */
+    int64_t mask_blocks;    /* mask blocks, all records */
+    int64_t packed_bytes;   /* sum of ceil(dnaSize / 4) */
+} kgma_twobit_info;
+int kgma_twobit_inspect(const char *path, kgma_twobit_info *info, char *err, int64_t err_cap);
+
 /* Build a synthetic genome on the device (benchmarks; no PCIe traffic): n_contigs records of the
  * given lengths, base i of record c = splitmix64(seed + c, i) >> 62 written as ASCII 'A','C','G','T',
  * then `n_plants` copies of `plant` (ASCII, length plant_len) written at the given (contig,

@@ -35,6 +35,7 @@
 #include "../../include/kgma.h"
 #include "kgma_device.h"
 #include "kgma_chain.h"
+#include "kgma_twobit.h"
 
 namespace kgma {
 hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs,
@@ -90,6 +91,8 @@ int motif_planes(int max_mm);
 hipError_t launch_motif(const MotifArgs &a, int P, int64_t n_tiles, hipStream_t st);
 int64_t revcomp_tile_bytes();
 hipError_t launch_revcomp(const RevcompArgs &a, int64_t n_tiles, hipStream_t st);
+int64_t twobit_tile_bytes();
+hipError_t launch_twobit_unpack(const TwobitArgs &a, int64_t n_tiles, hipStream_t st);
 int kdist_grid(int k, int64_t n_seqs);
 hipError_t launch_kdist(int mode, const uint8_t *seqs, const int64_t *off, int64_t n_seqs, int k, const double *ref,
                         uint32_t *scratch, double scale, double *out, unsigned long long *first_bad, hipStream_t st);
@@ -171,7 +174,7 @@ struct kgma_genome {
     int64_t total_words = 0;      // plane words incl. padding
     int64_t ascii_bytes = 0;
     std::vector<ContigDesc> cd;
-    std::vector<std::string> headers;          // FASTA header lines (without '>'), only for genomes built from FASTA text
+    std::vector<std::string> headers;          // FASTA header lines (without '>') or .2bit record names; empty for genomes built otherwise
     unsigned long long *first_bad = nullptr;   // pinned host copy, valid once pack_pending is cleared
     bool pack_pending = false;
     bool repack_deferred = false; // kgma_repack_scan_hits: the re-encoding is still to be launched -- by the next scan, group by group beside
@@ -389,6 +392,7 @@ struct kgma_ctx {
     // reverse complement (kgma_genome_revcomp): the tile table of the last call, on the device and as uploaded
     int64_t *d_rcprefix = nullptr; int64_t rcprefix_cap = 0;
     std::vector<int64_t> rcprefix;
+    double twobit_ms = -1;                   // kgma_genome_from_2bit_file: device time of the last call's unpack kernel (-1: none yet)
     std::vector<int64_t> contig_len;
     int64_t n_dists_per_kfv = 0;
     int64_t tile_windows = KGMA_TILE_WINDOWS;
@@ -1948,6 +1952,184 @@ int kgma_genome_from_fasta_file(kgma_ctx *ctx, const char *path, kgma_genome **o
     (void)munmap(map, (size_t)n);
     close(fd);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// .2bit file -> device genome (parser: kgma_twobit.cpp, kernel: kgma_twobit.hip)
+// ------------------------------------------------------------------------------------------
+int kgma_genome_from_2bit_file(kgma_ctx *ctx, const char *path, uint32_t flags, kgma_genome **out)
+{
+    if (!ctx) return KGMA_E_ARG;
+    if (!path || !out) return fail(ctx, KGMA_E_ARG, "null argument");
+    *out = nullptr;
+    if (flags & ~(uint32_t)KGMA_2BIT_NOMASK) return fail(ctx, KGMA_E_ARG, "kgma_genome_from_2bit_file: unknown flags 0x%x", flags);
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return fail(ctx, KGMA_E_ARG, "cannot open %s", path);
+    struct FdGuard { int fd; ~FdGuard() { close(fd); } } fd_guard{fd};
+    struct stat sb;
+    if (fstat(fd, &sb) != 0 || sb.st_size < 0) return fail(ctx, KGMA_E_ARG, "cannot stat %s", path);
+    if (!S_ISREG(sb.st_mode)) return fail(ctx, KGMA_E_ARG, "%s is not a regular file", path);
+    const bool dbg = getenv("KGMA_INGEST_DEBUG") != nullptr;
+    double tq = now_ms();
+    auto lap = [&](const char *what) {
+        if (!dbg) return;
+        const double t = now_ms();
+        fprintf(stderr, "  2bit ingest: %-28s %8.3f ms\n", what, t - tq);
+        tq = t;
+    };
+    // ---- the host reads and validates header, index and block tables: nothing below indexes with a value it has not checked ----
+    TwoBitFile f;
+    {
+        std::string msg;
+        const int prc = twobit_parse(fd, (int64_t)sb.st_size, TWOBIT_MAX_RECORDS, f, msg);
+        if (prc != KGMA_OK) return fail(ctx, prc, "%s: %s", path, msg.c_str());
+    }
+    lap("parse + validate (host)");
+    const int64_t nc = (int64_t)f.recs.size();
+    const bool masks = !(flags & KGMA_2BIT_NOMASK);
+    const int64_t n_nblk = (int64_t)f.n_blocks.size(), n_mblk = masks ? (int64_t)f.m_blocks.size() : 0;
+    static_assert(sizeof(TwoBitBlock) == sizeof(TwobitBlock) && sizeof(TwobitBlock) == 8, "the parser's blocks are uploaded as the kernel's");
+    // one table of int64 for the kernel: [tile_prefix: nc + 1][packed_off: nc][n_prefix: nc + 1][m_prefix: nc + 1]
+    std::vector<int64_t> lens((size_t)std::max<int64_t>(nc, 1), 0), tab((size_t)(4 * nc + 3), 0);
+    int64_t *tile_prefix = tab.data(), *packed_off = tile_prefix + (nc + 1), *n_prefix = packed_off + nc, *m_prefix = n_prefix + (nc + 1);
+    const int64_t per_tile = twobit_tile_bytes();
+    int64_t packed_total = 0;
+    for (int64_t c = 0; c < nc; c++) {
+        const TwoBitRecord &R = f.recs[(size_t)c];
+        lens[(size_t)c] = R.dna_size;
+        const int64_t slot = ((R.dna_size + 31) & ~31ll) + 32;         // (genome_layout; the kernel writes all of it)
+        tile_prefix[c + 1] = tile_prefix[c] + (slot + per_tile - 1) / per_tile;
+        packed_off[c] = packed_total;                                   // 16-byte aligned, whatever the byte it starts at in the file
+        packed_total += (R.packed_bytes + 15) & ~15ll;
+        n_prefix[c] = R.n_begin;
+        m_prefix[c] = n_nblk + (masks ? R.m_begin : 0);
+    }
+    n_prefix[nc] = n_nblk;
+    m_prefix[nc] = n_nblk + n_mblk;
+    const int64_t n_tiles = tile_prefix[nc];
+    if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_genome_from_2bit_file: %lld tiles exceed one launch", (long long)n_tiles);
+    (void)hipSetDevice(ctx->device);
+    NumaBind numa(ctx);                                              // (staging buffers and reading threads on the GPU's NUMA node)
+    StagePipe *pp = ctx_pipe(ctx);
+    if (!pp) return fail(ctx, KGMA_E_NOMEM, "cannot allocate the pinned staging buffers");
+    StagePipe &pipe = *pp;
+    kgma_genome *g = new (std::nothrow) kgma_genome();
+    if (!g) return fail(ctx, KGMA_E_NOMEM, "out of host memory");
+    // ONE transient device buffer, freed once the kernel is done: [table][N blocks][mask blocks][packed bytes, every record at a
+    // 16-byte aligned offset].  It is filled as one byte stream through the pinned staging pair: the host's tables are copied,
+    // the packed bytes are pread straight from the file, the gaps are zeros.
+    struct Seg { int64_t dev_off, len; const uint8_t *host; int64_t file_off; };   // host != nullptr: memory, else the file
+    std::vector<Seg> segs;
+    const int64_t tab_bytes = (int64_t)(tab.size() * sizeof(int64_t));
+    const int64_t blk_off = (tab_bytes + 15) & ~15ll;
+    const int64_t packed_base = (blk_off + (n_nblk + n_mblk) * (int64_t)sizeof(TwobitBlock) + 15) & ~15ll;
+    const int64_t buf_bytes = std::max<int64_t>(packed_base + packed_total, 16);
+    segs.push_back(Seg{0, tab_bytes, reinterpret_cast<const uint8_t *>(tab.data()), 0});
+    if (n_nblk > 0) segs.push_back(Seg{blk_off, n_nblk * 8, reinterpret_cast<const uint8_t *>(f.n_blocks.data()), 0});
+    if (n_mblk > 0) segs.push_back(Seg{blk_off + n_nblk * 8, n_mblk * 8, reinterpret_cast<const uint8_t *>(f.m_blocks.data()), 0});
+    for (int64_t c = 0; c < nc; c++)
+        if (f.recs[(size_t)c].packed_bytes > 0)
+            segs.push_back(Seg{packed_base + packed_off[c], f.recs[(size_t)c].packed_bytes, nullptr, f.recs[(size_t)c].packed_off});
+    uint8_t *d_buf = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&]() {
+        pipe.drain();
+        if (d_buf) (void)hipFree(d_buf);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    int rc = genome_layout(ctx, g, lens.data(), nc);
+    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
+    g->headers.resize((size_t)nc);
+    for (int64_t c = 0; c < nc; c++) g->headers[(size_t)c] = f.recs[(size_t)c].name;
+    lap("layout (genome allocations)");
+#define TB_TRY(expr)                                                                              \
+    do {                                                                                          \
+        hipError_t e__ = (expr);                                                                  \
+        if (e__ != hipSuccess) {                                                                  \
+            rc = fail(ctx, KGMA_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__));           \
+            cleanup();                                                                            \
+            kgma_genome_free(ctx, g);                                                             \
+            return rc;                                                                            \
+        }                                                                                         \
+    } while (0)
+    TB_TRY(hipMalloc(reinterpret_cast<void **>(&d_buf), (size_t)buf_bytes));
+    TB_TRY(hipEventCreate(&e0));
+    TB_TRY(hipEventCreate(&e1));
+    lap("transient buffer");
+    {
+        const int64_t stage_cap = (int64_t)pipe.cap;
+        const int n_thr = ingest_threads();
+        std::atomic<int> read_failed{0};
+        // bytes [b0, e0) of the staging buffer that holds device bytes w0 ... of the transient buffer
+        auto fill = [&](uint8_t *stage, int64_t w0, int64_t b0, int64_t e0_) {
+            int64_t at = w0 + b0;
+            const int64_t end = w0 + e0_;
+            size_t si = (size_t)(std::upper_bound(segs.begin(), segs.end(), at, [](int64_t x, const Seg &S) { return x < S.dev_off + S.len; }) - segs.begin());
+            while (at < end) {
+                if (si == segs.size() || segs[si].dev_off >= end) { memset(stage + (at - w0), 0, (size_t)(end - at)); break; }
+                const Seg &S = segs[si];
+                if (S.dev_off > at) { memset(stage + (at - w0), 0, (size_t)(S.dev_off - at)); at = S.dev_off; }
+                const int64_t n = std::min<int64_t>(end, S.dev_off + S.len) - at, rel = at - S.dev_off;
+                uint8_t *dst = stage + (at - w0);
+                if (S.host) {
+                    memcpy(dst, S.host + rel, (size_t)n);
+                } else {
+                    for (int64_t done = 0; done < n;) {
+                        const ssize_t got = pread(fd, dst + done, (size_t)(n - done), (off_t)(S.file_off + rel + done));
+                        if (got <= 0) { read_failed.store(1); memset(dst + done, 0, (size_t)(n - done)); break; }
+                        done += got;
+                    }
+                }
+                at += n;
+                if (at == S.dev_off + S.len) si++;
+            }
+        };
+        for (int64_t w0 = 0; w0 < buf_bytes; w0 += stage_cap) {
+            uint8_t *stage = pipe.acquire();               // (the other buffer may still be on its way to the device)
+            const int64_t len = std::min<int64_t>(stage_cap, buf_bytes - w0);
+            parallel_ranges(len, n_thr, (int64_t)1 << 20, [&](int, int64_t b0, int64_t e0_) { fill(stage, w0, b0, e0_); });
+            if (read_failed.load()) { cleanup(); kgma_genome_free(ctx, g); return fail(ctx, KGMA_E_ARG, "cannot read the packed bases of %s", path); }
+            TB_TRY(pipe.submit(d_buf + w0, (size_t)len));
+        }
+    }
+    lap("staged upload queued");
+    // ---- kernel, tail ----
+    const int64_t *d_tab = reinterpret_cast<const int64_t *>(d_buf);
+    const uint8_t *d_packed = d_buf + packed_base;
+    const TwobitBlock *d_blk = reinterpret_cast<const TwobitBlock *>(d_buf + blk_off);
+    TwobitArgs a{};
+    a.packed = d_packed; a.dst = g->d_ascii; a.cd = g->d_cd;
+    a.tile_prefix = d_tab; a.packed_off = d_tab + (nc + 1); a.n_prefix = d_tab + (2 * nc + 1); a.m_prefix = d_tab + (3 * nc + 2);
+    a.blk = d_blk; a.n_contigs = (int32_t)nc;
+    TB_TRY(hipEventRecord(e0, ctx->stream));
+    TB_TRY(launch_twobit_unpack(a, n_tiles, ctx->stream));
+    TB_TRY(hipEventRecord(e1, ctx->stream));
+    TB_TRY(hipMemsetAsync(g->d_ascii + (g->ascii_bytes - 64), 0, 64, ctx->stream));              // the text's 64 tail bytes
+    TB_TRY(hipStreamSynchronize(ctx->stream));
+    {
+        float ms = 0;
+        TB_TRY(hipEventElapsedTime(&ms, e0, e1));
+        ctx->twobit_ms = n_tiles > 0 ? ms : 0.0;
+    }
+#undef TB_TRY
+    lap("upload drained + kernel");
+    cleanup();
+    lap("free transients");
+    rc = kgma_genome_repack(ctx, g);
+    lap("pack launched");
+    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
+    *out = g;
+    return KGMA_OK;
+}
+
+int kgma_get_2bit_unpack_ms(kgma_ctx *ctx, double *ms)
+{
+    if (!ctx) return KGMA_E_ARG;
+    if (!ms) return fail(ctx, KGMA_E_ARG, "null argument");
+    if (ctx->twobit_ms < 0) return fail(ctx, KGMA_E_STATE, "kgma_get_2bit_unpack_ms: no kgma_genome_from_2bit_file has completed on this context");
+    *ms = ctx->twobit_ms;
+    return KGMA_OK;
 }
 
 int kgma_genome_header(const kgma_genome *g, int64_t contig, const char **text, int64_t *len)

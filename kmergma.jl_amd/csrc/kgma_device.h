@@ -365,4 +365,22 @@ struct RevcompArgs {
     int32_t pad;
 };
 
+// .2bit ingest (kgma_twobit.hip; kgma_genome_from_2bit_file): the packed bases of every record as they lie in the file, four per
+// byte, and the normalised N / mask block lists -> the resident residue text.  Tiled as the reverse complement above.
+constexpr int KGMA_TWOBIT_THREADS = 256;
+constexpr int KGMA_TWOBIT_ITERS = 4;                           // 16-byte chunks a lane takes per tile (a tile: 16 KiB of a record's slot)
+struct TwobitBlock { uint32_t start, end; };                   // residues start .. end - 1 of the record (0-based)
+struct TwobitArgs {
+    const uint8_t *packed;        // record c's packed bytes at packed + packed_off[c]: 16-byte aligned, padded to a multiple of 16
+    uint8_t *dst;                 // the genome's residue text: every byte of every record's slot is written
+    const ContigDesc *cd;
+    const int64_t *tile_prefix;   // [n_contigs + 1]: tiles of the records before record c (a tile never spans two records)
+    const int64_t *packed_off;    // [n_contigs]
+    const int64_t *n_prefix;      // [n_contigs + 1]: record c's N blocks are blk[n_prefix[c] .. n_prefix[c + 1])
+    const int64_t *m_prefix;      // [n_contigs + 1]: its mask blocks blk[m_prefix[c] .. m_prefix[c + 1])
+    const TwobitBlock *blk;       // per record: disjoint, increasing, not adjacent
+    int32_t n_contigs;
+    int32_t pad;
+};
+
 }  // namespace kgma

@@ -81,6 +81,25 @@ function genome_from_fasta(ctx::Context, genome_path::String)
     return DeviceGenome(ctx, g[])
 end
 
+# UCSC .2bit file -> device (kgma_genome_from_2bit_file): the packed bytes and the N / soft-mask interval lists are shipped as they
+# are (a quarter of the FASTA text's bytes) and expanded to the resident text by one kernel; mask = false ignores the soft-mask
+# blocks (all upper case, as twoBitToFa -noMask).  Record names come back through kgma_genome_header like FASTA header lines.
+const KGMA_2BIT_NOMASK = UInt32(1)
+function genome_from_2bit(ctx::Context, genome_path::String; mask::Bool = true)
+    g = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ctx, ccall((:kgma_genome_from_2bit_file, libkgma), Cint, (Ptr{Cvoid}, Cstring, UInt32, Ref{Ptr{Cvoid}}),
+                     ctx.h, genome_path, mask ? UInt32(0) : KGMA_2BIT_NOMASK, g))
+    return DeviceGenome(ctx, g[])
+end
+
+# a genome file by its content: the .2bit signature (either byte order; the library refuses a byte-swapped file with its own
+# message) in the first four bytes, else FASTA -- the file's name is not looked at
+function genome_from_path(ctx::Context, genome_path::String)
+    head = open(io -> read(io, 4), genome_path)
+    twobit = head == UInt8[0x43, 0x27, 0x41, 0x1a] || head == UInt8[0x1a, 0x41, 0x27, 0x43]
+    return twobit ? genome_from_2bit(ctx, genome_path) : genome_from_fasta(ctx, genome_path)
+end
+
 # one record (record_KmerGMA!): its residues as FASTX holds them
 function genome_from_record(ctx::Context, record::FASTA.Record)
     s = Vector{UInt8}(FASTA.sequence(String, record))

@@ -37,8 +37,10 @@ EXPORTS = [
     "kgma_set_strobe_ref", "kgma_strobe_scan", "kgma_exact_match", "kgma_get_matches",
     "kgma_motif_match", "kgma_get_motif_matches",
     "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
-    "kgma_get_block_sums",
+    "kgma_get_block_sums", "kgma_genome_from_2bit_file", "kgma_get_2bit_unpack_ms", "kgma_twobit_inspect",
 ]
+TWOBIT_NOMASK = 1                    # KGMA_2BIT_NOMASK
+TWOBIT_SIGNATURE = b"\x43\x27\x41\x1a"  # the first four bytes of a .2bit file in this machine's byte order
 FILTER_FORM_PRESUMMED = 1 << 16      # kgma_filter_stats.form: the filter read the block sums the step's pack wrote (KGMA_FUSE_SUMS)
 FILTER_OK, FILTER_OVERFLOW, FILTER_STREAMS, FILTER_FRACTION, FILTER_REMEMBERED = 0, 1, 2, 3, 4
 
@@ -67,6 +69,11 @@ class KgmaMatch(C.Structure):
 class KgmaMotifHit(C.Structure):
     _fields_ = [("motif", C.c_int32), ("contig", C.c_int32), ("start", C.c_int64), ("mismatches", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class KgmaTwobitInfo(C.Structure):
+    _fields_ = [("version", C.c_int32), ("reserved", C.c_int32), ("n_records", C.c_int64), ("total_bases", C.c_int64),
+                ("n_blocks", C.c_int64), ("mask_blocks", C.c_int64), ("packed_bytes", C.c_int64)]
 
 
 class KgmaStats(C.Structure):
@@ -153,6 +160,9 @@ def load():
     L.kgma_genome_from_fasta.argtypes = [vp, vp, i64, P(vp)]
     L.kgma_genome_from_fasta_file.argtypes = [vp, C.c_char_p, P(vp)]
     L.kgma_genome_header.argtypes = [vp, i64, P(C.c_char_p), P(i64)]
+    L.kgma_genome_from_2bit_file.argtypes = [vp, C.c_char_p, u32, P(vp)]
+    L.kgma_get_2bit_unpack_ms.argtypes = [vp, P(dbl)]
+    L.kgma_twobit_inspect.argtypes = [C.c_char_p, P(KgmaTwobitInfo), C.c_char_p, i64]
     L.kgma_genome_synthetic.argtypes = [vp, P(i64), i64, u64, C.c_char_p, i64, P(i64), P(i64), i64, P(vp)]
     L.kgma_genome_fetch.argtypes = [vp, vp, i64, i64, i64, C.c_char_p]
     L.kgma_genome_fetch_batch.argtypes = [vp, vp, i64, P(i64), P(i64), P(i64), C.c_char_p, i64]
@@ -226,6 +236,26 @@ def host_chain_values(seq: bytes, ref, k: int, windowsize: int, intervals) -> np
     if st != KGMA_OK:
         raise KgmaError(st, "kgma_host_chain_values failed")
     return out[:nn.value]
+
+
+def twobit_inspect(path) -> dict:
+    """kgma_twobit_inspect: what the host parser of genome_from_2bit makes of a .2bit file -- dict(version, n_records,
+    total_bases, n_blocks, mask_blocks, packed_bytes), block counts after normalisation.  Host only: needs no GPU.  A file the
+    parser refuses raises KgmaError with its status and message."""
+    info = KgmaTwobitInfo()
+    err = C.create_string_buffer(512)
+    st = load().kgma_twobit_inspect(os.fsencode(path), C.byref(info), err, len(err))
+    if st != KGMA_OK:
+        raise KgmaError(st, err.value.decode("utf-8", "replace"))
+    return {f: int(getattr(info, f)) for f, _ in KgmaTwobitInfo._fields_ if f != "reserved"}
+
+
+def is_twobit(path) -> bool:
+    """True when the file begins with the .2bit signature, in either byte order (a byte-swapped file is then refused by the
+    parser, with its own message, instead of being read as FASTA)."""
+    with open(path, "rb") as fh:
+        head = fh.read(4)
+    return head in (TWOBIT_SIGNATURE, TWOBIT_SIGNATURE[::-1])
 
 
 def chain_steps() -> int:
@@ -511,6 +541,24 @@ class Context:
         ptr = buf.ctypes.data_as(C.c_void_p) if buf.size else None
         self._check(load().kgma_genome_from_fasta(self._h, ptr, int(buf.size), C.byref(h)))
         return Genome(self, h)
+
+    def genome_from_2bit(self, path, mask: bool = True) -> Genome:
+        """kgma_genome_from_2bit_file: a UCSC .2bit file, shipped packed (0.25 byte per base) and expanded to the resident
+        text on the device; header(c) is record c's name.  mask=False ignores the soft-mask blocks (all upper case)."""
+        h = C.c_void_p()
+        self._check(load().kgma_genome_from_2bit_file(self._h, os.fsencode(path), 0 if mask else TWOBIT_NOMASK, C.byref(h)))
+        return Genome(self, h)
+
+    def twobit_unpack_ms(self) -> float:
+        """kgma_get_2bit_unpack_ms: device time of the unpack kernel in the last genome_from_2bit."""
+        ms = C.c_double(0)
+        self._check(load().kgma_get_2bit_unpack_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def genome_from_path(self, path) -> Genome:
+        """A genome file by its content: the .2bit signature in the first four bytes -> genome_from_2bit, anything else ->
+        genome_from_fasta (the file extension is not looked at)."""
+        return self.genome_from_2bit(path) if is_twobit(path) else self.genome_from_fasta(path)
 
     def genome_synthetic(self, contig_lens: Sequence[int], seed: int, plant: bytes = b"",
                          plants: Sequence = ()) -> Genome:

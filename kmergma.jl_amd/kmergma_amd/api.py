@@ -40,6 +40,7 @@ import numpy as np
 
 from . import _lib, headers, refprep
 from .fasta import Record, read_fasta, reverse_complement, write_fasta
+from .twobit import twobit_names_and_lengths
 
 log = logging.getLogger("KmerGMA")
 
@@ -55,12 +56,23 @@ def default_context(device: int = 0) -> "_lib.Context":
 
 class _GenomeView:
     """The records of a scan input: FASTA path -> parsed and packed on the device
-    (kgma_genome_from_fasta, replaces FASTX + getSeq at src/GenomeMiner.jl:31-35);
+    (kgma_genome_from_fasta, replaces FASTX + getSeq at src/GenomeMiner.jl:31-35); .2bit path (told by the file's first four
+    bytes) -> unpacked on the device (kgma_genome_from_2bit_file), the record names are the descriptions; an open device
+    genome (_lib.Genome) -> used as it is and NOT owned: free() leaves it open, so one resident genome serves many calls;
     list of Record -> uploaded from host memory.  Sequences of hits are read back on demand."""
 
     def __init__(self, ctx, genome_path):
-        if isinstance(genome_path, str):
-            self.genome = ctx.genome_from_fasta(genome_path)
+        self._owned = True
+        if isinstance(genome_path, _lib.Genome):
+            self.genome = genome_path
+            self._owned = False
+            try:
+                self.descriptions = [self.genome.header(c) for c in range(self.genome.n_contigs)]
+            except _lib.KgmaError:                 # (a genome made from host records or synthetically carries no names)
+                self.descriptions = [""] * self.genome.n_contigs
+            self._recs = None
+        elif isinstance(genome_path, str):
+            self.genome = ctx.genome_from_path(genome_path)
             self.descriptions = [self.genome.header(c) for c in range(self.genome.n_contigs)]
             self._recs = None
         else:
@@ -96,10 +108,12 @@ class _GenomeView:
         v.genome = self.genome.revcomp()
         v.descriptions = self.descriptions
         v._recs = None
+        v._owned = True
         return v
 
     def free(self):
-        self.genome.free()
+        if self._owned:
+            self.genome.free()
 
 
 STRANDS = ("+", "-", "both")
@@ -327,6 +341,11 @@ def findGenes(*, genome_path: str, ref_path: str, k: int = 6, KmerDistThr=0, buf
               ctx=None, strand: str = "+") -> list:
     """`findGenes` (src/API.jl:60-104). Returns [hits, (loci), (aligns), (dists)].
 
+    genome_path: a FASTA path, a UCSC .2bit path (told by the file's first four bytes, not its name), or a device genome
+    that is already open (ctx.genome_from_path / genome_from_2bit / genome_from_fasta): it is scanned where it lies and stays
+    open, so several gene families are searched on one resident genome without paying the ingest again.  The same holds for
+    findGenes_cluster_mode and Strobemer_findGenes.
+
     strand: "+" (default: the reference's scan), "-" (genes on the reverse strand, reported in forward coordinates with
     ` | Strand = -` in the header and the gene in reference orientation as the body) or "both" (the plus results followed by
     the minus results; not de-duplicated, a palindromic region may be reported twice): see ac_gma_testing.
@@ -533,9 +552,9 @@ def _query_bytes(query) -> bytes:
 
 
 def _open_subject(ctx, subject):
-    """(device genome, per-record identifier lookup, owned) for a FASTA path, an open device genome or a _GenomeView."""
+    """(device genome, per-record identifier lookup, owned) for a FASTA or .2bit path, an open device genome or a _GenomeView."""
     if isinstance(subject, str):
-        g = ctx.genome_from_fasta(subject)
+        g = ctx.genome_from_path(subject)
         return g, g, True
     if isinstance(subject, _GenomeView):
         return subject.genome, subject, False
@@ -552,7 +571,7 @@ def _identifier(src, c: int) -> str:
 def exactMatch_batch(queries, genome_or_path, *, overlap: bool = True, ctx=None) -> list:
     """exactMatch (src/ExactMatch.jl:100-121) for many queries in ONE pass over the genome (kgma_exact_match): per query
     the dict {identifier: [(lo, hi), ...]} over the records with at least one match, or the string "no match".
-    `genome_or_path`: a FASTA path, or a device genome that is already open (it stays open)."""
+    `genome_or_path`: a FASTA or .2bit path, or a device genome that is already open (it stays open)."""
     qs = [_query_bytes(q) for q in queries]
     if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
         raise TypeError("Invalid subject sequence type")
@@ -680,7 +699,7 @@ def motifMatch_batch(motifs, genome_or_path, *, max_mismatch=0, strand: str = "+
     """Many IUPAC motifs in ONE pass over the genome (kgma_motif_match): per motif the list of
     (record_index, identifier, lo, hi, strand, mismatches) -- 0-based record, 1-based inclusive lo:hi in forward coordinates --
     sorted by (record, lo, strand).  `max_mismatch`: one number for all motifs or one per motif.  Semantics: motifMatch.
-    `genome_or_path`: a FASTA path, or a device genome that is already open (it stays open)."""
+    `genome_or_path`: a FASTA or .2bit path, or a device genome that is already open (it stays open)."""
     ms, sent, tags = _motif_args(motifs, max_mismatch, strand)
     if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
         raise TypeError("Invalid subject sequence type")
@@ -727,17 +746,20 @@ def findRSS(genome_or_path, rss=HumanRSSD, max_mismatch: int = 1, strand: str = 
 def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
     """src/ExactMatch.jl:146-158: the full description line of every record -> the summed length of the records BEFORE it
     (what the scan reports as GenomePos).  Given an open device genome the headers and lengths come from its handle;
-    given a path the file is read on the host, as the reference does."""
+    given a path the file is read on the host, as the reference does (a .2bit path -- told by its first four bytes -- gives
+    its record names and dnaSizes from the file's index, after the library's parser has validated the file)."""
     if isinstance(fasta_file_path, _GenomeView):
         g = fasta_file_path.genome
         pairs = [(fasta_file_path.descriptions[c], g.contig_len(c)) for c in range(g.n_contigs)]
     elif isinstance(fasta_file_path, _lib.Genome):
         g = fasta_file_path
         pairs = [(g.header(c), g.contig_len(c)) for c in range(g.n_contigs)]
+    elif isinstance(fasta_file_path, str) and _lib.is_twobit(fasta_file_path):
+        pairs = twobit_names_and_lengths(fasta_file_path)              # (record name, dnaSize) from the file's index: host only
     elif isinstance(fasta_file_path, str):
         pairs = [(r.description, len(r.sequence)) for r in read_fasta(fasta_file_path)]
     else:
-        raise TypeError("expected a FASTA path or an open device genome")
+        raise TypeError("expected a FASTA or .2bit path or an open device genome")
     out, total = {}, 0
     for desc, n in pairs:
         out[desc] = total
