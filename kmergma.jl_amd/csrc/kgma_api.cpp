@@ -1158,6 +1158,10 @@ static int kfv_from_nonzeros(kgma_ctx *ctx, int32_t k, int j, std::vector<uint32
     // What the kernels keep in 32 bits: the int32 kernels E = (D - D0)/(2N) and N * (count difference); the 16-bit counter form of
     // stream8_kernel the LOCAL prefix of a 64-window step, |e| <= Smax + N n per window (its carries are 64-bit); the generic
     // kernel nothing (int64 throughout: D itself must fit)
+    // (fits32's second clause never decides: N n >= 2^30 gives dmax / 2N >= N n^2 / 2 >= 2^29 n.  big_ok's N < 2^22 decides alone
+    //  only for windows of 1, 2 or 3 k-mers -- Smax + N n <= 2^24 admits N up to 2^24 / n -- and every user of big_ok asks
+    //  stream8_c16_applies, which repeats it: tests/test_range_cases.py enumerates both.  The int32 kernels clamp their threshold
+    //  prefix TE at +-(2^30 - 1), twice what fits32 lets E reach; tests/test_gpu_range.py holds either side of each bound.)
     const __int128 dmax = s2 + (__int128)N * N * nk * nk;
     f.fits32 = !(dmax / (2 * N) >= ((__int128)1 << 29) || (__int128)N * nk >= ((__int128)1 << 30));
     f.big_ok = (__int128)64 * ((__int128)f.Smax + (__int128)N * nk) <= ((__int128)1 << 30) && N < ((int64_t)1 << 22);

@@ -162,15 +162,17 @@ def test_window_limit_is_the_16bit_count(ctx):
 
 
 def test_prefix_beyond_int32(ctx):
-    """Many reference sequences: N n^2 / 2 leaves int32 although the window is short -- the 64-bit carry form takes over."""
-    k, L = 6, 330
+    """Many reference sequences: N n^2 / 2 leaves int32 although the window is short -- the 64-bit carry form takes over.  (The
+    table of 12 000 near-copies is built directly, tests/range_cases.py: near_copies; the ends of that regime: test_gpu_range.py.)"""
+    from tests import range_cases as rc
+    k, L, N = 6, 330, 12_000
     rng = np.random.default_rng(5)
-    base = random_dna(rng, L)
-    refs = [Record(f"g{i}", mutate(rng, base, 0.02)) for i in range(12_000)]
-    RV, ws, cons, (S, N) = refprep.gen_ref_ws_cons(refs, k, return_int=True)
-    ref = dict(RV=RV, ws=ws, S=S, N=N, k=k)
+    ref = rc.ref_of("near_copies", k, L, N)
+    base, ws, nk = ref["base"], ref["ws"], L - k + 1
+    assert not rc.fits32(ref["S"], N, nk) and rc.big_ok(ref["S"], N, nk) and np.count_nonzero(ref["S"] % N) > 50
     contigs, _ = make_genome(rng, [50_000, 9000, ws, ws + 1], [base], n_plants_per_mb=200)
     hits, _ = _assert_single_parity(ctx, contigs, ref, _thr_for(rng, ref))
+    assert ctx.kernel_name().startswith("stream8_kernel"), ctx.kernel_name()
     assert len(hits) > 0
 
 
