@@ -256,13 +256,18 @@ __global__ __launch_bounds__(1024) void filter_sums_kernel(FilterArgs a, int K)
 // Fast path: the unit lies in one record, every word is full and of accepted letters, and K - 1 residues of the record follow it --
 // no position needs the mask.  Everything else (record ends, partial words, padding, several records in a unit, a residue to
 // report) goes word by word like pack_kernel's slow path, with the mask; keeping pack_word's one-residue-at-a-time branch out of
-// the fast path is also what keeps the kernel inside the 128 VGPRs of a 16-wave workgroup (113, no scratch).
+// the fast path is also what keeps the kernel inside the 128 VGPRs of a 16-wave workgroup (121, no scratch).
 constexpr int PS_UNIT = 128;
 
 __device__ __forceinline__ uint32_t ps_code(uint32_t ch)               // the code pack_word gives a residue (one it reports: 0)
 {
     ch &= 0xDFu;
     return (ch == 'C' ? 1u : 0u) | (ch == 'G' ? 2u : 0u) | ((ch == 'T' || ch == 'N') ? 3u : 0u);
+}
+__device__ __forceinline__ int64_t ps_uniform(const int64_t x)         // a wave-uniform value, to scalar registers
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(x >> 32));
+    return (int64_t)((uint64_t)hi << 32 | lo);
 }
 template <int K>
 __device__ __forceinline__ uint32_t ps_halo(const uint2 b)             // 2-bit codes of the first K - 1 of 8 residues
@@ -348,17 +353,29 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
     uint32_t *outs = reinterpret_cast<uint32_t *>(a.bsum);             // one dword per plane word: its two sums
 
     // a unit's record and path (wave-uniform), and on the fast path its loads
-    struct Unit { int c; int64_t w0; bool fast; u32x4_t v[4]; uint2 halo; };
+    struct Unit { int c; bool fast; u32x4_t v[4]; uint2 halo; };
+    // The record of the wave's latest unit, in scalar registers: c = the last record that starts at or before the unit's first word
+    // (record 0 in the lead padding), and `next`, the word at which record c + 1 starts (INT64_MAX behind the last).  A wave's units
+    // only move forward, so the record stands until a unit starts at or past `next`; only then it is looked up again, from the
+    // block's entry on -- once in about 60 units on a genome of 100 records.  A unit inside its record touches no memory for it.
+    int rc = 0;
+    int64_t r_word_off = 0, r_len = 0, r_ascii_off = 0, r_next = 0;    // (r_next = 0: the wave's first unit looks its record up)
     auto prepare = [&](const int64_t u, Unit &n) {
         const int64_t g0 = u * PS_UNIT;
-        int c = a.block_contig[g0 >> a.block_shift];
-        while (c + 1 < a.n_contigs && a.cd[c + 1].word_off <= g0) c++;
-        const ContigDesc d = a.cd[c];
-        n.c = c;
-        n.w0 = g0 - d.word_off;
-        n.fast = n.w0 >= 0 && g0 + PS_UNIT <= a.total_words && (n.w0 + PS_UNIT) * 32 + (K - 1) <= d.len;
+        if (g0 >= r_next) {
+            int c = a.block_contig[g0 >> a.block_shift];
+            while (c + 1 < a.n_contigs && a.cd[c + 1].word_off <= g0) c++;
+            const ContigDesc d = a.cd[c];
+            // (the addresses are wave-uniform and the loads vector loads all the same: the kernel writes global memory)
+            rc = __builtin_amdgcn_readfirstlane(c);
+            r_word_off = ps_uniform(d.word_off); r_len = ps_uniform(d.len); r_ascii_off = ps_uniform(d.ascii_off);
+            r_next = c + 1 < a.n_contigs ? ps_uniform(a.cd[c + 1].word_off) : INT64_MAX;
+        }
+        const int64_t w0 = g0 - r_word_off;
+        n.c = rc;
+        n.fast = w0 >= 0 && g0 + PS_UNIT <= a.total_words && (w0 + PS_UNIT) * 32 + (K - 1) <= r_len;
         if (n.fast) {
-            const uint8_t *base = a.ascii + d.ascii_off + n.w0 * 32;
+            const uint8_t *base = a.ascii + r_ascii_off + w0 * 32;
             const u32x4_t *p = reinterpret_cast<const u32x4_t *>(base) + 2 * lane;
             n.v[0] = __builtin_nontemporal_load(p);
             n.v[1] = __builtin_nontemporal_load(p + 1);
@@ -369,20 +386,24 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
         }
     };
     // (gb: a wave-uniform word index, so that the addresses are a scalar base plus the lane's offset)
-    auto store = [&](const int64_t gb, const int l, const uint2 r, const uint2 iw, const uint32_t s0, const uint32_t s1) {
+    auto store = [&](const int64_t gb, const int l, const uint2 r, const uint2 iw, const uint32_t s01) {
         if (a.planes != nullptr) {
             u32x2_t rv; rv.x = r.x; rv.y = r.y;
             __builtin_nontemporal_store(rv, reinterpret_cast<u32x2_t *>(out + gb) + l);
         }
         u32x2_t iv; iv.x = iw.x; iv.y = iw.y;
         __builtin_nontemporal_store(iv, reinterpret_cast<u32x2_t *>(out2 + gb) + l);
-        __builtin_nontemporal_store(s0 | (s1 << 16), outs + gb + l);
+        __builtin_nontemporal_store(s01, outs + gb + l);
     };
 
-    auto process = [&](const Unit &cu, const int64_t u) {
-        const int64_t g0 = u * PS_UNIT;
+    // A unit's work comes in two parts, so that the loop can take the next unit's loads over and issue the one after's between
+    // them: encode() leaves what a clean fast unit stores in registers (planes, 2-bit words, the four sums as two dwords), and
+    // the loop stores it; any other unit goes word by word (by_word) before the loop takes the next one over.
+    struct Enc { uint2 r0, r1, i0, i1; uint32_t s0, s1; };
+    auto encode = [&](const Unit &cu, Enc &e) -> bool {
         bool clean = false;
-        uint2 r0 = make_uint2(0u, 0u), r1 = r0, i0, i1;
+        uint2 r0 = make_uint2(0u, 0u), r1 = r0, i0 = r0, i1 = r0;
+        e.s0 = e.s1 = 0u;
         if (cu.fast) {
             uint32_t bad0, bad1;
             const uint4 a0 = make_uint4(cu.v[0].x, cu.v[0].y, cu.v[0].z, cu.v[0].w), b0 = make_uint4(cu.v[1].x, cu.v[1].y, cu.v[1].z, cu.v[1].w);
@@ -407,19 +428,23 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
             const uint32_t s00 = ps_sum16_pairs<K>(i0.x, i0.y, ptab);
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t s01 = ps_sum16_pairs<K>(i0.y, n0, ptab);
-            store(g0, lane, r0, i0, s00, s01);
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t s10 = ps_sum16_pairs<K>(i1.x, i1.y, ptab);
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t s11 = ps_sum16_pairs<K>(i1.y, n1, ptab);
-            store(g0 + 64, lane, r1, i1, s10, s11);
-            return;
+            e.s0 = s00 | (s01 << 16);
+            e.s1 = s10 | (s11 << 16);
         }
+        e.r0 = r0; e.r1 = r1; e.i0 = i0; e.i1 = i1;
+        return clean;
+    };
+    auto by_word = [&](const int64_t u, const int c0) {
+        const int64_t g0 = u * PS_UNIT;
 #pragma unroll 1
         for (int q = 0; q < PS_UNIT / 64; q++) {
             const int64_t g = g0 + q * 64 + lane;
             if (g >= a.total_words) continue;
-            int c = cu.c;
+            int c = c0;
             while (c + 1 < a.n_contigs && a.cd[c + 1].word_off <= g) c++;
             const ContigDesc d = a.cd[c];
             const int64_t w = g - d.word_off, L = d.len, base0 = w * 32;
@@ -440,16 +465,45 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
                 s0 = ps_sum16_masked<K>(iw.x, iw.y, tab, nv0);
                 s1 = ps_sum16_masked<K>(iw.y, h, tab, nv1);
             }
-            store(g0 + q * 64, lane, r, iw, s0, s1);
+            store(g0 + q * 64, lane, r, iw, s0 | (s1 << 16));
         }
     };
 
-    Unit nx;
-    if (wave0 < n_units) prepare(wave0, nx);
+    // The steady loop, per unit u of the wave (cu: u's loads, taken over; nx: those of the wave's next unit, in flight):
+    //   encode u -- wait for nx and take it over -- issue the loads of the unit after -- store u.
+    // Loads and stores count on one counter (vmcnt), in order: where the loop waits for nx, the only stores not yet acknowledged
+    // are those of the unit before u, a whole encode old, and u's own go out behind the new loads with nothing waiting on them.
+    // (Taking nx over behind u's stores, as `cu = nx` at the loop's head did, made every unit wait for its predecessor's stores to
+    // drain with no load in flight: EXPERIMENTS.md section 16.)  A record lookup, where one runs, waits at the same place.
+    if (wave0 >= n_units) return;
+    Unit cu, nx;
+    nx.c = 0; nx.fast = false; nx.halo = cu.halo = make_uint2(0u, 0u);
+#pragma unroll
+    for (int i = 0; i < 4; i++) nx.v[i] = cu.v[i] = u32x4_t{0u, 0u, 0u, 0u};
+    prepare(wave0, cu);
+    if (wave0 + n_waves < n_units) prepare(wave0 + n_waves, nx);
+    // (the first unit's loads are waited for here: a wait for them at the loop's head would stand in every iteration, behind the
+    //  stores and the new loads)
+#pragma unroll
+    for (int i = 0; i < 4; i++) asm volatile("" : "+v"(cu.v[i]));
+    asm volatile("" : "+v"(cu.halo.x), "+v"(cu.halo.y));
     for (int64_t u = wave0; u < n_units; u += n_waves) {
-        const Unit cu = nx;
-        if (u + n_waves < n_units) prepare(u + n_waves, nx);
-        process(cu, u);
+        Enc e;
+        const int c0 = cu.c;
+        const bool clean = encode(cu, e);
+        if (!clean) by_word(u, c0);                                    // (with its own loads and stores, and one buffer less alive)
+        __builtin_amdgcn_sched_barrier(0);
+        cu = nx;
+        // (the copy is pinned here: left to the compiler it sinks to the back-edge, behind the stores)
+#pragma unroll
+        for (int i = 0; i < 4; i++) asm volatile("" : "+v"(cu.v[i]));
+        asm volatile("" : "+v"(cu.halo.x), "+v"(cu.halo.y));
+        if (u + 2 * n_waves < n_units) prepare(u + 2 * n_waves, nx);
+        __builtin_amdgcn_sched_barrier(0);
+        if (clean) {
+            store(u * PS_UNIT, lane, e.r0, e.i0, e.s0);
+            store(u * PS_UNIT + 64, lane, e.r1, e.i1, e.s1);
+        }
     }
 }
 
@@ -507,6 +561,10 @@ static hipError_t pack_sums_launch(const PackSumsArgs &a, int n_cus, hipStream_t
     if (e != hipSuccess) return e;
     // persistent waves: one 16-wave workgroup per CU (at up to 128 VGPRs a second one would not be resident beside it)
     int64_t grid = n_cus;
+    if (const char *w = getenv("KGMA_PACK_WGS")) {                     // tests and experiments: at most so many workgroups, 1 ... CUs
+        const int64_t n = atoll(w);
+        grid = n < 1 ? 1 : n < n_cus ? n : n_cus;
+    }
     const int64_t need = ((a.total_words + PS_UNIT - 1) / PS_UNIT + 15) / 16;
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
