@@ -152,7 +152,11 @@ def ref_of(family, k, W, N, variant=0):
 def edge_N(pred, k, W, family, variant=0):
     """(edge-, edge+): the largest N for which PREDICATES[pred] holds for the family's table, and that N + 1."""
     p, nk = PREDICATES[pred], W - k + 1
-    ok = lambda N: p(table(family, k, W, N, variant), N, nk)
+    return bisect_edge(lambda N: p(table(family, k, W, N, variant), N, nk))
+
+
+def bisect_edge(ok):
+    """(edge-, edge+) of a predicate on the positive integers that holds at 1 and fails from some value on."""
     lo, hi = 1, 2
     assert ok(lo)
     while ok(hi):

@@ -47,6 +47,12 @@ def check_params(s: int, w_min: int, w_max: int, q: int) -> None:
 def strobe_bins(seq: bytes, s: int, w_min: int, w_max: int, q: int, n_lookup: int = None) -> np.ndarray:
     """Bin (0-based) of the randstrobe starting at every position of `seq` that has k residues to its right.
     Residues beyond `n_lookup` (default: all) are never looked up: a bad one there is read as 0."""
+    return strobe_bins_offsets(seq, s, w_min, w_max, q, n_lookup)[0]
+
+
+def strobe_bins_offsets(seq: bytes, s: int, w_min: int, w_max: int, q: int, n_lookup: int = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(bins, offsets): strobe_bins and, per position, the 1-based offset w_min..w_max the second s-mer was taken from (the last
+    one of score 0; w_min where none scores 0, which a look at (first + second) % q tells apart)."""
     check_params(s, w_min, w_max, q)
     k = w_max + s - 1
     codes = _CODE[np.frombuffer(seq, dtype=np.uint8)].copy()
@@ -57,18 +63,20 @@ def strobe_bins(seq: bytes, s: int, w_min: int, w_max: int, q: int, n_lookup: in
     codes[codes < 0] = 0
     n = codes.size - k + 1
     if n <= 0:
-        return np.zeros(0, dtype=np.int64)
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
     ns = codes.size - s + 1
     smer = np.zeros(ns, dtype=np.int64)
     for j in range(s):
         smer = smer * 4 + codes[j:j + ns]
     first = smer[:n]
     second = smer[w_min - 1:w_min - 1 + n].copy()
+    offset = np.full(n, w_min, dtype=np.int64)
     for i in range(w_min, w_max + 1):                   # ascending: the last offset of score 0 wins
         cand = smer[i - 1:i - 1 + n]
         zero = (first + cand) % q == 0
         second = np.where(zero, cand, second)
-    return first * 4 ** s + second
+        offset = np.where(zero, i, offset)
+    return first * 4 ** s + second, offset
 
 
 def get_strobe_2_mer(seq: bytes, s: int = 2, w_min: int = 3, w_max: int = 5, q: int = 5, withGap: bool = True) -> bytes:

@@ -13,6 +13,10 @@ from kmergma_amd import fasta, refprep
 from tests.conftest import DATA, GOLDEN
 
 PARAMS = [(2, 3, 5, 5), (3, 4, 7, 5), (1, 2, 4, 5), (2, 3, 5, 7), (2, 3, 5, 1)]
+# the edges of the parameters (tests/strobe_cases.py: SELECT_SETS): k = 16, w_min = 1, w_min = w_max, a score of 0 in every `zero`
+# word, the largest sum of two s-mers and one past it, a modulus beyond every sum
+EDGE_PARAMS = [(3, 1, 14, 33), (3, 4, 7, 97), (3, 12, 14, 126), (3, 14, 14, 5), (3, 4, 7, 2 ** 40), (2, 3, 5, 30), (2, 3, 5, 31),
+               (2, 1, 15, 2), (2, 2, 2, 1), (1, 1, 16, 2), (1, 1, 1, 1)]
 
 
 @pytest.fixture(scope="module")
@@ -44,9 +48,9 @@ def test_golden_count(gold, impl):
         assert counts[int(idx) - 1] == v
 
 
-@pytest.mark.parametrize("s,w_min,w_max,q", PARAMS)
+@pytest.mark.parametrize("s,w_min,w_max,q", PARAMS + EDGE_PARAMS)
 def test_bins_agree_with_per_position_definition(s, w_min, w_max, q):
-    rng = np.random.default_rng(7 + s + q)
+    rng = np.random.default_rng(7 + s + q % 1000)
     seq = bytes(rng.choice(np.frombuffer(b"ACGTN", dtype=np.uint8), size=400, p=[.24, .24, .24, .24, .04]))
     k = w_max + s - 1
     a = so.strobe_bins(seq, s, w_min, w_max, q)
@@ -55,7 +59,7 @@ def test_bins_agree_with_per_position_definition(s, w_min, w_max, q):
     assert a.tolist() == b.tolist() == c
 
 
-@pytest.mark.parametrize("s,w_min,w_max,q", PARAMS)
+@pytest.mark.parametrize("s,w_min,w_max,q", PARAMS + EDGE_PARAMS)
 def test_window_is_sliding_items_plus_permanent_copy(s, w_min, w_max, q):
     """After step i the reference's count vector is the W - k strobemers starting at i+1 .. i+W-k (1-based) plus one copy of
     the record's strobemer W-k+1 -- for every step of a record, the last one included."""
