@@ -2757,20 +2757,179 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
     return KGMA_OK;
 }
 
-int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_t flags)
-{
-    if (!ctx || !gc) return KGMA_E_ARG;
-    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping is updated
-    if (ctx->m == 0) return fail(ctx, KGMA_E_STATE, "kgma_set_refs has not been called");
-    if (mode != KGMA_MODE_SINGLE && mode != KGMA_MODE_OMN && mode != KGMA_MODE_STROBE) return fail(ctx, KGMA_E_ARG, "unknown mode %d", mode);
-    const bool strobe = mode == KGMA_MODE_STROBE;
-    if (strobe != ctx->strobe)
-        return fail(ctx, KGMA_E_STATE, strobe ? "a strobemer scan needs strobemer references (kgma_set_strobe_ref)"
-                                              : "the context holds strobemer references: a k-mer scan needs kgma_set_refs");
-    (void)hipSetDevice(ctx->device);
-    const int k = ctx->k, m_used = mode == KGMA_MODE_SINGLE ? 1 : ctx->m;
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// The host side of a scan (kgma_scan_device), in five steps: plan_scan decides which kernel serves the scan and how it is launched;
+// build_stream_table which windows each record evaluates and how they are cut into streams; reserve_results sizes the result block
+// and its pinned mirror; launch_group fills the parameters of one launch group and launches it (inside the overflow-retry loop);
+// collect_results reads the mirror back and hands the records to stitch_dips.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// One launch of the scan: the KFVs it takes and what the plan needs to know about them, worked out once
+struct LaunchGroup {
+    Group gr;
+    int nk = 0, nk_min = 0;            // k-mers of the launch's longest / shortest window
+    int n_sizes = 0;                   // distinct window sizes
+    int n_longer = 0;                  // KFVs whose window is longer than the launch's shortest
+    int n_plus1 = 0, n_plus2 = 0;      // ... one / two k-mers longer (five-KFV launches)
+    int64_t nmax = 0;                  // largest N
+    bool s16 = true, u8 = true;        // every S entry fits int16 / is below 256
+    bool need_wide = false;            // a KFV whose prefix leaves int32
+    bool one_size = true;
+    bool s8 = false;                   // stream8_kernel serves it (the generic and strobemer kernels count: they read the interleaved genome copy too)
+    int slots = 0;                     // streams resident per CU (stream kernels)
+    double weight = 0;                 // what the launch costs, in arbitrary units
+};
+
+// What kgma_scan_device decides before it touches the stream table: made once per scan by plan_scan
+struct ScanPlan {
+    int32_t mode = 0;
+    uint32_t flags = 0;
+    int k = 0, m_used = 0;
     int64_t maxws = 0;
-    for (int j = 0; j < m_used; j++) maxws = std::max(maxws, ctx->kfv[(size_t)j].W);
+    bool strobe = false, generic_all = false, generic_fp = false, use_stream = false;
+    bool overlap = false;              // the deferred pack runs beside the scan's launches (launch_overlapped)
+    bool natural_slots = false;        // every launch runs at its own residency, in rounds over one stream table
+    bool planes_needed = false;        // a launch reads the bit-plane copy of the genome
+    bool want_dists = false;
+    int eff_reserved = 0;              // CUs the streams are NOT sized for
+    int stream_nw = 0;                 // streams per CU the table is sized for
+    uint64_t geom_version = 0;         // what the stream table was sized for (its cache key)
+    char kernel_name[sizeof kgma_ctx::kernel_name] = "";
+    // the environment, read once per scan (not cached across scans: tests change it between scans of one process)
+    const char *kernel_env = nullptr;  // KGMA_KERNEL
+    bool filter_off = false;           // KGMA_FILTER=0
+    int debug_skip = 0;                // KGMA_DEBUG_SKIP (timing experiments only)
+    bool minslots = false;             // KGMA_STREAM_MINSLOTS
+    int rounds = 0, round_windows = 0; // KGMA_STREAM_ROUNDS, KGMA_STREAM_ROUND_WINDOWS (experiments; 0: not set)
+    int twokernel = -1;                // KGMA_TWOKERNEL (-1: not set)
+    bool geom_debug = false;           // KGMA_GEOM_DEBUG
+    std::vector<LaunchGroup> groups;
+};
+
+void read_scan_env(ScanPlan &p)
+{
+    p.kernel_env = getenv("KGMA_KERNEL");                        // testing only: run the other kernel where both apply
+    if (const char *e = getenv("KGMA_FILTER")) p.filter_off = atoi(e) == 0;
+    if (const char *e = getenv("KGMA_DEBUG_SKIP")) p.debug_skip = atoi(e);
+    p.minslots = getenv("KGMA_STREAM_MINSLOTS") != nullptr;
+    if (const char *e = getenv("KGMA_STREAM_ROUNDS")) p.rounds = std::max(1, atoi(e));
+    if (const char *e = getenv("KGMA_STREAM_ROUND_WINDOWS")) p.round_windows = std::max(64, atoi(e));
+    if (const char *e = getenv("KGMA_TWOKERNEL")) p.twokernel = atoi(e) != 0 ? 1 : 0;
+    p.geom_debug = getenv("KGMA_GEOM_DEBUG") != nullptr;
+}
+
+// (the KFVs of a group are in ascending window size)
+LaunchGroup describe_group(const kgma_ctx *ctx, Group &&group, bool generic_all)
+{
+    LaunchGroup L;
+    L.gr = std::move(group);
+    const Group &gr = L.gr;
+    const int k = ctx->k, n = (int)gr.kfvs.size();
+    const int64_t w0 = ctx->kfv[(size_t)gr.kfvs.front()].W;
+    L.nk = (int)(gr.W - k + 1);
+    L.nk_min = (int)(w0 - k + 1);
+    L.one_size = w0 == ctx->kfv[(size_t)gr.kfvs.back()].W;
+    int64_t prev = -1;
+    for (int j : gr.kfvs) {
+        const KfvInfo &f = ctx->kfv[(size_t)j];
+        if (f.W != prev) L.n_sizes++;
+        prev = f.W;
+        L.n_longer += f.W != w0 ? 1 : 0;
+        L.n_plus1 += f.W == w0 + 1 ? 1 : 0;
+        L.n_plus2 += f.W == w0 + 2 ? 1 : 0;
+        L.nmax = std::max(L.nmax, f.N);
+        L.s16 = L.s16 && f.Smax <= 32767;
+        L.u8 = L.u8 && f.Smax < 256;
+        L.need_wide = L.need_wide || !f.fits32;
+    }
+    if (generic_all) L.s8 = true;
+    else if (L.one_size && stream8_c16_applies(k, L.nk, n, L.nmax, L.s16, L.need_wide)) L.s8 = true;
+    else if (L.need_wide) L.s8 = false;
+    else if (stream8_wide_applies(k, L.nk_min, L.nk, n, L.nmax, L.u8, L.s16, L.n_plus1, L.n_plus2)) L.s8 = true;
+    else if (L.one_size) L.s8 = stream8_applies(k, L.nk, n, L.nmax, L.s16);
+    else L.s8 = stream8_derive_applies(k, L.nk_min, L.nk, n, L.nmax, L.s16);
+    return L;
+}
+
+// The distance-bound prefilter applies: one integer KFV on the 8-bit count-table kernel at k = 5, 6, no distance output
+// (filter_candidate_table decides whether it runs)
+bool filter_wanted(const kgma_ctx *ctx, const ScanPlan &p, bool ovl)
+{
+    const int k = p.k;
+    const KfvInfo &f0 = ctx->kfv[0];
+    const int nk0 = (int)(f0.W - k + 1);
+    return !p.filter_off && p.use_stream && !p.generic_all && p.m_used == 1 && p.groups.size() == 1 && p.groups[0].gr.kfvs.size() == 1 && p.groups[0].gr.kfvs[0] == 0 &&
+           !p.want_dists && !ovl && p.debug_skip == 0 && !f0.fp && f0.fits32 && !f0.S.empty() && stream8_applies(k, nk0, 1, f0.N, f0.Smax <= 32767) &&
+           !stream8_c16_applies(k, nk0, 1, f0.N, f0.Smax <= 32767, false) && filter_applies(k, f0.Smax);
+}
+
+// a re-encoding left to this scan (kgma_repack_scan_hits): beside the scan's launches when it is ONE stream8 launch of one KFV
+// (launch_overlapped), else one launch in front of it
+int plan_deferred_pack(kgma_ctx *ctx, kgma_genome *g, ScanPlan &p)
+{
+    g->bsum_fresh = false;                                             // (block sums are only good inside the scan whose pack wrote them)
+    if (!g->repack_deferred) return KGMA_OK;
+    p.overlap = p.use_stream && !p.generic_all && p.groups.size() == 1 && p.groups[0].gr.kfvs.size() == 1 && p.m_used == 1 && p.groups[0].s8 &&
+                g->d_planes == nullptr && overlap_setup(ctx);
+    if (p.overlap) return KGMA_OK;
+    g->repack_deferred = false;
+    // the pack carries the filter's block sums when the filter is going to run on byte entries (else: the plain pack, and
+    // the filter, if it runs after all, cuts its k-mers itself)
+    bool sums = false;
+    if (fuse_sums_possible(ctx, p.mode) && !g->bsum_failed && filter_wanted(ctx, p, false) && !filter_remembered(ctx, g)) {
+        const int64_t W0 = ctx->kfv[0].W;
+        int64_t total_nwin = 0;
+        for (const ContigDesc &d : g->cd) total_nwin += d.len >= W0 ? d.len - W0 + 1 : 0;
+        uint32_t U = 0;
+        sums = filter_bound(ctx, (int)(W0 - p.k + 1), total_nwin, &U);
+    }
+    if (sums && !g->d_bsum) {
+        if (hipMalloc(reinterpret_cast<void **>(&g->d_bsum), (size_t)g->total_words * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            g->d_bsum = nullptr; g->bsum_failed = true; sums = false;
+        } else g->device_bytes += g->total_words * 4;
+    }
+    return genome_repack(ctx, g, sums);
+}
+
+// Launches that keep different numbers of streams resident (one KFV: 32 per CU; four: 22): all launches share one
+// stream table.  Its streams per CU, S, are chosen so that every launch runs at its OWN residency s in
+// ceil(S / s) nearly full rounds (s = 22 and 32: S = 64 is 3 rounds of 22 and 2 of 32), weighing the launches by
+// their cost; with one residency (or nothing to gain) S = s and there is one round.
+void plan_natural_slots(ScanPlan &p)
+{
+    int s_max = 0;
+    for (const LaunchGroup &L : p.groups) s_max = std::max(s_max, L.slots);
+    if (s_max <= p.stream_nw) return;
+    auto cost = [&](int S) {
+        double c = 0;
+        for (const LaunchGroup &L : p.groups) c += L.weight * (double)(((S + L.slots - 1) / L.slots) * L.slots) / (double)S;
+        return c;
+    };
+    // (cutting every launch down to the smallest residency costs the others s / s_min; 0.9: fewer waves run a little faster each)
+    double best = 0;
+    for (const LaunchGroup &L : p.groups) best += L.weight * std::max(1.0, 0.9 * (double)L.slots / (double)p.stream_nw);
+    int best_S = 0;
+    for (int S = s_max; S <= 4 * s_max; S++)
+        if (cost(S) < best * 0.99) { best = cost(S); best_S = S; }
+    if (best_S > 0) { p.natural_slots = true; p.stream_nw = best_S; }
+}
+
+// Step 1: which kernel serves the scan, in which launches, at which residency.  Nothing here runs on the device but what these
+// decisions need: the occupancy queries, overlap_setup and the pack a step left to this scan.
+int plan_scan(kgma_ctx *ctx, kgma_genome *g, int32_t mode, uint32_t flags, ScanPlan &p)
+{
+    p.mode = mode;
+    p.flags = flags;
+    p.strobe = mode == KGMA_MODE_STROBE;
+    p.want_dists = (flags & KGMA_F_RETURN_DISTS) != 0;
+    const int k = p.k = ctx->k, m_used = p.m_used = mode == KGMA_MODE_SINGLE ? 1 : ctx->m;
+    for (int j = 0; j < m_used; j++) p.maxws = std::max(p.maxws, ctx->kfv[(size_t)j].W);
+    read_scan_env(p);
+    const char *kenv = p.kernel_env;
     // ---- which kernel: the count-table stream kernel for k <= 7 (one wave per stream), the bit-sliced
     //      kernel for longer k-mers (their 4^k counters do not fit a wave's share of the LDS)
     // (measured, 400 Mb random sequence: k=6 one KFV 294 vs 172 Gbp/s; below k=5 the 64 transitions of
@@ -2778,7 +2937,6 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     // Several KFVs: the 8-bit stream kernel takes the KFVs of ONE window size per launch (they share the k-mers, the
     // count table and the corrections), so the cluster engine's KFVs are grouped by window size for it; the bit-sliced
     // kernel groups up to 8 KFVs of up to 4 sizes.
-    const char *kenv = getenv("KGMA_KERNEL");                    // testing only: run the other kernel where both apply
     bool s8_all = k >= 5 && k <= 7 && !(kenv && !strcmp(kenv, "bitslice"));
     // (a KFV whose window has 384 ... 65535 k-mers at k = 5, 6, 7, or whose prefix leaves int32, takes the 16-bit counter form of the
     //  same kernel, which carries the prefix in 64 bits)
@@ -2795,341 +2953,248 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     // (k < 5, k > 7, S beyond int16 at k = 7, N >= 2^22).  KGMA_KERNEL=generic (testing): always.
     // k = 1 and k >= 11: only the generic kernel's 32-bit counter and wide hash forms serve them
     // (the strobemer kernel -- kgma_strobe.hip -- is a stream kernel of the same kind: one KFV, the same stream table and records)
-    bool generic_all = strobe || (kenv && !strcmp(kenv, "generic")) || k == 1 || k >= KGMA_WIDE_MIN_K;
+    p.generic_all = p.strobe || (kenv && !strcmp(kenv, "generic")) || k == 1 || k >= KGMA_WIDE_MIN_K;
     for (int j = 0; j < m_used; j++) {
         const KfvInfo &f = ctx->kfv[(size_t)j];
-        if (f.fp || ((f.W - k + 1 > KGMA_MAX_NK || !f.fits32) && !(s8_all && c16_ok(f)))) generic_all = true;
+        if (f.fp || ((f.W - k + 1 > KGMA_MAX_NK || !f.fits32) && !(s8_all && c16_ok(f)))) p.generic_all = true;
+        p.generic_fp = p.generic_fp || f.fp;
     }
-    bool generic_fp = false;
-    for (int j = 0; j < m_used; j++) generic_fp = generic_fp || ctx->kfv[(size_t)j].fp;
-    std::vector<Group> groups;
-    if (generic_all) { for (int j = 0; j < m_used; j++) groups.push_back(Group{ctx->kfv[(size_t)j].W, {j}}); }
-    else groups = make_groups(ctx, mode, s8_all);
-    auto group_need_wide = [&](const Group &gr) { bool w = false; for (int j : gr.kfvs) w = w || !ctx->kfv[(size_t)j].fits32; return w; };
-    auto group_nmax = [&](const Group &gr) { int64_t n = 0; for (int j : gr.kfvs) n = std::max(n, ctx->kfv[(size_t)j].N); return n; };
-    auto group_one_size = [&](const Group &gr) { return ctx->kfv[(size_t)gr.kfvs.front()].W == ctx->kfv[(size_t)gr.kfvs.back()].W; };
-    auto group_s16 = [&](const Group &gr) { bool ok = true; for (int j : gr.kfvs) ok = ok && ctx->kfv[(size_t)j].Smax <= 32767; return ok; };
-    auto group_nk_min = [&](const Group &gr) { return (int)(ctx->kfv[(size_t)gr.kfvs.front()].W - k + 1); };
-    auto group_u8 = [&](const Group &gr) { bool ok = true; for (int j : gr.kfvs) ok = ok && ctx->kfv[(size_t)j].Smax < 256; return ok; };
-    auto group_wide = [&](const Group &gr) {
-        const int64_t w0 = ctx->kfv[(size_t)gr.kfvs.front()].W;
-        int n1 = 0, n2 = 0;
-        for (int j : gr.kfvs) { n1 += ctx->kfv[(size_t)j].W == w0 + 1 ? 1 : 0; n2 += ctx->kfv[(size_t)j].W == w0 + 2 ? 1 : 0; }
-        return stream8_wide_applies(k, group_nk_min(gr), (int)(gr.W - k + 1), (int)gr.kfvs.size(), group_nmax(gr), group_u8(gr), group_s16(gr), n1, n2);
-    };
-    auto group_s8 = [&](const Group &gr) {
-        if (generic_all) return true;                                   // (reads the interleaved genome copy, like stream8_kernel)
-        if (group_one_size(gr) && stream8_c16_applies(k, (int)(gr.W - k + 1), (int)gr.kfvs.size(), group_nmax(gr), group_s16(gr), group_need_wide(gr))) return true;
-        if (group_need_wide(gr)) return false;
-        if (group_wide(gr)) return true;
-        if (group_one_size(gr)) return stream8_applies(k, (int)(gr.W - k + 1), (int)gr.kfvs.size(), group_nmax(gr), group_s16(gr));
-        return stream8_derive_applies(k, group_nk_min(gr), (int)(gr.W - k + 1), (int)gr.kfvs.size(), group_nmax(gr), group_s16(gr));
-    };
-    bool use_stream = (k >= 5 && k <= 6) || (k == 7 && s8_all);   // k = 7: only the 8-bit kernel (S tables in global memory) beats the bit-sliced one
-    for (const Group &gr : groups)
-        if (gr.kfvs.size() != 1 && !group_s8(gr)) use_stream = false;   // (the 16-bit multi-KFV stream kernel lost to the bit-sliced one: 99 vs 112 Gbp/s)
-    if (const char *kv = getenv("KGMA_KERNEL")) {      // testing only: run the other kernel where both apply
-        if (!strcmp(kv, "bitslice")) use_stream = false;
-        if (!strcmp(kv, "stream")) use_stream = k <= KGMA_STREAM_MAX_K;
+    if (p.generic_all) { for (int j = 0; j < m_used; j++) p.groups.push_back(describe_group(ctx, Group{ctx->kfv[(size_t)j].W, {j}}, true)); }
+    else for (Group &gr : make_groups(ctx, mode, s8_all)) p.groups.push_back(describe_group(ctx, std::move(gr), false));
+    p.use_stream = (k >= 5 && k <= 6) || (k == 7 && s8_all);   // k = 7: only the 8-bit kernel (S tables in global memory) beats the bit-sliced one
+    for (const LaunchGroup &L : p.groups)
+        if (L.gr.kfvs.size() != 1 && !L.s8) p.use_stream = false;   // (the 16-bit multi-KFV stream kernel lost to the bit-sliced one: 99 vs 112 Gbp/s)
+    if (kenv) {
+        if (!strcmp(kenv, "bitslice")) p.use_stream = false;
+        if (!strcmp(kenv, "stream")) p.use_stream = k <= KGMA_STREAM_MAX_K;
     }
-    if (generic_all) use_stream = true;                // (a stream kernel: same stream table, same records)
-    // a re-encoding left to this scan (kgma_repack_scan_hits): beside the scan's launches when it is ONE stream8 launch of one KFV
-    // (launch_overlapped), else one launch in front of it
-    // The distance-bound prefilter applies: one integer KFV on the 8-bit count-table kernel at k = 5, 6, no distance output
-    // (filter_candidate_table decides whether it runs)
-    auto filter_wanted = [&](bool ovl) {
-        const char *fe = getenv("KGMA_FILTER"), *ds = getenv("KGMA_DEBUG_SKIP");
-        const KfvInfo &f0 = ctx->kfv[0];
-        const int nk0 = (int)(f0.W - k + 1);
-        return !(fe && atoi(fe) == 0) && use_stream && !generic_all && m_used == 1 && groups.size() == 1 && groups[0].kfvs.size() == 1 && groups[0].kfvs[0] == 0 &&
-               !(flags & KGMA_F_RETURN_DISTS) && !ovl && !(ds && atoi(ds) != 0) && !f0.fp && f0.fits32 && !f0.S.empty() && stream8_applies(k, nk0, 1, f0.N, f0.Smax <= 32767) &&
-               !stream8_c16_applies(k, nk0, 1, f0.N, f0.Smax <= 32767, false) && filter_applies(k, f0.Smax);
-    };
-    bool overlap = false;
-    g->bsum_fresh = false;                                             // (block sums are only good inside the scan whose pack wrote them)
-    if (g->repack_deferred) {
-        overlap = use_stream && !generic_all && groups.size() == 1 && groups[0].kfvs.size() == 1 && m_used == 1 && group_s8(groups[0]) &&
-                  g->d_planes == nullptr && overlap_setup(ctx);
-        if (!overlap) {
-            g->repack_deferred = false;
-            // the pack carries the filter's block sums when the filter is going to run on byte entries (else: the plain pack, and
-            // the filter, if it runs after all, cuts its k-mers itself)
-            bool sums = false;
-            if (fuse_sums_possible(ctx, mode) && !g->bsum_failed && filter_wanted(false) && !filter_remembered(ctx, g)) {
-                const int64_t W0 = ctx->kfv[0].W;
-                int64_t total_nwin = 0;
-                for (const ContigDesc &d : g->cd) total_nwin += d.len >= W0 ? d.len - W0 + 1 : 0;
-                uint32_t U = 0;
-                sums = filter_bound(ctx, (int)(W0 - k + 1), total_nwin, &U);
-            }
-            if (sums && !g->d_bsum) {
-                if (hipMalloc(reinterpret_cast<void **>(&g->d_bsum), (size_t)g->total_words * 4) != hipSuccess) {
-                    (void)hipGetLastError();
-                    g->d_bsum = nullptr; g->bsum_failed = true; sums = false;
-                } else g->device_bytes += g->total_words * 4;
-            }
-            const int prc = genome_repack(ctx, g, sums);
-            if (prc) return prc;
+    if (p.generic_all) p.use_stream = true;            // (a stream kernel: same stream table, same records)
+    const int prc = plan_deferred_pack(ctx, g, p);
+    if (prc) return prc;
+    p.eff_reserved = p.overlap ? std::max(ctx->reserved_cus, ctx->ov_cus) : ctx->reserved_cus;   // (the scan's streams are sized for the CUs it gets)
+    p.stream_nw = 1 << 20;           // streams resident per CU (smallest over the launch groups)
+    if (p.generic_all) {
+        p.stream_nw = p.strobe ? strobe_slots_per_cu(ctx->st_s) : generic_slots_per_cu(k, p.generic_fp, (int)(p.maxws - k + 1));
+        if (p.stream_nw < 1) return fail(ctx, KGMA_E_HIP, "the %s kernel cannot be launched (k = %d)", p.strobe ? "strobemer" : "generic", k);
+    }
+    if (p.use_stream && !p.generic_all)
+        for (LaunchGroup &L : p.groups) {
+            L.slots = stream_slots_per_cu(k, L.nk, L.nk_min, L.n_longer, (int)L.gr.kfvs.size(), L.n_sizes, L.s16, L.nmax, L.u8, L.n_plus2, L.need_wide);
+            if (L.slots < 1) p.use_stream = false;
+            p.stream_nw = std::min(p.stream_nw, L.slots);
+            L.weight = 4.0 + (double)L.gr.kfvs.size();                  // (a launch costs about 55 + 13 per KFV, in arbitrary units)
         }
-    }
-    const int eff_reserved = overlap ? std::max(ctx->reserved_cus, ctx->ov_cus) : ctx->reserved_cus;   // (the scan's streams are sized for the CUs it gets)
-    int stream_nw = 1 << 20;         // streams resident per CU (smallest over the launch groups)
-    std::vector<int> launch_slots;
-    std::vector<double> launch_weight;
-    if (generic_all) {
-        stream_nw = strobe ? strobe_slots_per_cu(ctx->st_s) : generic_slots_per_cu(k, generic_fp, (int)(maxws - k + 1));
-        if (stream_nw < 1) return fail(ctx, KGMA_E_HIP, "the %s kernel cannot be launched (k = %d)", strobe ? "strobemer" : "generic", k);
-    }
-    if (use_stream && !generic_all)
-        for (const Group &gr : groups) {
-            int n_sizes = 0;
-            int64_t prev = -1;
-            for (int j : gr.kfvs) { if (ctx->kfv[(size_t)j].W != prev) n_sizes++; prev = ctx->kfv[(size_t)j].W; }
-            bool s16 = true;
-            for (int j : gr.kfvs) s16 = s16 && ctx->kfv[(size_t)j].Smax <= 32767;
-            int n_longer = 0;                  // KFVs whose window is longer than the launch's shortest
-            for (int j : gr.kfvs) n_longer += ctx->kfv[(size_t)j].W != ctx->kfv[(size_t)gr.kfvs.front()].W ? 1 : 0;
-            int n_plus2 = 0;                   // ... two k-mers longer (five-KFV launches)
-            for (int j : gr.kfvs) n_plus2 += ctx->kfv[(size_t)j].W == ctx->kfv[(size_t)gr.kfvs.front()].W + 2 ? 1 : 0;
-            const int nw = stream_slots_per_cu(k, (int)(gr.W - k + 1), group_nk_min(gr), n_longer, (int)gr.kfvs.size(), n_sizes, s16, group_nmax(gr),
-                                               group_u8(gr), n_plus2, group_need_wide(gr));
-            if (nw < 1) use_stream = false;
-            stream_nw = std::min(stream_nw, nw);
-            launch_slots.push_back(nw);
-            launch_weight.push_back(4.0 + (double)gr.kfvs.size());      // (a launch costs about 55 + 13 per KFV, in arbitrary units)
-        }
-    // Launches that keep different numbers of streams resident (one KFV: 32 per CU; four: 22): all launches share one
-    // stream table.  Its streams per CU, S, are chosen so that every launch runs at its OWN residency s in
-    // ceil(S / s) nearly full rounds (s = 22 and 32: S = 64 is 3 rounds of 22 and 2 of 32), weighing the launches by
-    // their cost; with one residency (or nothing to gain) S = s and there is one round.
-    bool natural_slots = false;
-    if (use_stream && !generic_all && !getenv("KGMA_STREAM_MINSLOTS")) {
-        int s_max = 0;
-        for (int sl : launch_slots) s_max = std::max(s_max, sl);
-        if (s_max > stream_nw) {
-            auto cost = [&](int S) {
-                double c = 0;
-                for (size_t i = 0; i < launch_slots.size(); i++) {
-                    const int sl = launch_slots[i];
-                    c += launch_weight[i] * (double)(((S + sl - 1) / sl) * sl) / (double)S;
-                }
-                return c;
-            };
-            // (cutting every launch down to the smallest residency costs the others s / s_min; 0.9: fewer waves run a little faster each)
-            double best = 0;
-            for (size_t i = 0; i < launch_slots.size(); i++)
-                best += launch_weight[i] * std::max(1.0, 0.9 * (double)launch_slots[i] / (double)stream_nw);
-            int best_S = 0;
-            for (int S = s_max; S <= 4 * s_max; S++)
-                if (cost(S) < best * 0.99) { best = cost(S); best_S = S; }
-            if (best_S > 0) { natural_slots = true; stream_nw = best_S; }
-        }
-    }
-    const int64_t nc = g->n_contigs;
-    const bool want_dists = (flags & KGMA_F_RETURN_DISTS) != 0;
+    if (p.use_stream && !p.generic_all && !p.minslots) plan_natural_slots(p);
     // (what the stream table was sized for: reserved CUs < 2^10, CUs < 2^14, streams per CU < 2^16 -- 64 bits, no packing games)
-    const uint64_t geom_version = use_stream ? (generic_all ? 3u : 2u) + ((uint64_t)(uint32_t)eff_reserved << 4) + ((uint64_t)(uint32_t)ctx->n_cus << 16) + ((uint64_t)(uint32_t)stream_nw << 32) : 1u;
+    p.geom_version = p.use_stream ? (p.generic_all ? 3u : 2u) + ((uint64_t)(uint32_t)p.eff_reserved << 4) + ((uint64_t)(uint32_t)ctx->n_cus << 16) + ((uint64_t)(uint32_t)p.stream_nw << 32) : 1u;
+    bool s8 = p.use_stream;
+    p.planes_needed = !p.use_stream;                   // every kernel but the 8-bit stream kernel reads the bit-plane copy of the genome
+    for (const LaunchGroup &L : p.groups) { s8 = s8 && L.s8; p.planes_needed = p.planes_needed || !L.s8; }
+    if (p.strobe) snprintf(p.kernel_name, sizeof p.kernel_name, "strobe_kernel<%d>", ctx->st_s);
+    else snprintf(p.kernel_name, sizeof p.kernel_name, p.generic_all ? (p.generic_fp ? "gen_kernel<f64,%d>" : "gen_kernel<%d>") : s8 ? "stream8_kernel<%d>" : p.use_stream ? "stream_kernel<%d>" : "scan_kernel<%d>", k);   // (+ pos_kernel for multi-KFV groups)
+    return KGMA_OK;
+}
+
+// Which windows a record of L residues evaluates (nwin) and how many of its residues the reference looks up on the way (looked;
+// -1: it raises a BoundsError)
+void record_windows_looked(const kgma_ctx *ctx, const ScanPlan &p, int64_t L, int64_t &nwin, int64_t &looked)
+{
+    const int k = p.k;
+    nwin = 0; looked = 0;
+    if (p.mode == KGMA_MODE_SINGLE) {
+        const int64_t W = ctx->kfv[0].W;
+        if (L >= W) { nwin = L - W + 1; looked = L; }   // GenomeMiner.jl:37-39,60
+    } else if (p.strobe) {
+        // StrobeGenomeMiner.jl:36,40,48-57: the first window (virtual window start 1) and one window per step i = 1 .. L - W - 1
+        // (start i + 1); the residues looked up are the first window's and those of the strobemers up to the one at L - k - 1
+        const int64_t W = ctx->kfv[0].W;
+        if (L >= W) { nwin = std::max<int64_t>(L - W, 1); looked = std::max<int64_t>(W, L - 2); }
+    } else if (L < k - 1) {
+        looked = -1;                                                   // BoundsError, OmnGenomeMiner.jl:84-86
+    } else {
+        looked = k - 1;                                                // :84-86
+        for (int j = 0; j < p.m_used; j++)
+            if (L >= ctx->kfv[(size_t)j].W) looked = std::max(looked, ctx->kfv[(size_t)j].W);   // :61-82
+        const int64_t n_iter = L - p.maxws - k + 2;                    // :89
+        if (n_iter >= 1) { nwin = n_iter + 1; looked = std::max(looked, L - k + 2); }   // seq[i+ws], :97
+    }
+}
+
+// windows per tile: fixed by the workgroup geometry for the bit-sliced kernel; for the stream
+// kernel one wave owns one stream, so the stream length is chosen to give every wave slot of the
+// chip (256 CUs x waves per workgroup) a whole number of equally long streams
+int64_t stream_length(const kgma_ctx *ctx, const ScanPlan &p, int64_t total_nwin)
+{
+    const int k = p.k;
+    const int64_t maxws = p.maxws;
+    if (!p.use_stream) return (int64_t)scan_tile_stride_words((int)(maxws - k + 1)) * 32;
+    const int64_t slots = (int64_t)std::max(1, ctx->n_cus - p.eff_reserved) * p.stream_nw;      // (kgma_set_reserved_cus; the pack / scan overlap)
+    int64_t rounds = std::max<int64_t>(1, (total_nwin + slots * KGMA_STREAM_MAX_WINDOWS - 1) / (slots * KGMA_STREAM_MAX_WINDOWS));
+    // Several rounds of shorter streams balance the CUs (the workgroups of a launch are handed out as earlier
+    // ones finish; measured at GRCh38 size, one KFV: 5.72 ms with one round, 5.13 ms with three; 400 Mb: 0.752 / 0.704 ms;
+    // 50.8 Mb: 0.118 ms with one round of 6.2 k windows, 0.124 with two, 0.135 with three), as long as a
+    // stream stays long against its warm-up (n k-mers) and the S-table staging of its workgroup.
     {
-        bool s8 = use_stream;
-        if (use_stream)
-            for (const Group &gr : groups) s8 = s8 && group_s8(gr);
-        if (strobe) snprintf(ctx->kernel_name, sizeof ctx->kernel_name, "strobe_kernel<%d>", ctx->st_s);
-        else snprintf(ctx->kernel_name, sizeof ctx->kernel_name, generic_all ? (generic_fp ? "gen_kernel<f64,%d>" : "gen_kernel<%d>") : s8 ? "stream8_kernel<%d>" : use_stream ? "stream_kernel<%d>" : "scan_kernel<%d>", k);   // (+ pos_kernel for multi-KFV groups)
+        int64_t want = 3, min_windows = std::max<int64_t>(8192, 8 * (maxws - k + 1));   // (a stream's warm-up is its window's n k-mers)
+        if (p.generic_all && !p.strobe && generic_count_mode(k, (int)(maxws - k + 1)) == 1) min_windows = std::max<int64_t>(min_windows, (int64_t)1 << (2 * k - 2));   // (and zeroing its global count table)
+        if (p.rounds) want = p.rounds;                                 // experiments
+        if (p.round_windows) min_windows = p.round_windows;
+        rounds = std::max(rounds, std::min<int64_t>(want, total_nwin / (slots * min_windows)));
     }
-
-    ctx->dips.clear();
-    ctx->hits.clear();
-    ctx->have_dists = false;
-    ctx->last_mode = -1;
-    ctx->scan_filtered = false;
-    memset(&ctx->fstats, 0, sizeof ctx->fstats);
-    ctx->fentries.clear();
-    {
-        // every kernel but the 8-bit stream kernel reads the bit-plane copy of the genome
-        bool planes_needed = !use_stream;
-        for (const Group &gr : groups) planes_needed = planes_needed || !group_s8(gr);
-        if (planes_needed) {
-            const int prc = ensure_planes(ctx, g);
-            if (prc != KGMA_OK) return prc;
-        }
-    }
-
-    // ---- which windows each record evaluates (tile table), cached per (genome, mode, W, k, kernel) ----
-    const bool tiles_cached = ctx->tk_uid == g->uid && ctx->tk_mode == mode && ctx->tk_maxws == maxws &&
-                              ctx->tk_k == k && ctx->tk_version == geom_version;
-    if (!tiles_cached) {
-        ctx->contig_len.resize((size_t)nc);
-        ctx->contig_nwin.assign((size_t)nc, 0);
-        ctx->contig_looked.assign((size_t)nc, 0);
-        ctx->contig_tile_base.assign((size_t)nc, -1);
-        ctx->tiles.clear();
-        int64_t dist_total = 0, bases = 0, windows = 0, total_nwin = 0;
-        for (int64_t c = 0; c < nc; c++) {
-            const int64_t L = g->cd[(size_t)c].len;
-            ctx->contig_len[(size_t)c] = L;
-            bases += L;
-            int64_t nwin = 0, looked = 0;
-            if (mode == KGMA_MODE_SINGLE) {
-                const int64_t W = ctx->kfv[0].W;
-                if (L >= W) { nwin = L - W + 1; looked = L; }   // GenomeMiner.jl:37-39,60
-            } else if (strobe) {
-                // StrobeGenomeMiner.jl:36,40,48-57: the first window (virtual window start 1) and one window per step i = 1 .. L - W - 1
-                // (start i + 1); the residues looked up are the first window's and those of the strobemers up to the one at L - k - 1
-                const int64_t W = ctx->kfv[0].W;
-                if (L >= W) { nwin = std::max<int64_t>(L - W, 1); looked = std::max<int64_t>(W, L - 2); }
-            } else {
-                if (L < k - 1) {
-                    looked = -1;                                                   // BoundsError, :84-86
-                } else {
-                    looked = k - 1;                                                // :84-86
-                    for (int j = 0; j < m_used; j++)
-                        if (L >= ctx->kfv[(size_t)j].W) looked = std::max(looked, ctx->kfv[(size_t)j].W);   // :61-82
-                    const int64_t n_iter = L - maxws - k + 2;                      // :89
-                    if (n_iter >= 1) { nwin = n_iter + 1; looked = std::max(looked, L - k + 2); }   // seq[i+ws], :97
-                }
-            }
-            ctx->contig_looked[(size_t)c] = looked;
-            ctx->contig_nwin[(size_t)c] = nwin;
-            total_nwin += nwin;
-        }
-        // windows per tile: fixed by the workgroup geometry for the bit-sliced kernel; for the stream
-        // kernel one wave owns one stream, so the stream length is chosen to give every wave slot of the
-        // chip (256 CUs x waves per workgroup) a whole number of equally long streams
-        int64_t P;
-        if (use_stream) {
-            const int64_t slots = (int64_t)std::max(1, ctx->n_cus - eff_reserved) * stream_nw;      // (kgma_set_reserved_cus; the pack / scan overlap)
-            int64_t rounds = std::max<int64_t>(1, (total_nwin + slots * KGMA_STREAM_MAX_WINDOWS - 1) / (slots * KGMA_STREAM_MAX_WINDOWS));
-            // Several rounds of shorter streams balance the CUs (the workgroups of a launch are handed out as earlier
-            // ones finish; measured at GRCh38 size, one KFV: 5.72 ms with one round, 5.13 ms with three; 400 Mb: 0.752 / 0.704 ms;
-            // 50.8 Mb: 0.118 ms with one round of 6.2 k windows, 0.124 with two, 0.135 with three), as long as a
-            // stream stays long against its warm-up (n k-mers) and the S-table staging of its workgroup.
-            {
-                int64_t want = 3, min_windows = std::max<int64_t>(8192, 8 * (maxws - k + 1));   // (a stream's warm-up is its window's n k-mers)
-                if (generic_all && !strobe && generic_count_mode(k, (int)(maxws - k + 1)) == 1) min_windows = std::max<int64_t>(min_windows, (int64_t)1 << (2 * k - 2));   // (and zeroing its global count table)
-                if (const char *re = getenv("KGMA_STREAM_ROUNDS")) want = std::max(1, atoi(re));               // experiments
-                if (const char *re = getenv("KGMA_STREAM_ROUND_WINDOWS")) min_windows = std::max(64, atoi(re));
-                rounds = std::max(rounds, std::min<int64_t>(want, total_nwin / (slots * min_windows)));
-            }
-            P = (total_nwin + slots * rounds - 1) / (slots * rounds);
-            P = ((P + 63) / 64) * 64;
-            // (a stream's warm-up is its window's n k-mers: at least 4 n windows per stream; streams start on 64-window boundaries)
-            P = std::min<int64_t>(std::max<int64_t>(P, std::max<int64_t>(KGMA_STREAM_MIN_WINDOWS, std::min<int64_t>(((4 * (maxws - k + 1) + 63) / 64) * 64, 1 << 16))),
-                                  KGMA_STREAM_MAX_WINDOWS);
-            // every record ends with a shorter stream: lengthen the streams until they fit the wave slots
-            // again (one stream too many would cost a whole extra round on one CU)
-            auto count_streams = [&](int64_t len) {
-                int64_t n = 0;
-                for (int64_t c = 0; c < nc; c++) n += (ctx->contig_nwin[(size_t)c] + len - 1) / len;
-                return n;
-            };
-            for (int it = 0; it < 64 && P < KGMA_STREAM_MAX_WINDOWS && count_streams(P) > slots * rounds; it++)
-                P = std::min<int64_t>(((P + P / 128 + 63) / 64) * 64, KGMA_STREAM_MAX_WINDOWS);
-        } else {
-            P = (int64_t)scan_tile_stride_words((int)(maxws - k + 1)) * 32;
-        }
-        if (getenv("KGMA_GEOM_DEBUG"))
-            fprintf(stderr, "scan geometry: %s, %d CUs (%d reserved), %d streams per CU, %lld windows -> streams of %lld\n", use_stream ? "stream" : "bitslice",
-                    ctx->n_cus, ctx->reserved_cus, use_stream ? stream_nw : 0, (long long)total_nwin, (long long)P);
-        const int64_t stride_words = P / 32;
-        ctx->tile_windows = P;
-        for (int64_t c = 0; c < nc; c++) {
-            const int64_t nwin = ctx->contig_nwin[(size_t)c];
-            if (nwin > 0) {
-                ctx->contig_tile_base[(size_t)c] = (int64_t)ctx->tiles.size();
-                const int64_t nt = (nwin + P - 1) / P;
-                for (int64_t t = 0; t < nt; t++) {
-                    TileDesc td;
-                    td.word_base = g->cd[(size_t)c].word_off + t * stride_words;
-                    td.win0 = t * P + 1;
-                    td.dist_base = dist_total + t * P - 1;
-                    td.n_valid = (int32_t)std::min<int64_t>(P, nwin - t * P);
-                    td.first_test = t == 0 ? 1 : 0;
-                    td.contig = (int32_t)c;
-                    td.pad = 0;
-                    ctx->tiles.push_back(td);
-                }
-                dist_total += nwin - 1;
-                windows += nwin * m_used;
-            }
-        }
-        ctx->n_dists_per_kfv = dist_total;
-        ctx->tk_bases = bases;
-        ctx->tk_windows = windows;
-        ctx->tk_uid = 0;   // set once the table is on the device
-    }
-    const int64_t n_tiles = (int64_t)ctx->tiles.size();
-    if (n_tiles > 0x7FFFFFF0ll) return fail(ctx, KGMA_E_UNSUPPORTED, "too many tiles");
-    const int64_t dist_total = ctx->n_dists_per_kfv;
-    ctx->stats.bases_scanned = ctx->tk_bases;
-    ctx->stats.windows_scanned = ctx->tk_windows;
-    ctx->stats.n_tiles = (int32_t)n_tiles;
-    ctx->stats.n_launches = 0;
-    ctx->stats.scan_ms = 0;
-    ctx->stats.n_at_threshold = 0;
-    ctx->stats.n_dips = ctx->stats.n_hits = ctx->stats.n_tie_flagged = 0;
-
-    // errors the reference raises while walking the records, in record order
-    auto check_records = [&]() -> int {
-        for (int64_t c = 0; c < nc; c++) {
-            const int64_t looked = ctx->contig_looked[(size_t)c];
-            if (looked < 0)
-                return fail(ctx, KGMA_E_BOUNDS, "record %lld has %lld residues, fewer than k-1 (BoundsError, OmnGenomeMiner.jl:84-86)",
-                            (long long)c, (long long)ctx->contig_len[(size_t)c]);
-            const unsigned long long fb = g->first_bad[(size_t)c];
-            if (fb != NO_BAD && (int64_t)fb <= looked)
-                return fail(ctx, KGMA_E_BADBASE, "record %lld position %llu: residue is not one of A/C/G/T/N (KeyError, Consts.jl:22-28)",
-                            (long long)c, fb);
-        }
-        return KGMA_OK;
+    int64_t P = (total_nwin + slots * rounds - 1) / (slots * rounds);
+    P = ((P + 63) / 64) * 64;
+    // (a stream's warm-up is its window's n k-mers: at least 4 n windows per stream; streams start on 64-window boundaries)
+    P = std::min<int64_t>(std::max<int64_t>(P, std::max<int64_t>(KGMA_STREAM_MIN_WINDOWS, std::min<int64_t>(((4 * (maxws - k + 1) + 63) / 64) * 64, 1 << 16))),
+                          KGMA_STREAM_MAX_WINDOWS);
+    // every record ends with a shorter stream: lengthen the streams until they fit the wave slots
+    // again (one stream too many would cost a whole extra round on one CU)
+    auto count_streams = [&](int64_t len) {
+        int64_t n = 0;
+        for (int64_t nwin : ctx->contig_nwin) n += (nwin + len - 1) / len;
+        return n;
     };
+    for (int it = 0; it < 64 && P < KGMA_STREAM_MAX_WINDOWS && count_streams(P) > slots * rounds; it++)
+        P = std::min<int64_t>(((P + P / 128 + 63) / 64) * 64, KGMA_STREAM_MAX_WINDOWS);
+    return P;
+}
 
-    if (n_tiles == 0) {
-        if (g->repack_deferred) {
-            g->repack_deferred = false;
-            const int prc = kgma_genome_repack(ctx, g);
-            if (prc) return prc;
-        }
-        int rc0 = genome_sync(ctx, g);
-        if (rc0) return rc0;
-        rc0 = check_records();
-        if (rc0) return rc0;
-        ctx->D0.assign((size_t)ctx->m, -1);
-        ctx->firstD.assign((size_t)ctx->m * (size_t)nc, -1);
-        ctx->dips.clear(); ctx->dip_argl.clear(); ctx->dip_aux.clear();
-        ctx->att.clear(); ctx->chain_pair.clear(); ctx->firstF.clear(); ctx->dip_fmin.clear(); ctx->dip_fexit.clear();
-        ctx->last_mode = mode;
-        ctx->have_dists = want_dists;
-        return KGMA_OK;
+// ---- which windows each record evaluates (tile table), cached per (genome, mode, W, k, kernel) ----
+bool stream_table_cached(const kgma_ctx *ctx, const kgma_genome *g, const ScanPlan &p)
+{
+    return ctx->tk_uid == g->uid && ctx->tk_mode == p.mode && ctx->tk_maxws == p.maxws && ctx->tk_k == p.k && ctx->tk_version == p.geom_version;
+}
+
+// Step 2: the stream (tile) table of the plan over the genome's records, on the host (kgma_scan_device uploads it)
+void build_stream_table(kgma_ctx *ctx, const kgma_genome *g, const ScanPlan &p)
+{
+    const int64_t nc = g->n_contigs;
+    ctx->contig_len.resize((size_t)nc);
+    ctx->contig_nwin.assign((size_t)nc, 0);
+    ctx->contig_looked.assign((size_t)nc, 0);
+    ctx->contig_tile_base.assign((size_t)nc, -1);
+    ctx->tiles.clear();
+    int64_t dist_total = 0, bases = 0, windows = 0, total_nwin = 0;
+    for (int64_t c = 0; c < nc; c++) {
+        const int64_t L = g->cd[(size_t)c].len;
+        ctx->contig_len[(size_t)c] = L;
+        bases += L;
+        record_windows_looked(ctx, p, L, ctx->contig_nwin[(size_t)c], ctx->contig_looked[(size_t)c]);
+        total_nwin += ctx->contig_nwin[(size_t)c];
     }
+    const int64_t P = stream_length(ctx, p, total_nwin);
+    if (p.geom_debug)
+        fprintf(stderr, "scan geometry: %s, %d CUs (%d reserved), %d streams per CU, %lld windows -> streams of %lld\n", p.use_stream ? "stream" : "bitslice",
+                ctx->n_cus, ctx->reserved_cus, p.use_stream ? p.stream_nw : 0, (long long)total_nwin, (long long)P);
+    const int64_t stride_words = P / 32;
+    ctx->tile_windows = P;
+    for (int64_t c = 0; c < nc; c++) {
+        const int64_t nwin = ctx->contig_nwin[(size_t)c];
+        if (nwin <= 0) continue;
+        ctx->contig_tile_base[(size_t)c] = (int64_t)ctx->tiles.size();
+        const int64_t nt = (nwin + P - 1) / P;
+        for (int64_t t = 0; t < nt; t++) {
+            TileDesc td;
+            td.word_base = g->cd[(size_t)c].word_off + t * stride_words;
+            td.win0 = t * P + 1;
+            td.dist_base = dist_total + t * P - 1;
+            td.n_valid = (int32_t)std::min<int64_t>(P, nwin - t * P);
+            td.first_test = t == 0 ? 1 : 0;
+            td.contig = (int32_t)c;
+            td.pad = 0;
+            ctx->tiles.push_back(td);
+        }
+        dist_total += nwin - 1;
+        windows += nwin * p.m_used;
+    }
+    ctx->n_dists_per_kfv = dist_total;
+    ctx->tk_bases = bases;
+    ctx->tk_windows = windows;
+    ctx->tk_uid = 0;   // set once the table is on the device
+}
 
+// errors the reference raises while walking the records, in record order
+int check_records(kgma_ctx *ctx, const kgma_genome *g)
+{
+    for (int64_t c = 0; c < g->n_contigs; c++) {
+        const int64_t looked = ctx->contig_looked[(size_t)c];
+        if (looked < 0)
+            return fail(ctx, KGMA_E_BOUNDS, "record %lld has %lld residues, fewer than k-1 (BoundsError, OmnGenomeMiner.jl:84-86)",
+                        (long long)c, (long long)ctx->contig_len[(size_t)c]);
+        const unsigned long long fb = g->first_bad[(size_t)c];
+        if (fb != NO_BAD && (int64_t)fb <= looked)
+            return fail(ctx, KGMA_E_BADBASE, "record %lld position %llu: residue is not one of A/C/G/T/N (KeyError, Consts.jl:22-28)",
+                        (long long)c, fb);
+    }
+    return KGMA_OK;
+}
+
+// a genome without a single window: the records are still walked for the reference's errors
+int scan_without_windows(kgma_ctx *ctx, kgma_genome *g, const ScanPlan &p)
+{
+    if (g->repack_deferred) {
+        g->repack_deferred = false;
+        const int prc = kgma_genome_repack(ctx, g);
+        if (prc) return prc;
+    }
+    int rc = genome_sync(ctx, g);
+    if (rc) return rc;
+    rc = check_records(ctx, g);
+    if (rc) return rc;
+    ctx->D0.assign((size_t)ctx->m, -1);
+    ctx->firstD.assign((size_t)ctx->m * (size_t)g->n_contigs, -1);
+    ctx->dips.clear(); ctx->dip_argl.clear(); ctx->dip_aux.clear();
+    ctx->att.clear(); ctx->chain_pair.clear(); ctx->firstF.clear(); ctx->dip_fmin.clear(); ctx->dip_fexit.clear();
+    ctx->last_mode = p.mode;
+    ctx->have_dists = p.want_dists;
+    return KGMA_OK;
+}
+
+// The result block on the device and its pinned mirror share one layout: counters | D0 slots | aux | records (one memset, one
+// download per scan; the mirror holds the first INLINE_RECS records)
+constexpr size_t INLINE_RECS = 4096;
+struct ResultBlock {
+    uint8_t *base;
+    int64_t d0_slots;
+    unsigned int *n_recs() const { return reinterpret_cast<unsigned int *>(base); }
+    unsigned int *aux_used() const { return reinterpret_cast<unsigned int *>(base + 4); }
+    unsigned long long *n_att() const { return reinterpret_cast<unsigned long long *>(base + 8); }
+    unsigned long long *n_cold() const { return reinterpret_cast<unsigned long long *>(base + 16); }
+    int64_t *D0() const { return reinterpret_cast<int64_t *>(base + KGMA_RES_HDR); }
+    uint8_t *aux() const { return base + KGMA_RES_HDR + d0_slots * 8; }
+    DevRecord *recs() const { return reinterpret_cast<DevRecord *>(aux() + KGMA_AUX_BYTES); }
+    static int64_t bytes(int64_t d0_slots, int64_t n_recs) { return KGMA_RES_HDR + d0_slots * 8 + KGMA_AUX_BYTES + n_recs * (int64_t)sizeof(DevRecord); }
+};
+inline ResultBlock device_results(const kgma_ctx *ctx) { return ResultBlock{ctx->d_res, ctx->res_d0_slots}; }
+inline ResultBlock host_results(const kgma_ctx *ctx) { return ResultBlock{ctx->h_pin, ctx->res_d0_slots}; }
+
+int res_reserve(kgma_ctx *ctx, int64_t d0_slots, int64_t recs)
+{
+    if (ctx->d_res && d0_slots <= ctx->res_d0_slots && recs <= (int64_t)ctx->rec_cap) return KGMA_OK;
+    d0_slots = std::max(d0_slots, ctx->res_d0_slots);
+    recs = std::max<int64_t>(recs, ctx->rec_cap);
+    int64_t cap = 0;
+    uint8_t *fresh = nullptr;
+    int r2 = dev_reserve(ctx, fresh, cap, ResultBlock::bytes(d0_slots, recs));
+    if (r2) return r2;
+    if (ctx->d_res) { (void)hipFree(ctx->d_res); ctx->device_bytes -= ctx->res_bytes; }
+    ctx->d_res = fresh; ctx->res_bytes = cap; ctx->res_d0_slots = d0_slots; ctx->rec_cap = (unsigned int)recs;
+    ctx->counters_clean = false;                     // a fresh block is not zeroed
+    return KGMA_OK;
+}
+
+// Step 3: room for the stream table, the result block, the distances and the pinned mirror
+int reserve_results(kgma_ctx *ctx, const ScanPlan &p, int64_t n_tiles)
+{
     int rc = dev_reserve(ctx, ctx->d_tiles, ctx->tiles_cap, n_tiles);
     if (rc) return rc;
-    // result block: counters | D0 | records (one memset, one download per scan)
-    auto res_reserve = [&](int64_t d0_slots, int64_t recs) -> int {
-        if (ctx->d_res && d0_slots <= ctx->res_d0_slots && recs <= (int64_t)ctx->rec_cap) return KGMA_OK;
-        d0_slots = std::max(d0_slots, ctx->res_d0_slots);
-        recs = std::max<int64_t>(recs, ctx->rec_cap);
-        int64_t cap = 0;
-        uint8_t *fresh = nullptr;
-        const int64_t bytes = KGMA_RES_HDR + d0_slots * 8 + KGMA_AUX_BYTES + recs * (int64_t)sizeof(DevRecord);
-        int r2 = dev_reserve(ctx, fresh, cap, bytes);
-        if (r2) return r2;
-        if (ctx->d_res) { (void)hipFree(ctx->d_res); ctx->device_bytes -= ctx->res_bytes; }
-        ctx->d_res = fresh; ctx->res_bytes = cap; ctx->res_d0_slots = d0_slots; ctx->rec_cap = (unsigned int)recs;
-        ctx->counters_clean = false;                     // a fresh block is not zeroed
-        return KGMA_OK;
-    };
-    rc = res_reserve(n_tiles * ctx->m, std::max<int64_t>(ctx->rec_cap, 1 << 16));
+    rc = res_reserve(ctx, n_tiles * ctx->m, std::max<int64_t>(ctx->rec_cap, 1 << 16));
     if (rc) return rc;
-    if (want_dists)
-        for (int j = 0; j < m_used; j++) {
-            rc = dev_reserve(ctx, ctx->d_dist[(size_t)j], ctx->dist_cap[(size_t)j], std::max<int64_t>(1, dist_total));
+    if (p.want_dists)
+        for (int j = 0; j < p.m_used; j++) {
+            rc = dev_reserve(ctx, ctx->d_dist[(size_t)j], ctx->dist_cap[(size_t)j], std::max<int64_t>(1, ctx->n_dists_per_kfv));
             if (rc) return rc;
         }
-    // pinned staging: [meta 16 B][D0 n_tiles*m*8][first INLINE_RECS records]
-    constexpr size_t INLINE_RECS = 4096;
-    const size_t d0_bytes = (size_t)ctx->res_d0_slots * sizeof(int64_t);
-    const size_t pin_need = KGMA_RES_HDR + d0_bytes + KGMA_AUX_BYTES + INLINE_RECS * sizeof(DevRecord);
+    const size_t pin_need = (size_t)ResultBlock::bytes(ctx->res_d0_slots, INLINE_RECS);
     if (pin_need > ctx->h_pin_cap) {
         if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
         ctx->h_pin = nullptr; ctx->h_pin_cap = 0;
@@ -3141,221 +3206,233 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_done), 16));
         ctx->counters_clean = false;
     }
-    unsigned int *h_nrecs = reinterpret_cast<unsigned int *>(ctx->h_pin);
-    unsigned long long *h_natt = reinterpret_cast<unsigned long long *>(ctx->h_pin + 8);
-    unsigned long long *h_ncold = reinterpret_cast<unsigned long long *>(ctx->h_pin + 16);
-    int64_t *h_D0 = reinterpret_cast<int64_t *>(ctx->h_pin + KGMA_RES_HDR);
-    const uint8_t *h_aux = ctx->h_pin + KGMA_RES_HDR + d0_bytes;
-    DevRecord *h_recs = reinterpret_cast<DevRecord *>(ctx->h_pin + KGMA_RES_HDR + d0_bytes + KGMA_AUX_BYTES);
+    return KGMA_OK;
+}
 
-    if (!tiles_cached) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tiles, ctx->tiles.data(), (size_t)n_tiles * sizeof(TileDesc), hipMemcpyHostToDevice, ctx->stream));
-        // the vector is pageable memory: the runtime stages it before returning, so it may be reused
-        ctx->tk_uid = g->uid; ctx->tk_mode = mode; ctx->tk_maxws = maxws; ctx->tk_k = k; ctx->tk_version = geom_version;
-    }
-
-    // ---- distance-bound prefilter: one integer KFV on the 8-bit count-table kernel at k = 5, 6, no distance output -- the exact
-    //      kernel then walks the candidate stream table instead of the regular one (filter_candidate_table)
+// the table the exact kernel walks (the prefilter's candidate streams, or the regular one): its streams, D0 slots and records
+struct ScanTables {
+    int64_t n_tiles = 0;               // streams of the regular table
+    int64_t n_scan = 0;                // streams of the table walked
+    const TileDesc *d_scan_tiles = nullptr;
     bool filtered = false;
-    if (filter_wanted(overlap)) {
-        rc = filter_candidate_table(ctx, g, (int)(ctx->kfv[0].W - k + 1), n_tiles, &filtered);
-        if (rc) return rc;
-    }
-    // the table the exact kernel walks: its streams, D0 slots and records
-    const int64_t n_scan = filtered ? (int64_t)ctx->ftiles.size() : n_tiles;
-    const TileDesc *d_scan_tiles = filtered ? ctx->d_ftiles : ctx->d_tiles;
+};
 
-    unsigned int n_recs = 0;
-    for (int attempt = 0;; attempt++) {
-        if (attempt > 0) ctx->ov_groups = 0;                          // (a repeated scan is one plain launch)
-        uint8_t *d_cnt = ctx->d_res;
-        int64_t *d_D0 = reinterpret_cast<int64_t *>(ctx->d_res + KGMA_RES_HDR);
-        uint8_t *d_aux = ctx->d_res + KGMA_RES_HDR + ctx->res_d0_slots * 8;
-        DevRecord *d_recs = reinterpret_cast<DevRecord *>(d_aux + KGMA_AUX_BYTES);
-        // (the previous scan's export_kernel normally left the counters at zero: no memset between steps)
-        if (!ctx->counters_clean) {
-            HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, KGMA_RES_HDR, ctx->stream));
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_done, 0, 16, ctx->stream));
-        }
-        ctx->counters_clean = false;
-        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        ctx->stats.n_launches = 0;
-        for (const Group &gr : groups) {
-            GroupParams gp;
-            memset(&gp, 0, sizeof gp);
-            ScanArgs a;
-            memset(&a, 0, sizeof a);
-            gp.n_kfv = (int32_t)gr.kfvs.size();
-            gp.k = k;
-            gp.nk = (int32_t)(gr.W - k + 1);                                  // largest window of the launch
-            gp.nk_min = (int32_t)(ctx->kfv[(size_t)gr.kfvs.front()].W - k + 1);
-            gp.nblocks = scan_nblocks(gp.nk);
-            gp.stream_slots = use_stream && !natural_slots ? stream_nw : 0;
-            gp.need_wide = group_need_wide(gr) ? 1 : 0;
-            if (const char *ds = getenv("KGMA_DEBUG_SKIP")) gp.debug_skip = atoi(ds);   // timing experiments only
-            for (size_t u = 0; u < gr.kfvs.size(); u++) {
-                const int j = gr.kfvs[u];
-                const KfvInfo &f = ctx->kfv[(size_t)j];
-                const int32_t nkj = (int32_t)(f.W - k + 1);
-                if (gp.n_sizes == 0 || gp.sizes[gp.n_sizes - 1] != nkj) gp.sizes[gp.n_sizes++] = nkj;   // ascending
-                gp.nk_of[u] = nkj;
-                gp.kfv_id[u] = j + 1;
-                gp.N[u] = (int32_t)f.N;
-                gp.T[u] = f.T;
-                gp.T_hi[u] = f.T_hi;
-                gp.sumS2[u] = f.sumS2;
-                gp.inv_scale[u] = 2.0 * (double)k * (double)f.N * (double)f.N;
-                if (u == 0) gp.s_fits_i16 = gp.s_fits_u8 = 1;
-                if (f.Smax > 32767) gp.s_fits_i16 = 0;
-                if (f.Smax > 255) gp.s_fits_u8 = 0;
-                a.dist[u] = want_dists ? ctx->d_dist[(size_t)j] : nullptr;
-            }
-            a.planes = g->d_planes;
-            a.inter = g->d_inter;
-            a.tiles = d_scan_tiles;
-            if (strobe) {
-                const KfvInfo &f = ctx->kfv[0];
-                StrobeParams sp;
-                memset(&sp, 0, sizeof sp);
-                sp.s = ctx->st_s; sp.w_min = ctx->st_wmin; sp.w_max = ctx->st_wmax;
-                sp.nk = (int32_t)(f.W - k);                            // the strobemers that slide; the window's permanent one comes on top
-                sp.N = (int32_t)f.N; sp.kfv_id = 1;
-                sp.n_slots = (int32_t)((int64_t)std::max(1, ctx->n_cus - ctx->reserved_cus) * stream_nw);
-                sp.T = f.T; sp.T_hi = f.T_hi; sp.sumS2 = f.sumS2; sp.inv_scale = gp.inv_scale[0];
-                sp.S = ctx->d_Stab;
-                for (int64_t v = 0; v < 128; v++)
-                    if (v % ctx->st_q == 0) sp.zero[v >> 5] |= 1u << (v & 31);
-                a.D0out = d_D0; a.recs = d_recs; a.rec_count = reinterpret_cast<unsigned int *>(d_cnt); a.rec_cap = ctx->rec_cap;
-                a.n_tiles = (int32_t)n_tiles; a.n_att = reinterpret_cast<unsigned long long *>(d_cnt + 8);
-                a.n_cold = reinterpret_cast<unsigned long long *>(d_cnt + 16);
-                HIP_TRY(ctx, launch_strobe(a, sp, ctx->stream));
-                ctx->stats.n_launches++;
-                continue;
-            }
-            if (generic_all) {
-                const int j = gr.kfvs[0];
-                const KfvInfo &f = ctx->kfv[(size_t)j];
-                const int64_t NBk = (int64_t)1 << (2 * k);
-                GenParams gg;
-                memset(&gg, 0, sizeof gg);
-                gg.k = k; gg.nk = gp.nk; gg.N = (int32_t)f.N; gg.kfv_id = j + 1; gg.fp = f.fp ? 1 : 0;
-                gg.n_slots = (int32_t)((int64_t)std::max(1, ctx->n_cus - ctx->reserved_cus) * stream_nw);
-                gg.T = f.T; gg.T_hi = f.T_hi; gg.sumS2 = f.sumS2;
-                gg.thr_lo = f.thr * (1.0 - std::ldexp(1.0, -ctx->band_log2)); gg.thr_hi = f.thr * (1.0 + std::ldexp(1.0, -ctx->band_log2));
-                gg.sumR2 = f.sumR2; gg.SF = 1.0 / (double)k; gg.inv_scale = gp.inv_scale[0];
-                gg.tie_rel = 9.313225746154785e-10;
-                if (f.sparse) {
-                    set_sparse_params(ctx, f, gg, f.fp);
-                } else {
-                    gg.S = ctx->d_Stab + (size_t)j * (size_t)NBk;
-                    gg.R = ctx->d_Rtab ? ctx->d_Rtab + (size_t)j * (size_t)NBk : nullptr;
-                    if (f.fp && !gg.R) return fail(ctx, KGMA_E_STATE, "internal: no Float64 table for KFV %d", j + 1);
-                }
-                generic_set_mode(gg, (int)(maxws - k + 1));           // (one geometry for every launch of the scan: its longest window decides)
-                if (getenv("KGMA_GEOM_DEBUG"))
-                    fprintf(stderr, "generic scan geometry: k %d, cmode %d, log2m %d, rebuild %d\n", k, gg.cmode, gg.hash_log2m, gg.hash_rebuild);
-                if (gg.cmode == 1 || gg.cmode == 4) {
-                    rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * generic_ctab_dwords(gg));
-                    if (rc) return rc;
-                    gg.ctab = ctx->d_gctab;
-                }
-                a.D0out = d_D0; a.recs = d_recs; a.rec_count = reinterpret_cast<unsigned int *>(d_cnt); a.rec_cap = ctx->rec_cap;
-                a.n_tiles = (int32_t)n_tiles; a.n_att = reinterpret_cast<unsigned long long *>(d_cnt + 8);
-                a.n_cold = reinterpret_cast<unsigned long long *>(d_cnt + 16);
-                HIP_TRY(ctx, launch_generic(a, gg, ctx->stream));
-                ctx->stats.n_launches++;
-                continue;
-            }
-            // all tables; the kernel indexes by KFV id.  The 16-bit stream kernel indexes k-mers as (hi bits << k) | lo bits,
-            // the bit-sliced kernel and the 8-bit stream kernel by the 2-bit interleaved code (first base least significant)
-            a.Stab = (use_stream && !group_s8(gr)) ? ctx->d_StabC : ctx->d_Stab;
-            a.Sinter = nullptr;
-            if (use_stream && group_s8(gr) && k >= 7) {
-                const int nv0 = stream8_variant((int)gr.kfvs.size());
-                const int nv = nv0 == 3 ? 4 : nv0;                     // row width in int16 slots (the kernel variant's)
-                rc = sinter_tables(ctx, gr.kfvs, nv, &a.Sinter, &a.Sbits);
-                if (rc) return rc;
-            }
-            if (use_stream && stream8_state_words(k, (int)gr.kfvs.size()) > 0) {
-                rc = dev_reserve(ctx, ctx->d_wstate, ctx->wstate_cap, n_tiles * stream8_state_words(k, (int)gr.kfvs.size()));
-                if (rc) return rc;
-                a.wave_state = ctx->d_wstate;
-            }
-            a.D0out = d_D0;                        // [KFV id - 1][tile]
-            a.recs = d_recs;
-            a.rec_count = reinterpret_cast<unsigned int *>(d_cnt);
-            a.rec_cap = ctx->rec_cap;
-            a.n_tiles = (int32_t)n_scan;
-            a.n_att = reinterpret_cast<unsigned long long *>(d_cnt + 8);
-            a.n_cold = reinterpret_cast<unsigned long long *>(d_cnt + 16);
-            a.tile0 = 0;
-            a.n_chunk_tiles = (int32_t)n_scan;
-            a.tile_windows = ctx->tile_windows;
-            // several KFVs, k <= 7: two kernels (match loop -> per-window differences; window pass with the S
-            // tables in LDS), in chunks of tiles so that the difference buffer stays bounded (kgma_pos.hip)
-            // (measured, 400 Mb: k=7 with 8 KFVs 10.5 vs 16.3 ms; at k <= 6 the bit-sliced kernel's own position
-            // phase, with one table at a time in LDS, is faster: 4.8 vs 7.5 ms at 5 KFVs.  KGMA_TWOKERNEL=1/0 forces)
-            bool two_kernels = !use_stream && gr.kfvs.size() >= 2 && k == KGMA_STREAM_MAX_K;
-            if (const char *tk = getenv("KGMA_TWOKERNEL")) two_kernels = !use_stream && gr.kfvs.size() >= 2 && k <= KGMA_STREAM_MAX_K && atoi(tk) != 0;
-            if (two_kernels) {
-                const int64_t P = ctx->tile_windows;
-                const int64_t per_tile = (int64_t)gp.n_sizes * P;                 // int16 elements
-                const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_tiles, (((int64_t)2 << 30) / 2) / per_tile));
-                rc = dev_reserve(ctx, ctx->d_diff, ctx->diff_cap, chunk * per_tile);
-                if (rc) return rc;
-                const int per_pass = std::max(1, pos_tables_per_pass(k));
-                for (int64_t t0 = 0; t0 < n_tiles; t0 += chunk) {
-                    a.tile0 = (int32_t)t0;
-                    a.n_chunk_tiles = (int32_t)std::min<int64_t>(chunk, n_tiles - t0);
-                    for (int z = 0; z < gp.n_sizes; z++) a.diff[z] = ctx->d_diff + (int64_t)z * chunk * P;
-                    a.Stab = ctx->d_Stab;
-                    HIP_TRY(ctx, launch_scan(a, gp, ctx->stream));
-                    ScanArgs b = a;
-                    b.Stab = ctx->d_StabC;
-                    for (int j0 = 0; j0 < gp.n_kfv; j0 += per_pass)
-                        HIP_TRY(ctx, launch_pos(b, gp, j0, std::min(per_pass, gp.n_kfv - j0), ctx->stream));
-                    ctx->stats.n_launches++;
-                }
-                continue;
-            }
-            if (overlap && g->repack_deferred) {
-                rc = launch_overlapped(ctx, g, a, gp, n_tiles);
-                if (rc) return rc;
-                ctx->stats.n_launches += ctx->ov_groups;
-                continue;
-            }
-            HIP_TRY(ctx, use_stream ? launch_stream(a, gp, ctx->stream) : launch_scan(a, gp, ctx->stream));
-            ctx->stats.n_launches++;
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        // last kernel: residues under tied minima are gathered on the device behind the scan (spares the host
-        // a second round trip for the Float64 tie replay; skipped when the caller wants pure exact arithmetic),
-        // then everything the host needs is written to the pinned mirror from inside the kernel (same layout:
-        // counters | D0 slots | aux | first INLINE_RECS records; records beyond the inline block need a copy
-        // afterwards, which only happens for dip-dense inputs) and the counters are reset: ONE synchronisation,
-        // no copy-engine launch, no memset before the next scan
-        (void)d_aux; (void)d_D0;
-        HIP_TRY(ctx, launch_export(ctx->d_res, ctx->h_pin_dev, ctx->res_d0_slots, n_scan * (int64_t)ctx->m, ctx->rec_cap,
-                                   (unsigned int)std::min<size_t>(INLINE_RECS, ctx->rec_cap), ((flags & KGMA_F_NO_TIE_RESOLVE) || strobe) ? 0 : 1,
-                                   d_scan_tiles, g->d_cd, g->d_ascii, ctx->d_Wtab, ctx->d_done, ctx->stream));
-        HIP_TRY(ctx, sync_spin(ctx->stream));
-        ctx->counters_clean = true;
-        if (g->pack_pending) {
-            float pms = 0;
-            if (ctx->ov_groups > 0) {
-                // (an overlapped step: the sums of the groups' kernel times -- the pack launches of all but the first group ran on
-                //  a few CUs beside the scan, so their times are long and mostly hidden)
-                for (int gi = 0; gi < ctx->ov_groups; gi++) { float t = 0; (void)hipEventElapsedTime(&t, ctx->ov_p0[gi], ctx->ov_p1[gi]); pms += t; }
-            } else (void)hipEventElapsedTime(&pms, ctx->evp0, ctx->evp1);
-            ctx->stats.pack_ms = pms;
-            g->pack_pending = false;
-        }
-        n_recs = *h_nrecs;
-        if (n_recs <= ctx->rec_cap) break;
-        if (attempt >= 4) return fail(ctx, KGMA_E_OVERFLOW, "record buffer overflow (%u records)", n_recs);
-        rc = res_reserve(n_tiles * ctx->m, (int64_t)n_recs + (n_recs >> 2) + 1024);
+void bind_results(ScanArgs &a, const kgma_ctx *ctx, int64_t n_streams)
+{
+    const ResultBlock d = device_results(ctx);
+    a.D0out = d.D0();                      // [KFV id - 1][tile]
+    a.recs = d.recs();
+    a.rec_count = d.n_recs();
+    a.rec_cap = ctx->rec_cap;
+    a.n_tiles = (int32_t)n_streams;
+    a.n_att = d.n_att();
+    a.n_cold = d.n_cold();
+}
+
+// the per-KFV part of a launch's parameters, shared by the scan and the chain kernel's launches (which add T / T_hi and
+// chain_invN / chain_form)
+void fill_group_params(const kgma_ctx *ctx, const std::vector<int> &kfvs, GroupParams &gp)
+{
+    const int k = ctx->k;
+    for (size_t u = 0; u < kfvs.size(); u++) {
+        const int j = kfvs[u];
+        const KfvInfo &f = ctx->kfv[(size_t)j];
+        const int32_t nkj = (int32_t)(f.W - k + 1);
+        if (gp.n_sizes == 0 || gp.sizes[gp.n_sizes - 1] != nkj) gp.sizes[gp.n_sizes++] = nkj;   // ascending
+        gp.nk_of[u] = nkj;
+        gp.kfv_id[u] = j + 1;                                   // (the kernel finds the S table and the first-window slot by it)
+        gp.N[u] = (int32_t)f.N;
+        gp.sumS2[u] = f.sumS2;
+        gp.inv_scale[u] = 2.0 * (double)k * (double)f.N * (double)f.N;
+        if (u == 0) gp.s_fits_i16 = gp.s_fits_u8 = 1;
+        if (f.Smax > 32767) gp.s_fits_i16 = 0;
+        if (f.Smax > 255) gp.s_fits_u8 = 0;
+    }
+}
+
+// the generic kernels' parameters for KFV j, shared by the scan and the chain: its table, the count mode of a window of nk_mode
+// k-mers and the global count table where that mode needs one (`what`: "scan" / "chain", for the debug line)
+int fill_gen_params(kgma_ctx *ctx, int j, int nk, int nk_mode, int32_t n_slots, bool fp, const char *what, GenParams &gg)
+{
+    const int k = ctx->k;
+    const KfvInfo &f = ctx->kfv[(size_t)j];
+    memset(&gg, 0, sizeof gg);
+    gg.k = k; gg.nk = nk; gg.N = (int32_t)f.N; gg.kfv_id = j + 1; gg.fp = fp ? 1 : 0;
+    gg.n_slots = n_slots;
+    gg.sumR2 = f.sumR2; gg.SF = 1.0 / (double)k;
+    if (f.sparse) {
+        set_sparse_params(ctx, f, gg, fp);
+    } else {
+        const int64_t NBk = (int64_t)1 << (2 * k);
+        gg.S = ctx->d_Stab + (size_t)j * (size_t)NBk;
+        gg.R = ctx->d_Rtab ? ctx->d_Rtab + (size_t)j * (size_t)NBk : nullptr;
+        if (fp && !gg.R) return fail(ctx, KGMA_E_STATE, "internal: no Float64 table for KFV %d", j + 1);
+    }
+    generic_set_mode(gg, nk_mode);
+    if (getenv("KGMA_GEOM_DEBUG"))
+        fprintf(stderr, "generic %s geometry: k %d, cmode %d, log2m %d, rebuild %d\n", what, k, gg.cmode, gg.hash_log2m, gg.hash_rebuild);
+    if (gg.cmode == 1 || gg.cmode == 4) {
+        const int rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * generic_ctab_dwords(gg));
+        if (rc) return rc;
+        gg.ctab = ctx->d_gctab;
+    }
+    return KGMA_OK;
+}
+
+int launch_group_strobe(kgma_ctx *ctx, const ScanPlan &p, const LaunchGroup &, const ScanTables &t, ScanArgs &a, const GroupParams &gp)
+{
+    const KfvInfo &f = ctx->kfv[0];
+    StrobeParams sp;
+    memset(&sp, 0, sizeof sp);
+    sp.s = ctx->st_s; sp.w_min = ctx->st_wmin; sp.w_max = ctx->st_wmax;
+    sp.nk = (int32_t)(f.W - p.k);                          // the strobemers that slide; the window's permanent one comes on top
+    sp.N = (int32_t)f.N; sp.kfv_id = 1;
+    sp.n_slots = (int32_t)((int64_t)std::max(1, ctx->n_cus - ctx->reserved_cus) * p.stream_nw);
+    sp.T = f.T; sp.T_hi = f.T_hi; sp.sumS2 = f.sumS2; sp.inv_scale = gp.inv_scale[0];
+    sp.S = ctx->d_Stab;
+    for (int64_t v = 0; v < 128; v++)
+        if (v % ctx->st_q == 0) sp.zero[v >> 5] |= 1u << (v & 31);
+    bind_results(a, ctx, t.n_tiles);                       // (never filtered)
+    HIP_TRY(ctx, launch_strobe(a, sp, ctx->stream));
+    ctx->stats.n_launches++;
+    return KGMA_OK;
+}
+
+int launch_group_generic(kgma_ctx *ctx, const ScanPlan &p, const LaunchGroup &L, const ScanTables &t, ScanArgs &a, const GroupParams &gp)
+{
+    const int j = L.gr.kfvs[0];
+    const KfvInfo &f = ctx->kfv[(size_t)j];
+    GenParams gg;
+    // (one geometry for every launch of the scan: its longest window decides)
+    const int rc = fill_gen_params(ctx, j, gp.nk, (int)(p.maxws - p.k + 1), (int32_t)((int64_t)std::max(1, ctx->n_cus - ctx->reserved_cus) * p.stream_nw),
+                                   f.fp, "scan", gg);
+    if (rc) return rc;
+    gg.T = f.T; gg.T_hi = f.T_hi; gg.sumS2 = f.sumS2;
+    gg.thr_lo = f.thr * (1.0 - std::ldexp(1.0, -ctx->band_log2)); gg.thr_hi = f.thr * (1.0 + std::ldexp(1.0, -ctx->band_log2));
+    gg.inv_scale = gp.inv_scale[0];
+    gg.tie_rel = 9.313225746154785e-10;
+    bind_results(a, ctx, t.n_tiles);                       // (never filtered)
+    HIP_TRY(ctx, launch_generic(a, gg, ctx->stream));
+    ctx->stats.n_launches++;
+    return KGMA_OK;
+}
+
+// several KFVs, k <= 7: two kernels (match loop -> per-window differences; window pass with the S
+// tables in LDS), in chunks of tiles so that the difference buffer stays bounded (kgma_pos.hip)
+int launch_group_two_kernel(kgma_ctx *ctx, const ScanPlan &p, const LaunchGroup &, const ScanTables &t, ScanArgs &a, const GroupParams &gp)
+{
+    const int64_t n_tiles = t.n_tiles;
+    const int64_t P = ctx->tile_windows;
+    const int64_t per_tile = (int64_t)gp.n_sizes * P;                 // int16 elements
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_tiles, (((int64_t)2 << 30) / 2) / per_tile));
+    const int rc = dev_reserve(ctx, ctx->d_diff, ctx->diff_cap, chunk * per_tile);
+    if (rc) return rc;
+    const int per_pass = std::max(1, pos_tables_per_pass(p.k));
+    for (int64_t t0 = 0; t0 < n_tiles; t0 += chunk) {
+        a.tile0 = (int32_t)t0;
+        a.n_chunk_tiles = (int32_t)std::min<int64_t>(chunk, n_tiles - t0);
+        for (int z = 0; z < gp.n_sizes; z++) a.diff[z] = ctx->d_diff + (int64_t)z * chunk * P;
+        a.Stab = ctx->d_Stab;
+        HIP_TRY(ctx, launch_scan(a, gp, ctx->stream));
+        ScanArgs b = a;
+        b.Stab = ctx->d_StabC;
+        for (int j0 = 0; j0 < gp.n_kfv; j0 += per_pass)
+            HIP_TRY(ctx, launch_pos(b, gp, j0, std::min(per_pass, gp.n_kfv - j0), ctx->stream));
+        ctx->stats.n_launches++;
+    }
+    return KGMA_OK;
+}
+
+// one launch of the stream kernel or the bit-sliced one -- or, with a pack left to this scan, the overlapped (pack, scan) pairs
+int launch_group_stream(kgma_ctx *ctx, kgma_genome *g, const ScanPlan &p, const LaunchGroup &, const ScanTables &t, ScanArgs &a, const GroupParams &gp)
+{
+    if (p.overlap && g->repack_deferred) {
+        const int rc = launch_overlapped(ctx, g, a, gp, t.n_tiles);
+        if (rc) return rc;
+        ctx->stats.n_launches += ctx->ov_groups;
+        return KGMA_OK;
+    }
+    HIP_TRY(ctx, p.use_stream ? launch_stream(a, gp, ctx->stream) : launch_scan(a, gp, ctx->stream));
+    ctx->stats.n_launches++;
+    return KGMA_OK;
+}
+
+// Step 4: the parameters of one launch group, and its launch by the kernel the plan chose
+int launch_group(kgma_ctx *ctx, kgma_genome *g, const ScanPlan &p, const LaunchGroup &L, const ScanTables &t)
+{
+    const int k = p.k, n_kfv = (int)L.gr.kfvs.size();
+    GroupParams gp;
+    memset(&gp, 0, sizeof gp);
+    ScanArgs a;
+    memset(&a, 0, sizeof a);
+    gp.n_kfv = n_kfv;
+    gp.k = k;
+    gp.nk = L.nk;                                                      // largest window of the launch
+    gp.nk_min = L.nk_min;
+    gp.nblocks = scan_nblocks(gp.nk);
+    gp.stream_slots = p.use_stream && !p.natural_slots ? p.stream_nw : 0;
+    gp.need_wide = L.need_wide ? 1 : 0;
+    gp.debug_skip = p.debug_skip;
+    fill_group_params(ctx, L.gr.kfvs, gp);
+    for (int u = 0; u < n_kfv; u++) {
+        const int j = L.gr.kfvs[(size_t)u];
+        gp.T[u] = ctx->kfv[(size_t)j].T;
+        gp.T_hi[u] = ctx->kfv[(size_t)j].T_hi;
+        a.dist[u] = p.want_dists ? ctx->d_dist[(size_t)j] : nullptr;
+    }
+    a.planes = g->d_planes;
+    a.inter = g->d_inter;
+    a.tiles = t.d_scan_tiles;
+    if (p.strobe) return launch_group_strobe(ctx, p, L, t, a, gp);
+    if (p.generic_all) return launch_group_generic(ctx, p, L, t, a, gp);
+    // all tables; the kernel indexes by KFV id.  The 16-bit stream kernel indexes k-mers as (hi bits << k) | lo bits,
+    // the bit-sliced kernel and the 8-bit stream kernel by the 2-bit interleaved code (first base least significant)
+    a.Stab = (p.use_stream && !L.s8) ? ctx->d_StabC : ctx->d_Stab;
+    a.Sinter = nullptr;
+    if (p.use_stream && L.s8 && k >= 7) {
+        const int nv0 = stream8_variant(n_kfv);
+        const int nv = nv0 == 3 ? 4 : nv0;                     // row width in int16 slots (the kernel variant's)
+        const int rc = sinter_tables(ctx, L.gr.kfvs, nv, &a.Sinter, &a.Sbits);
         if (rc) return rc;
     }
+    if (p.use_stream && stream8_state_words(k, n_kfv) > 0) {
+        const int rc = dev_reserve(ctx, ctx->d_wstate, ctx->wstate_cap, t.n_tiles * stream8_state_words(k, n_kfv));
+        if (rc) return rc;
+        a.wave_state = ctx->d_wstate;
+    }
+    bind_results(a, ctx, t.n_scan);
+    a.tile0 = 0;
+    a.n_chunk_tiles = (int32_t)t.n_scan;
+    a.tile_windows = ctx->tile_windows;
+    // (measured, 400 Mb: k=7 with 8 KFVs 10.5 vs 16.3 ms; at k <= 6 the bit-sliced kernel's own position
+    // phase, with one table at a time in LDS, is faster: 4.8 vs 7.5 ms at 5 KFVs.  KGMA_TWOKERNEL=1/0 forces)
+    bool two_kernels = !p.use_stream && n_kfv >= 2 && k == KGMA_STREAM_MAX_K;
+    if (p.twokernel >= 0) two_kernels = !p.use_stream && n_kfv >= 2 && k <= KGMA_STREAM_MAX_K && p.twokernel != 0;
+    if (two_kernels) return launch_group_two_kernel(ctx, p, L, t, a, gp);
+    return launch_group_stream(ctx, g, p, L, t, a, gp);
+}
+
+// the pack's time of a step whose pack this scan ran or waited for
+void note_pack_time(kgma_ctx *ctx, kgma_genome *g)
+{
+    if (!g->pack_pending) return;
+    float pms = 0;
+    if (ctx->ov_groups > 0) {
+        // (an overlapped step: the sums of the groups' kernel times -- the pack launches of all but the first group ran on
+        //  a few CUs beside the scan, so their times are long and mostly hidden)
+        for (int gi = 0; gi < ctx->ov_groups; gi++) { float t = 0; (void)hipEventElapsedTime(&t, ctx->ov_p0[gi], ctx->ov_p1[gi]); pms += t; }
+    } else (void)hipEventElapsedTime(&pms, ctx->evp0, ctx->evp1);
+    ctx->stats.pack_ms = pms;
+    g->pack_pending = false;
+}
+
+// Step 5: the scan's time from the events, the records from the mirror (and, beyond its inline block, from the device), the
+// streams' first distances on the host's lattice, and the dips stitched from the records
+int collect_results(kgma_ctx *ctx, kgma_genome *g, const ScanPlan &p, const ScanTables &t, unsigned int n_recs)
+{
+    const int k = p.k;
+    const int64_t nc = g->n_contigs, n_scan = t.n_scan;
+    const ResultBlock h = host_results(ctx);
     float ms = 0;
     // (a scan whose filter ran: from the filter's launch to the end of the exact kernel -- filter, read-back, table, exact launch)
     (void)hipEventElapsedTime(&ms, ctx->fstats.ran ? ctx->evf0 : ctx->ev0, ctx->ev1);
@@ -3365,48 +3442,146 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
         // wall time of the whole pack + scan region
         ctx->stats.overlap_ms = ms;
         ms = 0;
-        for (int gi = 0; gi < ctx->ov_groups; gi++) { float t = 0; (void)hipEventElapsedTime(&t, ctx->ov_s0[gi], ctx->ov_s1[gi]); ms += t; }
+        for (int gi = 0; gi < ctx->ov_groups; gi++) { float tg = 0; (void)hipEventElapsedTime(&tg, ctx->ov_s0[gi], ctx->ov_s1[gi]); ms += tg; }
         ctx->ov_groups = 0;
     }
     ctx->stats.scan_ms = ms;
-    rc = check_records();
+    int rc = check_records(ctx, g);
     if (rc) return rc;
 
     std::vector<DevRecord> recs((size_t)n_recs);
     const size_t n_inline = std::min<size_t>(n_recs, INLINE_RECS);
-    if (n_inline) memcpy(recs.data(), h_recs, n_inline * sizeof(DevRecord));
+    if (n_inline) memcpy(recs.data(), h.recs(), n_inline * sizeof(DevRecord));
     if (n_recs > n_inline)
-        HIP_TRY(ctx, hipMemcpy(recs.data() + n_inline,
-                               reinterpret_cast<DevRecord *>(ctx->d_res + KGMA_RES_HDR + ctx->res_d0_slots * 8 + KGMA_AUX_BYTES) + n_inline,
-                               ((size_t)n_recs - n_inline) * sizeof(DevRecord), hipMemcpyDeviceToHost));
-    ctx->D0.assign(h_D0, h_D0 + (size_t)n_scan * (size_t)ctx->m);
-    for (int j = 0; j < m_used; j++) {
+        HIP_TRY(ctx, hipMemcpy(recs.data() + n_inline, device_results(ctx).recs() + n_inline, ((size_t)n_recs - n_inline) * sizeof(DevRecord), hipMemcpyDeviceToHost));
+    ctx->D0.assign(h.D0(), h.D0() + (size_t)n_scan * (size_t)ctx->m);
+    for (int j = 0; j < p.m_used; j++) {
         // (Float64 KFV: the kernel wrote each stream's first distance as a double; the host works on the lattice)
         const KfvInfo &kf = ctx->kfv[(size_t)j];
         if (!kf.fp) continue;
-        for (int64_t t = 0; t < n_scan; t++) {
+        for (int64_t s = 0; s < n_scan; s++) {
             double dv;
-            memcpy(&dv, &ctx->D0[(size_t)j * (size_t)n_scan + (size_t)t], sizeof dv);
-            ctx->D0[(size_t)j * (size_t)n_scan + (size_t)t] = lattice_of(kf, k, dv);
+            memcpy(&dv, &ctx->D0[(size_t)j * (size_t)n_scan + (size_t)s], sizeof dv);
+            ctx->D0[(size_t)j * (size_t)n_scan + (size_t)s] = lattice_of(kf, k, dv);
         }
     }
     ctx->firstD.assign((size_t)ctx->m * (size_t)nc, -1);
     for (int j = 0; j < ctx->m; j++)
         for (int64_t c = 0; c < nc; c++) {
-            const int64_t tb = filtered ? ctx->fcontig_tile_base[(size_t)c] : ctx->contig_tile_base[(size_t)c];   // (the record's first stream starts at its first window)
+            const int64_t tb = t.filtered ? ctx->fcontig_tile_base[(size_t)c] : ctx->contig_tile_base[(size_t)c];   // (the record's first stream starts at its first window)
             if (tb >= 0) ctx->firstD[(size_t)j * (size_t)nc + (size_t)c] = ctx->D0[(size_t)j * (size_t)n_scan + (size_t)tb];
         }
-    ctx->stats.n_at_threshold = (int64_t)*h_natt;
-    if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "scan cold steps: %llu\n", *h_ncold);
-    ctx->aux_host = h_aux;
-    ctx->aux_used = *reinterpret_cast<const unsigned int *>(ctx->h_pin + 4);
-    ctx->have_dists = want_dists;
-    ctx->scan_filtered = filtered;
+    ctx->stats.n_at_threshold = (int64_t)*h.n_att();
+    if (p.geom_debug) fprintf(stderr, "scan cold steps: %llu\n", *h.n_cold());
+    ctx->aux_host = h.aux();
+    ctx->aux_used = *h.aux_used();
+    ctx->have_dists = p.want_dists;
+    ctx->scan_filtered = t.filtered;
     rc = stitch_dips(ctx, recs);
     if (rc) return rc;
-    ctx->last_mode = mode;
+    ctx->last_mode = p.mode;
     ctx->stats.device_bytes = ctx->device_bytes + g->device_bytes;
     return KGMA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_t flags)
+{
+    if (!ctx || !gc) return KGMA_E_ARG;
+    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping is updated
+    if (ctx->m == 0) return fail(ctx, KGMA_E_STATE, "kgma_set_refs has not been called");
+    if (mode != KGMA_MODE_SINGLE && mode != KGMA_MODE_OMN && mode != KGMA_MODE_STROBE) return fail(ctx, KGMA_E_ARG, "unknown mode %d", mode);
+    if ((mode == KGMA_MODE_STROBE) != ctx->strobe)
+        return fail(ctx, KGMA_E_STATE, mode == KGMA_MODE_STROBE ? "a strobemer scan needs strobemer references (kgma_set_strobe_ref)"
+                                                                : "the context holds strobemer references: a k-mer scan needs kgma_set_refs");
+    (void)hipSetDevice(ctx->device);
+    ScanPlan plan;
+    int rc = plan_scan(ctx, g, mode, flags, plan);
+    if (rc) return rc;
+    memcpy(ctx->kernel_name, plan.kernel_name, sizeof ctx->kernel_name);
+
+    ctx->dips.clear();
+    ctx->hits.clear();
+    ctx->have_dists = false;
+    ctx->last_mode = -1;
+    ctx->scan_filtered = false;
+    memset(&ctx->fstats, 0, sizeof ctx->fstats);
+    ctx->fentries.clear();
+    if (plan.planes_needed) {
+        rc = ensure_planes(ctx, g);
+        if (rc != KGMA_OK) return rc;
+    }
+
+    const bool tiles_cached = stream_table_cached(ctx, g, plan);
+    if (!tiles_cached) build_stream_table(ctx, g, plan);
+    const int64_t n_tiles = (int64_t)ctx->tiles.size();
+    if (n_tiles > 0x7FFFFFF0ll) return fail(ctx, KGMA_E_UNSUPPORTED, "too many tiles");
+    ctx->stats.bases_scanned = ctx->tk_bases;
+    ctx->stats.windows_scanned = ctx->tk_windows;
+    ctx->stats.n_tiles = (int32_t)n_tiles;
+    ctx->stats.n_launches = 0;
+    ctx->stats.scan_ms = 0;
+    ctx->stats.n_at_threshold = 0;
+    ctx->stats.n_dips = ctx->stats.n_hits = ctx->stats.n_tie_flagged = 0;
+    if (n_tiles == 0) return scan_without_windows(ctx, g, plan);
+
+    rc = reserve_results(ctx, plan, n_tiles);
+    if (rc) return rc;
+    if (!tiles_cached) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tiles, ctx->tiles.data(), (size_t)n_tiles * sizeof(TileDesc), hipMemcpyHostToDevice, ctx->stream));
+        // the vector is pageable memory: the runtime stages it before returning, so it may be reused
+        ctx->tk_uid = g->uid; ctx->tk_mode = mode; ctx->tk_maxws = plan.maxws; ctx->tk_k = plan.k; ctx->tk_version = plan.geom_version;
+    }
+
+    // ---- distance-bound prefilter: one integer KFV on the 8-bit count-table kernel at k = 5, 6, no distance output -- the exact
+    //      kernel then walks the candidate stream table instead of the regular one (filter_candidate_table)
+    ScanTables t;
+    if (filter_wanted(ctx, plan, plan.overlap)) {
+        rc = filter_candidate_table(ctx, g, (int)(ctx->kfv[0].W - plan.k + 1), n_tiles, &t.filtered);
+        if (rc) return rc;
+    }
+    t.n_tiles = n_tiles;
+    t.n_scan = t.filtered ? (int64_t)ctx->ftiles.size() : n_tiles;
+    t.d_scan_tiles = t.filtered ? ctx->d_ftiles : ctx->d_tiles;
+
+    unsigned int n_recs = 0;
+    for (int attempt = 0;; attempt++) {
+        if (attempt > 0) ctx->ov_groups = 0;                          // (a repeated scan is one plain launch)
+        // (the previous scan's export_kernel normally left the counters at zero: no memset between steps)
+        if (!ctx->counters_clean) {
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_res, 0, KGMA_RES_HDR, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_done, 0, 16, ctx->stream));
+        }
+        ctx->counters_clean = false;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        ctx->stats.n_launches = 0;
+        for (const LaunchGroup &L : plan.groups) {
+            rc = launch_group(ctx, g, plan, L, t);
+            if (rc) return rc;
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        // last kernel: residues under tied minima are gathered on the device behind the scan (spares the host
+        // a second round trip for the Float64 tie replay; skipped when the caller wants pure exact arithmetic),
+        // then everything the host needs is written to the pinned mirror from inside the kernel (same layout:
+        // counters | D0 slots | aux | first INLINE_RECS records; records beyond the inline block need a copy
+        // afterwards, which only happens for dip-dense inputs) and the counters are reset: ONE synchronisation,
+        // no copy-engine launch, no memset before the next scan
+        HIP_TRY(ctx, launch_export(ctx->d_res, ctx->h_pin_dev, ctx->res_d0_slots, t.n_scan * (int64_t)ctx->m, ctx->rec_cap,
+                                   (unsigned int)std::min<size_t>(INLINE_RECS, ctx->rec_cap), ((flags & KGMA_F_NO_TIE_RESOLVE) || plan.strobe) ? 0 : 1,
+                                   t.d_scan_tiles, g->d_cd, g->d_ascii, ctx->d_Wtab, ctx->d_done, ctx->stream));
+        HIP_TRY(ctx, sync_spin(ctx->stream));
+        ctx->counters_clean = true;
+        note_pack_time(ctx, g);
+        n_recs = *host_results(ctx).n_recs();
+        if (n_recs <= ctx->rec_cap) break;
+        if (attempt >= 4) return fail(ctx, KGMA_E_OVERFLOW, "record buffer overflow (%u records)", n_recs);
+        rc = res_reserve(ctx, n_tiles * ctx->m, (int64_t)n_recs + (n_recs >> 2) + 1024);
+        if (rc) return rc;
+    }
+    return collect_results(ctx, g, plan, t, n_recs);
 }
 
 }  // extern "C"
@@ -4161,16 +4336,13 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
             memset(&a, 0, sizeof a);
             gp.n_kfv = nslots; gp.k = k;
             gp.nk = gp.nk_min = (int32_t)(ctx->kfv[(size_t)L.kfvs[0]].W - k + 1);
+            gp.need_wide = ctx->kfv[(size_t)L.kfvs[0]].fits32 ? 0 : 1;
+            fill_group_params(ctx, L.kfvs, gp);
+            // (a launch's KFVs have one window size and one S width; the chain kernels do not look at s_fits_u8)
             gp.n_sizes = 1; gp.sizes[0] = gp.nk;
             gp.s_fits_i16 = L.s16 ? 1 : 0;
-            gp.need_wide = ctx->kfv[(size_t)L.kfvs[0]].fits32 ? 0 : 1;
             for (int u = 0; u < nslots; u++) {
                 const KfvInfo &f = ctx->kfv[(size_t)L.kfvs[(size_t)u]];
-                gp.nk_of[u] = gp.nk;
-                gp.kfv_id[u] = L.kfvs[(size_t)u] + 1;               // (the kernel finds the S table and the first-window slot by it)
-                gp.N[u] = (int32_t)f.N;
-                gp.sumS2[u] = f.sumS2;
-                gp.inv_scale[u] = 2.0 * (double)k * (double)f.N * (double)f.N;
                 gp.chain_invN[u] = 1.0 / (double)f.N;
                 gp.chain_form[u] = f.ref_form;
             }
@@ -4204,23 +4376,9 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
             a.chain.guard_abs = 9.313225746154785e-10;              // 2^-30 of the stream's first distance
             a.chain.status = ctx->d_cctl + 1;
             if (generic) {
-                const int j = L.kfvs[0];
-                const KfvInfo &f = ctx->kfv[(size_t)j];
-                GenParams gg;
-                memset(&gg, 0, sizeof gg);
-                gg.k = k; gg.nk = gp.nk; gg.N = (int32_t)f.N; gg.kfv_id = j + 1; gg.fp = 1;
-                gg.n_slots = (int32_t)((int64_t)std::max(1, ctx->n_cus) * generic_chain_slots_per_cu(k, gp.nk));
-                gg.sumR2 = f.sumR2; gg.SF = 1.0 / (double)k;
-                if (f.sparse) set_sparse_params(ctx, f, gg, true);
-                else gg.R = ctx->d_Rtab + (size_t)j * (size_t)((int64_t)1 << (2 * k));
-                generic_set_mode(gg, gp.nk);
-                if (getenv("KGMA_GEOM_DEBUG"))
-                    fprintf(stderr, "generic chain geometry: k %d, cmode %d, log2m %d, rebuild %d\n", k, gg.cmode, gg.hash_log2m, gg.hash_rebuild);
-                if (gg.cmode == 1 || gg.cmode == 4) {
-                    rc = dev_reserve(ctx, ctx->d_gctab, ctx->gctab_cap, (int64_t)gg.n_slots * generic_ctab_dwords(gg));
-                    if (rc) return rc;
-                    gg.ctab = ctx->d_gctab;
-                }
+                GenParams gg;                                       // (the chain walks the Float64 table whatever the KFV's form)
+                rc = fill_gen_params(ctx, L.kfvs[0], gp.nk, gp.nk, (int32_t)((int64_t)std::max(1, ctx->n_cus) * generic_chain_slots_per_cu(k, gp.nk)), true, "chain", gg);
+                if (rc) return rc;
                 HIP_TRY(ctx, launch_generic_chain(a, gg, ctx->stream));
                 continue;
             }
