@@ -620,6 +620,52 @@ int kgma_motif_match(kgma_ctx *ctx, const kgma_genome *g, const uint8_t *motifs,
                      int32_t n_motifs, const int32_t *max_mismatch /* n_motifs */);
 int kgma_get_motif_matches(kgma_ctx *ctx, kgma_motif_hit *out, int64_t cap, int64_t *n);
 
+/* Threshold calibration: the working form of src/DistanceTesting.jl on the device (kernels: kgma_calib.hip).  Both calls need
+ * the references of kgma_set_refs (KGMA_E_STATE before it, or after kgma_set_strobe_ref), serve 1 <= k <= 10 (references at
+ * k >= 11 are kept sparse: KGMA_E_UNSUPPORTED) and leave the references, the thresholds and the results of the last scan,
+ * kgma_exact_match and kgma_motif_match untouched; of kgma_stats they set only scan_ms (hipEvents around the launch) and
+ * n_launches.  kgma_scan_kernel_name afterwards names the form that ran: "calib_kernel<window|mutation,lds|global,int|f64>" --
+ * counters in LDS for k <= 7, in a per-workgroup global table (left all-zero) for k = 8 ... 10; integer or Float64 form.
+ *
+ * kgma_window_dists: the distance of n arbitrary windows of a resident genome to KFV `kfv` (1-based).  Window i is the W
+ * residues start[i] .. start[i] + W - 1 (1-based) of record contig[i] (0-based), W the window size kgma_set_refs was given for
+ * that KFV; it holds W - k + 1 k-mers.  Residues go through the reference's code table (A0 C1 G2 T3, N -> 3, either case) as in
+ * every scan; the definition does not depend on the engine.  The list may be unsorted, hold duplicates, or be empty.  A genome
+ * made by kgma_genome_revcomp is used in its own coordinates.
+ *   S/N KFV:      D_out[i] = sum_x (S[x] - N c[x])^2 exactly (the quantity kgma_hit.D holds), formed from the window's k-mer
+ *                 positions alone, D = sumS2 - 2 N sum_j S[x_j] + N^2 sum_j c[x_j]: the work is proportional to W, not to 4^k.
+ *                 dist_out[i] = (double)D / scale, scale as kgma_kfv_scale returns it: the bits the scans report as `dist`
+ *                 without chain replay.
+ *   Float64 KFV:  dist_out[i] = (1 / 2k) sum_x (ref[x] - c[x])^2 by a dense pass in one fixed order -- lane t of 256 sums the
+ *                 bins t, t + 256, ... of the device index order (first base least significant) in increasing order, a wave's
+ *                 64 lanes are combined by a shuffle tree (distances 32 ... 1), the four waves in order, times RN(1 / 2k);
+ *                 within (4^k + 4) 2^-53 (relative) of the exact value.  D_out[i] = llround(dist * scale).
+ * Either output may be NULL.  KGMA_E_ARG: kfv or a contig out of range, or a window that does not lie inside its record
+ * (kgma_last_error names the index).  KGMA_E_BADBASE: a residue outside A/C/G/T/N INSIDE a requested window (kgma_last_error
+ * names record and position; the outputs are then unspecified); such a residue elsewhere in the genome is no error.
+ *
+ * kgma_mutation_dists: for every (sequence i, rate r, trial t) the distance of the whole mutated sequence to the KFV,
+ * kmer_dist(mutate_seq(seq_i, rates[r]), KFV, k) -- the inner step of gen_sub_vs_ref (src/DistanceTesting.jl:69-84) -- in the
+ * forms and with the scale above; results at [(i * n_rates + r) * n_trials + t].  Sequence i is seqs[offsets[i] ..
+ * offsets[i + 1]); its own length decides the number of k-mers (shorter than k: nothing is counted, D = sumS2).  The mutated
+ * copy is never materialised: each lane forms the codes it needs.  The mutation is a counter-based hash, so that the host
+ * reproduces any single trial exactly (it cannot reproduce Julia's RNG: results agree with the reference statistically):
+ *   mix64(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+ *   G = 0x9E3779B97F4A7C15;  K = mix64(mix64(mix64(seed + G (i + 1)) + G (r + 1)) + G (t + 1))          (all mod 2^64)
+ *   residue j (0-based): z = mix64(K + G (j + 1)); substituted iff (z >> 11) < floor(rate * 2^53) -- a rate of 0 never
+ *   substitutes, a rate of 1 always does; the new base is MUT[b][((z & 0x7FF) * 3) >> 11] with MUT in the order of
+ *   mutation_dict (:38-42): A -> C G T, C -> A G T, G -> C A T, T -> C G A.  r enters the key: the same rate at another index of
+ *   `rates` draws other substitutions.  A result does not depend on the sequences, rates or trials that follow it.
+ * KGMA_E_ARG: a rate outside [0, 1] or not finite, n_rates < 1, n_trials < 1.  KGMA_E_BADBASE: a residue outside A/C/G/T in
+ * either case, N included (mutation_dict has no other key); kgma_last_error names sequence and position.  KGMA_E_UNSUPPORTED:
+ * a sequence whose sumS2 + N^2 n^2 leaves 61 bits, or more than 2^28 distances in one call. */
+int kgma_window_dists(kgma_ctx *ctx, const kgma_genome *g, int32_t kfv /* 1-based */, int64_t n,
+                      const int32_t *contig /* 0-based */, const int64_t *start /* 1-based */,
+                      int64_t *D_out /* n, may be NULL */, double *dist_out /* n, may be NULL */);
+int kgma_mutation_dists(kgma_ctx *ctx, int32_t kfv, const uint8_t *seqs, const int64_t *offsets /* n_seqs + 1 */,
+                        int64_t n_seqs, const double *rates, int32_t n_rates, int32_t n_trials, uint64_t seed,
+                        int64_t *D_out, double *dist_out /* [n_seqs][n_rates][n_trials], either may be NULL */);
+
 /* kgma_repack_scan_hits in two halves, for step loops that have other work to queue while the GPU scans
  * (bench.py with several ranks: the hit exchange of step i overlaps the scan of step i+1).  kgma_step_begin
  * hands the step to a helper thread owned by the context and returns at once; kgma_step_end waits for it

@@ -389,6 +389,15 @@ struct kgma_ctx {
     MotifHit *d_mout = nullptr; int64_t mout_cap = 0;
     unsigned long long *d_mctl = nullptr; int64_t mctl_cap = 0;
     std::vector<kgma_motif_hit> motif_hits;
+    // calibration (kgma_window_dists / kgma_mutation_dists; kgma_calib.hip): device buffers kept between calls.  d_cbtab is the
+    // k >= 8 kernels' counter table, zeroed when allocated and left all-zero by every launch
+    int64_t *d_cboff = nullptr; int64_t cboff_cap = 0;
+    int64_t *d_cbD = nullptr; int64_t cbD_cap = 0;
+    double *d_cbdist = nullptr; int64_t cbdist_cap = 0;
+    uint32_t *d_cbtab = nullptr; int64_t cbtab_cap = 0;
+    uint8_t *d_cbtext = nullptr; int64_t cbtext_cap = 0;
+    uint64_t *d_cbP = nullptr; int64_t cbP_cap = 0;
+    unsigned long long *d_cbbad = nullptr; int64_t cbbad_cap = 0;
     // reverse complement (kgma_genome_revcomp): the tile table of the last call, on the device and as uploaded
     int64_t *d_rcprefix = nullptr; int64_t rcprefix_cap = 0;
     std::vector<int64_t> rcprefix;
@@ -828,6 +837,9 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_mout) (void)hipFree(ctx->d_mout);
     if (ctx->d_mctl) (void)hipFree(ctx->d_mctl);
     if (ctx->d_rcprefix) (void)hipFree(ctx->d_rcprefix);
+    for (void *q : {(void *)ctx->d_cboff, (void *)ctx->d_cbD, (void *)ctx->d_cbdist, (void *)ctx->d_cbtab, (void *)ctx->d_cbtext,
+                    (void *)ctx->d_cbP, (void *)ctx->d_cbbad})
+        if (q) (void)hipFree(q);
     if (ctx->evp0) (void)hipEventDestroy(ctx->evp0);
     if (ctx->evp1) (void)hipEventDestroy(ctx->evp1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -5797,6 +5809,171 @@ int kgma_get_matches(kgma_ctx *ctx, kgma_match *out, int64_t cap, int64_t *n)
     if (!out) return KGMA_OK;
     if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_matches: capacity %lld < %lld", (long long)cap, (long long)*n);
     if (*n) memcpy(out, ctx->matches.data(), (size_t)*n * sizeof(kgma_match));
+    return KGMA_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// threshold calibration: distances of chosen windows of a genome and of mutated copies of sequences (the working form of
+// src/DistanceTesting.jl; kernels: kgma_calib.hip)
+// ------------------------------------------------------------------------------------------
+constexpr int64_t CALIB_TAB_DWORDS = (int64_t)1 << 24;   // calib_grid(k, ...) x 4^k counters at k = 8, 9, 10: 64 MiB
+
+// The checks both entry points make of the context and the KFV; *fo: the KFV.
+static int calib_kfv(kgma_ctx *ctx, const char *what, int32_t kfv, const KfvInfo **fo)
+{
+    if (ctx->strobe) return fail(ctx, KGMA_E_STATE, "%s: the context holds a strobemer reference (kgma_set_strobe_ref); call kgma_set_refs first", what);
+    if (ctx->m < 1) return fail(ctx, KGMA_E_STATE, "%s: no references (call kgma_set_refs first)", what);
+    if (kfv < 1 || kfv > ctx->m) return fail(ctx, KGMA_E_ARG, "%s: no such KFV: %d (1 ... %d)", what, kfv, ctx->m);
+    if (ctx->k > 10) return fail(ctx, KGMA_E_UNSUPPORTED, "%s: k = %d: references at k >= 11 are kept sparse; this call serves 1 <= k <= 10", what, ctx->k);
+    *fo = &ctx->kfv[(size_t)(kfv - 1)];
+    return KGMA_OK;
+}
+
+// What both share behind their checks: the KFV's tables, the counter table, one launch between the context's events, the
+// download.  a: text, item_off, n_items (> 0) and the source's own fields are set.  *bad: first_bad as the kernel left it.
+static int calib_launch(kgma_ctx *ctx, const char *what, int source, CalibArgs &a, const KfvInfo &f, int32_t kfv, int64_t *D_out,
+                        double *dist_out, unsigned long long *bad)
+{
+    const int k = ctx->k;
+    const int64_t NB = (int64_t)1 << (2 * k), n = a.n_items;
+    int rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbD, ctx->cbD_cap, n))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbdist, ctx->cbdist_cap, n))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbbad, ctx->cbbad_cap, 1))) return rc;
+    if (k > 7 && !ctx->d_cbtab) {
+        if ((rc = dev_reserve(ctx, ctx->d_cbtab, ctx->cbtab_cap, CALIB_TAB_DWORDS))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_cbtab, 0, (size_t)CALIB_TAB_DWORDS * 4, ctx->stream));
+    }
+    const int grid = calib_grid(k, n, ctx->n_cus);
+    if (k > 7 && (int64_t)grid * NB > CALIB_TAB_DWORDS) return fail(ctx, KGMA_E_STATE, "%s: internal error: counter table too small", what);
+    a.k = k; a.fp = f.fp ? 1 : 0;
+    a.S = ctx->d_Stab + (size_t)(kfv - 1) * (size_t)NB;
+    a.R = ctx->d_Rtab + (size_t)(kfv - 1) * (size_t)NB;
+    a.N = f.N; a.sumS2 = f.sumS2;
+    a.scale = 2.0 * (double)k * (double)f.N * (double)f.N;
+    a.half_inv_k = 1.0 / (double)(2 * k);
+    a.scratch = ctx->d_cbtab; a.D_out = ctx->d_cbD; a.dist_out = ctx->d_cbdist; a.first_bad = ctx->d_cbbad;
+    *bad = NO_BAD;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cbbad, bad, 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(ctx, launch_calib(a, source, grid, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(bad, ctx->d_cbbad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (dist_out) HIP_TRY(ctx, hipMemcpyAsync(dist_out, ctx->d_cbdist, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (D_out && !f.fp) HIP_TRY(ctx, hipMemcpyAsync(D_out, ctx->d_cbD, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double> tmp;
+    if (D_out && f.fp && !dist_out) {
+        tmp.resize((size_t)n);
+        HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), ctx->d_cbdist, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    ctx->stats.scan_ms = ms;
+    ctx->stats.n_launches = 1;
+    snprintf(ctx->kernel_name, sizeof ctx->kernel_name, "calib_kernel<%s,%s,%s>", source == 0 ? "window" : "mutation",
+             k <= 7 ? "lds" : "global", f.fp ? "f64" : "int");
+    if (D_out && f.fp && *bad == NO_BAD) {
+        // the header's D of a Float64 KFV: the distance on the host's integer lattice (lattice_of)
+        const double *d = dist_out ? dist_out : tmp.data();
+        for (int64_t i = 0; i < n; i++) D_out[i] = (int64_t)std::llround(d[i] * a.scale);
+    }
+    return KGMA_OK;
+}
+
+int kgma_window_dists(kgma_ctx *ctx, const kgma_genome *g, int32_t kfv, int64_t n, const int32_t *contig, const int64_t *start,
+                      int64_t *D_out, double *dist_out)
+{
+    if (!ctx || !g) return KGMA_E_ARG;
+    const KfvInfo *fp_ = nullptr;
+    int rc = calib_kfv(ctx, "kgma_window_dists", kfv, &fp_);
+    if (rc) return rc;
+    const KfvInfo &f = *fp_;
+    if (n < 0 || (n > 0 && (!contig || !start))) return fail(ctx, KGMA_E_ARG, "kgma_window_dists: null argument or n < 0");
+    std::vector<int64_t> off((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t c = contig[i];
+        if (c < 0 || c >= g->n_contigs) return fail(ctx, KGMA_E_ARG, "kgma_window_dists: window %lld: no record %lld", (long long)i, (long long)c);
+        const ContigDesc &d = g->cd[(size_t)c];
+        if (start[i] < 1 || start[i] > d.len - f.W + 1)
+            return fail(ctx, KGMA_E_ARG, "kgma_window_dists: window %lld: residues %lld .. %lld do not lie inside record %lld of %lld residues",
+                        (long long)i, (long long)start[i], (long long)(start[i] + f.W - 1), (long long)c, (long long)d.len);
+        off[(size_t)i] = d.ascii_off + (start[i] - 1);
+    }
+    ctx->stats.scan_ms = 0;
+    ctx->stats.n_launches = 0;
+    if (n == 0) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    if ((rc = dev_reserve(ctx, ctx->d_cboff, ctx->cboff_cap, n))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cboff, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    CalibArgs a;
+    memset(&a, 0, sizeof a);
+    a.text = g->d_ascii; a.item_off = ctx->d_cboff; a.n_items = n; a.W = f.W;
+    unsigned long long bad = NO_BAD;
+    if ((rc = calib_launch(ctx, "kgma_window_dists", 0, a, f, kfv, D_out, dist_out, &bad))) return rc;
+    if (bad != NO_BAD) {
+        // the smallest byte offset of a bad residue inside a requested window: its record is the last one that starts at or before it
+        int64_t c = 0;
+        for (int64_t r = 0; r < g->n_contigs; r++)
+            if (g->cd[(size_t)r].len > 0 && g->cd[(size_t)r].ascii_off <= (int64_t)bad &&
+                (int64_t)bad < g->cd[(size_t)r].ascii_off + g->cd[(size_t)r].len) c = r;
+        return fail(ctx, KGMA_E_BADBASE, "record %lld position %lld: residue is not one of A/C/G/T/N (KeyError, Consts.jl:22-28)", (long long)c,
+                    (long long)((int64_t)bad - g->cd[(size_t)c].ascii_off + 1));
+    }
+    return KGMA_OK;
+}
+
+int kgma_mutation_dists(kgma_ctx *ctx, int32_t kfv, const uint8_t *seqs, const int64_t *offsets, int64_t n_seqs, const double *rates,
+                        int32_t n_rates, int32_t n_trials, uint64_t seed, int64_t *D_out, double *dist_out)
+{
+    if (!ctx) return KGMA_E_ARG;
+    const KfvInfo *fp_ = nullptr;
+    int rc = calib_kfv(ctx, "kgma_mutation_dists", kfv, &fp_);
+    if (rc) return rc;
+    const KfvInfo &f = *fp_;
+    if (n_seqs < 0 || !offsets || !rates) return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: null argument or n_seqs < 0");
+    if (n_rates < 1 || n_trials < 1) return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: n_rates = %d, n_trials = %d (both at least 1)", n_rates, n_trials);
+    std::vector<uint64_t> P((size_t)n_rates);
+    for (int32_t r = 0; r < n_rates; r++) {
+        if (!std::isfinite(rates[r]) || rates[r] < 0.0 || rates[r] > 1.0)
+            return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: rates[%d] = %g is not in [0, 1]", r, rates[r]);
+        P[(size_t)r] = (uint64_t)std::floor(std::ldexp(rates[r], 53));
+    }
+    for (int64_t i = 0; i < n_seqs; i++) {
+        if (offsets[i + 1] < offsets[i]) return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: offsets[%lld] > offsets[%lld]", (long long)i, (long long)(i + 1));
+        const int64_t nk = std::max<int64_t>(offsets[i + 1] - offsets[i] - ctx->k + 1, 0);
+        if (!f.fp && (__int128)f.sumS2 + (__int128)f.N * f.N * nk * (__int128)nk >= ((__int128)1 << 61))
+            return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_mutation_dists: sequence %lld: N = %lld with %lld k-mers exceeds the int64 range of the device path",
+                        (long long)i, (long long)f.N, (long long)nk);
+        if (f.fp && nk > ((int64_t)1 << 31)) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_mutation_dists: sequence %lld: %lld k-mers exceed the 32-bit counters", (long long)i, (long long)nk);
+    }
+    const __int128 n_items128 = (__int128)n_seqs * n_rates * n_trials;
+    if (n_items128 > ((__int128)1 << 28)) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_mutation_dists: %lld x %d x %d distances in one call", (long long)n_seqs, n_rates, n_trials);
+    ctx->stats.scan_ms = 0;
+    ctx->stats.n_launches = 0;
+    if (n_seqs == 0) return KGMA_OK;
+    const int64_t base = offsets[0], bytes = offsets[n_seqs] - base;
+    if (bytes > 0 && !seqs) return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: null argument");
+    std::vector<int64_t> off((size_t)n_seqs + 1);
+    for (int64_t i = 0; i <= n_seqs; i++) off[(size_t)i] = offsets[i] - base;
+    (void)hipSetDevice(ctx->device);
+    if ((rc = dev_reserve(ctx, ctx->d_cboff, ctx->cboff_cap, n_seqs + 1))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbtext, ctx->cbtext_cap, bytes))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbP, ctx->cbP_cap, n_rates))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cboff, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cbtext, seqs + base, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cbP, P.data(), P.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    CalibArgs a;
+    memset(&a, 0, sizeof a);
+    a.text = ctx->d_cbtext; a.item_off = ctx->d_cboff; a.n_items = (int64_t)n_items128;
+    a.n_rates = n_rates; a.n_trials = n_trials; a.seed = seed; a.P = ctx->d_cbP;
+    unsigned long long bad = NO_BAD;
+    if ((rc = calib_launch(ctx, "kgma_mutation_dists", 1, a, f, kfv, D_out, dist_out, &bad))) return rc;
+    if (bad != NO_BAD) {
+        const int64_t si = (int64_t)(std::upper_bound(off.begin(), off.end(), (int64_t)bad) - off.begin()) - 1;
+        return fail(ctx, KGMA_E_BADBASE, "sequence %lld position %lld: residue is not one of A/C/G/T (mutation_dict has no other key, DistanceTesting.jl:38-42)",
+                    (long long)si, (long long)((int64_t)bad - off[(size_t)si] + 1));
+    }
     return KGMA_OK;
 }
 

@@ -383,4 +383,31 @@ struct TwobitArgs {
     int32_t pad;
 };
 
+// Distances of chosen windows / of mutated copies (kgma_calib.hip; kgma_window_dists, kgma_mutation_dists).  An item is a run
+// of residues of `text`: window source -- item i is the W residues at text + item_off[i]; mutation source -- item
+// (i * n_rates + r) * n_trials + t is sequence i, text + item_off[i] .. item_off[i + 1], under the trial key of (i, r, t).
+struct CalibArgs {
+    const uint8_t *text;          // the genome's residue text / the uploaded sequences
+    const int64_t *item_off;      // window source: [n_items] byte offsets; mutation source: [n_seqs + 1]
+    int64_t n_items;
+    int64_t W;                    // window source: residues per window
+    int32_t k, fp;                // k-mer length (1 ... 10); Float64 form
+    int32_t n_rates, n_trials;    // mutation source
+    uint64_t seed;                // mutation source
+    const uint64_t *P;            // mutation source: [n_rates] floor(rate * 2^53)
+    const int32_t *S;             // integer form: the KFV's S table, device index order (first base least significant)
+    const double *R;              // Float64 form: the KFV as given, same index order
+    int64_t N, sumS2;             // integer form
+    double scale;                 // integer form: 2 k N^2 (dist = D / scale)
+    double half_inv_k;            // Float64 form: RN(1 / 2k)
+    uint32_t *scratch;            // k >= 8: 4^k counters per workgroup, all zero between items and launches
+    int64_t *D_out;               // integer form: [n_items]
+    double *dist_out;             // [n_items]
+    unsigned long long *first_bad;   // smallest byte offset in `text` of a residue outside the source's alphabet
+};
+int calib_grid(int k, int64_t n_items, int n_cus);   // workgroups of a launch = rows of CalibArgs::scratch
+#ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_H                   // (host files that do not see the HIP runtime include this header too)
+hipError_t launch_calib(const CalibArgs &a, int source /* 0: windows, 1: mutated copies */, int grid, hipStream_t st);
+#endif
+
 }  // namespace kgma

@@ -561,6 +561,40 @@ end
 motifMatch(motif, genome::Union{String, DeviceGenome}; max_mismatch::Integer = 0, ctx::Context = default_context()) =
     motifMatch([motif], genome; max_mismatch = max_mismatch, ctx = ctx)[1]
 
+# ---- threshold calibration (the working form of src/DistanceTesting.jl): kgma_window_dists, kgma_mutation_dists -------------
+
+"""
+    window_dists(g, kfv, contig, start) -> (D, dist)
+The distance to KFV `kfv` (1-based, of the references last given to the context) of the windows that begin at `start[i]` (1-based)
+of record `contig[i]` (0-based); the window size is that KFV's.  D: the exact integer distance of an S/N KFV.
+"""
+function window_dists(g::DeviceGenome, kfv::Integer, contig::Vector{Int32}, start::Vector{Int64})
+    ctx = g.ctx
+    n = length(contig)
+    length(start) == n || throw(ArgumentError("need one start per contig"))
+    D = Vector{Int64}(undef, n); dist = Vector{Float64}(undef, n)
+    check(ctx, ccall((:kgma_window_dists, libkgma), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                     ctx.h, g.h, kfv, n, contig, start, D, dist))
+    return D, dist
+end
+
+"""
+    mutation_dists(ctx, seqs, kfv, rates; n_trials = 42, seed = 42) -> (D, dist), each [trial, rate, sequence]
+kmer_dist(mutate_seq(seq, rate), KFV, k) for every sequence, rate and trial (the inner step of gen_sub_vs_ref), the mutated
+copies never materialised.  The substitutions come from a counter-based hash (include/kgma.h), not from Julia's RNG.
+"""
+function mutation_dists(ctx::Context, seqs::Vector{String}, kfv::Integer, rates::Vector{Float64}; n_trials::Integer = 42, seed::Integer = 42)
+    text = Vector{UInt8}(join(seqs))
+    offsets = Int64[0; cumsum(Int64[ncodeunits(s) for s in seqs])]
+    D = Array{Int64}(undef, n_trials, length(rates), length(seqs)); dist = Array{Float64}(undef, n_trials, length(rates), length(seqs))
+    check(ctx, ccall((:kgma_mutation_dists, libkgma), Cint,
+                     (Ptr{Cvoid}, Int32, Ptr{UInt8}, Ptr{Int64}, Int64, Ptr{Float64}, Int32, Int32, UInt64, Ptr{Int64}, Ptr{Float64}),
+                     ctx.h, kfv, text, offsets, length(seqs), rates, length(rates), n_trials, seed % UInt64, D, dist))
+    return D, dist
+end
+
 export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, HumanRSSV, HumanRSSD, Context
+export window_dists, mutation_dists
 
 end # module

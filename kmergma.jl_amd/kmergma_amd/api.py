@@ -34,6 +34,7 @@ Differences a caller can observe (all documented in DESIGN.md):
 from __future__ import annotations
 
 import logging
+import math
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -741,6 +742,184 @@ def findRSS(genome_or_path, rss=HumanRSSD, max_mismatch: int = 1, strand: str = 
     """Recombination signal sequences on a genome: motifMatch with the 23-nt-spacer RSS, one mismatch and both strands as the
     defaults.  (The reference's Align_RSS / is_RSS are not mirrored: DESIGN.md, section 8.)"""
     return motifMatch(rss, genome_or_path, max_mismatch=max_mismatch, strand=strand, ctx=ctx)
+
+
+# ---- threshold calibration (kgma_window_dists, kgma_mutation_dists): the working form of src/DistanceTesting.jl --------------
+
+_M64 = (1 << 64) - 1
+_GOLDEN64 = 0x9E3779B97F4A7C15
+# mutation_dict (src/DistanceTesting.jl:38-42), in its order
+_MUT = {ord("A"): b"CGT", ord("C"): b"AGT", ord("G"): b"CAT", ord("T"): b"CGA"}
+
+
+def _mix64(z):
+    """The splitmix64 finaliser on numpy uint64 (scalars or arrays; wraps mod 2^64)."""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _seq_bytes(seq) -> bytes:
+    if isinstance(seq, Record):
+        return bytes(seq.sequence)
+    return seq.encode() if isinstance(seq, str) else bytes(seq)
+
+
+def mutate_seq(seq, mut_rate, *, seed: int = 42, stream=(0, 0, 0)) -> bytes:
+    """`mutate_seq` (src/DistanceTesting.jl:57-67): a copy of `seq` in which every residue is substituted with probability
+    `mut_rate` by one of the three other bases, in mutation_dict's order.  The host mirror of the rule kgma_mutation_dists
+    applies on the device (kgma.h): `stream` = (i, r, t) is the (sequence, rate, trial) index of the copy, so
+    mutation_dists(seqs, ...)[i, r, t] is the distance of mutate_seq(seqs[i], rates[r], seed=seed, stream=(i, r, t)).
+    An unsubstituted residue keeps its byte (and case); a substituted one is upper case.  A residue outside A/C/G/T (either
+    case) raises KeyError, substituted or not (the reference looks mutation_dict up only when it substitutes).
+
+    DEVIATION (documented in DESIGN.md): the reference draws from Julia's global RNG (`rand(1)[1] <= mut_rate`;
+    `rand(mutation_dict[...])`), which cannot be reproduced outside Julia.  This uses a counter-based hash of (seed, stream,
+    position), so the result agrees statistically but not bitwise."""
+    s = _seq_bytes(seq)
+    rate = float(mut_rate)
+    if not (0.0 <= rate <= 1.0):
+        raise ValueError(f"mut_rate = {mut_rate} is not in [0, 1]")
+    a = np.frombuffer(s, dtype=np.uint8)
+    up = a & 0xDF
+    ok = (up == 65) | (up == 67) | (up == 71) | (up == 84)
+    if not bool(ok.all()):
+        j = int(np.flatnonzero(~ok)[0])
+        raise KeyError(f"position {j + 1}: residue {s[j:j + 1]!r} is not one of A/C/G/T (mutation_dict has no other key)")
+    G = np.uint64(_GOLDEN64)
+    with np.errstate(over="ignore"):
+        K = np.uint64(int(seed) & _M64)
+        for idx in stream:
+            K = _mix64(K + G * np.uint64(int(idx) + 1))
+        z = _mix64(K + G * np.arange(1, a.size + 1, dtype=np.uint64))
+    P = np.uint64(int(np.floor(np.ldexp(rate, 53))))
+    hit = (z >> np.uint64(11)) < P
+    pick = (((z & np.uint64(0x7FF)) * np.uint64(3)) >> np.uint64(11)).astype(np.int64)
+    lut = np.zeros((256, 3), dtype=np.uint8)
+    for b, row in _MUT.items():
+        lut[b] = np.frombuffer(row, dtype=np.uint8)
+    out = a.copy()
+    out[hit] = lut[up[hit], pick[hit]]
+    return out.tobytes()
+
+
+def sample_window_starts(record_lens, W: int, n_samples: int, seed: int):
+    """(contig, start): windows of W residues drawn from the records of the given lengths -- 0-based record (int32), 1-based
+    start (int64).  The valid windows are all (record, s) with 1 <= s <= L - W + 1; a record shorter than W has none.  At most
+    `n_samples` of them: every one once, in order.  Otherwise `np.random.default_rng(seed).integers(0, total, n_samples)`
+    mapped through the records' cumulative window counts, sorted (duplicates stay).  A pure host function."""
+    lens = np.asarray(list(record_lens), dtype=np.int64)
+    counts = np.maximum(lens - int(W) + 1, 0)
+    cum = np.cumsum(counts)
+    total = int(cum[-1]) if cum.size else 0
+    if total <= int(n_samples):
+        draws = np.arange(total, dtype=np.int64)
+    else:
+        draws = np.sort(np.random.default_rng(seed).integers(0, total, int(n_samples)).astype(np.int64))
+    contig = np.searchsorted(cum, draws, side="right")
+    start = draws - (cum[contig] - counts[contig]) + 1 if draws.size else draws
+    return contig.astype(np.int32), start.astype(np.int64)
+
+
+def off_lattice_threshold(est: float, scale: float) -> float:
+    """The threshold halfway between the two attainable distances around `est`: an S/N KFV's distances are the lattice
+    D / scale (D an integer, scale = 2 k N^2: Context.kfv_scale), and (floor(est * scale) + 0.5) / scale decides exactly the
+    windows `est` decides unless est lies on the lattice itself -- then the windows AT est count as below -- while no window
+    lies within the 2^-30 guard band of it ("at threshold", kgma_set_refs)."""
+    return (math.floor(est * scale) + 0.5) / scale
+
+
+def _calib_subject(ctx, genome_or_path):
+    if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
+        raise TypeError("expected a FASTA or .2bit path or an open device genome")
+    g, _src, owned = _open_subject(ctx, genome_or_path)
+    return g, owned
+
+
+def window_dists(genome_or_path, RV, windowsize: int, k: int, contig, start, *, n_refs: Optional[int] = None, ctx=None):
+    """(D, dist) of the windows of `windowsize` residues at `start[i]` (1-based) of record `contig[i]` (0-based) to the KFV
+    `RV`: kgma_window_dists.  `genome_or_path`: a FASTA path, a .2bit path or an open device genome (it stays open; pass
+    Genome.revcomp() for the minus strand, in its own coordinates).  Answers "how far off is this locus?" without a
+    whole-genome scan.  Sets the context's references to (RV, windowsize)."""
+    ctx = ctx or default_context()
+    ctx.set_refs(int(k), [np.asarray(RV, dtype=np.float64)], [int(windowsize)], [1.0], None if n_refs is None else [int(n_refs)])
+    g, owned = _calib_subject(ctx, genome_or_path)
+    try:
+        return ctx.window_dists(g, 1, contig, start)
+    finally:
+        if owned:
+            g.free()
+
+
+def estimate_threshold_from_genome(genome_or_path, RV, windowsize, k: int, *, n_samples: int = 100_000, seed: int = 42,
+                                   buffer: float = 8, quantile: Optional[float] = None, off_lattice: bool = True,
+                                   n_refs=None, ctx=None):
+    """estimate_optimal_threshold (src/DistanceTesting.jl:8-32) with the genome's own windows in the place of `randdnaseq`:
+    the mean distance to the KFV of `n_samples` windows drawn from the genome (sample_window_starts; all of them when the
+    genome has no more), minus `buffer` -- math.fsum(d) / n - buffer, independent of order.  A real genome is not uniform
+    (repeats, skewed composition, runs of N that the scan counts as T), so this is the distribution the scan actually tests.
+    quantile=q (0 < q <= 1): instead the ceil(q n)-th smallest sampled distance minus `buffer`, no interpolation.
+    `RV` and `windowsize` may be lists (the cluster case; every KFV with its own window size and the same draw rule): a list
+    is returned then.  off_lattice (default) with an S/N KFV: the result is moved to (floor(est * scale) + 0.5) / scale,
+    halfway between two attainable distances, so that no window can be "at threshold" in kgma_set_refs's sense and the chain
+    replay has no pair to decide.  Pass the result as KmerDistThr / KmerDistThrs; findGenes' own default
+    stays estimate_optimal_threshold.  Sets the context's references."""
+    many = isinstance(windowsize, (list, tuple, np.ndarray))
+    RVs = [np.asarray(r, dtype=np.float64) for r in (RV if many else [RV])]
+    Ws = [int(w) for w in (windowsize if many else [windowsize])]
+    if len(RVs) != len(Ws):
+        raise ValueError("need one window size per KFV")
+    if quantile is not None and not (0.0 < float(quantile) <= 1.0):
+        raise ValueError(f"quantile = {quantile} is not in (0, 1]")
+    nr = None if n_refs is None else [int(x) for x in (n_refs if many else [n_refs])]
+    ctx = ctx or default_context()
+    ctx.set_refs(int(k), RVs, Ws, [1.0] * len(Ws), nr)
+    g, owned = _calib_subject(ctx, genome_or_path)
+    out = []
+    try:
+        lens = [g.contig_len(c) for c in range(g.n_contigs)]
+        for j, W in enumerate(Ws):
+            contig, start = sample_window_starts(lens, W, n_samples, seed)
+            if contig.size == 0:
+                raise ValueError(f"no record holds a window of {W} residues")
+            _D, d = ctx.window_dists(g, j + 1, contig, start)
+            n = int(d.size)
+            if quantile is None:
+                est = math.fsum(d.tolist()) / n - buffer
+            else:
+                est = float(np.sort(d)[math.ceil(float(quantile) * n) - 1]) - buffer
+            if off_lattice and not ctx.kfv_is_float(j + 1):
+                scale = ctx.kfv_scale(j + 1)
+                est = off_lattice_threshold(est, scale)
+            out.append(est)
+    finally:
+        if owned:
+            g.free()
+    return out if many else out[0]
+
+
+def mutation_dists(ref_path_or_seqs, RV, k: int, *, rates=None, n_trials: int = 42, seed: int = 42,
+                   n_refs: Optional[int] = None, ctx=None) -> np.ndarray:
+    """The working form of gen_sub_vs_ref (src/DistanceTesting.jl:69-84, which refers to an undefined `vgene`): for every
+    sequence i (the records of a FASTA path, or a list of bytes / str / Record), rate r and trial t the distance
+    kmer_dist(mutate_seq(seq_i, rates[r]), RV, k), as a Float64 array [n_seqs, n_rates, n_trials] -- how far a gene may have
+    diverged and still fall below a threshold.  One device call (kgma_mutation_dists); the mutated copies are never
+    materialised, and entry [i, r, t] is reproduced on the host by mutate_seq(seq_i, rates[r], seed=seed, stream=(i, r, t)).
+    rates: default 0:0.0125:1.  Sets the context's references."""
+    if rates is None:
+        rates = np.arange(0, 1 + 1e-9, 0.0125)
+    rates = np.asarray(rates, dtype=np.float64)
+    seqs = [r.sequence for r in read_fasta(ref_path_or_seqs)] if isinstance(ref_path_or_seqs, str) else [_seq_bytes(s) for s in ref_path_or_seqs]
+    ctx = ctx or default_context()
+    # (the window size plays no part here: a sequence's own length decides its number of k-mers)
+    ctx.set_refs(int(k), [np.asarray(RV, dtype=np.float64)], [int(k) + 1], [1.0], None if n_refs is None else [int(n_refs)])
+    return ctx.mutation_dists(seqs, 1, rates, n_trials, seed)[1]
+
+
+def gen_sub_vs_ref(num_seeds: int = 42, stepsize: float = 0.0125, *, k: int = 6, RKV: str, ctx=None) -> np.ndarray:
+    """`gen_sub_vs_ref` (src/DistanceTesting.jl:69-84) with the reference's signature: the reference file's own sequences
+    against its KFV, [n_seqs, n_rates, num_seeds] (trial t stands for the reference's seed t + 1)."""
+    return mutation_dists(RKV, refprep.gen_ref_ws_cons(RKV, k)[0], k, rates=np.arange(0, 1 + 1e-9, stepsize), n_trials=num_seeds, ctx=ctx)
 
 
 def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
