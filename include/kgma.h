@@ -666,6 +666,42 @@ int kgma_mutation_dists(kgma_ctx *ctx, int32_t kfv, const uint8_t *seqs, const i
                         int64_t n_seqs, const double *rates, int32_t n_rates, int32_t n_trials, uint64_t seed,
                         int64_t *D_out, double *dist_out /* [n_seqs][n_rates][n_trials], either may be NULL */);
 
+/* The same two calls for the strobemer engine (kernel: strobe_calib_kernel, kgma_calib.hip), whose reference docstring reads "there
+ * is not distance threshold estimation yet" and whose default KmerDistThr = 30 is the k-mer engine's: the strobemer distance
+ * lives on another lattice -- 4^(2s) bins, D / scale with scale = 2 k N^2, k = w_max + s - 1, which is exactly what
+ * kgma_kfv_scale(ctx, 1, ...) returns after kgma_set_strobe_ref.  Both calls need the reference of kgma_set_strobe_ref
+ * (KGMA_E_STATE before it, or after kgma_set_refs; kgma_window_dists and kgma_mutation_dists in turn keep refusing a strobemer
+ * reference), leave the reference, the threshold and the hits, dips, distances, alignments, matches and motif matches of earlier
+ * calls untouched, and set of kgma_stats only scan_ms and n_launches.  kgma_scan_kernel_name afterwards:
+ * "strobe_calib_kernel<window|mutation,s>".  Either output may be NULL.  D is exact in int64: D = sumS2 - 2 N sum_j S[x_j] +
+ * N^2 sum_j c[x_j] over the item's randstrobes j, x_j their bins (first * 4^s + second, the rule kgma_strobe_scan counts by),
+ * with 4^(2s) 32-bit counters in LDS; dist_out = (double)D / scale.
+ *
+ * kgma_strobe_window_dists: window i is THE SCAN'S window with start start[i] (1-based) of record contig[i] (0-based), W the
+ * window size kgma_set_strobe_ref was given, read as literally as the scan reads the reference: the window with start 1 holds the
+ * W - k + 1 randstrobes that start at residues 1 .. W - k + 1 of the record; a window with start q >= 2 holds the W - k
+ * randstrobes that start at q .. q + W - k - 1 PLUS one permanent copy of the record's randstrobe at residue W - k + 1 (the
+ * reference's update re-enters the previous window's last randstrobe, so that one never leaves).  W - k + 1 items either way.
+ * Valid starts: 1 <= start <= max(1, L - W) on a record of L >= W residues -- the first window and the windows the scan tests
+ * (its steps 1 .. L - W - 1, start = step + 1).  D_out[i] is exactly what kgma_hit.D, kgma_get_first_window (start 1) and, divided
+ * by the scale, kgma_get_dists report for that window.  The list may be unsorted, hold duplicates, or be empty; a genome made by
+ * kgma_genome_revcomp is used in its own coordinates.  KGMA_E_ARG: a null list, a contig out of range, a record shorter than W, a
+ * start outside the range above (kgma_last_error names the index).  KGMA_E_BADBASE: a residue outside A/C/G/T/N among the residues
+ * a requested window's items read -- residues q .. q + W - 2 of the record and, for q >= 2, the k residues W - k + 1 .. W of the
+ * permanent item; for q = 1, residues 1 .. W -- (kgma_last_error names record and position; the outputs are then unspecified);
+ * such a residue elsewhere in the genome is no error.
+ *
+ * kgma_strobe_mutation_dists: for every (sequence i, rate r, trial t) the distance of the reference to the randstrobe counts of
+ * the whole mutated sequence: all len - k + 1 randstrobes and no permanent item (len < k: D = sumS2).  The mutation rule, the key
+ * derivation, the layout [(i * n_rates + r) * n_trials + t] and the argument errors are those of kgma_mutation_dists; the working
+ * form of test_strobe_2_mer_dists (src/StrobemerGMA/MonteCarloBenchmark.jl:2-23).  KGMA_E_UNSUPPORTED: a sequence whose
+ * sumS2 + N^2 n^2 leaves 61 bits, or more than 2^28 distances in one call. */
+int kgma_strobe_window_dists(kgma_ctx *ctx, const kgma_genome *g, int64_t n, const int32_t *contig /* 0-based */,
+                             const int64_t *start /* 1-based */, int64_t *D_out /* n, may be NULL */, double *dist_out /* n, may be NULL */);
+int kgma_strobe_mutation_dists(kgma_ctx *ctx, const uint8_t *seqs, const int64_t *offsets /* n_seqs + 1 */, int64_t n_seqs,
+                               const double *rates, int32_t n_rates, int32_t n_trials, uint64_t seed,
+                               int64_t *D_out, double *dist_out /* [n_seqs][n_rates][n_trials], either may be NULL */);
+
 /* kgma_repack_scan_hits in two halves, for step loops that have other work to queue while the GPU scans
  * (bench.py with several ranks: the hit exchange of step i overlaps the scan of step i+1).  kgma_step_begin
  * hands the step to a helper thread owned by the context and returns at once; kgma_step_end waits for it

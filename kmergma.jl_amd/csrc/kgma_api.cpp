@@ -3302,8 +3302,7 @@ int launch_group_strobe(kgma_ctx *ctx, const ScanPlan &p, const LaunchGroup &, c
     sp.n_slots = (int32_t)((int64_t)std::max(1, ctx->n_cus - ctx->reserved_cus) * p.stream_nw);
     sp.T = f.T; sp.T_hi = f.T_hi; sp.sumS2 = f.sumS2; sp.inv_scale = gp.inv_scale[0];
     sp.S = ctx->d_Stab;
-    for (int64_t v = 0; v < 128; v++)
-        if (v % ctx->st_q == 0) sp.zero[v >> 5] |= 1u << (v & 31);
+    strobe_zero_mask(ctx->st_q, sp.zero);
     bind_results(a, ctx, t.n_tiles);                       // (never filtered)
     HIP_TRY(ctx, launch_strobe(a, sp, ctx->stream));
     ctx->stats.n_launches++;
@@ -5881,6 +5880,18 @@ static int calib_launch(kgma_ctx *ctx, const char *what, int source, CalibArgs &
     return KGMA_OK;
 }
 
+// KGMA_E_BADBASE of the window calls.  bad: the smallest byte offset of a bad residue the requested windows looked up; its record is
+// the one it lies in.
+static int window_bad(kgma_ctx *ctx, const kgma_genome *g, unsigned long long bad)
+{
+    int64_t c = 0;
+    for (int64_t r = 0; r < g->n_contigs; r++)
+        if (g->cd[(size_t)r].len > 0 && g->cd[(size_t)r].ascii_off <= (int64_t)bad &&
+            (int64_t)bad < g->cd[(size_t)r].ascii_off + g->cd[(size_t)r].len) c = r;
+    return fail(ctx, KGMA_E_BADBASE, "record %lld position %lld: residue is not one of A/C/G/T/N (KeyError, Consts.jl:22-28)", (long long)c,
+                (long long)((int64_t)bad - g->cd[(size_t)c].ascii_off + 1));
+}
+
 int kgma_window_dists(kgma_ctx *ctx, const kgma_genome *g, int32_t kfv, int64_t n, const int32_t *contig, const int64_t *start,
                       int64_t *D_out, double *dist_out)
 {
@@ -5911,16 +5922,67 @@ int kgma_window_dists(kgma_ctx *ctx, const kgma_genome *g, int32_t kfv, int64_t 
     a.text = g->d_ascii; a.item_off = ctx->d_cboff; a.n_items = n; a.W = f.W;
     unsigned long long bad = NO_BAD;
     if ((rc = calib_launch(ctx, "kgma_window_dists", 0, a, f, kfv, D_out, dist_out, &bad))) return rc;
-    if (bad != NO_BAD) {
-        // the smallest byte offset of a bad residue inside a requested window: its record is the last one that starts at or before it
-        int64_t c = 0;
-        for (int64_t r = 0; r < g->n_contigs; r++)
-            if (g->cd[(size_t)r].len > 0 && g->cd[(size_t)r].ascii_off <= (int64_t)bad &&
-                (int64_t)bad < g->cd[(size_t)r].ascii_off + g->cd[(size_t)r].len) c = r;
-        return fail(ctx, KGMA_E_BADBASE, "record %lld position %lld: residue is not one of A/C/G/T/N (KeyError, Consts.jl:22-28)", (long long)c,
-                    (long long)((int64_t)bad - g->cd[(size_t)c].ascii_off + 1));
-    }
+    if (bad != NO_BAD) return window_bad(ctx, g, bad);
     return KGMA_OK;
+}
+
+// What kgma_mutation_dists and kgma_strobe_mutation_dists share behind the check of their references: the argument checks (a
+// sequence of len residues holds len - k + 1 `unit`s), the uploads and the mutation source's fields of `a`.  off: the sequences'
+// offsets from the first one's; empty: there is nothing to launch.
+struct MutationUpload { std::vector<int64_t> off; std::vector<uint64_t> P; bool empty = true; };   // (what the copies read lives until the launch's synchronise)
+static int mutation_source(kgma_ctx *ctx, const char *what, const char *unit, const KfvInfo &f, const uint8_t *seqs, const int64_t *offsets,
+                           int64_t n_seqs, const double *rates, int32_t n_rates, int32_t n_trials, uint64_t seed, CalibArgs &a,
+                           MutationUpload &u)
+{
+    std::vector<int64_t> &off = u.off;
+    std::vector<uint64_t> &P = u.P;
+    u.empty = true;
+    if (n_seqs < 0 || !offsets || !rates) return fail(ctx, KGMA_E_ARG, "%s: null argument or n_seqs < 0", what);
+    if (n_rates < 1 || n_trials < 1) return fail(ctx, KGMA_E_ARG, "%s: n_rates = %d, n_trials = %d (both at least 1)", what, n_rates, n_trials);
+    P.assign((size_t)n_rates, 0);
+    for (int32_t r = 0; r < n_rates; r++) {
+        if (!std::isfinite(rates[r]) || rates[r] < 0.0 || rates[r] > 1.0)
+            return fail(ctx, KGMA_E_ARG, "%s: rates[%d] = %g is not in [0, 1]", what, r, rates[r]);
+        P[(size_t)r] = (uint64_t)std::floor(std::ldexp(rates[r], 53));
+    }
+    for (int64_t i = 0; i < n_seqs; i++) {
+        if (offsets[i + 1] < offsets[i]) return fail(ctx, KGMA_E_ARG, "%s: offsets[%lld] > offsets[%lld]", what, (long long)i, (long long)(i + 1));
+        const int64_t nk = std::max<int64_t>(offsets[i + 1] - offsets[i] - ctx->k + 1, 0);
+        if (!f.fp && (__int128)f.sumS2 + (__int128)f.N * f.N * nk * (__int128)nk >= ((__int128)1 << 61))
+            return fail(ctx, KGMA_E_UNSUPPORTED, "%s: sequence %lld: N = %lld with %lld %s exceeds the int64 range of the device path", what,
+                        (long long)i, (long long)f.N, (long long)nk, unit);
+        if (f.fp && nk > ((int64_t)1 << 31))
+            return fail(ctx, KGMA_E_UNSUPPORTED, "%s: sequence %lld: %lld %s exceed the 32-bit counters", what, (long long)i, (long long)nk, unit);
+    }
+    const __int128 n_items128 = (__int128)n_seqs * n_rates * n_trials;
+    if (n_items128 > ((__int128)1 << 28)) return fail(ctx, KGMA_E_UNSUPPORTED, "%s: %lld x %d x %d distances in one call", what, (long long)n_seqs, n_rates, n_trials);
+    ctx->stats.scan_ms = 0;
+    ctx->stats.n_launches = 0;
+    if (n_seqs == 0) return KGMA_OK;
+    const int64_t base = offsets[0], bytes = offsets[n_seqs] - base;
+    if (bytes > 0 && !seqs) return fail(ctx, KGMA_E_ARG, "%s: null argument", what);
+    off.resize((size_t)n_seqs + 1);
+    for (int64_t i = 0; i <= n_seqs; i++) off[(size_t)i] = offsets[i] - base;
+    (void)hipSetDevice(ctx->device);
+    int rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cboff, ctx->cboff_cap, n_seqs + 1))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbtext, ctx->cbtext_cap, bytes))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbP, ctx->cbP_cap, n_rates))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cboff, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cbtext, seqs + base, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cbP, P.data(), P.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    memset(&a, 0, sizeof a);
+    a.text = ctx->d_cbtext; a.item_off = ctx->d_cboff; a.n_items = (int64_t)n_items128;
+    a.n_rates = n_rates; a.n_trials = n_trials; a.seed = seed; a.P = ctx->d_cbP;
+    u.empty = false;
+    return KGMA_OK;
+}
+
+static int mutation_bad(kgma_ctx *ctx, const std::vector<int64_t> &off, unsigned long long bad)
+{
+    const int64_t si = (int64_t)(std::upper_bound(off.begin(), off.end(), (int64_t)bad) - off.begin()) - 1;
+    return fail(ctx, KGMA_E_BADBASE, "sequence %lld position %lld: residue is not one of A/C/G/T (mutation_dict has no other key, DistanceTesting.jl:38-42)",
+                (long long)si, (long long)((int64_t)bad - off[(size_t)si] + 1));
 }
 
 int kgma_mutation_dists(kgma_ctx *ctx, int32_t kfv, const uint8_t *seqs, const int64_t *offsets, int64_t n_seqs, const double *rates,
@@ -5931,49 +5993,111 @@ int kgma_mutation_dists(kgma_ctx *ctx, int32_t kfv, const uint8_t *seqs, const i
     int rc = calib_kfv(ctx, "kgma_mutation_dists", kfv, &fp_);
     if (rc) return rc;
     const KfvInfo &f = *fp_;
-    if (n_seqs < 0 || !offsets || !rates) return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: null argument or n_seqs < 0");
-    if (n_rates < 1 || n_trials < 1) return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: n_rates = %d, n_trials = %d (both at least 1)", n_rates, n_trials);
-    std::vector<uint64_t> P((size_t)n_rates);
-    for (int32_t r = 0; r < n_rates; r++) {
-        if (!std::isfinite(rates[r]) || rates[r] < 0.0 || rates[r] > 1.0)
-            return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: rates[%d] = %g is not in [0, 1]", r, rates[r]);
-        P[(size_t)r] = (uint64_t)std::floor(std::ldexp(rates[r], 53));
-    }
-    for (int64_t i = 0; i < n_seqs; i++) {
-        if (offsets[i + 1] < offsets[i]) return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: offsets[%lld] > offsets[%lld]", (long long)i, (long long)(i + 1));
-        const int64_t nk = std::max<int64_t>(offsets[i + 1] - offsets[i] - ctx->k + 1, 0);
-        if (!f.fp && (__int128)f.sumS2 + (__int128)f.N * f.N * nk * (__int128)nk >= ((__int128)1 << 61))
-            return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_mutation_dists: sequence %lld: N = %lld with %lld k-mers exceeds the int64 range of the device path",
-                        (long long)i, (long long)f.N, (long long)nk);
-        if (f.fp && nk > ((int64_t)1 << 31)) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_mutation_dists: sequence %lld: %lld k-mers exceed the 32-bit counters", (long long)i, (long long)nk);
-    }
-    const __int128 n_items128 = (__int128)n_seqs * n_rates * n_trials;
-    if (n_items128 > ((__int128)1 << 28)) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_mutation_dists: %lld x %d x %d distances in one call", (long long)n_seqs, n_rates, n_trials);
-    ctx->stats.scan_ms = 0;
-    ctx->stats.n_launches = 0;
-    if (n_seqs == 0) return KGMA_OK;
-    const int64_t base = offsets[0], bytes = offsets[n_seqs] - base;
-    if (bytes > 0 && !seqs) return fail(ctx, KGMA_E_ARG, "kgma_mutation_dists: null argument");
-    std::vector<int64_t> off((size_t)n_seqs + 1);
-    for (int64_t i = 0; i <= n_seqs; i++) off[(size_t)i] = offsets[i] - base;
-    (void)hipSetDevice(ctx->device);
-    if ((rc = dev_reserve(ctx, ctx->d_cboff, ctx->cboff_cap, n_seqs + 1))) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_cbtext, ctx->cbtext_cap, bytes))) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_cbP, ctx->cbP_cap, n_rates))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cboff, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cbtext, seqs + base, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cbP, P.data(), P.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     CalibArgs a;
-    memset(&a, 0, sizeof a);
-    a.text = ctx->d_cbtext; a.item_off = ctx->d_cboff; a.n_items = (int64_t)n_items128;
-    a.n_rates = n_rates; a.n_trials = n_trials; a.seed = seed; a.P = ctx->d_cbP;
+    MutationUpload u;
+    if ((rc = mutation_source(ctx, "kgma_mutation_dists", "k-mers", f, seqs, offsets, n_seqs, rates, n_rates, n_trials, seed, a, u)) || u.empty)
+        return rc;
     unsigned long long bad = NO_BAD;
     if ((rc = calib_launch(ctx, "kgma_mutation_dists", 1, a, f, kfv, D_out, dist_out, &bad))) return rc;
-    if (bad != NO_BAD) {
-        const int64_t si = (int64_t)(std::upper_bound(off.begin(), off.end(), (int64_t)bad) - off.begin()) - 1;
-        return fail(ctx, KGMA_E_BADBASE, "sequence %lld position %lld: residue is not one of A/C/G/T (mutation_dict has no other key, DistanceTesting.jl:38-42)",
-                    (long long)si, (long long)((int64_t)bad - off[(size_t)si] + 1));
+    if (bad != NO_BAD) return mutation_bad(ctx, u.off, bad);
+    return KGMA_OK;
+}
+
+// ---- the same two calls for the strobemer engine's reference (kgma_set_strobe_ref; kernel: strobe_calib_kernel) ----
+static int strobe_calib_ref(kgma_ctx *ctx, const char *what)
+{
+    if (!ctx->strobe || ctx->m < 1)
+        return fail(ctx, KGMA_E_STATE, "%s: the context holds no strobemer reference (call kgma_set_strobe_ref first)", what);
+    return KGMA_OK;
+}
+
+// What both share behind their checks, as calib_launch: the reference's table and parameters, one launch between the context's
+// events, the download.  a.c: text, item_off, n_items (> 0) and the source's own fields are set; a.rec_off for the window source.
+static int strobe_calib_launch(kgma_ctx *ctx, int source, StrobeCalibArgs &a, int64_t *D_out, double *dist_out, unsigned long long *bad)
+{
+    const KfvInfo &f = ctx->kfv[0];
+    const int64_t n = a.c.n_items;
+    int rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbD, ctx->cbD_cap, n))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbdist, ctx->cbdist_cap, n))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->d_cbbad, ctx->cbbad_cap, 1))) return rc;
+    a.s = ctx->st_s; a.w_min = ctx->st_wmin; a.w_max = ctx->st_wmax;
+    strobe_zero_mask(ctx->st_q, a.zero);
+    a.c.k = ctx->k;
+    a.c.S = ctx->d_Stab;
+    a.c.N = f.N; a.c.sumS2 = f.sumS2;
+    a.c.scale = 2.0 * (double)ctx->k * (double)f.N * (double)f.N;      // = kgma_kfv_scale: what the strobemer scan divides by
+    a.c.D_out = ctx->d_cbD; a.c.dist_out = ctx->d_cbdist; a.c.first_bad = ctx->d_cbbad;
+    *bad = NO_BAD;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cbbad, bad, 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(ctx, launch_strobe_calib(a, source, calib_grid(1, n, ctx->n_cus), ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(bad, ctx->d_cbbad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (dist_out) HIP_TRY(ctx, hipMemcpyAsync(dist_out, ctx->d_cbdist, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (D_out) HIP_TRY(ctx, hipMemcpyAsync(D_out, ctx->d_cbD, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    ctx->stats.scan_ms = ms;
+    ctx->stats.n_launches = 1;
+    snprintf(ctx->kernel_name, sizeof ctx->kernel_name, "strobe_calib_kernel<%s,%d>", source == 0 ? "window" : "mutation", ctx->st_s);
+    return KGMA_OK;
+}
+
+int kgma_strobe_window_dists(kgma_ctx *ctx, const kgma_genome *g, int64_t n, const int32_t *contig, const int64_t *start, int64_t *D_out,
+                             double *dist_out)
+{
+    if (!ctx || !g) return KGMA_E_ARG;
+    int rc = strobe_calib_ref(ctx, "kgma_strobe_window_dists");
+    if (rc) return rc;
+    const int64_t W = ctx->kfv[0].W;
+    if (n < 0 || (n > 0 && (!contig || !start))) return fail(ctx, KGMA_E_ARG, "kgma_strobe_window_dists: null argument or n < 0");
+    // [window offsets | offsets of the windows' records]
+    std::vector<int64_t> off((size_t)(2 * n));
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t c = contig[i];
+        if (c < 0 || c >= g->n_contigs) return fail(ctx, KGMA_E_ARG, "kgma_strobe_window_dists: window %lld: no record %lld", (long long)i, (long long)c);
+        const ContigDesc &d = g->cd[(size_t)c];
+        if (d.len < W)
+            return fail(ctx, KGMA_E_ARG, "kgma_strobe_window_dists: window %lld: record %lld of %lld residues is shorter than the window (%lld): the scan skips it",
+                        (long long)i, (long long)c, (long long)d.len, (long long)W);
+        if (start[i] < 1 || start[i] > std::max<int64_t>(1, d.len - W))
+            return fail(ctx, KGMA_E_ARG, "kgma_strobe_window_dists: window %lld: start %lld is not one of 1 .. %lld, the window starts of record %lld of %lld residues",
+                        (long long)i, (long long)start[i], (long long)std::max<int64_t>(1, d.len - W), (long long)c, (long long)d.len);
+        off[(size_t)i] = d.ascii_off + (start[i] - 1);
+        off[(size_t)(n + i)] = d.ascii_off;
     }
+    ctx->stats.scan_ms = 0;
+    ctx->stats.n_launches = 0;
+    if (n == 0) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    if ((rc = dev_reserve(ctx, ctx->d_cboff, ctx->cboff_cap, 2 * n))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cboff, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    StrobeCalibArgs a;
+    memset(&a, 0, sizeof a);
+    a.c.text = g->d_ascii; a.c.item_off = ctx->d_cboff; a.rec_off = ctx->d_cboff + n; a.c.n_items = n; a.c.W = W;
+    unsigned long long bad = NO_BAD;
+    if ((rc = strobe_calib_launch(ctx, 0, a, D_out, dist_out, &bad))) return rc;
+    if (bad != NO_BAD) return window_bad(ctx, g, bad);
+    return KGMA_OK;
+}
+
+int kgma_strobe_mutation_dists(kgma_ctx *ctx, const uint8_t *seqs, const int64_t *offsets, int64_t n_seqs, const double *rates,
+                               int32_t n_rates, int32_t n_trials, uint64_t seed, int64_t *D_out, double *dist_out)
+{
+    if (!ctx) return KGMA_E_ARG;
+    int rc = strobe_calib_ref(ctx, "kgma_strobe_mutation_dists");
+    if (rc) return rc;
+    StrobeCalibArgs a;
+    memset(&a, 0, sizeof a);
+    MutationUpload u;
+    if ((rc = mutation_source(ctx, "kgma_strobe_mutation_dists", "strobemers", ctx->kfv[0], seqs, offsets, n_seqs, rates, n_rates, n_trials, seed,
+                              a.c, u)) || u.empty)
+        return rc;
+    unsigned long long bad = NO_BAD;
+    if ((rc = strobe_calib_launch(ctx, 1, a, D_out, dist_out, &bad))) return rc;
+    if (bad != NO_BAD) return mutation_bad(ctx, u.off, bad);
     return KGMA_OK;
 }
 

@@ -17,6 +17,8 @@
 //   MODE 0, in ONE fixed order: lane t of the 256 sums the bins t, t + 256, ... of the DEVICE index order (first base
 //   least significant) in increasing order, the 64 lanes of a wave are combined by a shuffle tree (distances 32, 16,
 //   ... 1), the four waves in wave order, and the total is multiplied by RN(1 / 2k).  The pass clears what it reads.
+// Strobemer form (strobe_calib_kernel, below calib_kernel): the integer form over randstrobe bins, for the strobemer engine's
+//   reference (kgma_strobe_window_dists, kgma_strobe_mutation_dists).
 //
 // Mutation rule (kgma.h, kgma_mutation_dists): mix64 is the splitmix64 finaliser, G = 0x9E3779B97F4A7C15,
 //   K = mix64(mix64(mix64(seed + G (i + 1)) + G (r + 1)) + G (t + 1)) for sequence i, rate r, trial t;
@@ -24,8 +26,10 @@
 //   new base = MUT[b][((z & 0x7FF) * 3) >> 11], MUT in the order of mutation_dict (src/DistanceTesting.jl:38-42).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "kgma_device.h"
+#include "kgma_strobe_bin.h"
 
 namespace kgma {
 
@@ -187,6 +191,77 @@ __global__ __launch_bounds__(CB_THREADS) void calib_kernel(const CalibArgs a)
         }
         __syncthreads();                          // counters cleared (and the wave partials free) before the next item
     }
+}
+
+// The strobemer form (kgma_strobe_window_dists, kgma_strobe_mutation_dists): the integer form above with the randstrobe bin of the
+// k = w_max + s - 1 residues at a position (strobe_bin, the rule strobe_kernel scans with) in the place of the k-mer, and the
+// 4^(2s) 32-bit counters in LDS.  What the reference's count vector holds, read literally (kgma_strobe.hip): an item has
+// n = len - k + 1 strobemers, the n - 1 at residues 0 .. n - 2 and a LAST one at residue `last` -- n - 1 for a mutated copy (all
+// of the sequence's strobemers), and for a window the strobemer at residue W - k of the window's RECORD: its permanent item,
+// which is the window's own last strobemer only for the record's first window.  The residues looked up are those the items read.
+template <class SRC, int SS>
+__global__ __launch_bounds__(CB_THREADS) void strobe_calib_kernel(const StrobeCalibArgs a)
+{
+    constexpr uint32_t NB = 1u << (4 * SS);
+    constexpr bool WINDOW = std::is_same<SRC, WindowSource>::value;
+    __shared__ uint32_t cnt[NB];
+    __shared__ int64_t wave_s[CB_THREADS / 64], wave_c[CB_THREADS / 64];
+    const int tid = threadIdx.x, k = a.c.k;
+    const int w_min = a.w_min, w_max = a.w_max;
+    const uint32_t z0 = a.zero[0], z1 = a.zero[1], z2 = a.zero[2], z3 = a.zero[3];
+    for (uint32_t x = tid; x < NB; x += CB_THREADS) cnt[x] = 0;
+    __syncthreads();
+    for (int64_t item = blockIdx.x; item < a.c.n_items; item += gridDim.x) {
+        const SRC src(a.c, item);
+        const int64_t n = src.len - k + 1;        // strobemers (<= 0: nothing is counted)
+        const int64_t last = WINDOW ? a.rec_off[item] + (src.len - k) - src.bad_base : n - 1;
+        auto bin_at = [&](int64_t p) {
+            return strobe_bin<SS>(kmer_at(src, p < n - 1 ? p : last, k), w_min, w_max, z0, z1, z2, z3);
+        };
+        // a mutated copy: every residue is looked up, as in calib_kernel; a window: residues 0 .. W - 2 and the permanent item's k
+        for (int64_t i = tid; i < (WINDOW ? src.len - 1 : src.len); i += CB_THREADS)
+            if (src.code(i) < 0) atomicMin(a.c.first_bad, (unsigned long long)(src.bad_base + i));
+        if (WINDOW && tid < k && src.code(last + tid) < 0) atomicMin(a.c.first_bad, (unsigned long long)(src.bad_base + last + tid));
+        for (int64_t p = tid; p < n; p += CB_THREADS) atomicAdd(&cnt[bin_at(p)], 1u);
+        __syncthreads();
+        const int32_t *S = a.c.S;
+        int64_t sS = 0, sC = 0;
+        for (int64_t p = tid; p < n; p += CB_THREADS) {
+            const uint32_t v = bin_at(p);
+            sS += S[v];
+            sC += cnt[v];
+        }
+        sS = wave_sum(sS); sC = wave_sum(sC);
+        if ((tid & 63) == 0) { wave_s[tid >> 6] = sS; wave_c[tid >> 6] = sC; }
+        __syncthreads();                          // every count has been read: the positions may be cleared
+        for (int64_t p = tid; p < n; p += CB_THREADS) cnt[bin_at(p)] = 0;
+        if (tid == 0) {
+            int64_t tS = 0, tC = 0;
+            for (int w = 0; w < CB_THREADS / 64; w++) { tS += wave_s[w]; tC += wave_c[w]; }
+            const int64_t D = a.c.sumS2 - 2 * a.c.N * tS + a.c.N * a.c.N * tC;
+            a.c.D_out[item] = D;
+            a.c.dist_out[item] = (double)D / a.c.scale;
+        }
+        __syncthreads();                          // counters cleared (and the wave partials free) before the next item
+    }
+}
+
+template <class SRC>
+static hipError_t launch_strobe_calib_src(const StrobeCalibArgs &a, int grid, hipStream_t st)
+{
+    auto fn = a.s == 1 ? &strobe_calib_kernel<SRC, 1> : a.s == 2 ? &strobe_calib_kernel<SRC, 2> : &strobe_calib_kernel<SRC, 3>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(CB_THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+// source 0: genome windows, 1: mutated copies.  `grid` = calib_grid(1, ...): the counters are in LDS.
+hipError_t launch_strobe_calib(const StrobeCalibArgs &a, int source, int grid, hipStream_t st)
+{
+    if (a.c.n_items <= 0) return hipSuccess;
+    if (a.s < 1 || a.s > KGMA_STROBE_MAX_S || a.w_min < 1 || a.w_min > a.w_max || a.c.k != a.w_max + a.s - 1 || a.c.k > KGMA_STROBE_MAX_K ||
+        grid < 1 || (source == 0 && (a.rec_off == nullptr || a.c.W <= a.c.k)))
+        return hipErrorInvalidConfiguration;
+    return source == 0 ? launch_strobe_calib_src<WindowSource>(a, grid, st) : launch_strobe_calib_src<MutationSource>(a, grid, st);
 }
 
 // workgroups of a launch (= rows of the global counter table when k > 7: at most 64 MiB of it)

@@ -218,6 +218,13 @@ struct StrobeParams {
 };
 constexpr int KGMA_STROBE_MAX_S = 3;                           // 4^(2s) 16-bit counters per wave and the S table fit the LDS; sums fit `zero`
 constexpr int KGMA_STROBE_MAX_K = 16;                          // a strobemer's residues are one dword of the 2-bit genome copy
+// the zero-score mask words of the bin rule (kgma_strobe_bin.h) for the modulus q >= 1
+inline void strobe_zero_mask(int64_t q, uint32_t zero[4])
+{
+    for (int i = 0; i < 4; i++) zero[i] = 0;
+    for (int64_t v = 0; v < 128; v++)
+        if (v % q == 0) zero[v >> 5] |= 1u << (v & 31);
+}
 
 // Count-table stream kernel (kgma_stream.hip): one wave per stream of consecutive window starts.
 constexpr int KGMA_STREAM_MIN_WINDOWS = 2048;                  // shorter streams waste their warm-up (n k-mers)
@@ -406,8 +413,20 @@ struct CalibArgs {
     unsigned long long *first_bad;   // smallest byte offset in `text` of a residue outside the source's alphabet
 };
 int calib_grid(int k, int64_t n_items, int n_cus);   // workgroups of a launch = rows of CalibArgs::scratch
+// The strobemer form (strobe_calib_kernel; kgma_strobe_window_dists, kgma_strobe_mutation_dists): the integer form above with the
+// randstrobe bin (StrobeParams, kgma_strobe_bin.h) in the place of the k-mer and 4^(2s) 32-bit counters in LDS.  `c` is read as
+// above with k = w_max + s - 1 and S in natural bin order; fp, R, half_inv_k and scratch are not used.  An item of the window
+// source holds W - k + 1 strobemers: those at residues 0 .. W - k - 1 of the window, and the one at residue W - k of the window's
+// RECORD (its permanent item, which for the record's first window is the window's own last strobemer).
+struct StrobeCalibArgs {
+    CalibArgs c;
+    const int64_t *rec_off;       // window source: [n_items] byte offset in `text` of the first residue of the item's record
+    int32_t s, w_min, w_max, pad;
+    uint32_t zero[4];             // strobe_zero_mask
+};
 #ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_H                   // (host files that do not see the HIP runtime include this header too)
 hipError_t launch_calib(const CalibArgs &a, int source /* 0: windows, 1: mutated copies */, int grid, hipStream_t st);
+hipError_t launch_strobe_calib(const StrobeCalibArgs &a, int source, int grid, hipStream_t st);
 #endif
 
 }  // namespace kgma

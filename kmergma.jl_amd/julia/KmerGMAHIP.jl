@@ -594,7 +594,39 @@ function mutation_dists(ctx::Context, seqs::Vector{String}, kfv::Integer, rates:
     return D, dist
 end
 
+"""
+    strobe_window_dists(g, contig, start) -> (D, dist)
+The same for the strobemer reference last given to the context (kgma_set_strobe_ref): the strobemer scan's window with start
+`start[i]` (1 ... max(1, L - W)) of record `contig[i]` -- W - k + 1 randstrobes, the record's permanent one included for start >= 2.
+dist = D / (2 k N^2), k = w_max + s - 1.
+"""
+function strobe_window_dists(g::DeviceGenome, contig::Vector{Int32}, start::Vector{Int64})
+    ctx = g.ctx
+    n = length(contig)
+    length(start) == n || throw(ArgumentError("need one start per contig"))
+    D = Vector{Int64}(undef, n); dist = Vector{Float64}(undef, n)
+    check(ctx, ccall((:kgma_strobe_window_dists, libkgma), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                     ctx.h, g.h, n, contig, start, D, dist))
+    return D, dist
+end
+
+"""
+    strobe_mutation_dists(ctx, seqs, rates; n_trials = 42, seed = 42) -> (D, dist), each [trial, rate, sequence]
+The distance of the strobemer reference to the randstrobe counts of mutate_seq(seq, rate) for every sequence, rate and trial: the
+working form of test_strobe_2_mer_dists (src/StrobemerGMA/MonteCarloBenchmark.jl:2-23).
+"""
+function strobe_mutation_dists(ctx::Context, seqs::Vector{String}, rates::Vector{Float64}; n_trials::Integer = 42, seed::Integer = 42)
+    text = Vector{UInt8}(join(seqs))
+    offsets = Int64[0; cumsum(Int64[ncodeunits(s) for s in seqs])]
+    D = Array{Int64}(undef, n_trials, length(rates), length(seqs)); dist = Array{Float64}(undef, n_trials, length(rates), length(seqs))
+    check(ctx, ccall((:kgma_strobe_mutation_dists, libkgma), Cint,
+                     (Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int64}, Int64, Ptr{Float64}, Int32, Int32, UInt64, Ptr{Int64}, Ptr{Float64}),
+                     ctx.h, text, offsets, length(seqs), rates, length(rates), n_trials, seed % UInt64, D, dist))
+    return D, dist
+end
+
 export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, HumanRSSV, HumanRSSD, Context
-export window_dists, mutation_dists
+export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists
 
 end # module

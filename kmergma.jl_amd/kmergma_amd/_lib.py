@@ -38,7 +38,7 @@ EXPORTS = [
     "kgma_motif_match", "kgma_get_motif_matches",
     "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
     "kgma_get_block_sums", "kgma_genome_from_2bit_file", "kgma_get_2bit_unpack_ms", "kgma_twobit_inspect",
-    "kgma_window_dists", "kgma_mutation_dists",
+    "kgma_window_dists", "kgma_mutation_dists", "kgma_strobe_window_dists", "kgma_strobe_mutation_dists",
 ]
 TWOBIT_NOMASK = 1                    # KGMA_2BIT_NOMASK
 TWOBIT_SIGNATURE = b"\x43\x27\x41\x1a"  # the first four bytes of a .2bit file in this machine's byte order
@@ -216,6 +216,8 @@ def load():
                                        P(dbl), i64, P(i64), P(dbl)]
     L.kgma_window_dists.argtypes = [vp, vp, i32, i64, P(i32), P(i64), P(i64), P(dbl)]
     L.kgma_mutation_dists.argtypes = [vp, i32, C.c_char_p, P(i64), i64, P(dbl), i32, i32, u64, P(i64), P(dbl)]
+    L.kgma_strobe_window_dists.argtypes = [vp, vp, i64, P(i32), P(i64), P(i64), P(dbl)]
+    L.kgma_strobe_mutation_dists.argtypes = [vp, C.c_char_p, P(i64), i64, P(dbl), i32, i32, u64, P(i64), P(dbl)]
     L.kgma_stream.argtypes = [vp]
     L.kgma_stream.restype = vp
     L.kgma_scan_kernel_name.argtypes = [vp]
@@ -853,6 +855,39 @@ class Context:
         self._check(load().kgma_mutation_dists(self._h, int(kfv), text, _np_ptr(off, C.c_int64), ns, _np_ptr(rt_arg, C.c_double), nr, nt,
                                                C.c_uint64(int(seed) & (2 ** 64 - 1)), _np_ptr(D, C.c_int64), _np_ptr(dist, C.c_double)))
         n = int(np.prod(shape))
+        return D[:n].reshape(shape), dist[:n].reshape(shape)
+
+    def strobe_window_dists(self, genome: "Genome", contig, start):
+        """kgma_strobe_window_dists: (D, dist) of the strobemer scan's windows with start `start[i]` (1-based, 1 ... max(1, L - W))
+        of record `contig[i]` (0-based) against the reference of set_strobe_ref: the W - k + 1 randstrobes the scan's count
+        vector holds there, the record's permanent one (position W - k + 1) included for start >= 2.  D: int64, exactly what
+        hits()["D"] and first_window() report; dist = D / kfv_scale(1).  Any list: unsorted, with duplicates, empty."""
+        c = np.ascontiguousarray(np.asarray(contig, dtype=np.int32).ravel())
+        s = np.ascontiguousarray(np.asarray(start, dtype=np.int64).ravel())
+        if c.size != s.size:
+            raise ValueError("need one start per contig")
+        n = int(c.size)
+        D = np.zeros(max(n, 1), dtype=np.int64)
+        dist = np.zeros(max(n, 1), dtype=np.float64)
+        self._check(load().kgma_strobe_window_dists(self._h, genome._h, n, _np_ptr(c, C.c_int32) if n else None,
+                                                    _np_ptr(s, C.c_int64) if n else None, _np_ptr(D, C.c_int64), _np_ptr(dist, C.c_double)))
+        return D[:n], dist[:n]
+
+    def strobe_mutation_dists(self, seqs, rates, n_trials: int, seed: int):
+        """kgma_strobe_mutation_dists: (D, dist), each [n_seqs, n_rates, n_trials]: the distance of the reference of set_strobe_ref
+        to the randstrobe counts of api.mutate_seq(seq_i, rates[r], seed=seed, stream=(i, r, t)) -- all len - k + 1 of them, no
+        permanent item --, never materialised on the device.  Keys, layout and errors as mutation_dists."""
+        text, off = self._concat(seqs)
+        ns = off.size - 1
+        rt = np.ascontiguousarray(np.asarray(rates, dtype=np.float64).ravel())
+        nr, nt = int(rt.size), int(n_trials)
+        shape = (ns, max(nr, 0), max(nt, 0))
+        n = int(np.prod(shape))
+        D = np.zeros(max(n, 1), dtype=np.int64)
+        dist = np.zeros(D.size, dtype=np.float64)
+        rt_arg = rt if nr else np.zeros(1, dtype=np.float64)
+        self._check(load().kgma_strobe_mutation_dists(self._h, text, _np_ptr(off, C.c_int64), ns, _np_ptr(rt_arg, C.c_double), nr, nt,
+                                                      C.c_uint64(int(seed) & (2 ** 64 - 1)), _np_ptr(D, C.c_int64), _np_ptr(dist, C.c_double)))
         return D[:n].reshape(shape), dist[:n].reshape(shape)
 
     def step_hits(self, genome: "Genome", mode: int, buff: int = 50, genome_pos: int = 0, flags: int = 0) -> np.ndarray:

@@ -922,6 +922,94 @@ def gen_sub_vs_ref(num_seeds: int = 42, stepsize: float = 0.0125, *, k: int = 6,
     return mutation_dists(RKV, refprep.gen_ref_ws_cons(RKV, k)[0], k, rates=np.arange(0, 1 + 1e-9, stepsize), n_trials=num_seeds, ctx=ctx)
 
 
+# ---- the same for the strobemer engine (kgma_strobe_window_dists, kgma_strobe_mutation_dists) ------------------------------------
+# Strobemer_findGenes says "there is not distance threshold estimation yet"; its default KmerDistThr = 30 is the k-mer engine's.
+
+def strobe_window_dists(genome_or_path, RV, windowsize: int, contig, start, *, s: int, w_min: int, w_max: int, q: int,
+                        n_refs: Optional[int] = None, ctx=None):
+    """(D, dist) of the strobemer scan's windows with start `start[i]` (1-based) of record `contig[i]` (0-based) to the
+    strobemer KFV `RV` (gen_ref_ws_cons_strobe): kgma_strobe_window_dists.  A window is what StrobeGMA!'s count vector holds
+    after step start - 1: W - k + 1 randstrobes (k = w_max + s - 1), for start >= 2 the W - k that start at start ..
+    start + W - k - 1 plus the record's randstrobe W - k + 1, which never leaves.  Valid starts: 1 ... max(1, L - W) on a
+    record of L >= W residues.  dist is on the engine's scale, D / (2 k N^2): the numbers KmerDistThr is compared with.
+    `genome_or_path` as window_dists.  Sets the context's reference to (RV, windowsize)."""
+    ctx = ctx or default_context()
+    ctx.set_strobe_ref(s, w_min, w_max, q, np.asarray(RV, dtype=np.float64), int(windowsize), 1.0, n_refs)
+    g, owned = _calib_subject(ctx, genome_or_path)
+    try:
+        return ctx.strobe_window_dists(g, contig, start)
+    finally:
+        if owned:
+            g.free()
+
+
+def estimate_strobe_threshold_from_genome(genome_or_path, RV, windowsize, *, s: int, w_min: int, w_max: int, q: int,
+                                          n_samples: int = 100_000, seed: int = 42, buffer: float = 0,
+                                          quantile: Optional[float] = None, off_lattice: bool = True, n_refs=None, ctx=None):
+    """estimate_threshold_from_genome for the strobemer engine, by its rules: math.fsum(d) / n - buffer over the distances of
+    `n_samples` of the genome's own windows (all of them when it has no more), or with quantile=q (0 < q <= 1) the
+    ceil(q n)-th smallest minus `buffer`; then off_lattice_threshold on the engine's scale 2 k N^2, k = w_max + s - 1.  The
+    windows are drawn by sample_window_starts(lens, W + 1, ...): windows of W + 1 residues have exactly the scan's valid starts
+    1 .. L - W (a record of exactly W residues has its first window only, which the scan never tests: it is not drawn).
+    buffer defaults to 0, not to the 8 of estimate_optimal_threshold: that figure was chosen for the k-mer distance, the
+    strobemer distance lives on another lattice (4^(2s) bins, scale 2 (w_max + s - 1) N^2), and nothing has been measured
+    for it.  Pass the result as KmerDistThr of Strobemer_findGenes.  Sets the context's reference."""
+    if quantile is not None and not (0.0 < float(quantile) <= 1.0):
+        raise ValueError(f"quantile = {quantile} is not in (0, 1]")
+    W = int(windowsize)
+    ctx = ctx or default_context()
+    ctx.set_strobe_ref(s, w_min, w_max, q, np.asarray(RV, dtype=np.float64), W, 1.0, None if n_refs is None else int(n_refs))
+    g, owned = _calib_subject(ctx, genome_or_path)
+    try:
+        lens = [g.contig_len(c) for c in range(g.n_contigs)]
+        contig, start = sample_window_starts(lens, W + 1, n_samples, seed)
+        if contig.size == 0:
+            raise ValueError(f"no record holds a tested window of {W} residues (none is longer than {W})")
+        _D, d = ctx.strobe_window_dists(g, contig, start)
+        n = int(d.size)
+        if quantile is None:
+            est = math.fsum(d.tolist()) / n - buffer
+        else:
+            est = float(np.sort(d)[math.ceil(float(quantile) * n) - 1]) - buffer
+        return off_lattice_threshold(est, ctx.kfv_scale(1)) if off_lattice else est
+    finally:
+        if owned:
+            g.free()
+
+
+def strobe_mutation_dists(ref_path_or_seqs, RV, *, s: int, w_min: int, w_max: int, q: int, rates=None, n_trials: int = 42,
+                          seed: int = 42, n_refs: Optional[int] = None, ctx=None) -> np.ndarray:
+    """mutation_dists for the strobemer engine: for every sequence i, rate r and trial t the distance of the strobemer KFV `RV`
+    to the randstrobe counts of mutate_seq(seq_i, rates[r], seed=seed, stream=(i, r, t)), on the engine's scale
+    1 / (2 (w_max + s - 1)), as a Float64 array [n_seqs, n_rates, n_trials].  One device call (kgma_strobe_mutation_dists); the
+    copies are never materialised.  rates: default 0:0.0125:1.  Sets the context's reference."""
+    if rates is None:
+        rates = np.arange(0, 1 + 1e-9, 0.0125)
+    rates = np.asarray(rates, dtype=np.float64)
+    seqs = [r.sequence for r in read_fasta(ref_path_or_seqs)] if isinstance(ref_path_or_seqs, str) else [_seq_bytes(x) for x in ref_path_or_seqs]
+    ctx = ctx or default_context()
+    # (the window size plays no part here: a sequence's own length decides its number of randstrobes)
+    ctx.set_strobe_ref(s, w_min, w_max, q, np.asarray(RV, dtype=np.float64), int(w_max) + int(s), 1.0, n_refs)
+    return ctx.strobe_mutation_dists(seqs, rates, n_trials, seed)[1]
+
+
+def test_strobe_2_mer_dists(Rkv: str, num_seeds: int = 42, stepsize: float = 0.0125, *, s: int = 2, w_min: int = 3, w_max: int = 5,
+                            q: int = 5, ctx=None) -> np.ndarray:
+    """`test_strobe_2_mer_dists` (src/StrobemerGMA/MonteCarloBenchmark.jl:2-23) with the reference's signature, finished: RKV
+    is the randstrobe count of the file's FIRST record (N = 1; the engine's ungapped_strobe_2_mer_count -- the reference's
+    `strobe_2_mer_count` is not defined), and that record stands for the `vgene` the reference leaves undefined.  Returns a Float64 array [n_rates, num_seeds], rates 0:stepsize:1 (column t stands for the reference's seed
+    t + 1; row 0, rate 0, is the record's distance to itself: 0).  Values are on the engine's scale 1 / (2 k), k = w_max + s - 1;
+    the reference multiplies by 1 / (2 getK(RKV)) = 1 / (4 s) instead: its figure is this one times k / (2 s)."""
+    rec = read_fasta(Rkv)[0].sequence
+    RKV = refprep.ungapped_strobe_2_mer_count(rec, s, w_min, w_max, q)
+    d = strobe_mutation_dists([rec], RKV, s=s, w_min=w_min, w_max=w_max, q=q, rates=np.arange(0, 1 + 1e-9, stepsize),
+                              n_trials=num_seeds, n_refs=1, ctx=ctx)
+    return d[0]
+
+
+test_strobe_2_mer_dists.__test__ = False          # (the reference's name; not a pytest test)
+
+
 def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
     """src/ExactMatch.jl:146-158: the full description line of every record -> the summed length of the records BEFORE it
     (what the scan reports as GenomePos).  Given an open device genome the headers and lengths come from its handle;
