@@ -702,6 +702,53 @@ int kgma_strobe_mutation_dists(kgma_ctx *ctx, const uint8_t *seqs, const int64_t
                                const double *rates, int32_t n_rates, int32_t n_trials, uint64_t seed,
                                int64_t *D_out, double *dist_out /* [n_seqs][n_rates][n_trials], either may be NULL */);
 
+/* ---- gene assignment: which reference gene is each hit closest to? (kgma_assign.hip, kgma_assign.cpp) ----
+ * Every query (a hit's residues) is aligned against every reference of a batch under the hit aligner's model -- the one of
+ * kgma_host_semiglobal_cigar(reference, query): Gotoh affine gaps, the reference global, the query's ends free, a gap of length L
+ * scoring gap_open_score + L * gap_extend_score, EDNAFULL over A/C/G/T/N, any byte outside A/C/G/T in either case counting as N
+ * (there is no KGMA_E_BADBASE here).  A score-only kernel fills the n_queries x n_refs matrix; per query the `top` references are
+ * chosen -- higher score first, lower reference index among equal scores -- and only those pairs are aligned with a traceback
+ * (match, then deletion, then insertion; a gap extended where extending and opening tie), whose columns are counted:
+ * out[q * top + t] describes query q's (t+1)-th best reference.  The CIGAR letters mean what kgma_host_semiglobal_cigar writes
+ * ('=' / 'X': a reference residue against an equal / other query residue, N never equal; 'I': a reference residue against a gap;
+ * 'D': a query residue against a gap), and the counts are those of its CIGAR for that pair.
+ *
+ * kgma_assign_seqs takes the queries from the host (query q = queries[query_offsets[q] .. query_offsets[q + 1])), kgma_assign_ranges
+ * from the resident genome (query q = residues lo[q] .. hi[q], 1-based inclusive, of record contig[q], 0-based).  The references
+ * are refs[ref_offsets[r] .. ref_offsets[r + 1]).  `scores`, when not NULL, receives the whole matrix, row-major.
+ * n_queries == 0: KGMA_OK.  KGMA_E_ARG: a null pointer, n_refs < 1, top < 1 or top > n_refs, an empty reference or query,
+ * offsets that decrease, a range outside its record, a positive gap score.  KGMA_E_UNSUPPORTED: a reference or query longer than
+ * 8191 residues (KGMA_ASSIGN_MAX_LEN), more than 2^30 pairs in one call, or gap scores with
+ * -gap_open_score - 8192 * gap_extend_score > 2^27: beyond that a cell could come within reach of the kernel's "no alignment"
+ * sentinel, -2^29.  kgma_last_error names the offending item.  Nothing stays allocated after the call, whatever it returns;
+ * it needs no kgma_set_refs. */
+#define KGMA_ASSIGN_MAX_LEN 8191
+typedef struct {
+    int32_t ref;        /* 0-based index into the reference batch */
+    int32_t score;      /* optimum semi-global score of (reference global, query ends free) */
+    int32_t n_eq, n_x;  /* '=' and 'X' columns */
+    int32_t n_ins;      /* 'I' columns: a reference residue against a gap */
+    int32_t n_del;      /* 'D' columns NOT in a leading or trailing D run (those are the query's free overhang) */
+    int32_t q_lo, q_hi; /* 1-based query positions left after removing the leading / trailing D runs; q_hi < q_lo: none */
+} kgma_assignment;
+int kgma_assign_seqs(kgma_ctx *ctx, const uint8_t *refs, const int64_t *ref_offsets /* n_refs + 1 */, int32_t n_refs,
+                     const uint8_t *queries, const int64_t *query_offsets /* n_queries + 1 */, int64_t n_queries,
+                     int32_t gap_open_score, int32_t gap_extend_score, int32_t top,
+                     kgma_assignment *out /* n_queries * top */, int32_t *scores /* n_queries * n_refs, or NULL */);
+int kgma_assign_ranges(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *refs, const int64_t *ref_offsets /* n_refs + 1 */,
+                       int32_t n_refs, int64_t n_queries, const int32_t *contig /* 0-based */, const int64_t *lo,
+                       const int64_t *hi /* 1-based inclusive */, int32_t gap_open_score, int32_t gap_extend_score, int32_t top,
+                       kgma_assignment *out, int32_t *scores);
+/* The last assignment call of the context: device time of its score launches and of its trace launches (hipEvents), the pairs
+ * scored, their DP cells (sum of reference length x query length), the pairs traced and the kernel launches.  All zero before the
+ * first call and after a call that failed or had no queries. */
+typedef struct {
+    double score_ms, trace_ms;
+    int64_t n_pairs, n_cells, n_traced;
+    int32_t n_score_launches, n_trace_launches;
+} kgma_assign_stats;
+int kgma_get_assign_stats(kgma_ctx *ctx, kgma_assign_stats *out);
+
 /* kgma_repack_scan_hits in two halves, for step loops that have other work to queue while the GPU scans
  * (bench.py with several ranks: the hit exchange of step i overlaps the scan of step i+1).  kgma_step_begin
  * hands the step to a helper thread owned by the context and returns at once; kgma_step_end waits for it

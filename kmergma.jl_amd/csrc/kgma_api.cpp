@@ -36,6 +36,7 @@
 #include "kgma_device.h"
 #include "kgma_chain.h"
 #include "kgma_twobit.h"
+#include "kgma_assign.h"
 
 namespace kgma {
 hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs,
@@ -407,8 +408,21 @@ struct kgma_ctx {
     int64_t tile_windows = KGMA_TILE_WINDOWS;
     bool have_dists = false;
     kgma_stats stats{};
+    kgma_assign_stats assign_stats{};        // the last kgma_assign_seqs / kgma_assign_ranges (kgma_assign.cpp)
     int64_t device_bytes = 0;
 };
+
+// kgma_assign.h: the view kgma_assign.cpp has of the two structs above
+namespace kgma {
+int ctx_fail(kgma_ctx *ctx, int code, const char *message)
+{
+    if (ctx) ctx->err = message;
+    return code;
+}
+void ctx_device(const kgma_ctx *ctx, int *device, hipStream_t *stream) { *device = ctx->device; *stream = ctx->stream; }
+kgma_assign_stats *ctx_assign_stats(kgma_ctx *ctx) { return &ctx->assign_stats; }
+GenomeText genome_text(const kgma_genome *g) { return GenomeText{g->d_ascii, g->d_cd, g->cd.data(), g->n_contigs}; }
+}  // namespace kgma
 
 namespace {
 

@@ -1,6 +1,7 @@
 // kgma_device.h -- structures shared between the host side (kgma_api.cpp) and the gfx950 kernels
 // (kgma_kernels.hip).  Internal to libkgma; the public boundary is include/kgma.h.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace kgma {
@@ -424,7 +425,38 @@ struct StrobeCalibArgs {
     int32_t s, w_min, w_max, pad;
     uint32_t zero[4];             // strobe_zero_mask
 };
+// Gene assignment (kgma_assign.hip; kgma_assign_seqs, kgma_assign_ranges): queries x references, semi-global scores, then the
+// column counts of every query's chosen references.  One launch covers the queries of one LENGTH CLASS (its LDS is sized by
+// max_n, the longest query of the class) and a chunk of its pairs / jobs.
+struct AssignArgs {
+    const uint8_t *text;          // range source: the genome's residue text; sequence source: the uploaded queries
+    const ContigDesc *cd;         // range source: the genome's record table
+    const int32_t *q_contig;      // range source: [n_queries] record (0-based)
+    const int64_t *q_pos;         // range source: [n_queries] first residue (1-based); sequence source: byte offset in `text`
+    const int32_t *q_n;           // [n_queries] residues, 1 ... max_n for the queries of this launch
+    const uint8_t *refs;          // the references' residues, one after the other
+    const int64_t *ref_off;       // [n_refs + 1]
+    int32_t n_refs;
+    int32_t go, ge;               // penalties (positive)
+    int32_t max_n;
+    int64_t first;                // score: first pair of the launch (pair p: query items[p / n_refs], reference p % n_refs);
+                                  // trace: first job of the launch
+    const int32_t *items;         // score: the class's queries
+    int32_t *scores;              // score: [n_queries][n_refs]
+    const int32_t *job_q, *job_r; // trace: query and reference of every job
+    uint8_t *trace;               // trace: trace_stride bytes per workgroup of the launch
+    int64_t trace_stride;
+    int32_t *out;                 // trace: 8 int32 per job = kgma_assignment
+};
+constexpr int KGMA_ASSIGN_LEN_MAX = 8191;                      // longest query or reference (LDS rows of the wavefront)
+constexpr int KGMA_ASSIGN_CLASS_BOUNDS[3] = {255, 1023, KGMA_ASSIGN_LEN_MAX};   // longest query of each length class
+constexpr int64_t KGMA_ASSIGN_PAIRS_PER_LAUNCH = 1 << 16;      // pairs of one score launch (= its grid)
+constexpr int64_t KGMA_ASSIGN_TRACE_BYTES = (int64_t)1 << 30;  // trace bytes of one trace launch at most (one job at least)
+int64_t assign_trace_bytes(int m, int n);
+size_t assign_lds_bytes(int max_n);
+
 #ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_H                   // (host files that do not see the HIP runtime include this header too)
+hipError_t launch_assign(const AssignArgs &a, int source /* 0: genome ranges, 1: uploaded sequences */, bool trace, int grid, hipStream_t st);
 hipError_t launch_calib(const CalibArgs &a, int source /* 0: windows, 1: mutated copies */, int grid, hipStream_t st);
 hipError_t launch_strobe_calib(const StrobeCalibArgs &a, int source, int grid, hipStream_t st);
 #endif

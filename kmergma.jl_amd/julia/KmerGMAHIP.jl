@@ -18,7 +18,7 @@
 
 module KmerGMAHIP
 
-using KmerGMA, FASTX, BioSequences, BioAlignments, Mmap
+using KmerGMA, FASTX, BioSequences, BioAlignments, Mmap, Printf
 
 const libkgma = get(ENV, "KGMA_LIB", joinpath(@__DIR__, "..", "libkgma.so"))
 
@@ -626,7 +626,71 @@ function strobe_mutation_dists(ctx::Context, seqs::Vector{String}, rates::Vector
     return D, dist
 end
 
+# ---- gene assignment (kgma_assign_seqs, kgma_assign_ranges) ---------------------------------------------------------------------
+"One reference a hit was aligned to: mirrors kgma_assignment (include/kgma.h), `ref` 0-based as in the C ABI."
+struct KgmaAssignment
+    ref::Int32; score::Int32; n_eq::Int32; n_x::Int32; n_ins::Int32; n_del::Int32; q_lo::Int32; q_hi::Int32
+end
+const Assignment = NamedTuple{(:ref_id, :ref_index, :score, :identity, :n_eq, :n_x, :n_ins, :n_del, :q_lo, :q_hi),
+                              Tuple{String, Int, Int, Float64, Int, Int, Int, Int, Int, Int}}
+
+function assignment(ids::Vector{String}, a::KgmaAssignment)
+    d = a.n_eq + a.n_x + a.n_ins + a.n_del
+    return Assignment((ids[a.ref + 1], a.ref + 1, a.score, d == 0 ? 0.0 : a.n_eq / d, a.n_eq, a.n_x, a.n_ins, a.n_del, a.q_lo, a.q_hi))
+end
+
+function assign_refs(ref)
+    recs = ref isa String ? open(collect, FASTA.Reader, ref) : ref
+    ids = String[r isa FASTA.Record ? String(FASTA.identifier(r)) : "" for r in recs]
+    seqs = String[r isa FASTA.Record ? String(FASTA.sequence(r)) : String(r) for r in recs]
+    return ids, seqs
+end
+
+pack_seqs(seqs::Vector{String}) = (Vector{UInt8}(join(seqs)), Int64[0; cumsum(Int64[ncodeunits(s) for s in seqs])])
+
+"""
+    assignGenes(hits, ref; top = 1, gap_open_score = -69, gap_extend_score = -1, annotate = false) -> Vector{Vector{Assignment}}
+Names every hit's nearest reference genes: every hit record's body against every reference (a FASTA path or records) under the
+hit aligner's model on the device, per hit its `top` references (higher score first, the earlier reference among equal scores)
+with the column counts of that alignment; `ref_index` is 1-based here.  `annotate = true` returns copies of the records with
+` | Ref = <id> | Identity = <x.xxx>` appended to the description instead.
+"""
+function assignGenes(hits::Vector{FASTA.Record}, ref; top::Integer = 1, gap_open_score::Integer = -69, gap_extend_score::Integer = -1,
+                     annotate::Bool = false, ctx::Context = default_context())
+    ids, refs = assign_refs(ref)
+    isempty(hits) && return annotate ? FASTA.Record[] : Vector{Assignment}[]
+    rtext, roff = pack_seqs(refs)
+    qtext, qoff = pack_seqs(String[String(FASTA.sequence(h)) for h in hits])
+    out = Matrix{KgmaAssignment}(undef, top, length(hits))            # [t, hit]: the C ABI's out[hit * top + t]
+    check(ctx, ccall((:kgma_assign_seqs, libkgma), Cint,
+                     (Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int64}, Int32, Ptr{UInt8}, Ptr{Int64}, Int64, Int32, Int32, Int32, Ptr{KgmaAssignment}, Ptr{Int32}),
+                     ctx.h, rtext, roff, length(refs), qtext, qoff, length(hits), gap_open_score, gap_extend_score, top, out, C_NULL))
+    res = [Assignment[assignment(ids, out[t, i]) for t in 1:top] for i in eachindex(hits)]
+    annotate || return res
+    return [FASTA.Record(string(FASTA.description(h), " | Ref = ", a[1].ref_id, " | Identity = ", @sprintf("%.3f", a[1].identity)),
+                         FASTA.sequence(h)) for (h, a) in zip(hits, res)]
+end
+
+"""
+    assign_ranges(g, contig, lo, hi, ref; top = 1, ...) -> Vector{Vector{Assignment}}
+The same for ranges lo[i]:hi[i] (1-based, inclusive) of record contig[i] (0-based, as in the C ABI) of an open DeviceGenome.
+"""
+function assign_ranges(g::DeviceGenome, contig::Vector{Int32}, lo::Vector{Int64}, hi::Vector{Int64}, ref; top::Integer = 1,
+                       gap_open_score::Integer = -69, gap_extend_score::Integer = -1)
+    ctx = g.ctx
+    n = length(contig)
+    length(lo) == n == length(hi) || throw(ArgumentError("need one lo and one hi per contig"))
+    ids, refs = assign_refs(ref)
+    rtext, roff = pack_seqs(refs)
+    out = Matrix{KgmaAssignment}(undef, top, n)
+    check(ctx, ccall((:kgma_assign_ranges, libkgma), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int64}, Int32, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Int32, Int32, Int32,
+                      Ptr{KgmaAssignment}, Ptr{Int32}),
+                     ctx.h, g.h, rtext, roff, length(refs), n, contig, lo, hi, gap_open_score, gap_extend_score, top, out, C_NULL))
+    return [Assignment[assignment(ids, out[t, i]) for t in 1:top] for i in 1:n]
+end
+
 export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, HumanRSSV, HumanRSSD, Context
-export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists
+export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists, assignGenes, assign_ranges
 
 end # module

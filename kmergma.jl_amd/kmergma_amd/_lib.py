@@ -39,7 +39,9 @@ EXPORTS = [
     "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
     "kgma_get_block_sums", "kgma_genome_from_2bit_file", "kgma_get_2bit_unpack_ms", "kgma_twobit_inspect",
     "kgma_window_dists", "kgma_mutation_dists", "kgma_strobe_window_dists", "kgma_strobe_mutation_dists",
+    "kgma_assign_seqs", "kgma_assign_ranges", "kgma_get_assign_stats",
 ]
+ASSIGN_MAX_LEN = 8191                # KGMA_ASSIGN_MAX_LEN
 TWOBIT_NOMASK = 1                    # KGMA_2BIT_NOMASK
 TWOBIT_SIGNATURE = b"\x43\x27\x41\x1a"  # the first four bytes of a .2bit file in this machine's byte order
 FILTER_FORM_PRESUMMED = 1 << 16      # kgma_filter_stats.form: the filter read the block sums the step's pack wrote (KGMA_FUSE_SUMS)
@@ -94,6 +96,11 @@ class KgmaFilterStats(C.Structure):
                 ("positions", C.c_int64), ("total_windows", C.c_int64), ("bound", C.c_int64), ("filter_ms", C.c_double)]
 
 
+class KgmaAssignStats(C.Structure):
+    _fields_ = [("score_ms", C.c_double), ("trace_ms", C.c_double), ("n_pairs", C.c_int64), ("n_cells", C.c_int64),
+                ("n_traced", C.c_int64), ("n_score_launches", C.c_int32), ("n_trace_launches", C.c_int32)]
+
+
 HIT_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("cmi", "<i8"), ("lo", "<i8"), ("hi", "<i8"),
                       ("genome_pos", "<i8"), ("dist", "<f8"), ("D", "<i8"), ("flags", "<u4"), ("reserved", "<u4")])
 
@@ -103,6 +110,9 @@ DIP_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("start", "<i8"), ("end
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("contig", "<i4"), ("start", "<i8")])
 
 MOTIF_HIT_DTYPE = np.dtype([("motif", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("mismatches", "<i4"), ("reserved", "<i4")])
+
+ASSIGNMENT_DTYPE = np.dtype([("ref", "<i4"), ("score", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"),
+                             ("q_lo", "<i4"), ("q_hi", "<i4")])   # kgma_assignment
 
 ALIGN_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                        C.POINTER(C.c_int64), C.POINTER(C.c_int64))
@@ -218,6 +228,9 @@ def load():
     L.kgma_mutation_dists.argtypes = [vp, i32, C.c_char_p, P(i64), i64, P(dbl), i32, i32, u64, P(i64), P(dbl)]
     L.kgma_strobe_window_dists.argtypes = [vp, vp, i64, P(i32), P(i64), P(i64), P(dbl)]
     L.kgma_strobe_mutation_dists.argtypes = [vp, C.c_char_p, P(i64), i64, P(dbl), i32, i32, u64, P(i64), P(dbl)]
+    L.kgma_assign_seqs.argtypes = [vp, C.c_char_p, P(i64), i32, C.c_char_p, P(i64), i64, i32, i32, i32, vp, P(i32)]
+    L.kgma_assign_ranges.argtypes = [vp, vp, C.c_char_p, P(i64), i32, i64, P(i32), P(i64), P(i64), i32, i32, i32, vp, P(i32)]
+    L.kgma_get_assign_stats.argtypes = [vp, P(KgmaAssignStats)]
     L.kgma_stream.argtypes = [vp]
     L.kgma_stream.restype = vp
     L.kgma_scan_kernel_name.argtypes = [vp]
@@ -889,6 +902,45 @@ class Context:
         self._check(load().kgma_strobe_mutation_dists(self._h, text, _np_ptr(off, C.c_int64), ns, _np_ptr(rt_arg, C.c_double), nr, nt,
                                                       C.c_uint64(int(seed) & (2 ** 64 - 1)), _np_ptr(D, C.c_int64), _np_ptr(dist, C.c_double)))
         return D[:n].reshape(shape), dist[:n].reshape(shape)
+
+    def assign_seqs(self, refs, queries, gap_open: int = -69, gap_extend: int = -1, top: int = 1):
+        """kgma_assign_seqs: every query (bytes) against every reference (bytes) under the hit aligner's model.  Returns
+        (out, scores): out is an ASSIGNMENT_DTYPE array [n_queries, top] -- per query its `top` best references, higher score
+        first, lower index among equal scores, with the column counts of that alignment --, scores the int32 matrix
+        [n_queries, n_refs]."""
+        rtext, roff = self._concat(refs)
+        qtext, qoff = self._concat(queries)
+        nr, nq, top = roff.size - 1, qoff.size - 1, int(top)
+        out = np.zeros((nq, max(top, 0)), dtype=ASSIGNMENT_DTYPE)
+        scores = np.zeros((nq, max(nr, 0)), dtype=np.int32)
+        self._check(load().kgma_assign_seqs(self._h, rtext, _np_ptr(roff, C.c_int64), nr, qtext, _np_ptr(qoff, C.c_int64), nq,
+                                            int(gap_open), int(gap_extend), top, out.ctypes.data if out.size else None,
+                                            _np_ptr(scores, C.c_int32) if scores.size else None))
+        return out, scores
+
+    def assign_ranges(self, genome: "Genome", refs, contig, lo, hi, gap_open: int = -69, gap_extend: int = -1, top: int = 1):
+        """kgma_assign_ranges: as assign_seqs, the queries being residues lo[i] .. hi[i] (1-based inclusive) of record contig[i]
+        (0-based) of the resident genome."""
+        rtext, roff = self._concat(refs)
+        c = np.ascontiguousarray(np.asarray(contig, dtype=np.int32).ravel())
+        a = np.ascontiguousarray(np.asarray(lo, dtype=np.int64).ravel())
+        b = np.ascontiguousarray(np.asarray(hi, dtype=np.int64).ravel())
+        if not (c.size == a.size == b.size):
+            raise ValueError("need one lo and one hi per contig")
+        nr, nq, top = roff.size - 1, int(c.size), int(top)
+        out = np.zeros((nq, max(top, 0)), dtype=ASSIGNMENT_DTYPE)
+        scores = np.zeros((nq, max(nr, 0)), dtype=np.int32)
+        self._check(load().kgma_assign_ranges(self._h, genome._h, rtext, _np_ptr(roff, C.c_int64), nr, nq,
+                                              _np_ptr(c, C.c_int32) if nq else None, _np_ptr(a, C.c_int64) if nq else None,
+                                              _np_ptr(b, C.c_int64) if nq else None, int(gap_open), int(gap_extend), top,
+                                              out.ctypes.data if out.size else None, _np_ptr(scores, C.c_int32) if scores.size else None))
+        return out, scores
+
+    def assign_stats(self) -> dict:
+        """kgma_get_assign_stats: device times and counts of the last assign_seqs / assign_ranges."""
+        s = KgmaAssignStats()
+        self._check(load().kgma_get_assign_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in KgmaAssignStats._fields_}
 
     def step_hits(self, genome: "Genome", mode: int, buff: int = 50, genome_pos: int = 0, flags: int = 0) -> np.ndarray:
         """repack + scan + hits in ONE library call (kgma_repack_scan_hits); returns the hits as a structured

@@ -35,7 +35,7 @@ from __future__ import annotations
 
 import logging
 import math
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -1008,6 +1008,99 @@ def test_strobe_2_mer_dists(Rkv: str, num_seeds: int = 42, stepsize: float = 0.0
 
 
 test_strobe_2_mer_dists.__test__ = False          # (the reference's name; not a pytest test)
+
+
+# ---- gene assignment: which reference gene is each hit closest to? (kgma_assign_seqs, kgma_assign_ranges) -----------------------
+class Assignment(NamedTuple):
+    """One reference a hit was aligned to (the hit aligner's model, reference global, the hit's ends free)."""
+    ref_id: str          # the reference's FASTA identifier ("" for references given as bare sequences)
+    ref_index: int       # 0-based position in the reference batch
+    score: int           # optimum semi-global score
+    identity: float      # n_eq / (n_eq + n_x + n_ins + n_del); 0.0 when the alignment has no such column
+    n_eq: int            # '=' columns
+    n_x: int             # 'X' columns
+    n_ins: int           # 'I' columns: a reference residue against a gap
+    n_del: int           # 'D' columns inside the alignment (the hit's free overhang at either end is not counted)
+    q_lo: int            # the hit's residues q_lo .. q_hi (1-based) are what lies between the two overhangs
+    q_hi: int
+
+
+def _assignment(ref_id: str, ref: int, score: int, n_eq: int, n_x: int, n_ins: int, n_del: int, q_lo: int, q_hi: int) -> Assignment:
+    d = n_eq + n_x + n_ins + n_del
+    return Assignment(ref_id, ref, score, n_eq / d if d else 0.0, n_eq, n_x, n_ins, n_del, q_lo, q_hi)
+
+
+def _assign_refs(ref_path_or_seqs):
+    """(identifiers, sequences) of a reference FASTA path or a list of Record / bytes / str."""
+    recs = read_fasta(ref_path_or_seqs) if isinstance(ref_path_or_seqs, str) else list(ref_path_or_seqs)
+    ids, seqs = [], []
+    for r in recs:
+        if isinstance(r, Record):
+            parts = r.description.split(None, 1)
+            ids.append(parts[0] if parts else "")
+        else:
+            ids.append("")
+        seqs.append(_seq_bytes(r))
+    if not seqs:
+        raise ValueError("no reference sequences")
+    return ids, seqs
+
+
+def _assignments(ids, out) -> list:
+    return [[_assignment(ids[int(a["ref"])], *(int(a[f]) for f in ("ref", "score", "n_eq", "n_x", "n_ins", "n_del", "q_lo", "q_hi")))
+             for a in row] for row in out]
+
+
+def annotated_header(description: str, best: Assignment) -> str:
+    """A hit's header with its best reference appended after the last existing field (a minus-strand hit's ` | Strand = -`
+    included): ` | Ref = <id> | Identity = <3 decimals>`."""
+    return f"{description} | Ref = {best.ref_id} | Identity = {best.identity:.3f}"
+
+
+def assignGenes(hits, ref_path_or_seqs, *, top: int = 1, gap_open_score: int = -69, gap_extend_score: int = -1,
+                annotate: bool = False, ctx=None):
+    """Names every hit's nearest reference genes.  `hits`: the records findGenes / findGenes_cluster_mode / Strobemer_findGenes
+    return (or bare sequences); their bodies are the queries -- a minus-strand hit's body is already in reference orientation,
+    so both strands work without coordinates.  `ref_path_or_seqs`: a FASTA path or a list of Record / bytes / str.  Every hit
+    is scored against every reference on the device (kgma_assign_seqs), its `top` references -- higher score first, the earlier
+    reference among equal scores -- are aligned with a traceback, and per hit the list of their Assignment tuples is returned.
+    annotate=True returns instead copies of the records with ` | Ref = <id> | Identity = <x.xxx>` of the best reference
+    appended to the header (hits must be records then)."""
+    hits = list(hits)
+    ids, seqs = _assign_refs(ref_path_or_seqs)
+    if not 1 <= int(top) <= len(seqs):
+        raise ValueError(f"top = {top} is not one of 1 .. {len(seqs)} (the number of references)")
+    if annotate and not all(isinstance(h, Record) for h in hits):
+        raise TypeError("annotate=True needs hit records")
+    queries = [_seq_bytes(h) for h in hits]
+    if not hits:
+        return []
+    ctx = ctx or default_context()
+    out, _ = ctx.assign_seqs(seqs, queries, gap_open_score, gap_extend_score, int(top))
+    res = _assignments(ids, out)
+    if annotate:
+        return [Record(annotated_header(h.description, a[0]), h.sequence) for h, a in zip(hits, res)]
+    return res
+
+
+def assign_ranges(genome_or_path, contig, lo, hi, ref_path_or_seqs, *, top: int = 1, gap_open_score: int = -69,
+                  gap_extend_score: int = -1, ctx=None) -> list:
+    """assignGenes for ranges of a resident genome, which never leave the device: query i is residues lo[i] .. hi[i] (1-based
+    inclusive) of record contig[i] (0-based) of `genome_or_path` -- a FASTA or .2bit path, or a device genome that is already
+    open (it stays open), as for motifMatch.  Per range the list of its `top` Assignment tuples (kgma_assign_ranges)."""
+    if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
+        raise TypeError("Invalid subject sequence type")
+    ids, seqs = _assign_refs(ref_path_or_seqs)
+    if not 1 <= int(top) <= len(seqs):
+        raise ValueError(f"top = {top} is not one of 1 .. {len(seqs)} (the number of references)")
+    ctx = ctx or default_context()
+    g, _src, owned = _open_subject(ctx, genome_or_path)
+    try:
+        out, _ = ctx.assign_ranges(g, seqs, contig, lo, hi, gap_open_score, gap_extend_score, int(top))
+    finally:
+        if owned:
+            g.free()
+    return _assignments(ids, out)
 
 
 def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
