@@ -749,6 +749,67 @@ typedef struct {
 } kgma_assign_stats;
 int kgma_get_assign_stats(kgma_ctx *ctx, kgma_assign_stats *out);
 
+/* ---- all-pairs k-mer distances (kgma_kmat.hip, kgma_kmat.cpp) ----
+ * D[a][b] = sum_x (c_a[x] - c_b[x])^2 with c_s = kmer_count(s, k) (src/Kmers.jl:14-28: residues through A0 C1 G2 T3 N3 in either
+ * case, nothing counted for a sequence shorter than k), an exact integer, and dist[a][b] = RN(1 / 2k) * (double)D: bit for bit
+ * kmer_dist(a, b, k) (src/Kmers.jl:54-56).  Both matrices are row-major [n_a][n_b]; either pointer may be NULL.
+ *
+ * kgma_kmer_dist_matrix takes A from the host (sequence i = a[a_off[i] .. a_off[i + 1])); b == NULL means B = A (the symmetric
+ * matrix, zero diagonal; b_off and n_b are ignored).  kgma_kmer_dist_matrix_ranges takes A from the resident genome: residues
+ * lo[i] .. hi[i] (1-based inclusive) of record contig[i] (0-based); hi = lo - 1 is an empty range.  B is always uploaded.
+ * kgma_kmer_nearest / kgma_kmer_nearest_ranges keep the matrix on the device and return per row of A its n_near nearest of B, in
+ * the order (D ascending, index in B ascending): index[n_a][n_near] and D_near[n_a][n_near] (either may be NULL); b == NULL in
+ * kgma_kmer_nearest is B = A as well (a sequence's nearest is then itself, at D = 0).
+ *
+ * Every residue of every sequence is looked up, also of one shorter than k; a byte outside A/C/G/T/N is KGMA_E_BADBASE (the
+ * reference's KeyError), and kgma_last_error names the side, the sequence and the position.  In a genome only the residues inside
+ * a requested range count.  KGMA_E_ARG: a null pointer, k < 1, offsets that decrease, a range outside its record, n_a < 0,
+ * n_b < 1, n_near outside 1 .. min(n_b, KGMA_KMAT_MAX_NEAR).  KGMA_E_UNSUPPORTED: k > 10, a sequence of more than
+ * KGMA_KMAT_MAX_LEN residues (a count must fit 16 bits and D 31), more than 2^30 pairs in one call.  n_a == 0: KGMA_OK.  Nothing
+ * stays allocated after a call, whatever it returns; the calls need no kgma_set_refs and leave references, hits and every
+ * earlier result untouched. */
+#define KGMA_KMAT_MAX_LEN 32767
+#define KGMA_KMAT_MAX_NEAR 128
+int kgma_kmer_dist_matrix(kgma_ctx *ctx, int32_t k, const uint8_t *a, const int64_t *a_off /* n_a + 1 */, int64_t n_a,
+                          const uint8_t *b /* NULL: B = A */, const int64_t *b_off /* n_b + 1 */, int32_t n_b,
+                          int32_t *D, double *dist);
+int kgma_kmer_dist_matrix_ranges(kgma_ctx *ctx, const kgma_genome *genome, int32_t k, int64_t n_a, const int32_t *contig /* 0-based */,
+                                 const int64_t *lo, const int64_t *hi /* 1-based inclusive */, const uint8_t *b, const int64_t *b_off,
+                                 int32_t n_b, int32_t *D, double *dist);
+int kgma_kmer_nearest(kgma_ctx *ctx, int32_t k, const uint8_t *a, const int64_t *a_off, int64_t n_a, const uint8_t *b,
+                      const int64_t *b_off, int32_t n_b, int32_t n_near, int32_t *index, int32_t *D_near);
+int kgma_kmer_nearest_ranges(kgma_ctx *ctx, const kgma_genome *genome, int32_t k, int64_t n_a, const int32_t *contig, const int64_t *lo,
+                             const int64_t *hi, const uint8_t *b, const int64_t *b_off, int32_t n_b, int32_t n_near, int32_t *index,
+                             int32_t *D_near);
+/* The last of the four calls above on the context (a screened assignment counts: it makes one): device time of the matrix launches
+ * (the |c_a|^2 pass and the matrix kernel) and of the select launch (hipEvents), the pairs, the launches, and the form that ran:
+ * form 0 = count tables in LDS (k <= 7), 1 = one table per workgroup in global memory (k >= 8); tile = sequences of B per
+ * workgroup, chunks = workgroups that share a tile.  All zero before the first call and after a call that failed or was empty. */
+typedef struct {
+    double kmat_ms, select_ms;
+    int64_t n_pairs;
+    int32_t n_launches, form, tile, chunks;
+} kgma_kmat_stats;
+int kgma_get_kmat_stats(kgma_ctx *ctx, kgma_kmat_stats *out);
+
+/* kgma_assign_seqs / kgma_assign_ranges with a k-mer prescreen: kgma_kmer_nearest(screen_k, queries, references, n_near) chooses
+ * every query's candidates, the score kernel runs over those n_near pairs per query only, and selection and traceback are as in
+ * the unscreened calls.  out[q * top + t] is the (t+1)-th best AMONG THE CANDIDATES (higher score first, lower reference index
+ * among equal scores); with n_near == n_refs it is the unscreened call's `out`.  cand (n_queries * n_near, or NULL) receives the
+ * candidates' reference indices in (D, index) order, scores (n_queries * n_near, or NULL) their scores in the same order.
+ * 1 <= top <= n_near <= min(n_refs, KGMA_KMAT_MAX_NEAR), 1 <= screen_k <= 10 (KGMA_E_ARG / KGMA_E_UNSUPPORTED as above);
+ * lengths follow KGMA_ASSIGN_MAX_LEN.  The k-mer pass follows kmer_count: a byte outside A/C/G/T/N in a query (inside its range)
+ * or a reference is KGMA_E_BADBASE here, whereas the unscreened calls keep counting such bytes as N.  kgma_get_kmat_stats and
+ * kgma_get_assign_stats both describe the call. */
+int kgma_assign_seqs_screened(kgma_ctx *ctx, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs, const uint8_t *queries,
+                              const int64_t *query_offsets, int64_t n_queries, int32_t gap_open_score, int32_t gap_extend_score,
+                              int32_t top, int32_t screen_k, int32_t n_near, kgma_assignment *out /* n_queries * top */,
+                              int32_t *cand /* n_queries * n_near, or NULL */, int32_t *scores /* n_queries * n_near, or NULL */);
+int kgma_assign_ranges_screened(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs,
+                                int64_t n_queries, const int32_t *contig, const int64_t *lo, const int64_t *hi, int32_t gap_open_score,
+                                int32_t gap_extend_score, int32_t top, int32_t screen_k, int32_t n_near, kgma_assignment *out,
+                                int32_t *cand, int32_t *scores);
+
 /* kgma_repack_scan_hits in two halves, for step loops that have other work to queue while the GPU scans
  * (bench.py with several ranks: the hit exchange of step i overlaps the scan of step i+1).  kgma_step_begin
  * hands the step to a helper thread owned by the context and returns at once; kgma_step_end waits for it

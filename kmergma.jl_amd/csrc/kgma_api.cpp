@@ -409,10 +409,11 @@ struct kgma_ctx {
     bool have_dists = false;
     kgma_stats stats{};
     kgma_assign_stats assign_stats{};        // the last kgma_assign_seqs / kgma_assign_ranges (kgma_assign.cpp)
+    kgma_kmat_stats kmat_stats{};            // the last kgma_kmer_dist_matrix / kgma_kmer_nearest (kgma_kmat.cpp)
     int64_t device_bytes = 0;
 };
 
-// kgma_assign.h: the view kgma_assign.cpp has of the two structs above
+// kgma_assign.h: the view kgma_assign.cpp and kgma_kmat.cpp have of the two structs above
 namespace kgma {
 int ctx_fail(kgma_ctx *ctx, int code, const char *message)
 {
@@ -420,7 +421,9 @@ int ctx_fail(kgma_ctx *ctx, int code, const char *message)
     return code;
 }
 void ctx_device(const kgma_ctx *ctx, int *device, hipStream_t *stream) { *device = ctx->device; *stream = ctx->stream; }
+int ctx_n_cus(const kgma_ctx *ctx) { return ctx->n_cus; }
 kgma_assign_stats *ctx_assign_stats(kgma_ctx *ctx) { return &ctx->assign_stats; }
+kgma_kmat_stats *ctx_kmat_stats(kgma_ctx *ctx) { return &ctx->kmat_stats; }
 GenomeText genome_text(const kgma_genome *g) { return GenomeText{g->d_ascii, g->d_cd, g->cd.data(), g->n_contigs}; }
 }  // namespace kgma
 

@@ -6,6 +6,9 @@
 // every query's top references on the host (the matrix is small: a partial sort per row), run the trace kernel over the chosen
 // pairs -- again per class, in chunks whose trace bytes fit KGMA_ASSIGN_TRACE_BYTES -- and bring the assignments down.  Every
 // device buffer belongs to the call and is freed before it returns.
+//
+// The screened calls (kgma_assign_seqs_screened, kgma_assign_ranges_screened) first ask kgma_kmat.cpp for every query's n_near
+// nearest references by k-mer distance; the matrix then has n_near columns, column c of query q being reference cand[q][c].
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,43 +36,6 @@ int failf(kgma_ctx *ctx, int code, const char *fmt, ...)
     va_end(ap);
     return ctx_fail(ctx, code, buf);
 }
-
-// Everything the call holds on the device, released by the destructor on every path out
-struct DeviceHold {
-    std::vector<void *> mem;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    template <class T>
-    hipError_t alloc(T *&p, size_t count)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(1, count) * sizeof(T));
-        if (e == hipSuccess) mem.push_back(q);
-        p = static_cast<T *>(q);
-        return e;
-    }
-    template <class T>
-    hipError_t upload(T *&p, const T *src, size_t count, hipStream_t st)
-    {
-        hipError_t e = alloc(p, count);
-        if (e == hipSuccess && count) e = hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st);
-        return e;
-    }
-    ~DeviceHold()
-    {
-        for (void *q : mem) (void)hipFree(q);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-};
-
-struct Queries {                      // either source, after validation
-    int source = 1;                   // 0: genome ranges, 1: uploaded sequences
-    GenomeText g{};                   // source 0
-    const int32_t *contig = nullptr;  // source 0
-    const uint8_t *text = nullptr;    // source 1: the bytes [base, base + bytes)
-    int64_t bytes = 0;
-    std::vector<int64_t> pos;         // source 0: first residue (1-based); source 1: offset in `text`
-    std::vector<int32_t> n;
-};
 
 int check_refs(kgma_ctx *ctx, const char *fn, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs, int32_t go, int32_t ge,
                int32_t top, int64_t n_queries, const void *out)
@@ -100,10 +66,12 @@ int check_refs(kgma_ctx *ctx, const char *fn, const uint8_t *refs, const int64_t
         if (e__ != hipSuccess) return failf(ctx, KGMA_E_HIP, "%s: %s failed: %s", fn, #expr, hipGetErrorString(e__)); \
     } while (0)
 
+// cand == nullptr: every reference is a column (n_cols = n_refs); otherwise cand[q * n_cols + c] names column c of query q
 int run(kgma_ctx *ctx, const char *fn, const Queries &Q, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs, int32_t go,
-        int32_t ge, int32_t top, kgma_assignment *out, int32_t *scores)
+        int32_t ge, int32_t top, kgma_assignment *out, int32_t *scores, const int32_t *cand = nullptr, int32_t n_cols = 0)
 {
     const int64_t H = (int64_t)Q.n.size();
+    if (!cand) n_cols = n_refs;
     int device = 0;
     hipStream_t st = nullptr;
     ctx_device(ctx, &device, &st);
@@ -132,7 +100,7 @@ int run(kgma_ctx *ctx, const char *fn, const Queries &Q, const uint8_t *refs, co
     memset(&a, 0, sizeof a);
     uint8_t *d_refs = nullptr, *d_text = nullptr;
     int64_t *d_roff = nullptr, *d_pos = nullptr;
-    int32_t *d_n = nullptr, *d_contig = nullptr, *d_items = nullptr, *d_scores = nullptr;
+    int32_t *d_n = nullptr, *d_contig = nullptr, *d_items = nullptr, *d_scores = nullptr, *d_cand = nullptr;
     A_TRY(hold.upload(d_refs, refs + rbase, (size_t)roff[(size_t)n_refs], st));
     A_TRY(hold.upload(d_roff, roff.data(), roff.size(), st));
     A_TRY(hold.upload(d_pos, Q.pos.data(), (size_t)H, st));
@@ -145,16 +113,17 @@ int run(kgma_ctx *ctx, const char *fn, const Queries &Q, const uint8_t *refs, co
         A_TRY(hold.upload(d_text, Q.text, (size_t)Q.bytes, st));
         a.text = d_text;
     }
-    A_TRY(hold.alloc(d_scores, (size_t)(H * n_refs)));
+    if (cand) A_TRY(hold.upload(d_cand, cand, (size_t)(H * n_cols), st));
+    A_TRY(hold.alloc(d_scores, (size_t)(H * n_cols)));
     for (hipEvent_t &e : hold.ev) A_TRY(hipEventCreate(&e));
     a.q_pos = d_pos; a.q_n = d_n; a.refs = d_refs; a.ref_off = d_roff; a.n_refs = n_refs; a.go = -go; a.ge = -ge;
-    a.scores = d_scores;
+    a.scores = d_scores; a.cand = d_cand; a.n_cols = n_cols;
 
     kgma_assign_stats S{};
     // ---- score pass -------------------------------------------------------------------------------------------
     A_TRY(hipEventRecord(hold.ev[0], st));
     for (int c = 0; c < NC; c++) {
-        const int64_t pairs = (int64_t)items[c].size() * n_refs;
+        const int64_t pairs = (int64_t)items[c].size() * n_cols;
         a.max_n = class_max[c];
         a.items = d_items + item0[c];
         for (int64_t p = 0; p < pairs; p += KGMA_ASSIGN_PAIRS_PER_LAUNCH) {
@@ -166,8 +135,8 @@ int run(kgma_ctx *ctx, const char *fn, const Queries &Q, const uint8_t *refs, co
     A_TRY(hipEventRecord(hold.ev[1], st));
     std::vector<int32_t> own;
     int32_t *mat = scores;
-    if (!mat) { own.resize((size_t)(H * n_refs)); mat = own.data(); }
-    A_TRY(hipMemcpyAsync(mat, d_scores, (size_t)(H * n_refs) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (!mat) { own.resize((size_t)(H * n_cols)); mat = own.data(); }
+    A_TRY(hipMemcpyAsync(mat, d_scores, (size_t)(H * n_cols) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     A_TRY(hipStreamSynchronize(st));
 
     // ---- selection: per query the `top` references, higher score first, lower index among equal scores ------------
@@ -175,16 +144,18 @@ int run(kgma_ctx *ctx, const char *fn, const Queries &Q, const uint8_t *refs, co
     std::vector<int32_t> job_q, job_r;
     std::vector<int64_t> job_slot;
     int64_t job0[NC + 1];
-    std::vector<int32_t> order((size_t)n_refs);
+    std::vector<int32_t> order((size_t)n_cols);
     for (int c = 0; c < NC; c++) {
         job0[c] = (int64_t)job_q.size();
         for (int32_t q : items[c]) {
-            const int32_t *row = mat + (int64_t)q * n_refs;
+            const int32_t *row = mat + (int64_t)q * n_cols;
+            const int32_t *name = cand ? cand + (int64_t)q * n_cols : nullptr;     // a column's reference (the column itself without)
             std::iota(order.begin(), order.end(), 0);
-            std::partial_sort(order.begin(), order.begin() + top, order.end(),
-                              [row](int32_t x, int32_t y) { return row[x] != row[y] ? row[x] > row[y] : x < y; });
+            std::partial_sort(order.begin(), order.begin() + top, order.end(), [row, name](int32_t x, int32_t y) {
+                return row[x] != row[y] ? row[x] > row[y] : name ? name[x] < name[y] : x < y;
+            });
             for (int32_t t = 0; t < top; t++) {
-                job_q.push_back(q); job_r.push_back(order[(size_t)t]); job_slot.push_back((int64_t)q * top + t);
+                job_q.push_back(q); job_r.push_back(name ? name[order[(size_t)t]] : order[(size_t)t]); job_slot.push_back((int64_t)q * top + t);
             }
         }
     }
@@ -231,31 +202,23 @@ int run(kgma_ctx *ctx, const char *fn, const Queries &Q, const uint8_t *refs, co
     S.score_ms = ms;
     A_TRY(hipEventElapsedTime(&ms, hold.ev[2], hold.ev[3]));
     S.trace_ms = ms;
-    S.n_pairs = H * n_refs;
+    S.n_pairs = H * n_cols;
     S.n_traced = J;
-    int64_t sum_n = 0;
-    for (int32_t n : Q.n) sum_n += n;
-    S.n_cells = sum_n * roff[(size_t)n_refs];
+    if (cand) {
+        for (int64_t p = 0; p < H * n_cols; p++) S.n_cells += (int64_t)Q.n[(size_t)(p / n_cols)] * (roff[(size_t)cand[p] + 1] - roff[(size_t)cand[p]]);
+    } else {
+        int64_t sum_n = 0;
+        for (int32_t n : Q.n) sum_n += n;
+        S.n_cells = sum_n * roff[(size_t)n_refs];
+    }
     *ctx_assign_stats(ctx) = S;
     return KGMA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int kgma_assign_seqs(kgma_ctx *ctx, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs, const uint8_t *queries,
-                     const int64_t *query_offsets, int64_t n_queries, int32_t gap_open_score, int32_t gap_extend_score, int32_t top,
-                     kgma_assignment *out, int32_t *scores)
+// The queries of the two sources, validated.  *empty: n_queries == 0 (KGMA_OK, nothing to do).
+int seq_queries(kgma_ctx *ctx, const char *fn, const uint8_t *queries, const int64_t *query_offsets, int64_t n_queries, Queries &Q)
 {
-    static const char fn[] = "kgma_assign_seqs";
-    if (!ctx) return KGMA_E_ARG;
-    *ctx_assign_stats(ctx) = kgma_assign_stats{};
-    int rc = check_refs(ctx, fn, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, n_queries, out);
-    if (rc) return rc;
-    if (n_queries == 0) return KGMA_OK;
     if (!queries || !query_offsets) return failf(ctx, KGMA_E_ARG, "%s: null queries", fn);
-    Queries Q;
     Q.source = 1;
     Q.pos.resize((size_t)n_queries);
     Q.n.resize((size_t)n_queries);
@@ -270,22 +233,13 @@ int kgma_assign_seqs(kgma_ctx *ctx, const uint8_t *refs, const int64_t *ref_offs
     }
     Q.text = queries + base;
     Q.bytes = query_offsets[n_queries] - base;
-    return run(ctx, fn, Q, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, out, scores);
+    return KGMA_OK;
 }
 
-int kgma_assign_ranges(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs,
-                       int64_t n_queries, const int32_t *contig, const int64_t *lo, const int64_t *hi, int32_t gap_open_score,
-                       int32_t gap_extend_score, int32_t top, kgma_assignment *out, int32_t *scores)
+int range_queries(kgma_ctx *ctx, const char *fn, const kgma_genome *genome, int64_t n_queries, const int32_t *contig, const int64_t *lo,
+                  const int64_t *hi, Queries &Q)
 {
-    static const char fn[] = "kgma_assign_ranges";
-    if (!ctx) return KGMA_E_ARG;
-    *ctx_assign_stats(ctx) = kgma_assign_stats{};
-    if (!genome) return failf(ctx, KGMA_E_ARG, "%s: null genome", fn);
-    int rc = check_refs(ctx, fn, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, n_queries, out);
-    if (rc) return rc;
-    if (n_queries == 0) return KGMA_OK;
     if (!contig || !lo || !hi) return failf(ctx, KGMA_E_ARG, "%s: null ranges", fn);
-    Queries Q;
     Q.source = 0;
     Q.g = genome_text(genome);
     Q.contig = contig;
@@ -302,7 +256,101 @@ int kgma_assign_ranges(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *
         Q.pos[(size_t)q] = lo[q];
         Q.n[(size_t)q] = (int32_t)n;
     }
+    return KGMA_OK;
+}
+
+int check_screen(kgma_ctx *ctx, const char *fn, int32_t n_refs, int32_t top, int32_t screen_k, int32_t n_near)
+{
+    if (n_refs >= 1 && (n_near < 1 || n_near > n_refs || n_near > KGMA_KMAT_MAX_NEAR))
+        return failf(ctx, KGMA_E_ARG, "%s: n_near = %d is not one of 1 .. min(n_refs = %d, %d)", fn, n_near, n_refs, KGMA_KMAT_MAX_NEAR);
+    if (n_refs >= 1 && top > n_near) return failf(ctx, KGMA_E_ARG, "%s: top = %d exceeds n_near = %d", fn, top, n_near);
+    if (screen_k < 1) return failf(ctx, KGMA_E_ARG, "%s: screen_k = %d", fn, screen_k);
+    if (screen_k > 10) return failf(ctx, KGMA_E_UNSUPPORTED, "%s: screen_k = %d: the prescreen serves k = 1 ... 10", fn, screen_k);
+    return KGMA_OK;
+}
+
+// The prescreen, then the assignment over its candidates
+int run_screened(kgma_ctx *ctx, const char *fn, const Queries &Q, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs, int32_t go,
+                 int32_t ge, int32_t top, int32_t screen_k, int32_t n_near, kgma_assignment *out, int32_t *cand, int32_t *scores)
+{
+    std::vector<int64_t> roff((size_t)n_refs + 1);
+    for (int32_t r = 0; r <= n_refs; r++) roff[(size_t)r] = ref_offsets[r] - ref_offsets[0];
+    std::vector<int32_t> own;
+    if (!cand) { own.resize(Q.n.size() * (size_t)n_near); cand = own.data(); }
+    int rc = kmat_run(ctx, fn, screen_k, Q, "query", refs + ref_offsets[0], roff.data(), n_refs, "reference", n_near, nullptr, nullptr, cand, nullptr);
+    if (rc) return rc;
+    rc = run(ctx, fn, Q, refs, ref_offsets, n_refs, go, ge, top, out, scores, cand, n_near);
+    if (rc) *ctx_kmat_stats(ctx) = kgma_kmat_stats{};
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kgma_assign_seqs(kgma_ctx *ctx, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs, const uint8_t *queries,
+                     const int64_t *query_offsets, int64_t n_queries, int32_t gap_open_score, int32_t gap_extend_score, int32_t top,
+                     kgma_assignment *out, int32_t *scores)
+{
+    static const char fn[] = "kgma_assign_seqs";
+    if (!ctx) return KGMA_E_ARG;
+    *ctx_assign_stats(ctx) = kgma_assign_stats{};
+    int rc = check_refs(ctx, fn, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, n_queries, out);
+    if (rc) return rc;
+    if (n_queries == 0) return KGMA_OK;
+    Queries Q;
+    if ((rc = seq_queries(ctx, fn, queries, query_offsets, n_queries, Q))) return rc;
     return run(ctx, fn, Q, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, out, scores);
+}
+
+int kgma_assign_ranges(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs,
+                       int64_t n_queries, const int32_t *contig, const int64_t *lo, const int64_t *hi, int32_t gap_open_score,
+                       int32_t gap_extend_score, int32_t top, kgma_assignment *out, int32_t *scores)
+{
+    static const char fn[] = "kgma_assign_ranges";
+    if (!ctx) return KGMA_E_ARG;
+    *ctx_assign_stats(ctx) = kgma_assign_stats{};
+    if (!genome) return failf(ctx, KGMA_E_ARG, "%s: null genome", fn);
+    int rc = check_refs(ctx, fn, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, n_queries, out);
+    if (rc) return rc;
+    if (n_queries == 0) return KGMA_OK;
+    Queries Q;
+    if ((rc = range_queries(ctx, fn, genome, n_queries, contig, lo, hi, Q))) return rc;
+    return run(ctx, fn, Q, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, out, scores);
+}
+
+int kgma_assign_seqs_screened(kgma_ctx *ctx, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs, const uint8_t *queries,
+                              const int64_t *query_offsets, int64_t n_queries, int32_t gap_open_score, int32_t gap_extend_score,
+                              int32_t top, int32_t screen_k, int32_t n_near, kgma_assignment *out, int32_t *cand, int32_t *scores)
+{
+    static const char fn[] = "kgma_assign_seqs_screened";
+    if (!ctx) return KGMA_E_ARG;
+    *ctx_assign_stats(ctx) = kgma_assign_stats{};
+    *ctx_kmat_stats(ctx) = kgma_kmat_stats{};
+    int rc = check_refs(ctx, fn, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, n_queries, out);
+    if (rc || (rc = check_screen(ctx, fn, n_refs, top, screen_k, n_near))) return rc;
+    if (n_queries == 0) return KGMA_OK;
+    Queries Q;
+    if ((rc = seq_queries(ctx, fn, queries, query_offsets, n_queries, Q))) return rc;
+    return run_screened(ctx, fn, Q, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, screen_k, n_near, out, cand, scores);
+}
+
+int kgma_assign_ranges_screened(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs,
+                                int64_t n_queries, const int32_t *contig, const int64_t *lo, const int64_t *hi, int32_t gap_open_score,
+                                int32_t gap_extend_score, int32_t top, int32_t screen_k, int32_t n_near, kgma_assignment *out,
+                                int32_t *cand, int32_t *scores)
+{
+    static const char fn[] = "kgma_assign_ranges_screened";
+    if (!ctx) return KGMA_E_ARG;
+    *ctx_assign_stats(ctx) = kgma_assign_stats{};
+    *ctx_kmat_stats(ctx) = kgma_kmat_stats{};
+    if (!genome) return failf(ctx, KGMA_E_ARG, "%s: null genome", fn);
+    int rc = check_refs(ctx, fn, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, n_queries, out);
+    if (rc || (rc = check_screen(ctx, fn, n_refs, top, screen_k, n_near))) return rc;
+    if (n_queries == 0) return KGMA_OK;
+    Queries Q;
+    if ((rc = range_queries(ctx, fn, genome, n_queries, contig, lo, hi, Q))) return rc;
+    return run_screened(ctx, fn, Q, refs, ref_offsets, n_refs, gap_open_score, gap_extend_score, top, screen_k, n_near, out, cand, scores);
 }
 
 int kgma_get_assign_stats(kgma_ctx *ctx, kgma_assign_stats *out)

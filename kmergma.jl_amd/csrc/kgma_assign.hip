@@ -149,7 +149,8 @@ __device__ __forceinline__ int32_t sweep(const WaveLds &w, const uint8_t *__rest
 
 }  // namespace
 
-// Pair p of the launch: query items[p / n_refs], reference p % n_refs.  scores[query * n_refs + reference] = H(m, n).
+// Pair p of the launch: query items[p / n_cols], column p % n_cols; the column is the reference itself, or -- a screened call --
+// names it through the candidate table.  scores[query * n_cols + column] = H(m, n).
 template <class SRC>
 __global__ __launch_bounds__(64) void assign_score_kernel(const AssignArgs a)
 {
@@ -157,12 +158,13 @@ __global__ __launch_bounds__(64) void assign_score_kernel(const AssignArgs a)
     const WaveLds w = wave_lds(sh, a.max_n);
     const int lane = threadIdx.x;
     const int64_t p = a.first + blockIdx.x;
-    const int q = a.items[p / a.n_refs], r = (int)(p % a.n_refs);
+    const int q = a.items[p / a.n_cols], col = (int)(p % a.n_cols);
+    const int r = a.cand ? a.cand[(int64_t)q * a.n_cols + col] : col;
     const int n = a.q_n[q];
     load_query(w, SRC::text(a, q), n, lane);
     const int64_t r0 = a.ref_off[r];
     const int32_t score = sweep<false>(w, a.refs + r0, (int)(a.ref_off[r + 1] - r0), n, a.go, a.ge, lane, nullptr);
-    if (lane == 0) a.scores[(int64_t)q * a.n_refs + r] = score;
+    if (lane == 0) a.scores[(int64_t)q * a.n_cols + col] = score;
 }
 
 // Job b of the launch: query job_q[first + b] against reference job_r[first + b].  out[job] = its kgma_assignment (8 int32).

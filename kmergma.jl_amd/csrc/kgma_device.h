@@ -439,10 +439,12 @@ struct AssignArgs {
     int32_t n_refs;
     int32_t go, ge;               // penalties (positive)
     int32_t max_n;
-    int64_t first;                // score: first pair of the launch (pair p: query items[p / n_refs], reference p % n_refs);
+    int64_t first;                // score: first pair of the launch (pair p: query q = items[p / n_cols], column p % n_cols);
                                   // trace: first job of the launch
     const int32_t *items;         // score: the class's queries
-    int32_t *scores;              // score: [n_queries][n_refs]
+    int32_t *scores;              // score: [n_queries][n_cols]
+    const int32_t *cand;          // score: nullptr -- a column IS its reference (n_cols = n_refs); otherwise the screened call's
+    int32_t n_cols, pad;          //        candidate table [n_queries][n_cols]: column c of query q is reference cand[q * n_cols + c]
     const int32_t *job_q, *job_r; // trace: query and reference of every job
     uint8_t *trace;               // trace: trace_stride bytes per workgroup of the launch
     int64_t trace_stride;
@@ -455,8 +457,40 @@ constexpr int64_t KGMA_ASSIGN_TRACE_BYTES = (int64_t)1 << 30;  // trace bytes of
 int64_t assign_trace_bytes(int m, int n);
 size_t assign_lds_bytes(int max_n);
 
+// All-pairs k-mer distances (kgma_kmat.hip; kgma_kmer_dist_matrix, kgma_kmer_nearest and their _ranges forms).  The A side is
+// described as AssignArgs describes its queries (a run of an uploaded buffer, or a range of a record of the resident text); B is
+// always an uploaded buffer.  D[a][b] = na[a] + |c_b|^2 - 2 * sum_p c_b[x_p], p over the k-mer positions of a.
+struct KmatArgs {
+    const uint8_t *text;          // range source: the genome's residue text; sequence source: the uploaded A sequences
+    const ContigDesc *cd;         // range source: the genome's record table
+    const int32_t *q_contig;      // range source: [n_a] record (0-based)
+    const int64_t *q_pos;         // range source: [n_a] first residue (1-based); sequence source: byte offset in `text`
+    const int32_t *q_n;           // [n_a] residues, 0 ... KGMA_KMAT_LEN_MAX
+    const uint8_t *b_text;        // B's residues, one sequence after the other
+    const int64_t *b_off;         // [n_b + 1]
+    int64_t n_a;
+    int32_t n_b, k;
+    int64_t rows_per_chunk;       // matrix kernel: rows of A of one blockIdx.y
+    uint32_t *na;                 // [n_a] |c_a|^2: written by the norm kernel, read by the matrix kernel
+    uint32_t *scratch;            // k >= 8: 4^k counters per workgroup, all zero between sequences and launches
+    int32_t *D;                   // [n_a][n_b]
+    double *dist;                 // [n_a][n_b] or nullptr
+    double half_inv_k;            // RN(1 / 2k)
+    unsigned long long *bad;      // [2] side A, side B: smallest (sequence << 16 | 0-based position) of a residue outside A/C/G/T/N
+    int32_t n_near, pad;          // select kernel
+    int32_t *near_index, *near_D; // select kernel: [n_a][n_near]
+};
+constexpr int KGMA_KMAT_LEN_MAX = 32767;                       // a count fits 16 bits, D fits 31
+constexpr int KGMA_KMAT_THREADS = 256;
+constexpr int KGMA_KMAT_MIN_ROWS = 64;                         // rows of a chunk at least (unless A has fewer): amortises a tile's build
+constexpr int kmat_tile(int k) { return k <= 5 ? 16 : k == 6 ? 8 : k == 7 ? 4 : 1; }   // sequences of B per workgroup
+int kmat_scratch_rows(int k);                                  // k >= 8: workgroups of a launch at most = rows of KmatArgs::scratch
+
 #ifdef HIP_INCLUDE_HIP_HIP_RUNTIME_H                   // (host files that do not see the HIP runtime include this header too)
 hipError_t launch_assign(const AssignArgs &a, int source /* 0: genome ranges, 1: uploaded sequences */, bool trace, int grid, hipStream_t st);
+hipError_t launch_kmat_norm(const KmatArgs &a, int source, int grid, hipStream_t st);
+hipError_t launch_kmat(const KmatArgs &a, int source, int grid_x, int grid_y, hipStream_t st);
+hipError_t launch_kmat_select(const KmatArgs &a, hipStream_t st);
 hipError_t launch_calib(const CalibArgs &a, int source /* 0: windows, 1: mutated copies */, int grid, hipStream_t st);
 hipError_t launch_strobe_calib(const StrobeCalibArgs &a, int source, int grid, hipStream_t st);
 #endif

@@ -690,7 +690,77 @@ function assign_ranges(g::DeviceGenome, contig::Vector{Int32}, lo::Vector{Int64}
     return [Assignment[assignment(ids, out[t, i]) for t in 1:top] for i in 1:n]
 end
 
+# ---- all-pairs k-mer distances (kgma_kmer_dist_matrix, kgma_kmer_nearest) and the prescreened assignment ------------------------
+"""
+    kmer_dist_matrix(seqs_a, seqs_b = nothing; k = 6, integer = false) -> Matrix
+`kmer_dist(a, b, k)` of every sequence of `seqs_a` to every sequence of `seqs_b` on the device (`nothing`: A against A): the
+Float64 matrix [a, b], bit for bit the package's values, or with `integer = true` the exact Int32 D = Σ (c_a − c_b)².
+"""
+function kmer_dist_matrix(seqs_a::Vector{String}, seqs_b::Union{Nothing, Vector{String}} = nothing; k::Integer = 6, integer::Bool = false,
+                          ctx::Context = default_context())
+    atext, aoff = pack_seqs(seqs_a)
+    nb = seqs_b === nothing ? length(seqs_a) : length(seqs_b)
+    btext, boff = seqs_b === nothing ? (C_NULL, C_NULL) : pack_seqs(seqs_b)
+    D = Matrix{Int32}(undef, nb, length(seqs_a))                      # [b, a]: the C ABI's row-major D[a][b]
+    dist = Matrix{Float64}(undef, nb, length(seqs_a))
+    check(ctx, ccall((:kgma_kmer_dist_matrix, libkgma), Cint,
+                     (Ptr{Cvoid}, Int32, Ptr{UInt8}, Ptr{Int64}, Int64, Ptr{UInt8}, Ptr{Int64}, Int32, Ptr{Int32}, Ptr{Float64}),
+                     ctx.h, k, atext, aoff, length(seqs_a), btext, boff, seqs_b === nothing ? 0 : nb, D, dist))
+    return integer ? permutedims(D) : permutedims(dist)
+end
+
+"The same with ranges lo[i]:hi[i] (1-based, inclusive; hi = lo - 1: empty) of record contig[i] (0-based) of an open DeviceGenome as A."
+function kmer_dist_matrix_ranges(g::DeviceGenome, contig::Vector{Int32}, lo::Vector{Int64}, hi::Vector{Int64}, seqs_b::Vector{String};
+                                 k::Integer = 6, integer::Bool = false)
+    btext, boff = pack_seqs(seqs_b)
+    D = Matrix{Int32}(undef, length(seqs_b), length(contig))
+    dist = Matrix{Float64}(undef, length(seqs_b), length(contig))
+    check(g.ctx, ccall((:kgma_kmer_dist_matrix_ranges, libkgma), Cint,
+                       (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{UInt8}, Ptr{Int64}, Int32, Ptr{Int32}, Ptr{Float64}),
+                       g.ctx.h, g.h, k, length(contig), contig, lo, hi, btext, boff, length(seqs_b), D, dist))
+    return integer ? permutedims(D) : permutedims(dist)
+end
+
+"""
+    nearest_refs(hits, ref; k = 6, n = 1) -> Vector{Vector{Tuple{String, Int, Float64}}}
+Per hit its `n` nearest references by k-mer distance, nearest first, the earlier reference among equal distances:
+(ref_id, ref_index (1-based), dist).  The matrix stays on the device (kgma_kmer_nearest; kgma_kmer_nearest_ranges takes ranges).
+"""
+function nearest_refs(hits::Vector{FASTA.Record}, ref; k::Integer = 6, n::Integer = 1, ctx::Context = default_context())
+    ids, refs = assign_refs(ref)
+    qtext, qoff = pack_seqs(String[String(FASTA.sequence(h)) for h in hits])
+    rtext, roff = pack_seqs(refs)
+    index = Matrix{Int32}(undef, n, length(hits))
+    Dn = Matrix{Int32}(undef, n, length(hits))
+    check(ctx, ccall((:kgma_kmer_nearest, libkgma), Cint,
+                     (Ptr{Cvoid}, Int32, Ptr{UInt8}, Ptr{Int64}, Int64, Ptr{UInt8}, Ptr{Int64}, Int32, Int32, Ptr{Int32}, Ptr{Int32}),
+                     ctx.h, k, qtext, qoff, length(hits), rtext, roff, length(refs), n, index, Dn))
+    return [[(ids[index[t, i] + 1], Int(index[t, i]) + 1, (1.0 / (2k)) * Dn[t, i]) for t in 1:n] for i in eachindex(hits)]
+end
+
+"""
+    assignGenes_screened(hits, ref; prescreen = 8, prescreen_k = 6, top = 1, ...) -> Vector{Vector{Assignment}}
+`assignGenes` over every hit's `prescreen` nearest references by k-mer distance only (kgma_assign_seqs_screened; the ranges form
+is kgma_assign_ranges_screened with kgma_assign_ranges' arguments plus screen_k and n_near).  A residue outside A/C/G/T/N is an
+error here, whereas `assignGenes` counts it as N.
+"""
+function assignGenes_screened(hits::Vector{FASTA.Record}, ref; prescreen::Integer = 8, prescreen_k::Integer = 6, top::Integer = 1,
+                              gap_open_score::Integer = -69, gap_extend_score::Integer = -1, ctx::Context = default_context())
+    ids, refs = assign_refs(ref)
+    isempty(hits) && return Vector{Assignment}[]
+    rtext, roff = pack_seqs(refs)
+    qtext, qoff = pack_seqs(String[String(FASTA.sequence(h)) for h in hits])
+    out = Matrix{KgmaAssignment}(undef, top, length(hits))
+    check(ctx, ccall((:kgma_assign_seqs_screened, libkgma), Cint,
+                     (Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int64}, Int32, Ptr{UInt8}, Ptr{Int64}, Int64, Int32, Int32, Int32, Int32, Int32,
+                      Ptr{KgmaAssignment}, Ptr{Int32}, Ptr{Int32}),
+                     ctx.h, rtext, roff, length(refs), qtext, qoff, length(hits), gap_open_score, gap_extend_score, top, prescreen_k, prescreen,
+                     out, C_NULL, C_NULL))
+    return [Assignment[assignment(ids, out[t, i]) for t in 1:top] for i in eachindex(hits)]
+end
+
 export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, HumanRSSV, HumanRSSD, Context
 export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists, assignGenes, assign_ranges
+export kmer_dist_matrix, kmer_dist_matrix_ranges, nearest_refs, assignGenes_screened
 
 end # module

@@ -40,8 +40,13 @@ EXPORTS = [
     "kgma_get_block_sums", "kgma_genome_from_2bit_file", "kgma_get_2bit_unpack_ms", "kgma_twobit_inspect",
     "kgma_window_dists", "kgma_mutation_dists", "kgma_strobe_window_dists", "kgma_strobe_mutation_dists",
     "kgma_assign_seqs", "kgma_assign_ranges", "kgma_get_assign_stats",
+    "kgma_kmer_dist_matrix", "kgma_kmer_dist_matrix_ranges", "kgma_kmer_nearest", "kgma_kmer_nearest_ranges", "kgma_get_kmat_stats",
+    "kgma_assign_seqs_screened", "kgma_assign_ranges_screened",
 ]
 ASSIGN_MAX_LEN = 8191                # KGMA_ASSIGN_MAX_LEN
+KMAT_MAX_LEN = 32767                 # KGMA_KMAT_MAX_LEN
+KMAT_MAX_NEAR = 128                  # KGMA_KMAT_MAX_NEAR
+KMAT_FORM_LDS, KMAT_FORM_GLOBAL = 0, 1   # kgma_kmat_stats.form
 TWOBIT_NOMASK = 1                    # KGMA_2BIT_NOMASK
 TWOBIT_SIGNATURE = b"\x43\x27\x41\x1a"  # the first four bytes of a .2bit file in this machine's byte order
 FILTER_FORM_PRESUMMED = 1 << 16      # kgma_filter_stats.form: the filter read the block sums the step's pack wrote (KGMA_FUSE_SUMS)
@@ -99,6 +104,11 @@ class KgmaFilterStats(C.Structure):
 class KgmaAssignStats(C.Structure):
     _fields_ = [("score_ms", C.c_double), ("trace_ms", C.c_double), ("n_pairs", C.c_int64), ("n_cells", C.c_int64),
                 ("n_traced", C.c_int64), ("n_score_launches", C.c_int32), ("n_trace_launches", C.c_int32)]
+
+
+class KgmaKmatStats(C.Structure):
+    _fields_ = [("kmat_ms", C.c_double), ("select_ms", C.c_double), ("n_pairs", C.c_int64), ("n_launches", C.c_int32),
+                ("form", C.c_int32), ("tile", C.c_int32), ("chunks", C.c_int32)]
 
 
 HIT_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("cmi", "<i8"), ("lo", "<i8"), ("hi", "<i8"),
@@ -231,6 +241,14 @@ def load():
     L.kgma_assign_seqs.argtypes = [vp, C.c_char_p, P(i64), i32, C.c_char_p, P(i64), i64, i32, i32, i32, vp, P(i32)]
     L.kgma_assign_ranges.argtypes = [vp, vp, C.c_char_p, P(i64), i32, i64, P(i32), P(i64), P(i64), i32, i32, i32, vp, P(i32)]
     L.kgma_get_assign_stats.argtypes = [vp, P(KgmaAssignStats)]
+    L.kgma_kmer_dist_matrix.argtypes = [vp, i32, C.c_char_p, P(i64), i64, C.c_char_p, P(i64), i32, P(i32), P(dbl)]
+    L.kgma_kmer_dist_matrix_ranges.argtypes = [vp, vp, i32, i64, P(i32), P(i64), P(i64), C.c_char_p, P(i64), i32, P(i32), P(dbl)]
+    L.kgma_kmer_nearest.argtypes = [vp, i32, C.c_char_p, P(i64), i64, C.c_char_p, P(i64), i32, i32, P(i32), P(i32)]
+    L.kgma_kmer_nearest_ranges.argtypes = [vp, vp, i32, i64, P(i32), P(i64), P(i64), C.c_char_p, P(i64), i32, i32, P(i32), P(i32)]
+    L.kgma_get_kmat_stats.argtypes = [vp, P(KgmaKmatStats)]
+    L.kgma_assign_seqs_screened.argtypes = [vp, C.c_char_p, P(i64), i32, C.c_char_p, P(i64), i64, i32, i32, i32, i32, i32, vp, P(i32), P(i32)]
+    L.kgma_assign_ranges_screened.argtypes = [vp, vp, C.c_char_p, P(i64), i32, i64, P(i32), P(i64), P(i64), i32, i32, i32, i32, i32, vp,
+                                              P(i32), P(i32)]
     L.kgma_stream.argtypes = [vp]
     L.kgma_stream.restype = vp
     L.kgma_scan_kernel_name.argtypes = [vp]
@@ -941,6 +959,115 @@ class Context:
         s = KgmaAssignStats()
         self._check(load().kgma_get_assign_stats(self._h, C.byref(s)))
         return {name: getattr(s, name) for name, _ in KgmaAssignStats._fields_}
+
+    @staticmethod
+    def _ranges(contig, lo, hi):
+        c = np.ascontiguousarray(np.asarray(contig, dtype=np.int32).ravel())
+        a = np.ascontiguousarray(np.asarray(lo, dtype=np.int64).ravel())
+        b = np.ascontiguousarray(np.asarray(hi, dtype=np.int64).ravel())
+        if not (c.size == a.size == b.size):
+            raise ValueError("need one lo and one hi per contig")
+        n = int(c.size)
+        return n, (_np_ptr(c, C.c_int32) if n else None, _np_ptr(a, C.c_int64) if n else None, _np_ptr(b, C.c_int64) if n else None), (c, a, b)
+
+    def kmer_dist_matrix(self, seqs_a, seqs_b=None, k: int = 6):
+        """kgma_kmer_dist_matrix: (D, dist), each [n_a, n_b]: D[i, j] = sum_x (c_i[x] - c_j[x])^2 over the k-mer counts of
+        sequence i of `seqs_a` and sequence j of `seqs_b` (int32, exact), dist = (1 / 2k) * D = kmer_dist(a_i, b_j, k) bit for
+        bit (float64).  seqs_b=None: B = A, the symmetric matrix."""
+        atext, aoff = self._concat(seqs_a)
+        na = aoff.size - 1
+        if seqs_b is None:
+            btext, boff, nb = None, None, na
+        else:
+            btext, boff = self._concat(seqs_b)
+            nb = boff.size - 1
+        D = np.zeros((na, max(nb, 0)), dtype=np.int32)
+        dist = np.zeros(D.shape, dtype=np.float64)
+        self._check(load().kgma_kmer_dist_matrix(self._h, int(k), atext, _np_ptr(aoff, C.c_int64), na, btext,
+                                                 _np_ptr(boff, C.c_int64) if boff is not None else None, 0 if seqs_b is None else nb,
+                                                 _np_ptr(D, C.c_int32) if D.size else None, _np_ptr(dist, C.c_double) if D.size else None))
+        return D, dist
+
+    def kmer_dist_matrix_ranges(self, genome: "Genome", contig, lo, hi, seqs_b, k: int = 6):
+        """kgma_kmer_dist_matrix_ranges: as kmer_dist_matrix, A being residues lo[i] .. hi[i] (1-based inclusive; hi = lo - 1:
+        empty) of record contig[i] (0-based) of the resident genome."""
+        btext, boff = self._concat(seqs_b)
+        nb = boff.size - 1
+        na, ptrs, _keep = self._ranges(contig, lo, hi)
+        D = np.zeros((na, max(nb, 0)), dtype=np.int32)
+        dist = np.zeros(D.shape, dtype=np.float64)
+        self._check(load().kgma_kmer_dist_matrix_ranges(self._h, genome._h, int(k), na, *ptrs, btext, _np_ptr(boff, C.c_int64), nb,
+                                                        _np_ptr(D, C.c_int32) if D.size else None,
+                                                        _np_ptr(dist, C.c_double) if D.size else None))
+        return D, dist
+
+    def kmer_nearest(self, seqs_a, seqs_b, k: int = 6, n_near: int = 1):
+        """kgma_kmer_nearest: (index, D_near), each int32 [n_a, n_near]: per sequence of A its n_near nearest of B in the order
+        (D ascending, index ascending).  The matrix stays on the device.  seqs_b=None: B = A."""
+        atext, aoff = self._concat(seqs_a)
+        na = aoff.size - 1
+        if seqs_b is None:
+            btext, boff, nb = None, None, 0
+        else:
+            btext, boff = self._concat(seqs_b)
+            nb = boff.size - 1
+        index = np.zeros((na, max(int(n_near), 0)), dtype=np.int32)
+        Dn = np.zeros(index.shape, dtype=np.int32)
+        self._check(load().kgma_kmer_nearest(self._h, int(k), atext, _np_ptr(aoff, C.c_int64), na, btext,
+                                             _np_ptr(boff, C.c_int64) if boff is not None else None, nb, int(n_near),
+                                             _np_ptr(index, C.c_int32) if index.size else None, _np_ptr(Dn, C.c_int32) if Dn.size else None))
+        return index, Dn
+
+    def kmer_nearest_ranges(self, genome: "Genome", contig, lo, hi, seqs_b, k: int = 6, n_near: int = 1):
+        """kgma_kmer_nearest_ranges: kmer_nearest for ranges of the resident genome."""
+        btext, boff = self._concat(seqs_b)
+        nb = boff.size - 1
+        na, ptrs, _keep = self._ranges(contig, lo, hi)
+        index = np.zeros((na, max(int(n_near), 0)), dtype=np.int32)
+        Dn = np.zeros(index.shape, dtype=np.int32)
+        self._check(load().kgma_kmer_nearest_ranges(self._h, genome._h, int(k), na, *ptrs, btext, _np_ptr(boff, C.c_int64), nb, int(n_near),
+                                                    _np_ptr(index, C.c_int32) if index.size else None,
+                                                    _np_ptr(Dn, C.c_int32) if Dn.size else None))
+        return index, Dn
+
+    def kmat_stats(self) -> dict:
+        """kgma_get_kmat_stats: device times, pairs, launches and kernel form of the last distance-matrix / nearest call."""
+        s = KgmaKmatStats()
+        self._check(load().kgma_get_kmat_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in KgmaKmatStats._fields_}
+
+    def assign_seqs_screened(self, refs, queries, gap_open: int = -69, gap_extend: int = -1, top: int = 1, screen_k: int = 6,
+                             n_near: int = 8):
+        """kgma_assign_seqs_screened: assign_seqs over every query's n_near nearest references by k-mer distance (screen_k) only.
+        Returns (out, cand, scores): out as assign_seqs -- the best AMONG THE CANDIDATES --, cand the int32 [n_queries, n_near]
+        candidate reference indices in (D, index) order, scores their int32 scores in the same order.  Unlike assign_seqs a byte
+        outside A/C/G/T/N is a BadBaseError (the k-mer pass follows kmer_count)."""
+        rtext, roff = self._concat(refs)
+        qtext, qoff = self._concat(queries)
+        nr, nq, top, nn = roff.size - 1, qoff.size - 1, int(top), int(n_near)
+        out = np.zeros((nq, max(top, 0)), dtype=ASSIGNMENT_DTYPE)
+        cand = np.zeros((nq, max(nn, 0)), dtype=np.int32)
+        scores = np.zeros(cand.shape, dtype=np.int32)
+        self._check(load().kgma_assign_seqs_screened(self._h, rtext, _np_ptr(roff, C.c_int64), nr, qtext, _np_ptr(qoff, C.c_int64), nq,
+                                                     int(gap_open), int(gap_extend), top, int(screen_k), nn,
+                                                     out.ctypes.data if out.size else None, _np_ptr(cand, C.c_int32) if cand.size else None,
+                                                     _np_ptr(scores, C.c_int32) if scores.size else None))
+        return out, cand, scores
+
+    def assign_ranges_screened(self, genome: "Genome", refs, contig, lo, hi, gap_open: int = -69, gap_extend: int = -1, top: int = 1,
+                               screen_k: int = 6, n_near: int = 8):
+        """kgma_assign_ranges_screened: as assign_seqs_screened, the queries being ranges of the resident genome."""
+        rtext, roff = self._concat(refs)
+        nq, ptrs, _keep = self._ranges(contig, lo, hi)
+        nr, top, nn = roff.size - 1, int(top), int(n_near)
+        out = np.zeros((nq, max(top, 0)), dtype=ASSIGNMENT_DTYPE)
+        cand = np.zeros((nq, max(nn, 0)), dtype=np.int32)
+        scores = np.zeros(cand.shape, dtype=np.int32)
+        self._check(load().kgma_assign_ranges_screened(self._h, genome._h, rtext, _np_ptr(roff, C.c_int64), nr, nq, *ptrs,
+                                                       int(gap_open), int(gap_extend), top, int(screen_k), nn,
+                                                       out.ctypes.data if out.size else None, _np_ptr(cand, C.c_int32) if cand.size else None,
+                                                       _np_ptr(scores, C.c_int32) if scores.size else None))
+        return out, cand, scores
 
     def step_hits(self, genome: "Genome", mode: int, buff: int = 50, genome_pos: int = 0, flags: int = 0) -> np.ndarray:
         """repack + scan + hits in ONE library call (kgma_repack_scan_hits); returns the hits as a structured

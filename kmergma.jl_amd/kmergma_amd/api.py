@@ -1057,26 +1057,42 @@ def annotated_header(description: str, best: Assignment) -> str:
     return f"{description} | Ref = {best.ref_id} | Identity = {best.identity:.3f}"
 
 
+def _check_prescreen(prescreen, top: int, n_refs: int) -> None:
+    if isinstance(prescreen, bool) or not isinstance(prescreen, (int, np.integer)):
+        raise ValueError(f"prescreen = {prescreen!r} is neither None nor an integer")
+    if not int(top) <= int(prescreen) <= min(n_refs, _lib.KMAT_MAX_NEAR):
+        raise ValueError(f"prescreen = {prescreen} is not one of top = {top} .. {min(n_refs, _lib.KMAT_MAX_NEAR)} "
+                         f"(min(number of references, {_lib.KMAT_MAX_NEAR}))")
+
+
 def assignGenes(hits, ref_path_or_seqs, *, top: int = 1, gap_open_score: int = -69, gap_extend_score: int = -1,
-                annotate: bool = False, ctx=None):
+                annotate: bool = False, prescreen: Optional[int] = None, prescreen_k: int = 6, ctx=None):
     """Names every hit's nearest reference genes.  `hits`: the records findGenes / findGenes_cluster_mode / Strobemer_findGenes
     return (or bare sequences); their bodies are the queries -- a minus-strand hit's body is already in reference orientation,
     so both strands work without coordinates.  `ref_path_or_seqs`: a FASTA path or a list of Record / bytes / str.  Every hit
     is scored against every reference on the device (kgma_assign_seqs), its `top` references -- higher score first, the earlier
     reference among equal scores -- are aligned with a traceback, and per hit the list of their Assignment tuples is returned.
     annotate=True returns instead copies of the records with ` | Ref = <id> | Identity = <x.xxx>` of the best reference
-    appended to the header (hits must be records then)."""
+    appended to the header (hits must be records then).
+    prescreen=n (top <= n <= min(number of references, 128)) aligns a hit only against its n nearest references by k-mer
+    distance at k = prescreen_k (kgma_assign_seqs_screened): what is returned is then the best among those candidates, and a
+    residue outside A/C/G/T/N raises BadBaseError where the unscreened call counts it as N.  None is the unscreened call."""
     hits = list(hits)
     ids, seqs = _assign_refs(ref_path_or_seqs)
     if not 1 <= int(top) <= len(seqs):
         raise ValueError(f"top = {top} is not one of 1 .. {len(seqs)} (the number of references)")
+    if prescreen is not None:
+        _check_prescreen(prescreen, top, len(seqs))
     if annotate and not all(isinstance(h, Record) for h in hits):
         raise TypeError("annotate=True needs hit records")
     queries = [_seq_bytes(h) for h in hits]
     if not hits:
         return []
     ctx = ctx or default_context()
-    out, _ = ctx.assign_seqs(seqs, queries, gap_open_score, gap_extend_score, int(top))
+    if prescreen is None:
+        out, _ = ctx.assign_seqs(seqs, queries, gap_open_score, gap_extend_score, int(top))
+    else:
+        out = ctx.assign_seqs_screened(seqs, queries, gap_open_score, gap_extend_score, int(top), int(prescreen_k), int(prescreen))[0]
     res = _assignments(ids, out)
     if annotate:
         return [Record(annotated_header(h.description, a[0]), h.sequence) for h, a in zip(hits, res)]
@@ -1084,23 +1100,78 @@ def assignGenes(hits, ref_path_or_seqs, *, top: int = 1, gap_open_score: int = -
 
 
 def assign_ranges(genome_or_path, contig, lo, hi, ref_path_or_seqs, *, top: int = 1, gap_open_score: int = -69,
-                  gap_extend_score: int = -1, ctx=None) -> list:
+                  gap_extend_score: int = -1, prescreen: Optional[int] = None, prescreen_k: int = 6, ctx=None) -> list:
     """assignGenes for ranges of a resident genome, which never leave the device: query i is residues lo[i] .. hi[i] (1-based
     inclusive) of record contig[i] (0-based) of `genome_or_path` -- a FASTA or .2bit path, or a device genome that is already
-    open (it stays open), as for motifMatch.  Per range the list of its `top` Assignment tuples (kgma_assign_ranges)."""
+    open (it stays open), as for motifMatch.  Per range the list of its `top` Assignment tuples (kgma_assign_ranges).
+    prescreen / prescreen_k: as in assignGenes (kgma_assign_ranges_screened)."""
     if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
         raise TypeError("Invalid subject sequence type")
     ids, seqs = _assign_refs(ref_path_or_seqs)
     if not 1 <= int(top) <= len(seqs):
         raise ValueError(f"top = {top} is not one of 1 .. {len(seqs)} (the number of references)")
+    if prescreen is not None:
+        _check_prescreen(prescreen, top, len(seqs))
     ctx = ctx or default_context()
     g, _src, owned = _open_subject(ctx, genome_or_path)
     try:
-        out, _ = ctx.assign_ranges(g, seqs, contig, lo, hi, gap_open_score, gap_extend_score, int(top))
+        if prescreen is None:
+            out, _ = ctx.assign_ranges(g, seqs, contig, lo, hi, gap_open_score, gap_extend_score, int(top))
+        else:
+            out = ctx.assign_ranges_screened(g, seqs, contig, lo, hi, gap_open_score, gap_extend_score, int(top), int(prescreen_k),
+                                             int(prescreen))[0]
     finally:
         if owned:
             g.free()
     return _assignments(ids, out)
+
+
+# ---- all-pairs k-mer distances (kgma_kmer_dist_matrix, kgma_kmer_nearest) ---------------------------------------------------------
+def kmer_dist_matrix(seqs_a, seqs_b=None, k: int = 6, *, integer: bool = False, ctx=None) -> np.ndarray:
+    """kmer_dist(a, b, k) (src/Kmers.jl:54-56) of every sequence of `seqs_a` to every sequence of `seqs_b`, on the device: the
+    Float64 matrix [n_a, n_b], bit for bit the reference's values; integer=True returns instead the exact int32
+    D = sum_x (c_a[x] - c_b[x])^2 (dist = (1 / 2k) * D).  Either side: a FASTA path or a list of Record / bytes / str.
+    seqs_b=None: every sequence of A against every other (symmetric, zero diagonal).  1 <= k <= 10; sequences of at most
+    32767 residues; a residue outside A/C/G/T/N raises BadBaseError (the reference's KeyError)."""
+    _ids, a = _assign_refs(seqs_a)
+    b = None if seqs_b is None else _assign_refs(seqs_b)[1]
+    ctx = ctx or default_context()
+    D, dist = ctx.kmer_dist_matrix(a, b, int(k))
+    return D if integer else dist
+
+
+def kmer_dist_matrix_ranges(genome_or_path, contig, lo, hi, ref_path_or_seqs, k: int = 6, *, integer: bool = False, ctx=None) -> np.ndarray:
+    """kmer_dist_matrix with ranges of a resident genome as the A side: row i is residues lo[i] .. hi[i] (1-based inclusive;
+    hi = lo - 1: empty) of record contig[i] (0-based) of `genome_or_path` -- a FASTA or .2bit path, or a device genome that is
+    already open (it stays open), as for assign_ranges.  Only residues inside a requested range can raise BadBaseError."""
+    if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
+        raise TypeError("Invalid subject sequence type")
+    _ids, b = _assign_refs(ref_path_or_seqs)
+    ctx = ctx or default_context()
+    g, _src, owned = _open_subject(ctx, genome_or_path)
+    try:
+        D, dist = ctx.kmer_dist_matrix_ranges(g, contig, lo, hi, b, int(k))
+    finally:
+        if owned:
+            g.free()
+    return D if integer else dist
+
+
+def nearest_refs(hits, ref_path_or_seqs, *, k: int = 6, n: int = 1, ctx=None) -> list:
+    """Per hit (a record or a bare sequence) the list of its `n` nearest references by k-mer distance, nearest first, the earlier
+    reference among equal distances: (ref_id, ref_index, dist) tuples.  The distance matrix never leaves the device
+    (kgma_kmer_nearest)."""
+    hits = list(hits)
+    ids, seqs = _assign_refs(ref_path_or_seqs)
+    if not 1 <= int(n) <= min(len(seqs), _lib.KMAT_MAX_NEAR):
+        raise ValueError(f"n = {n} is not one of 1 .. {min(len(seqs), _lib.KMAT_MAX_NEAR)} (min(number of references, {_lib.KMAT_MAX_NEAR}))")
+    queries = [_seq_bytes(h) for h in hits]
+    if not hits:
+        return []
+    ctx = ctx or default_context()
+    index, D = ctx.kmer_nearest(queries, seqs, int(k), int(n))
+    half_inv_k = 1.0 / (2 * int(k))
+    return [[(ids[int(r)], int(r), half_inv_k * float(d)) for r, d in zip(ri, di)] for ri, di in zip(index, D)]
 
 
 def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
