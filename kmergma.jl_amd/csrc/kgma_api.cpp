@@ -257,6 +257,16 @@ struct StepWorker {
     int rc = 0;
 };
 
+// One set of the device chain's output buffers (chunk records, pool of raw increments in units of 16 bytes, first-window D per
+// stream) with the pinned mirror they come down into.  Two sets alternate: batch i comes down (copy stream) and is walked by
+// the host while batch i + 1 runs
+struct ChainBufferSet {
+    ChainChunk *chunks = nullptr; int64_t chunks_cap = 0;
+    ChainChunk *pool = nullptr; int64_t pool_cap = 0;
+    int64_t *D0 = nullptr; int64_t D0_cap = 0;
+    uint8_t *pin = nullptr; size_t pin_cap = 0;
+};
+
 struct kgma_ctx {
     StepWorker *worker = nullptr;
     int device = 0;
@@ -286,23 +296,16 @@ struct kgma_ctx {
     StagePipe *pipe = nullptr;
     uint8_t *d_ingest = nullptr; int64_t ingest_cap = 0;                 // raw FASTA text on the device
     uint32_t *d_icounts = nullptr; int64_t icounts_cap = 0;
-    // chain on the device (stream8_kernel<..., CHAIN>): stream table, chunk records, raw increments, hot-chunk bits,
-    // first-window D per stream, {raw cursor, status}; one pinned mirror for what comes back
+    // chain on the device (stream8_kernel<..., CHAIN>): stream table, the two sets of output buffers, hot-chunk bits,
+    // {raw cursor, status}
     TileDesc *d_ctiles = nullptr; int64_t ctiles_cap = 0;
-    ChainChunk *d_cchunks = nullptr; int64_t cchunks_cap = 0;
-    ChainChunk *d_cpool = nullptr; int64_t cpool_cap = 0;                // units of 16 bytes
-    ChainChunk *d_cchunks2 = nullptr; int64_t cchunks2_cap = 0;          // second output set: batch i comes down (copy stream) while batch i + 1 runs
-    ChainChunk *d_cpool2 = nullptr; int64_t cpool2_cap = 0;
-    int64_t *d_cD02 = nullptr; int64_t cD02_cap = 0;
+    ChainBufferSet cset[2];
     hipStream_t chain_copy_stream = nullptr;
     int32_t *d_wstate = nullptr; int64_t wstate_cap = 0;                 // k = 7 multi-KFV launches: per-stream state (ScanArgs::wave_state)
     uint32_t *d_chot = nullptr; int64_t chot_cap = 0;                    // [hot bit words | prefix per word]
     uint64_t *d_chmask = nullptr; int64_t chmask_cap = 0;                // hot steps of each hot chunk
     double cpool_per_step = 0;                                           // pool units per step the last chain launches needed beyond their hot steps
-    int64_t *d_cD0 = nullptr; int64_t cD0_cap = 0;
     unsigned int *d_cctl = nullptr;
-    uint8_t *h_cpin = nullptr; size_t cpin_cap = 0;
-    uint8_t *h_cpin2 = nullptr; size_t cpin2_cap = 0;      // second download buffer: batch i + 1 comes down while the host walks batch i
     uint64_t next_uid = 1;
     // key of the tile table currently on the device
     uint64_t tk_uid = 0, tk_version = 0; int tk_mode = -1, tk_k = 0; int64_t tk_maxws = 0;
@@ -459,6 +462,18 @@ int dev_reserve(kgma_ctx *ctx, T *&ptr, int64_t &cap, int64_t need)
     cap = n;
     ctx->device_bytes += n * (int64_t)sizeof(T);
     return KGMA_OK;
+}
+
+// Grow a pinned host buffer to `need` elements and `spare` more; false: no memory (the buffer is gone)
+template <class T>
+bool grow_pinned(T *&buf, size_t &cap, size_t need, size_t spare)
+{
+    if (need <= cap) return true;
+    if (buf) (void)hipHostFree(buf);
+    buf = nullptr; cap = 0;
+    if (hipHostMalloc(reinterpret_cast<void **>(&buf), (need + spare) * sizeof(T), hipHostMallocDefault) != hipSuccess) return false;
+    cap = need + spare;
+    return true;
 }
 
 // natural k-mer value (first base most significant, 2 bits per base, Kmers.jl:37-43) -> index order
@@ -829,19 +844,15 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_ingest) (void)hipFree(ctx->d_ingest);
     if (ctx->d_icounts) (void)hipFree(ctx->d_icounts);
     if (ctx->d_ctiles) (void)hipFree(ctx->d_ctiles);
-    if (ctx->d_cchunks) (void)hipFree(ctx->d_cchunks);
-    if (ctx->d_cpool) (void)hipFree(ctx->d_cpool);
-    if (ctx->d_cchunks2) (void)hipFree(ctx->d_cchunks2);
-    if (ctx->d_cpool2) (void)hipFree(ctx->d_cpool2);
-    if (ctx->d_cD02) (void)hipFree(ctx->d_cD02);
+    for (ChainBufferSet &cs : ctx->cset) {
+        for (void *d : {(void *)cs.chunks, (void *)cs.pool, (void *)cs.D0}) if (d) (void)hipFree(d);
+        if (cs.pin) (void)hipHostFree(cs.pin);
+    }
     if (ctx->chain_copy_stream) (void)hipStreamDestroy(ctx->chain_copy_stream);
     if (ctx->d_wstate) (void)hipFree(ctx->d_wstate);
     if (ctx->d_chmask) (void)hipFree(ctx->d_chmask);
     if (ctx->d_chot) (void)hipFree(ctx->d_chot);
-    if (ctx->d_cD0) (void)hipFree(ctx->d_cD0);
     if (ctx->d_cctl) (void)hipFree(ctx->d_cctl);
-    if (ctx->h_cpin) (void)hipHostFree(ctx->h_cpin);
-    if (ctx->h_cpin2) (void)hipHostFree(ctx->h_cpin2);
     if (ctx->d_gath) (void)hipFree(ctx->d_gath);
     if (ctx->d_xq) (void)hipFree(ctx->d_xq);
     if (ctx->d_xtext) (void)hipFree(ctx->d_xtext);
@@ -4044,6 +4055,12 @@ static int replay_hits(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64_
 // walks each pair's chunks in order (kgma_chain.cpp: run_chain_walks) -- an integer add per regular chunk, hardware
 // additions through the chunks that hold a wanted window or may change binade.  Pairs the kernel does not serve
 // (k, window length, a KFV that is not RN(S * (1/N))) or whose walk fails a check are left to the host chain.
+//
+// The host control, per batch of pairs (ChainBatch): plan_chain_launches, plan_chain_streams and mark_hot_steps decide
+// everything before the device is touched (ChainPlan); reserve_chain_buffers and run_chain_kernels size the buffers and
+// launch (with the pool-regrowth retry); start_download lays out the pinned mirror and starts the copies; finish --
+// first_windows, then the export or walk_pairs -- is the host part, run by chain_on_device on a worker while the next
+// batch's device part runs.
 // ------------------------------------------------------------------------------------------
 static void reset_chain_stats(kgma_ctx *ctx)
 {
@@ -4059,174 +4076,183 @@ struct ChainPair {
     int64_t last;
 };
 
-struct ChainDevInfo { int64_t pairs = 0, windows = 0, raw_steps = 0, streams = 0, chunks = 0; double kernel_ms = 0, walk_ms = 0, setup_ms = 0, copy_ms = 0, max_drift = 0; int attempts = 0; };
+// What the device chains of one call add up to.  Two threads write it, each its own fields: the thread that runs the batches'
+// device parts (plan, launches) the first line, the one that runs a batch's host part (ChainBatch::finish: chain_on_device's
+// worker, or the same thread when nothing follows the batch) the second.
+struct ChainDevInfo {
+    int64_t chunks = 0; double setup_ms = 0, kernel_ms = 0; int attempts = 0;
+    int64_t pairs = 0, windows = 0, raw_steps = 0, streams = 0; double copy_ms = 0, walk_ms = 0, max_drift = 0;
+};
 
-static bool chain_device_enabled()
+// The chain's switches, read once per entry (chain_decide, kgma_chain_values, kgma_chain_export) and never kept on the
+// context: tests change them between calls on one context
+struct ChainEnv {
+    bool debug = false;                            // KGMA_CHAIN_DEBUG
+    bool host_only = false;                        // KGMA_CHAIN=host (tests): chain_decide keeps every pair on the host chain
+    int generic = -1;                              // KGMA_CHAIN_GENERIC (tests): 0 / 1 never / always the generic chain kernel; -1: not set
+    int group = 1;                                 // KGMA_CHAIN_GROUP: KFVs per chain launch, 1 .. 4
+    bool stream_set = false; int64_t stream = 0;   // KGMA_CHAIN_STREAM (experiments / tests): transitions per stream
+    int64_t pool_units = 0;                        // KGMA_CHAIN_POOL_UNITS (tests: force the regrowth); 0: not set
+    int64_t batch_windows = (int64_t)1 << 35;      // KGMA_CHAIN_BATCH_WINDOWS (tests): windows per device batch
+    int64_t batch_bytes = (int64_t)2 << 30;        // KGMA_CHAIN_BATCH_MB (experiments): 2-bit codes per host batch
+    int threads = 1;                               // KGMA_CHAIN_THREADS: host threads of the chains and walks, 1 .. 64
+};
+
+static ChainEnv read_chain_env()
 {
-    const char *e = getenv("KGMA_CHAIN");                  // testing: KGMA_CHAIN=host keeps every pair on the host chain
-    return !(e && !strcmp(e, "host"));
+    ChainEnv v;
+    v.debug = getenv("KGMA_CHAIN_DEBUG") != nullptr;
+    if (const char *e = getenv("KGMA_CHAIN")) v.host_only = !strcmp(e, "host");
+    if (const char *e = getenv("KGMA_CHAIN_GENERIC")) v.generic = atoi(e);
+    if (const char *e = getenv("KGMA_CHAIN_GROUP")) v.group = std::max(1, std::min(4, atoi(e)));
+    if (const char *e = getenv("KGMA_CHAIN_STREAM")) { v.stream_set = true; v.stream = atoll(e); }
+    if (const char *e = getenv("KGMA_CHAIN_POOL_UNITS")) v.pool_units = std::max<int64_t>(1, atoll(e));
+    if (const char *e = getenv("KGMA_CHAIN_BATCH_WINDOWS")) v.batch_windows = std::max<int64_t>(1, atoll(e));
+    if (const char *e = getenv("KGMA_CHAIN_BATCH_MB")) v.batch_bytes = std::max<int64_t>(1, atoll(e)) << 20;
+    v.threads = (int)std::thread::hardware_concurrency();
+    if (const char *e = getenv("KGMA_CHAIN_THREADS")) v.threads = atoi(e);
+    v.threads = std::max(1, std::min(v.threads, 64));
+    return v;
 }
-
-static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vector<ChainPair> &pairs, std::vector<size_t> el, std::vector<char> &done,
-                                 ChainDevInfo &info, bool export_only = false, int pin_sel = 0, std::function<int()> *deferred = nullptr, bool generic = false);
 
 // which chain kernel serves a KFV: 1 = stream8_kernel<..., CHAIN> (k = 5, 6, 7, S/N KFVs in one of the two forms), 2 = the generic chain
 // kernel (any k, any window, any KFV: it reads the caller's table), 0 = none (the host chain).  KGMA_CHAIN_GENERIC=0 / 1 (tests):
 // never / always the generic one.
-static int chain_kernel_for(const kgma_ctx *ctx, const KfvInfo &f)
+static int chain_kernel_for(const kgma_ctx *ctx, const KfvInfo &f, const ChainEnv &env)
 {
     const int k = ctx->k, nk = (int)(f.W - k + 1);
-    const char *ge = getenv("KGMA_CHAIN_GENERIC");
     const bool s8 = !f.fp && (f.fits32 || f.big_ok) && chain_applies(k, nk, f.N, f.Smax <= 32767, !f.fits32) && f.ref_form >= 0 &&
                     chain_slots_per_cu(k, f.Smax <= 32767, 1, nk, !f.fits32) >= 1;
-    if (s8 && !(ge && atoi(ge) == 1)) return 1;
-    if (ge && atoi(ge) == 0) return 0;
+    if (s8 && env.generic != 1) return 1;
+    if (env.generic == 0) return 0;
     return k >= 1 && k <= KGMA_MAX_K && nk >= 1 && nk <= KGMA_MAX_NK_WIDE && generic_chain_slots_per_cu(k, nk) >= 1 ? 2 : 0;
 }
 
-static int chain_on_device(kgma_ctx *ctx, const kgma_genome *g, std::vector<ChainPair> &pairs, std::vector<char> &done, ChainDevInfo &info)
+// 2 k N^2: a KFV's exact distance is D / chain_scale
+static double chain_scale(int k, const KfvInfo &f)
 {
-    std::vector<size_t> el8, elg;
-    for (size_t i = 0; i < pairs.size(); i++) {
-        const ChainPair &p = pairs[i];
-        if (p.last < 2) continue;
-        const int which = chain_kernel_for(ctx, ctx->kfv[(size_t)p.j]);
-        if (which == 1) el8.push_back(i);
-        else if (which == 2) elg.push_back(i);
-    }
-    if (el8.empty() && elg.empty()) return KGMA_OK;
-    (void)hipSetDevice(ctx->device);
-    NumaBind numa(ctx);                      // (the pinned download buffers and the walking threads on the GPU's NUMA node: gigabytes come back on dense inputs)
-    // batches of bounded size (2^35 windows: a chunk array of 128 MiB), in record order; the host part of a batch overlaps
-    // the device part of the next, so what stays exposed is the LAST batch's host part: smaller batches, shorter tail
-    // (config 5, 2.5e11 windows, 1.31 s of kernels: 1577 ms with 2^36, 1499 ms with 2^35, 1542 ms with 2^34)
-    int64_t BATCH_WINDOWS = (int64_t)1 << 35;
-    if (const char *e = getenv("KGMA_CHAIN_BATCH_WINDOWS")) BATCH_WINDOWS = std::max<int64_t>(1, atoll(e));   // tests
-    // The host part of a batch (first windows, chunk walks) runs on a worker while the device works on the next batch;
-    // two pinned download buffers alternate.  (At most one worker at a time: it is joined before the next one starts.)
-    struct Worker {
-        std::thread th;
-        int rc = KGMA_OK;
-        int join() { if (th.joinable()) th.join(); const int r = rc; rc = KGMA_OK; return r; }
-        ~Worker() { if (th.joinable()) th.join(); }
-    } worker;
-    int sel = 0;
-    for (int pass = 0; pass < 2; pass++) {
-    const std::vector<size_t> &el = pass == 0 ? el8 : elg;
-    for (size_t u0 = 0; u0 < el.size();) {
-        size_t u1 = u0;
-        int64_t w = 0;
-        while (u1 < el.size() && (u1 == u0 || w + pairs[el[u1]].last <= BATCH_WINDOWS)) w += pairs[el[u1++]].last;
-        std::function<int()> fin;
-        const bool more = u1 < el.size() || worker.th.joinable() || (pass == 0 && !elg.empty());
-        const double tb0 = now_ms();
-        const int rc = chain_on_device_batch(ctx, g, pairs, std::vector<size_t>(el.begin() + (long)u0, el.begin() + (long)u1), done, info, false, sel,
-                                             more ? &fin : nullptr, pass == 1);
-        const double tb1 = now_ms();
-        const int wrc = worker.join();
-        if (getenv("KGMA_CHAIN_DEBUG")) fprintf(stderr, "  chain batch: device part %.2f ms, then %.2f ms waiting for the previous batch's host part\n", tb1 - tb0, now_ms() - tb1);
-        if (rc) return rc;
-        if (wrc) return fail(ctx, wrc, "internal: first window of a chained record");
-        if (fin) {
-            Worker *wk = &worker;
-            worker.th = std::thread([wk, fin = std::move(fin)]() mutable { wk->rc = fin(); });
-        }
-        sel ^= 1;
-        u0 = u1;
-    }
-    }
-    const double tj0 = now_ms();
-    const int wrc = worker.join();
-    if (getenv("KGMA_CHAIN_DEBUG")) fprintf(stderr, "  chain: %.2f ms waiting for the last batch's host part\n", now_ms() - tj0);
-    if (wrc) return fail(ctx, wrc, "internal: first window of a chained record");
-    return KGMA_OK;
+    return 2.0 * (double)k * (double)f.N * (double)f.N;
 }
 
-static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vector<ChainPair> &pairs, std::vector<size_t> el, std::vector<char> &done,
-                                 ChainDevInfo &info, bool export_only, int pin_sel, std::function<int()> *deferred, bool generic)
+// One host chain of KFV `f` over a record given as 2-bit codes: windows 1 .. last, sampled at `iv`
+static ChainJob chain_job(const KfvInfo &f, int k, const uint32_t *packed, int64_t n_res, int64_t last, const ChainInterval *iv, size_t n_iv, double *out)
 {
-    const int k = ctx->k;
-    const double ts0 = now_ms();
-    // ---- launch groups: the KFVs of one window size share the count table of a pass, so up to `maxg` of them that are
-    //      wanted on this batch CAN go into one launch (slots; a record's streams carry the mask of the slots it is flagged
-    //      for).  Measured, it does not pay: the flags are sparse (config 5: 268 of 800 (record, KFV) pairs, a record is
-    //      rarely wanted for two KFVs of one size), every slot costs its prefix sum in every step, and the 2-4 slot variants
-    //      spill 60-320 scalar registers -- config 4 (k = 6): chain kernels 16.0 ms with one KFV per launch, 18.8 ms with
-    //      two slots, 30.4 ms with four; a 20 Gb config-5 genome (k = 7): 145 ms against 191 ms with four slots.  So: one
-    //      KFV per launch; KGMA_CHAIN_GROUP=2..4 keeps the grouped form reachable for tests and for tie-dense inputs.
-    int maxg = 1;
-    if (const char *e = getenv("KGMA_CHAIN_GROUP")) maxg = std::max(1, std::min(4, atoi(e)));
-    if (generic) maxg = 1;                                             // (the generic chain kernel walks one KFV)
-    struct Launch { std::vector<int> kfvs; size_t t0, t1; int64_t T, chunk0, n_chunks; size_t d0_off; bool s16; };
-    struct PairStreams { size_t s0, s1; int64_t T; };            // into `streams` (per pair: its slot's chunk and D0 indices)
+    ChainJob J;
+    J.seq = nullptr; J.packed = packed; J.n_res = n_res; f.chain_ref(J);
+    J.k = k; J.W = f.W; J.last_window = last; J.iv = iv; J.n_iv = n_iv; J.out = out; J.n_out = 0; J.ok = false;
+    return J;
+}
+
+// the chain's value at window 1: kmer_count! + sqeuclidean of the first window (GenomeMiner.jl:42-47), on the host
+static ChainJob first_window_job(const KfvInfo &f, int k, const uint32_t *packed, double *out)
+{
+    static const ChainInterval one{1, 1};
+    return chain_job(f, k, packed, f.W, 1, &one, 1, out);
+}
+
+// ---- the plan of one batch: everything that is decided before the device is touched ----------------------------------
+struct ChainLaunch { std::vector<int> kfvs; size_t t0, t1; int64_t T, chunk0, n_chunks; size_t d0_off; bool s16; };
+struct PairStreams { size_t s0, s1; int64_t T; };                // into `streams` (per pair: its slot's chunk and D0 indices)
+
+struct ChainPlan {
+    bool generic = false;                                         // the generic chain kernel's batch (one KFV per launch)
+    std::vector<ChainLaunch> launches;
     std::vector<TileDesc> tiles;
     std::vector<ChainStream> streams;
     std::vector<size_t> stream_d0;                                // index of each stream's first-window D in the downloaded array
-    std::vector<PairStreams> ps(el.size());
-    std::vector<Launch> launches;
+    std::vector<PairStreams> ps;                                  // per pair of the batch
     int64_t n_chunks = 0, total_steps = 0;
     size_t d0_total = 0;
-    {
-        // KFVs wanted, by (k-mers per window, int16 tables)
-        std::vector<int> kf;
-        for (size_t u : el) kf.push_back(pairs[u].j);
-        std::sort(kf.begin(), kf.end());
-        kf.erase(std::unique(kf.begin(), kf.end()), kf.end());
-        std::stable_sort(kf.begin(), kf.end(), [&](int a, int b) {
-            const KfvInfo &fa = ctx->kfv[(size_t)a], &fb = ctx->kfv[(size_t)b];
-            if (fa.W != fb.W) return fa.W < fb.W;
-            return (fa.Smax <= 32767) > (fb.Smax <= 32767);
-        });
-        for (size_t i = 0; i < kf.size();) {
-            const KfvInfo &f0 = ctx->kfv[(size_t)kf[i]];
-            const bool s16 = f0.Smax <= 32767;
-            size_t e = i + 1;
-            while (!generic && e < kf.size() && (int)(e - i) < (s16 ? maxg : 1) && ctx->kfv[(size_t)kf[e]].W == f0.W && (ctx->kfv[(size_t)kf[e]].Smax <= 32767) == s16 &&
-                   f0.fits32 && ctx->kfv[(size_t)kf[e]].fits32 && chain_slots_per_cu(k, s16, (int)(e - i) + 1, (int)(f0.W - k + 1), false) > 0)
-                e++;
-            Launch L;
-            L.kfvs.assign(kf.begin() + (long)i, kf.begin() + (long)e);
-            L.s16 = s16; L.t0 = L.t1 = 0; L.T = 0; L.chunk0 = L.n_chunks = 0; L.d0_off = 0;
-            launches.push_back(L);
-            i = e;
-        }
+    // hot steps: every step that holds a transition into a wanted window, as one 64-bit mask per chunk that has any
+    size_t hot_words = 0;
+    std::vector<uint32_t> hot;                                    // [bit per chunk | hot chunks before each word]
+    std::vector<uint64_t> hot_masks;                              // (never empty: one zero word when no chunk is hot)
+    int64_t hot_steps = 0, hot_chunks = 0;
+
+    int64_t n_tiles() const { return (int64_t)tiles.size(); }
+    // (beyond these the batch is left to the host chain)
+    bool fits() const { return n_tiles() <= 0x7FFFFFF0ll && n_chunks <= 0x7FFFFFF0ll && (int64_t)d0_total <= 0x7FFFFFF0ll; }
+};
+
+// ---- launch groups: the KFVs of one window size share the count table of a pass, so up to `maxg` of them that are
+//      wanted on this batch CAN go into one launch (slots; a record's streams carry the mask of the slots it is flagged
+//      for).  Measured, it does not pay: the flags are sparse (config 5: 268 of 800 (record, KFV) pairs, a record is
+//      rarely wanted for two KFVs of one size), every slot costs its prefix sum in every step, and the 2-4 slot variants
+//      spill 60-320 scalar registers -- config 4 (k = 6): chain kernels 16.0 ms with one KFV per launch, 18.8 ms with
+//      two slots, 30.4 ms with four; a 20 Gb config-5 genome (k = 7): 145 ms against 191 ms with four slots.  So: one
+//      KFV per launch; KGMA_CHAIN_GROUP=2..4 keeps the grouped form reachable for tests and for tie-dense inputs.
+static void plan_chain_launches(const kgma_ctx *ctx, const ChainEnv &env, const std::vector<ChainPair> &pairs, const std::vector<size_t> &el, ChainPlan &plan)
+{
+    const int k = ctx->k;
+    const int maxg = plan.generic ? 1 : env.group;                     // (the generic chain kernel walks one KFV)
+    // KFVs wanted, by (k-mers per window, int16 tables)
+    std::vector<int> kf;
+    for (size_t u : el) kf.push_back(pairs[u].j);
+    std::sort(kf.begin(), kf.end());
+    kf.erase(std::unique(kf.begin(), kf.end()), kf.end());
+    std::stable_sort(kf.begin(), kf.end(), [&](int a, int b) {
+        const KfvInfo &fa = ctx->kfv[(size_t)a], &fb = ctx->kfv[(size_t)b];
+        if (fa.W != fb.W) return fa.W < fb.W;
+        return (fa.Smax <= 32767) > (fb.Smax <= 32767);
+    });
+    for (size_t i = 0; i < kf.size();) {
+        const KfvInfo &f0 = ctx->kfv[(size_t)kf[i]];
+        const bool s16 = f0.Smax <= 32767;
+        size_t e = i + 1;
+        while (!plan.generic && e < kf.size() && (int)(e - i) < (s16 ? maxg : 1) && ctx->kfv[(size_t)kf[e]].W == f0.W && (ctx->kfv[(size_t)kf[e]].Smax <= 32767) == s16 &&
+               f0.fits32 && ctx->kfv[(size_t)kf[e]].fits32 && chain_slots_per_cu(k, s16, (int)(e - i) + 1, (int)(f0.W - k + 1), false) > 0)
+            e++;
+        ChainLaunch L;
+        L.kfvs.assign(kf.begin() + (long)i, kf.begin() + (long)e);
+        L.s16 = s16; L.t0 = L.t1 = 0; L.T = 0; L.chunk0 = L.n_chunks = 0; L.d0_off = 0;
+        plan.launches.push_back(L);
+        i = e;
     }
-    for (Launch &L : launches) {
+}
+
+// Per launch: its records, the stream length, the stream table (tiles) and every pair's view of its record's streams
+static void plan_chain_streams(const kgma_ctx *ctx, const kgma_genome *g, const ChainEnv &env, const std::vector<ChainPair> &pairs, const std::vector<size_t> &el,
+                               ChainPlan &plan)
+{
+    const int k = ctx->k;
+    std::vector<TileDesc> &tiles = plan.tiles;
+    plan.ps.assign(el.size(), PairStreams{0, 0, 0});
+    for (ChainLaunch &L : plan.launches) {
         const int nslots = (int)L.kfvs.size();
         const int nk = (int)(ctx->kfv[(size_t)L.kfvs[0]].W - k + 1);
         // the records of this launch: per record the slots wanted and the last window any of them wants
-        struct Rec { int32_t c; uint32_t mask; int64_t last; };
-        std::vector<Rec> recs;
+        struct LaunchRecord { int32_t c; uint32_t mask; int64_t last; };
+        std::vector<LaunchRecord> recs;
         for (size_t u = 0; u < el.size(); u++) {
             const ChainPair &p = pairs[el[u]];
             const auto it = std::find(L.kfvs.begin(), L.kfvs.end(), p.j);
             if (it == L.kfvs.end()) continue;
             const uint32_t bit = 1u << (it - L.kfvs.begin());
-            auto r = std::find_if(recs.begin(), recs.end(), [&](const Rec &x) { return x.c == p.c; });
-            if (r == recs.end()) recs.push_back(Rec{p.c, bit, p.last});
+            auto r = std::find_if(recs.begin(), recs.end(), [&](const LaunchRecord &x) { return x.c == p.c; });
+            if (r == recs.end()) recs.push_back(LaunchRecord{p.c, bit, p.last});
             else { r->mask |= bit; r->last = std::max(r->last, p.last); }
         }
-        std::sort(recs.begin(), recs.end(), [](const Rec &a, const Rec &b) { return a.c < b.c; });
+        std::sort(recs.begin(), recs.end(), [](const LaunchRecord &a, const LaunchRecord &b) { return a.c < b.c; });
         int64_t windows = 0;
-        for (const Rec &r : recs) windows += r.last;
+        for (const LaunchRecord &r : recs) windows += r.last;
         // transitions per stream: about three rounds of streams over the chip, 64 | T (streams start on plane words), at most
         // 2^18 (the drift a stream may add stays far below the guard band)
         int64_t T;
         {
             const int64_t slots = (int64_t)std::max(1, ctx->n_cus) *
-                                  (generic ? generic_chain_slots_per_cu(k, nk) : chain_slots_per_cu(k, L.s16, nslots, nk, !ctx->kfv[(size_t)L.kfvs[0]].fits32));
+                                  (plan.generic ? generic_chain_slots_per_cu(k, nk) : chain_slots_per_cu(k, L.s16, nslots, nk, !ctx->kfv[(size_t)L.kfvs[0]].fits32));
             T = (windows + slots * 3 - 1) / (slots * 3);
-            if (const char *e = getenv("KGMA_CHAIN_STREAM")) T = atoll(e);                     // experiments / tests
+            if (env.stream_set) T = env.stream;
             // (a stream's warm-up is its window's n k-mers: streams of at least 4 n transitions)
             T = std::min<int64_t>(std::max<int64_t>(((T + 63) / 64) * 64, std::max<int64_t>(1024, (((int64_t)4 * nk + 63) / 64) * 64)), (int64_t)1 << 18);
         }
         L.T = T;
         L.t0 = tiles.size();
-        L.chunk0 = n_chunks;
+        L.chunk0 = plan.n_chunks;
         int64_t local_chunks = 0;
         std::vector<std::pair<size_t, size_t>> rec_tiles(recs.size());
         for (size_t ri = 0; ri < recs.size(); ri++) {
-            const Rec &r = recs[ri];
+            const LaunchRecord &r = recs[ri];
             rec_tiles[ri].first = tiles.size();
             for (int64_t win0 = 1; win0 < r.last; win0 += T) {
                 TileDesc td;
@@ -4240,15 +4266,15 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
                 tiles.push_back(td);
                 const int64_t nb = ((int64_t)td.n_valid + nk - 1 + 63) >> 6;
                 local_chunks += (nb + KGMA_CHAIN_STEPS - 1) / KGMA_CHAIN_STEPS;
-                total_steps += nb * __builtin_popcount(r.mask);
+                plan.total_steps += nb * __builtin_popcount(r.mask);
             }
             rec_tiles[ri].second = tiles.size();
         }
         L.t1 = tiles.size();
         L.n_chunks = local_chunks;
-        n_chunks += local_chunks * nslots;
-        L.d0_off = d0_total;
-        d0_total += (size_t)ctx->m * (L.t1 - L.t0);                   // the kernel indexes first-window D by [KFV][stream of the launch]
+        plan.n_chunks += local_chunks * nslots;
+        L.d0_off = plan.d0_total;
+        plan.d0_total += (size_t)ctx->m * (L.t1 - L.t0);              // the kernel indexes first-window D by [KFV][stream of the launch]
         // every pair's view of its record's streams: its own slot's chunk records and first-window D
         for (size_t u = 0; u < el.size(); u++) {
             const ChainPair &p = pairs[el[u]];
@@ -4257,160 +4283,209 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
             const int64_t slot = it - L.kfvs.begin();
             size_t ri = 0;
             while (recs[ri].c != p.c) ri++;
-            ps[u].s0 = streams.size();
-            ps[u].T = T;
+            plan.ps[u].s0 = plan.streams.size();
+            plan.ps[u].T = T;
             for (size_t t = rec_tiles[ri].first; t < rec_tiles[ri].second; t++) {
                 const TileDesc &td = tiles[t];
                 if (td.win0 >= p.last) break;                           // (the record's streams go on for another slot)
-                streams.push_back(ChainStream{td.win0, td.dist_base + slot * L.n_chunks, 0, td.n_valid, 0});
-                stream_d0.push_back(L.d0_off + (size_t)p.j * (L.t1 - L.t0) + (t - L.t0));
+                plan.streams.push_back(ChainStream{td.win0, td.dist_base + slot * L.n_chunks, 0, td.n_valid, 0});
+                plan.stream_d0.push_back(L.d0_off + (size_t)p.j * (L.t1 - L.t0) + (t - L.t0));
             }
-            ps[u].s1 = streams.size();
+            plan.ps[u].s1 = plan.streams.size();
         }
     }
-    const int64_t n_tiles = (int64_t)tiles.size();
-    if (n_tiles > 0x7FFFFFF0ll || n_chunks > 0x7FFFFFF0ll || (int64_t)d0_total > 0x7FFFFFF0ll) return KGMA_OK;   // (left to the host chain)
+}
 
-    // hot steps: every step that holds a transition into a wanted window, as one 64-bit mask per chunk that has any
-    const size_t hot_words = (size_t)(n_chunks + 31) / 32 + 1;
-    std::vector<uint32_t> hot(2 * hot_words, 0u);                      // [bit per chunk | hot chunks before each word]
-    std::vector<uint64_t> hot_masks;
-    int64_t hot_steps = 0;
-    {
-        std::vector<std::pair<int64_t, uint64_t>> marks;               // (chunk, step bit), in stream order per pair
-        for (size_t u = 0; u < el.size(); u++) {
-            const ChainPair &p = pairs[el[u]];
-            const int nk = (int)(ctx->kfv[(size_t)p.j].W - k + 1);
-            for (const ChainInterval &x : p.iv)
-                for (int64_t w = std::max<int64_t>(x.lo, 2); w <= x.hi; w++) {
-                    const int64_t si = (w - 2) / ps[u].T;
-                    const ChainStream &S = streams[ps[u].s0 + (size_t)si];
-                    const int64_t pos = (w - S.win0) + nk - 1;
-                    const int64_t cid = S.chunk_base + (pos >> (6 + KGMA_CHAIN_STEPS_LOG2));
-                    marks.emplace_back(cid, (uint64_t)1 << ((pos >> 6) & (KGMA_CHAIN_STEPS - 1)));
-                    // (jump to the step's last window: the windows of one step share the bit)
-                    const int64_t w_step_last = S.win0 + (pos | 63) - nk + 1;
-                    if (w_step_last > w) w = std::min(w_step_last, std::min<int64_t>(x.hi, S.win0 + S.n_valid - 1));
-                }
-        }
-        std::sort(marks.begin(), marks.end());
-        for (size_t i = 0; i < marks.size();) {
-            uint64_t m = 0;
-            size_t j = i;
-            while (j < marks.size() && marks[j].first == marks[i].first) m |= marks[j++].second;
-            hot[(size_t)(marks[i].first >> 5)] |= 1u << (marks[i].first & 31);
-            hot_masks.push_back(m);
-            hot_steps += __builtin_popcountll(m);
-            i = j;
-        }
-        uint32_t before = 0;
-        for (size_t wd = 0; wd < hot_words; wd++) { hot[hot_words + wd] = before; before += (uint32_t)__builtin_popcount(hot[wd]); }
+static void mark_hot_steps(const kgma_ctx *ctx, const std::vector<ChainPair> &pairs, const std::vector<size_t> &el, ChainPlan &plan)
+{
+    const int k = ctx->k;
+    const size_t hot_words = plan.hot_words = (size_t)(plan.n_chunks + 31) / 32 + 1;
+    plan.hot.assign(2 * hot_words, 0u);
+    std::vector<std::pair<int64_t, uint64_t>> marks;                   // (chunk, step bit), in stream order per pair
+    for (size_t u = 0; u < el.size(); u++) {
+        const ChainPair &p = pairs[el[u]];
+        const int nk = (int)(ctx->kfv[(size_t)p.j].W - k + 1);
+        for (const ChainInterval &x : p.iv)
+            for (int64_t w = std::max<int64_t>(x.lo, 2); w <= x.hi; w++) {
+                const int64_t si = (w - 2) / plan.ps[u].T;
+                const ChainStream &S = plan.streams[plan.ps[u].s0 + (size_t)si];
+                const int64_t pos = (w - S.win0) + nk - 1;
+                const int64_t cid = S.chunk_base + (pos >> (6 + KGMA_CHAIN_STEPS_LOG2));
+                marks.emplace_back(cid, (uint64_t)1 << ((pos >> 6) & (KGMA_CHAIN_STEPS - 1)));
+                // (jump to the step's last window: the windows of one step share the bit)
+                const int64_t w_step_last = S.win0 + (pos | 63) - nk + 1;
+                if (w_step_last > w) w = std::min(w_step_last, std::min<int64_t>(x.hi, S.win0 + S.n_valid - 1));
+            }
     }
-    const int64_t hot_chunks = (int64_t)hot_masks.size();
-    if (hot_masks.empty()) hot_masks.push_back(0);
+    std::sort(marks.begin(), marks.end());
+    for (size_t i = 0; i < marks.size();) {
+        uint64_t m = 0;
+        size_t j = i;
+        while (j < marks.size() && marks[j].first == marks[i].first) m |= marks[j++].second;
+        plan.hot[(size_t)(marks[i].first >> 5)] |= 1u << (marks[i].first & 31);
+        plan.hot_masks.push_back(m);
+        plan.hot_steps += __builtin_popcountll(m);
+        i = j;
+    }
+    uint32_t before = 0;
+    for (size_t wd = 0; wd < hot_words; wd++) { plan.hot[hot_words + wd] = before; before += (uint32_t)__builtin_popcount(plan.hot[wd]); }
+    plan.hot_chunks = (int64_t)plan.hot_masks.size();
+    if (plan.hot_masks.empty()) plan.hot_masks.push_back(0);
+}
 
-    int rc = dev_reserve(ctx, ctx->d_ctiles, ctx->ctiles_cap, n_tiles);
+// ---- the device part of one batch ---------------------------------------------------------------------------------------
+// (everything but the pool, which run_chain_kernels sizes; `set`: the other set may still be on its way to the host)
+static int reserve_chain_buffers(kgma_ctx *ctx, const ChainPlan &plan, ChainBufferSet &set)
+{
+    int rc = dev_reserve(ctx, ctx->d_ctiles, ctx->ctiles_cap, plan.n_tiles());
     if (rc) return rc;
-    // (output buffers and download buffer number pin_sel: the other set may still be on its way to the host)
-    ChainChunk *&d_cchunks = pin_sel ? ctx->d_cchunks2 : ctx->d_cchunks;
-    int64_t &cchunks_cap = pin_sel ? ctx->cchunks2_cap : ctx->cchunks_cap;
-    ChainChunk *&d_cpool = pin_sel ? ctx->d_cpool2 : ctx->d_cpool;
-    int64_t &cpool_cap = pin_sel ? ctx->cpool2_cap : ctx->cpool_cap;
-    int64_t *&d_cD0 = pin_sel ? ctx->d_cD02 : ctx->d_cD0;
-    int64_t &cD0_cap = pin_sel ? ctx->cD02_cap : ctx->cD0_cap;
     if (!ctx->chain_copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->chain_copy_stream, hipStreamNonBlocking));
-    rc = dev_reserve(ctx, d_cchunks, cchunks_cap, n_chunks);
+    rc = dev_reserve(ctx, set.chunks, set.chunks_cap, plan.n_chunks);
     if (rc) return rc;
-    rc = dev_reserve(ctx, ctx->d_chot, ctx->chot_cap, (int64_t)hot.size());
+    rc = dev_reserve(ctx, ctx->d_chot, ctx->chot_cap, (int64_t)plan.hot.size());
     if (rc) return rc;
-    rc = dev_reserve(ctx, ctx->d_chmask, ctx->chmask_cap, (int64_t)hot_masks.size());
+    rc = dev_reserve(ctx, ctx->d_chmask, ctx->chmask_cap, (int64_t)plan.hot_masks.size());
     if (rc) return rc;
-    rc = dev_reserve(ctx, d_cD0, cD0_cap, (int64_t)d0_total);
+    rc = dev_reserve(ctx, set.D0, set.D0_cap, (int64_t)plan.d0_total);
     if (rc) return rc;
     if (!ctx->d_cctl) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_cctl), 16));
+    return KGMA_OK;
+}
 
+// One launch of the batch: the parameters of its KFVs, its slice of the stream table, the batch's output buffers
+static int launch_chain_group(kgma_ctx *ctx, const kgma_genome *g, const ChainPlan &plan, const ChainLaunch &L, const ChainBufferSet &set, int64_t pool_units)
+{
+    const int k = ctx->k, nslots = (int)L.kfvs.size();
+    GroupParams gp;
+    memset(&gp, 0, sizeof gp);
+    ScanArgs a;
+    memset(&a, 0, sizeof a);
+    gp.n_kfv = nslots; gp.k = k;
+    gp.nk = gp.nk_min = (int32_t)(ctx->kfv[(size_t)L.kfvs[0]].W - k + 1);
+    gp.need_wide = ctx->kfv[(size_t)L.kfvs[0]].fits32 ? 0 : 1;
+    fill_group_params(ctx, L.kfvs, gp);
+    // (a launch's KFVs have one window size and one S width; the chain kernels do not look at s_fits_u8)
+    gp.n_sizes = 1; gp.sizes[0] = gp.nk;
+    gp.s_fits_i16 = L.s16 ? 1 : 0;
+    for (int u = 0; u < nslots; u++) {
+        const KfvInfo &f = ctx->kfv[(size_t)L.kfvs[(size_t)u]];
+        gp.chain_invN[u] = 1.0 / (double)f.N;
+        gp.chain_form[u] = f.ref_form;
+    }
+    a.inter = g->d_inter;
+    a.tiles = ctx->d_ctiles + L.t0;
+    a.n_tiles = (int32_t)(L.t1 - L.t0);
+    a.Stab = ctx->d_Stab;
+    if (!plan.generic && k >= 7) {
+        // k = 7: the kernel gathers S from global memory, one row of int16 slots per k-mer (the scan's compacted layout)
+        const int nv = nslots == 3 ? 4 : nslots;                       // row width in int16 slots (the kernel variant's)
+        const int rc = sinter_tables(ctx, L.kfvs, nv, &a.Sinter, &a.Sbits);
+        if (rc) return rc;
+    }
+    if (!plan.generic && stream8_state_words(k, nslots) > 0) {
+        const int rc = dev_reserve(ctx, ctx->d_wstate, ctx->wstate_cap, (int64_t)(L.t1 - L.t0) * stream8_state_words(k, nslots));
+        if (rc) return rc;
+        a.wave_state = ctx->d_wstate;
+    }
+    a.D0out = set.D0 + L.d0_off;                                       // [KFV][stream of this launch]
+    a.n_chunk_tiles = a.n_tiles;
+    a.chain.chunks = set.chunks;
+    a.chain.pool = set.pool;
+    a.chain.pool_cursor = ctx->d_cctl;
+    a.chain.pool_cap = (unsigned int)pool_units;
+    a.chain.hot = ctx->d_chot;
+    a.chain.hot_prefix = ctx->d_chot + plan.hot_words;
+    a.chain.hot_masks = ctx->d_chmask;
+    a.chain.chunk_stride = L.n_chunks;
+    a.chain.SF = 1.0 / (double)k;                                      // src/API.jl:86,204
+    a.chain.guard = 1.862645149230957e-09;                             // 2^-29
+    a.chain.guard_abs = 9.313225746154785e-10;                         // 2^-30 of the stream's first distance
+    a.chain.status = ctx->d_cctl + 1;
+    if (plan.generic) {
+        GenParams gg;                                                  // (the chain walks the Float64 table whatever the KFV's form)
+        const int rc = fill_gen_params(ctx, L.kfvs[0], gp.nk, gp.nk, (int32_t)((int64_t)std::max(1, ctx->n_cus) * generic_chain_slots_per_cu(k, gp.nk)), true, "chain", gg);
+        if (rc) return rc;
+        HIP_TRY(ctx, launch_generic_chain(a, gg, ctx->stream));
+        return KGMA_OK;
+    }
+    HIP_TRY(ctx, launch_chain(a, gp, ctx->stream));
+    return KGMA_OK;
+}
+
+// One batch of pairs on the device.  It owns what its host part needs -- the plan, the download layout, the list of its pairs --
+// so that finish() can run on chain_on_device's worker after the frame that built the batch is gone: finish() touches what the
+// batch owns, the pinned mirror of its buffer set (not reused before the worker is joined), the context's reference tables
+// (constant during the call) and, of the caller's, `pairs` / `done` / `info` alone, which outlive the worker (chain_on_device
+// joins it before it returns).  The worker and the launching thread write disjoint fields of `info` (ChainDevInfo) and disjoint
+// elements of `done` and of the pairs' values.
+struct ChainBatch {
+    kgma_ctx *ctx; const kgma_genome *g; ChainEnv env;
+    std::vector<ChainPair> &pairs; std::vector<char> &done; ChainDevInfo &info;
+    std::vector<size_t> el;                        // the batch's pairs (indices into `pairs`)
+    ChainBufferSet *set;                           // output buffers and pinned mirror of this batch
+    bool export_only = false;                      // kgma_chain_export: the pair's material goes to the context, nothing is walked
+    ChainPlan plan;
+    int64_t pool_units = 0;                        // the pool the launches ran with, cut to what they used
+    bool downloading = false;                      // start_download() ran: finish() is due
+    // the download: [D0 per stream | chunk records | the used part of the pool | per record the residues of its first window]
+    struct RecordSlice { int32_t c; size_t dw_off, dw; };
+    std::vector<RecordSlice> recs;
+    size_t off_D0 = 0, off_chunks = 0, off_raw = 0, off_first = 0;
+    const uint8_t *pin = nullptr;
+    hipStream_t copy_stream = nullptr;
+    double t_copy0 = 0;
+
+    ChainBatch(kgma_ctx *ctx_, const kgma_genome *g_, const ChainEnv &env_, std::vector<ChainPair> &pairs_, std::vector<char> &done_, ChainDevInfo &info_,
+               std::vector<size_t> el_, int sel, bool generic)
+        : ctx(ctx_), g(g_), env(env_), pairs(pairs_), done(done_), info(info_), el(std::move(el_)), set(&ctx_->cset[sel]) { plan.generic = generic; }
+
+    int start_download();
+    int finish();
+
+private:
+    bool first_windows(std::vector<double> &first) const;
+    void export_pair(const std::vector<double> &first);
+    void walk_pairs(const std::vector<double> &first);
+};
+
+// Upload the plan, launch every group, read the control words back; a launch that ran out of pool is repeated once with the
+// pool it asked for.  *served = false with KGMA_OK: no room (or a batch beyond the pool's index range) -- the host chain
+static int run_chain_kernels(ChainBatch &b, bool *served)
+{
+    kgma_ctx *ctx = b.ctx;
+    const ChainPlan &plan = b.plan;
+    ChainBufferSet &set = *b.set;
+    ChainDevInfo &info = b.info;
+    *served = false;
     // pool (16-byte units): 32 per raw step + up to KGMA_CHAIN_STEPS entries per detailed chunk.  The hot steps are
     // known; for the steps that go raw on a binade change there is room for one in a few hundred, and the launch is
     // repeated once with what it asked for if that was short
-    info.setup_ms += now_ms() - ts0;
-    info.chunks += n_chunks;
-    const int64_t full_units = total_steps * 33 + n_chunks + 64;       // every step raw
-    const int64_t hot_units = hot_steps * 32 + hot_chunks * KGMA_CHAIN_STEPS;
+    const int64_t total_steps = plan.total_steps;
+    const int64_t full_units = total_steps * 33 + plan.n_chunks + 64;  // every step raw
+    const int64_t hot_units = plan.hot_steps * 32 + plan.hot_chunks * KGMA_CHAIN_STEPS;
     int64_t pool_units = hot_units + std::max<int64_t>(1 << 18, std::min<int64_t>(total_steps / 3, (int64_t)1 << 29));
     if (ctx->cpool_per_step > 0)                                       // (what the previous scans of this context needed, with a margin)
         pool_units = std::max(pool_units, hot_units + (int64_t)(1.25 * ctx->cpool_per_step * (double)total_steps) + (1 << 16));
-    if (const char *e = getenv("KGMA_CHAIN_POOL_UNITS")) pool_units = std::max<int64_t>(1, atoll(e));   // tests: force the regrowth
+    if (b.env.pool_units > 0) pool_units = b.env.pool_units;
     for (int attempt = 0;; attempt++) {
         info.attempts = std::max(info.attempts, attempt + 1);
         pool_units = std::min<int64_t>(pool_units, full_units);
         if (pool_units > 0xFFFFFFF0ll) return KGMA_OK;
-        if (cpool_cap < pool_units) {
+        if (set.pool_cap < pool_units) {
             ChainChunk *fresh = nullptr;
             int64_t cap = 0;
             if (dev_reserve(ctx, fresh, cap, pool_units) != KGMA_OK) { ctx->err.clear(); (void)hipGetLastError(); return KGMA_OK; }   // no room: host chain
-            if (d_cpool) { (void)hipFree(d_cpool); ctx->device_bytes -= cpool_cap * (int64_t)sizeof(ChainChunk); }
-            d_cpool = fresh; cpool_cap = cap;
+            if (set.pool) { (void)hipFree(set.pool); ctx->device_bytes -= set.pool_cap * (int64_t)sizeof(ChainChunk); }
+            set.pool = fresh; set.pool_cap = cap;
         }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctiles, tiles.data(), (size_t)n_tiles * sizeof(TileDesc), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_chot, hot.data(), hot.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_chmask, hot_masks.data(), hot_masks.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctiles, plan.tiles.data(), (size_t)plan.n_tiles() * sizeof(TileDesc), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_chot, plan.hot.data(), plan.hot.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_chmask, plan.hot_masks.data(), plan.hot_masks.size() * 8, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_cctl, 0, 16, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (const Launch &L : launches) {
-            const int nslots = (int)L.kfvs.size();
-            GroupParams gp;
-            memset(&gp, 0, sizeof gp);
-            ScanArgs a;
-            memset(&a, 0, sizeof a);
-            gp.n_kfv = nslots; gp.k = k;
-            gp.nk = gp.nk_min = (int32_t)(ctx->kfv[(size_t)L.kfvs[0]].W - k + 1);
-            gp.need_wide = ctx->kfv[(size_t)L.kfvs[0]].fits32 ? 0 : 1;
-            fill_group_params(ctx, L.kfvs, gp);
-            // (a launch's KFVs have one window size and one S width; the chain kernels do not look at s_fits_u8)
-            gp.n_sizes = 1; gp.sizes[0] = gp.nk;
-            gp.s_fits_i16 = L.s16 ? 1 : 0;
-            for (int u = 0; u < nslots; u++) {
-                const KfvInfo &f = ctx->kfv[(size_t)L.kfvs[(size_t)u]];
-                gp.chain_invN[u] = 1.0 / (double)f.N;
-                gp.chain_form[u] = f.ref_form;
-            }
-            a.inter = g->d_inter;
-            a.tiles = ctx->d_ctiles + L.t0;
-            a.n_tiles = (int32_t)(L.t1 - L.t0);
-            a.Stab = ctx->d_Stab;
-            if (!generic && k >= 7) {
-                // k = 7: the kernel gathers S from global memory, one row of int16 slots per k-mer (the scan's compacted layout)
-                const int nv = nslots == 3 ? 4 : nslots;               // row width in int16 slots (the kernel variant's)
-                rc = sinter_tables(ctx, L.kfvs, nv, &a.Sinter, &a.Sbits);
-                if (rc) return rc;
-            }
-            if (!generic && stream8_state_words(k, nslots) > 0) {
-                rc = dev_reserve(ctx, ctx->d_wstate, ctx->wstate_cap, (int64_t)(L.t1 - L.t0) * stream8_state_words(k, nslots));
-                if (rc) return rc;
-                a.wave_state = ctx->d_wstate;
-            }
-            a.D0out = d_cD0 + L.d0_off;                       // [KFV][stream of this launch]
-            a.n_chunk_tiles = a.n_tiles;
-            a.chain.chunks = d_cchunks;
-            a.chain.pool = d_cpool;
-            a.chain.pool_cursor = ctx->d_cctl;
-            a.chain.pool_cap = (unsigned int)pool_units;
-            a.chain.hot = ctx->d_chot;
-            a.chain.hot_prefix = ctx->d_chot + hot_words;
-            a.chain.hot_masks = ctx->d_chmask;
-            a.chain.chunk_stride = L.n_chunks;
-            a.chain.SF = 1.0 / (double)k;                           // src/API.jl:86,204
-            a.chain.guard = 1.862645149230957e-09;                  // 2^-29
-            a.chain.guard_abs = 9.313225746154785e-10;              // 2^-30 of the stream's first distance
-            a.chain.status = ctx->d_cctl + 1;
-            if (generic) {
-                GenParams gg;                                       // (the chain walks the Float64 table whatever the KFV's form)
-                rc = fill_gen_params(ctx, L.kfvs[0], gp.nk, gp.nk, (int32_t)((int64_t)std::max(1, ctx->n_cus) * generic_chain_slots_per_cu(k, gp.nk)), true, "chain", gg);
-                if (rc) return rc;
-                HIP_TRY(ctx, launch_generic_chain(a, gg, ctx->stream));
-                continue;
-            }
-            HIP_TRY(ctx, launch_chain(a, gp, ctx->stream));
+        for (const ChainLaunch &L : plan.launches) {
+            const int rc = launch_chain_group(ctx, b.g, plan, L, set, pool_units);
+            if (rc) return rc;
         }
         HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
         unsigned int ctl[4] = {0, 0, 0, 0};
@@ -4419,8 +4494,8 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
         info.kernel_ms += ms;
-        if (getenv("KGMA_CHAIN_DEBUG"))
-            fprintf(stderr, "  chain batch: %zu pairs, %lld steps, %lld hot units, pool of %lld units, %u asked for%s, attempt %d, kernels %.2f ms\n", el.size(),
+        if (b.env.debug)
+            fprintf(stderr, "  chain batch: %zu pairs, %lld steps, %lld hot units, pool of %lld units, %u asked for%s, attempt %d, kernels %.2f ms\n", b.el.size(),
                     (long long)total_steps, (long long)hot_units, (long long)pool_units, ctl[0], (ctl[1] & 1u) ? " (ran out)" : "", attempt, ms);
         if (ctl[1] & 2u) return fail(ctx, KGMA_E_HIP, "internal: the chain kernel gave up on a stream (hash table of the window's k-mers)");
         if (!(ctl[1] & 1u)) {
@@ -4432,96 +4507,106 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
         if (attempt >= 1 || pool_units >= full_units) return KGMA_OK;                 // (cannot happen: the second pool is what the first launch asked for)
         pool_units = (int64_t)ctl[0] + (ctl[0] >> 4) + 4096;
     }
+    b.pool_units = pool_units;
+    *served = true;
+    return KGMA_OK;
+}
 
-    // ---- download: D0 per stream, chunk records, the used part of the raw pool; the pairs' first residues ----
-    const double tc0 = now_ms();
-    struct Rec { int32_t c; size_t dw_off, dw; };
-    std::vector<Rec> recs;
+// ---- download: D0 per stream, chunk records, the used part of the raw pool; the pairs' first residues ----
+int ChainBatch::start_download()
+{
+    t_copy0 = now_ms();
     size_t first_dw = 0;
-    for (size_t u = 0; u < el.size(); u++) {
-        const ChainPair &p = pairs[el[u]];
+    for (size_t u : el) {
+        const ChainPair &p = pairs[u];
         const size_t dw = (size_t)((ctx->kfv[(size_t)p.j].W + 15) / 16);
-        auto it = std::find_if(recs.begin(), recs.end(), [&](const Rec &r) { return r.c == p.c; });
-        if (it == recs.end()) recs.push_back(Rec{p.c, 0, dw});
+        auto it = std::find_if(recs.begin(), recs.end(), [&](const RecordSlice &r) { return r.c == p.c; });
+        if (it == recs.end()) recs.push_back(RecordSlice{p.c, 0, dw});
         else it->dw = std::max(it->dw, dw);
     }
-    for (Rec &r : recs) { r.dw_off = first_dw; first_dw += r.dw + 2; }
-    const size_t off_D0 = 0, off_chunks = off_D0 + d0_total * 8, off_raw = off_chunks + (size_t)n_chunks * sizeof(ChainChunk),
-                 off_first = off_raw + (size_t)pool_units * sizeof(ChainChunk), pin_need = off_first + first_dw * 4 + 64;
-    uint8_t *&pin_buf = pin_sel ? ctx->h_cpin2 : ctx->h_cpin;        // (its previous user, two batches ago, has been joined)
-    size_t &pin_cap = pin_sel ? ctx->cpin2_cap : ctx->cpin_cap;
-    if (pin_need > pin_cap) {
-        if (pin_buf) (void)hipHostFree(pin_buf);
-        pin_buf = nullptr; pin_cap = 0;
-        const size_t cap = pin_need + (pin_need >> 2);
-        if (hipHostMalloc(reinterpret_cast<void **>(&pin_buf), cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return KGMA_OK; }
-        pin_cap = cap;
-    }
-    uint8_t *const pin = pin_buf;
-    // (the launches have finished: the copies go to their own stream, and the worker below waits for them, so that the next
+    for (RecordSlice &r : recs) { r.dw_off = first_dw; first_dw += r.dw + 2; }
+    off_D0 = 0; off_chunks = off_D0 + plan.d0_total * 8; off_raw = off_chunks + (size_t)plan.n_chunks * sizeof(ChainChunk);
+    off_first = off_raw + (size_t)pool_units * sizeof(ChainChunk);
+    const size_t pin_need = off_first + first_dw * 4 + 64;
+    // (the mirror's previous user, two batches ago, has been joined)
+    if (!grow_pinned(set->pin, set->pin_cap, pin_need, pin_need >> 2)) { (void)hipGetLastError(); return KGMA_OK; }
+    uint8_t *const dst = set->pin;
+    pin = dst;
+    // (the launches have finished: the copies go to their own stream, and finish() waits for them, so that the next
     //  batch's launches -- into the other set of buffers -- run while this batch comes down)
-    hipStream_t cs = ctx->chain_copy_stream;
-    HIP_TRY(ctx, hipMemcpyAsync(pin + off_D0, d_cD0, d0_total * 8, hipMemcpyDeviceToHost, cs));
-    HIP_TRY(ctx, hipMemcpyAsync(pin + off_chunks, d_cchunks, (size_t)n_chunks * sizeof(ChainChunk), hipMemcpyDeviceToHost, cs));
+    hipStream_t cs = copy_stream = ctx->chain_copy_stream;
+    HIP_TRY(ctx, hipMemcpyAsync(dst + off_D0, set->D0, plan.d0_total * 8, hipMemcpyDeviceToHost, cs));
+    HIP_TRY(ctx, hipMemcpyAsync(dst + off_chunks, set->chunks, (size_t)plan.n_chunks * sizeof(ChainChunk), hipMemcpyDeviceToHost, cs));
     if (pool_units > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(pin + off_raw, d_cpool, (size_t)pool_units * sizeof(ChainChunk), hipMemcpyDeviceToHost, cs));
-    for (const Rec &r : recs)
-        HIP_TRY(ctx, hipMemcpyAsync(pin + off_first + r.dw_off * 4, g->d_inter + 2 * g->cd[(size_t)r.c].word_off, r.dw * 4, hipMemcpyDeviceToHost, cs));
-    const int device = ctx->device;
-    // ---- host part: first windows and chunk walks (on a worker when more batches follow) ----
-    auto finish = [=, &pairs, &done, &info, streams = std::move(streams), stream_d0 = std::move(stream_d0), el = std::move(el), ps = std::move(ps),
-                   recs = std::move(recs)]() mutable -> int {
-    (void)hipSetDevice(device);
-    if (hipStreamSynchronize(cs) != hipSuccess) return (int)KGMA_E_HIP;
-    info.copy_ms += now_ms() - tc0;
+        HIP_TRY(ctx, hipMemcpyAsync(dst + off_raw, set->pool, (size_t)pool_units * sizeof(ChainChunk), hipMemcpyDeviceToHost, cs));
+    for (const RecordSlice &r : recs)
+        HIP_TRY(ctx, hipMemcpyAsync(dst + off_first + r.dw_off * 4, g->d_inter + 2 * g->cd[(size_t)r.c].word_off, r.dw * 4, hipMemcpyDeviceToHost, cs));
+    downloading = true;
+    return KGMA_OK;
+}
+
+// ---- host part: first windows and chunk walks (chain_on_device runs it on a worker when more batches follow) ----
+int ChainBatch::finish()
+{
+    downloading = false;
+    (void)hipSetDevice(ctx->device);
+    if (hipStreamSynchronize(copy_stream) != hipSuccess) return (int)KGMA_E_HIP;
+    info.copy_ms += now_ms() - t_copy0;
     const double tw0 = now_ms();
+    std::vector<ChainStream> &streams = plan.streams;
     const int64_t *h_D0 = reinterpret_cast<const int64_t *>(pin + off_D0);
-    for (size_t t = 0; t < streams.size(); t++) streams[t].D0 = h_D0[stream_d0[t]];
-    if (generic) {
+    for (size_t t = 0; t < streams.size(); t++) streams[t].D0 = h_D0[plan.stream_d0[t]];
+    if (plan.generic) {
         // (the generic chain kernel reports each stream's first distance as a double: onto the KFV's integer lattice)
         for (size_t u = 0; u < el.size(); u++) {
             const KfvInfo &f = ctx->kfv[(size_t)pairs[el[u]].j];
-            for (size_t t = ps[u].s0; t < ps[u].s1; t++) {
+            for (size_t t = plan.ps[u].s0; t < plan.ps[u].s1; t++) {
                 double dv;
                 memcpy(&dv, &streams[t].D0, sizeof dv);
-                streams[t].D0 = lattice_of(f, k, dv);
+                streams[t].D0 = lattice_of(f, ctx->k, dv);
             }
         }
     }
-
-    // the chain's value at window 1: kmer_count! + sqeuclidean of the first window (GenomeMiner.jl:42-47), on the host
     std::vector<double> first(el.size(), 0.0);
-    {
-        std::vector<ChainJob> jobs(el.size());
-        static const ChainInterval one{1, 1};
-        for (size_t u = 0; u < el.size(); u++) {
-            const ChainPair &p = pairs[el[u]];
-            const KfvInfo &f = ctx->kfv[(size_t)p.j];
-            size_t off = 0;
-            for (const Rec &r : recs) if (r.c == p.c) off = r.dw_off;
-            ChainJob &J = jobs[u];
-            J.seq = nullptr; J.packed = reinterpret_cast<const uint32_t *>(pin + off_first) + off; J.n_res = f.W; f.chain_ref(J);
-            J.k = k; J.W = f.W; J.last_window = 1; J.iv = &one; J.n_iv = 1; J.out = &first[u]; J.n_out = 0; J.ok = false;
-        }
-        run_chain_jobs(jobs.data(), jobs.size(), 1);
-        for (size_t u = 0; u < el.size(); u++)
-            if (!jobs[u].ok) return (int)KGMA_E_HIP;
+    if (!first_windows(first)) return (int)KGMA_E_HIP;
+    if (export_only) { export_pair(first); return KGMA_OK; }
+    walk_pairs(first);
+    info.streams += plan.n_tiles();
+    info.walk_ms += now_ms() - tw0;
+    return KGMA_OK;
+}
+
+bool ChainBatch::first_windows(std::vector<double> &first) const
+{
+    std::vector<ChainJob> jobs(el.size());
+    for (size_t u = 0; u < el.size(); u++) {
+        const ChainPair &p = pairs[el[u]];
+        size_t off = 0;
+        for (const RecordSlice &r : recs) if (r.c == p.c) off = r.dw_off;
+        jobs[u] = first_window_job(ctx->kfv[(size_t)p.j], ctx->k, reinterpret_cast<const uint32_t *>(pin + off_first) + off, &first[u]);
     }
-    if (export_only) {
-        // (kgma_chain_export: one pair; its material goes to the caller, who walks it where the whole record's pieces meet)
-        ctx->cx_streams.assign(streams.begin(), streams.end());
-        const ChainChunk *hc = reinterpret_cast<const ChainChunk *>(pin + off_chunks), *hp = reinterpret_cast<const ChainChunk *>(pin + off_raw);
-        ctx->cx_chunks.assign(hc, hc + n_chunks);
-        ctx->cx_pool.assign(hp, hp + pool_units);
-        ctx->cx_first = first.empty() ? 0.0 : first[0];
-        for (size_t u = 0; u < el.size(); u++) done[el[u]] = 1;
-        info.pairs += (int64_t)el.size();
-        info.streams += n_tiles;
-        return KGMA_OK;
-    }
-    int n_threads = (int)std::thread::hardware_concurrency();
-    if (const char *e = getenv("KGMA_CHAIN_THREADS")) n_threads = atoi(e);
-    n_threads = std::max(1, std::min(n_threads, 64));
+    run_chain_jobs(jobs.data(), jobs.size(), 1);
+    for (size_t u = 0; u < el.size(); u++)
+        if (!jobs[u].ok) return false;
+    return true;
+}
+
+// (kgma_chain_export: one pair; its material goes to the caller, who walks it where the whole record's pieces meet)
+void ChainBatch::export_pair(const std::vector<double> &first)
+{
+    ctx->cx_streams.assign(plan.streams.begin(), plan.streams.end());
+    const ChainChunk *hc = reinterpret_cast<const ChainChunk *>(pin + off_chunks), *hp = reinterpret_cast<const ChainChunk *>(pin + off_raw);
+    ctx->cx_chunks.assign(hc, hc + plan.n_chunks);
+    ctx->cx_pool.assign(hp, hp + pool_units);
+    ctx->cx_first = first.empty() ? 0.0 : first[0];
+    for (size_t u = 0; u < el.size(); u++) done[el[u]] = 1;
+    info.pairs += (int64_t)el.size();
+    info.streams += plan.n_tiles();
+}
+
+void ChainBatch::walk_pairs(const std::vector<double> &first)
+{
+    const int k = ctx->k;
     std::vector<ChainWalkJob> walks(el.size());
     for (size_t u = 0; u < el.size(); u++) {
         ChainPair &p = pairs[el[u]];
@@ -4529,36 +4614,109 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
         ChainWalkJob &J = walks[u];
         J = ChainWalkJob{};
         J.first = first[u];
-        J.scale = 2.0 * (double)k * (double)f.N * (double)f.N;
+        J.scale = chain_scale(k, f);
         J.nk = (int)(f.W - k + 1);
-        J.streams = streams.data() + ps[u].s0; J.n_streams = ps[u].s1 - ps[u].s0;
+        J.streams = plan.streams.data() + plan.ps[u].s0; J.n_streams = plan.ps[u].s1 - plan.ps[u].s0;
         J.chunks = reinterpret_cast<const ChainChunk *>(pin + off_chunks);
         J.pool = reinterpret_cast<const ChainChunk *>(pin + off_raw);
         J.pool_units = pool_units;
         J.iv = p.iv.data(); J.n_iv = p.iv.size(); J.out = p.val.data();
     }
-    run_chain_walks(walks.data(), walks.size(), n_threads);
+    run_chain_walks(walks.data(), walks.size(), env.threads);
     for (size_t u = 0; u < el.size(); u++) {
         const ChainWalkJob &J = walks[u];
+        const ChainPair &p = pairs[el[u]];
         info.max_drift = std::max(info.max_drift, J.max_drift);
-        if (J.status != CHAIN_WALK_OK || J.n_out != (int64_t)pairs[el[u]].val.size()) {
-            if (getenv("KGMA_CHAIN_DEBUG"))
-                fprintf(stderr, "chain on the device: record %d KFV %d left to the host (status %d, %lld of %zu values, drift %.3g)\n", pairs[el[u]].c,
-                        pairs[el[u]].j + 1, J.status, (long long)J.n_out, pairs[el[u]].val.size(), J.max_drift);
+        if (J.status != CHAIN_WALK_OK || J.n_out != (int64_t)p.val.size()) {
+            if (env.debug)
+                fprintf(stderr, "chain on the device: record %d KFV %d left to the host (status %d, %lld of %zu values, drift %.3g)\n", p.c,
+                        p.j + 1, J.status, (long long)J.n_out, p.val.size(), J.max_drift);
             continue;
         }
         done[el[u]] = 1;
         info.pairs++;
-        info.windows += pairs[el[u]].last;
+        info.windows += p.last;
         info.raw_steps += J.raw_steps;
     }
-    info.streams += n_tiles;
-    info.walk_ms += now_ms() - tw0;
-    return KGMA_OK;
-    };
-    if (deferred && !export_only) { *deferred = std::move(finish); return KGMA_OK; }
-    const int frc = finish();
+}
+
+// The device part of a batch, up to the start of its download; then its host part, unless the caller takes it (`defer`: the
+// batch says whether one is due, ChainBatch::downloading).  A batch that does not fit is left as it is: the host chain.
+static int run_chain_batch(ChainBatch &b, bool defer)
+{
+    kgma_ctx *ctx = b.ctx;
+    const double ts0 = now_ms();
+    plan_chain_launches(ctx, b.env, b.pairs, b.el, b.plan);
+    plan_chain_streams(ctx, b.g, b.env, b.pairs, b.el, b.plan);
+    if (!b.plan.fits()) return KGMA_OK;
+    mark_hot_steps(ctx, b.pairs, b.el, b.plan);
+    int rc = reserve_chain_buffers(ctx, b.plan, *b.set);
+    if (rc) return rc;
+    b.info.setup_ms += now_ms() - ts0;
+    b.info.chunks += b.plan.n_chunks;
+    bool served = false;
+    rc = run_chain_kernels(b, &served);
+    if (rc || !served) return rc;
+    rc = b.start_download();
+    if (rc || !b.downloading || defer) return rc;
+    const int frc = b.finish();
     if (frc) return fail(ctx, frc, "internal: first window of a chained record");
+    return KGMA_OK;
+}
+
+static int chain_on_device(kgma_ctx *ctx, const kgma_genome *g, const ChainEnv &env, std::vector<ChainPair> &pairs, std::vector<char> &done, ChainDevInfo &info)
+{
+    std::vector<size_t> el8, elg;
+    for (size_t i = 0; i < pairs.size(); i++) {
+        const ChainPair &p = pairs[i];
+        if (p.last < 2) continue;
+        const int which = chain_kernel_for(ctx, ctx->kfv[(size_t)p.j], env);
+        if (which == 1) el8.push_back(i);
+        else if (which == 2) elg.push_back(i);
+    }
+    if (el8.empty() && elg.empty()) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    NumaBind numa(ctx);                      // (the pinned download buffers and the walking threads on the GPU's NUMA node: gigabytes come back on dense inputs)
+    // batches of bounded size (2^35 windows: a chunk array of 128 MiB), in record order; the host part of a batch overlaps
+    // the device part of the next, so what stays exposed is the LAST batch's host part: smaller batches, shorter tail
+    // (config 5, 2.5e11 windows, 1.31 s of kernels: 1577 ms with 2^36, 1499 ms with 2^35, 1542 ms with 2^34)
+    // The host part of a batch (first windows, chunk walks) runs on a worker while the device works on the next batch;
+    // two sets of output buffers, each with its pinned mirror, alternate.  (At most one worker at a time: it is joined before
+    // the next one starts.)
+    struct Worker {
+        std::thread th;
+        int rc = KGMA_OK;
+        int join() { if (th.joinable()) th.join(); const int r = rc; rc = KGMA_OK; return r; }
+        ~Worker() { if (th.joinable()) th.join(); }
+    } worker;
+    int sel = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        const std::vector<size_t> &el = pass == 0 ? el8 : elg;
+        for (size_t u0 = 0; u0 < el.size();) {
+            size_t u1 = u0;
+            int64_t w = 0;
+            while (u1 < el.size() && (u1 == u0 || w + pairs[el[u1]].last <= env.batch_windows)) w += pairs[el[u1++]].last;
+            const bool more = u1 < el.size() || worker.th.joinable() || (pass == 0 && !elg.empty());
+            const double tb0 = now_ms();
+            auto batch = std::make_unique<ChainBatch>(ctx, g, env, pairs, done, info, std::vector<size_t>(el.begin() + (long)u0, el.begin() + (long)u1), sel, pass == 1);
+            const int rc = run_chain_batch(*batch, more);
+            const double tb1 = now_ms();
+            const int wrc = worker.join();
+            if (env.debug) fprintf(stderr, "  chain batch: device part %.2f ms, then %.2f ms waiting for the previous batch's host part\n", tb1 - tb0, now_ms() - tb1);
+            if (rc) return rc;
+            if (wrc) return fail(ctx, wrc, "internal: first window of a chained record");
+            if (batch->downloading) {
+                Worker *wk = &worker;
+                worker.th = std::thread([wk, b = std::move(batch)]() { wk->rc = b->finish(); });
+            }
+            sel ^= 1;
+            u0 = u1;
+        }
+    }
+    const double tj0 = now_ms();
+    const int wrc = worker.join();
+    if (env.debug) fprintf(stderr, "  chain: %.2f ms waiting for the last batch's host part\n", now_ms() - tj0);
+    if (wrc) return fail(ctx, wrc, "internal: first window of a chained record");
     return KGMA_OK;
 }
 
@@ -4572,131 +4730,131 @@ static int chain_on_device_batch(kgma_ctx *ctx, const kgma_genome *g, std::vecto
 // dip and the first window) have the same exact minimum -- the superset of "a dip's minimum equals the
 // stale running minimum" (GenomeMiner.jl:93-103), which is only known once the hit state machine runs.
 // Every other pair has no exact tie anywhere, so exact arithmetic and the chain decide alike.
+// chain_decide, below, is the list of its phases.
 // ------------------------------------------------------------------------------------------
-// (*drift_out, when given: instead of failing on a chain that has drifted beyond the guard band's half width, the largest drift seen
-//  is returned there with status CHAIN_DRIFT_RETRY, and kgma_scan repeats the scan with a band that covers it)
-constexpr int CHAIN_DRIFT_RETRY = -77;
-static int chain_decide(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64_t buff, double *drift_out = nullptr)
-{
-    const double t0 = now_ms();
-    const int k = ctx->k, m = ctx->m;
-    const int64_t nc = (int64_t)ctx->contig_len.size();
-    reset_chain_stats(ctx);
-    // (A) ties inside one dip are decided where that is provably independent of the chain's history
-    {
-        TieResolver tr{ctx, g, {}, {}, {}, nullptr, {}, {}};
-        if (g) tr.prefetch();                                          // (no genome: kgma_replay_dips, residues through the source)
-        for (size_t i = 0; i < ctx->dips.size(); i++) {
-            kgma_dip &d = ctx->dips[i];
-            if (!(d.flags & KGMA_HIT_TIE)) continue;
-            const TieResolver::Result r = tr.replay(d.kfv - 1, d.contig, d.argmin, d.D_min, d.argmin, ctx->dip_argl[i], d.D_min, false,
-                                                    g ? tr.prefetched(i) : nullptr);
-            if (r.ok && !r.sensitive) {
-                d.argmin = r.pos;
-                d.flags = (d.flags & ~(uint32_t)KGMA_HIT_TIE) | KGMA_HIT_TIE_RESOLVED;
-            }
-        }
-    }
-    // ---- select the pairs ------------------------------------------------------------------
-    typedef ChainPair Pair;
-    std::vector<Pair> pairs;
-    int64_t why_count[5] = {0, 0, 0, 0, 0};
-    // (cluster engine) does the widest candidate range of a dip meet that of another dip of its record?
-    std::vector<char> dip_meets_other(ctx->dips.size(), 0);
-    if (mode == KGMA_MODE_OMN) {
-        struct Rg { int64_t lo, hi; size_t u; };
-        std::vector<Rg> rg;
-        size_t u0 = 0;
-        const size_t ndp = ctx->dips.size();
-        while (u0 < ndp) {
-            size_t u1 = u0;
-            rg.clear();
-            while (u1 < ndp && ctx->dips[u1].contig == ctx->dips[u0].contig) {
-                const kgma_dip &d = ctx->dips[u1];
-                const int64_t W = ctx->kfv[(size_t)(d.kfv - 1)].W;
-                rg.push_back(Rg{d.start - 1 - buff, d.end - 1 + W - 1 + buff, u1});     // CMI = best window - 1, anywhere in the dip
-                u1++;
-            }
-            std::sort(rg.begin(), rg.end(), [](const Rg &a, const Rg &b) { return a.lo < b.lo; });
-            int64_t reach = INT64_MIN;                                                 // farthest end among the ranges before
-            for (size_t i = 0; i < rg.size(); i++) {
-                if (reach >= rg[i].lo) dip_meets_other[rg[i].u] = 1;
-                if (i + 1 < rg.size() && rg[i + 1].lo <= rg[i].hi) dip_meets_other[rg[i].u] = 1;
-                reach = std::max(reach, rg[i].hi);
-            }
-            u0 = u1;
-        }
-    }
-    {
-        size_t di = 0, ai = 0;
-        const size_t nd = ctx->dips.size(), na = ctx->att.size();
-        std::vector<int64_t> mins;
-        while (di < nd || ai < na) {
-            int32_t c, j;
-            const bool dip_first = di < nd && (ai >= na || ctx->dips[di].contig < ctx->att[ai].contig ||
-                                               (ctx->dips[di].contig == ctx->att[ai].contig && ctx->dips[di].kfv - 1 <= ctx->att[ai].kfv));
-            if (dip_first) { c = ctx->dips[di].contig; j = ctx->dips[di].kfv - 1; }
-            else { c = ctx->att[ai].contig; j = ctx->att[ai].kfv; }
-            Pair p{c, j, di, di, ai, ai, {}, {}, 0};
-            while (p.d1 < nd && ctx->dips[p.d1].contig == c && ctx->dips[p.d1].kfv - 1 == j) p.d1++;
-            while (p.a1 < na && ctx->att[p.a1].contig == c && ctx->att[p.a1].kfv == j) p.a1++;
-            di = p.d1; ai = p.a1;
-            bool need = p.a1 > p.a0;
-            int why = need ? 1 : 0;                                    // (KGMA_CHAIN_DEBUG: what selected the pair)
-            mins.clear();
-            mins.push_back(ctx->firstD[(size_t)j * (size_t)nc + (size_t)c]);
-            for (size_t u = p.d0; u < p.d1; u++) {
-                if (ctx->dips[u].flags & (KGMA_HIT_TIE | KGMA_HIT_AT_THRESHOLD)) { need = true; if (!why) why = (ctx->dips[u].flags & KGMA_HIT_TIE) ? 2 : 3; }
-                mins.push_back(ctx->dips[u].D_min);
-            }
-            if (!need && mode == KGMA_MODE_SINGLE) {
-                // the single engine's alignment does not feed back (GenomeMiner.jl:96-99): with no other tie in
-                // the pair its state machine is a function of the dips alone, so "a dip's minimum equals the
-                // running minimum" is found by running it (GenomeMiner.jl:82-104)
-                const int64_t W = ctx->kfv[0].W;
-                int64_t currmin = mins[0], CMI = 2, goal_ind = 0;
-                bool stop = true;
-                for (size_t u = p.d0; u < p.d1 && !need; u++) {
-                    const kgma_dip &d = ctx->dips[u];
-                    if (near_tie(ctx->kfv[0], d.D_min, currmin)) need = true;
-                    if (d.D_min < currmin) { currmin = d.D_min; CMI = d.argmin + k - 2; stop = false; }
-                    if (d.exit_pos == 0 || stop) continue;
-                    stop = true;
-                    CMI += 1;
-                    if (CMI > goal_ind) { goal_ind = CMI + W - 1; currmin = d.D_exit; }
-                }
-            } else if (!need) {
-                // cluster engine: whether a hit is emitted (and the running minimum reset) depends on the alignment
-                // callback (OmnGenomeMiner.jl:126,139,152), so its state machine cannot be run ahead.  What can tie:
-                // a dip's minimum with the first window's value (curr_mins starts there, :73-74), or with the STALE
-                // minimum an earlier dip A of the same KFV left behind -- and a dip only leaves one when it is
-                // suppressed (:126 CMI in prev_hit_range, :139 aligned range not disjoint from it); the accepted hit's
-                // range is a sub-range of its candidate range max(CMI-buff,1) : CMI+ws-1+buff, so A can only be suppressed
-                // if its candidate range meets that of another dip of the record (any KFV).  Superset taken: equal minima
-                // A before B where A's widest possible candidate range meets another dip's.
-                const KfvInfo &fj = ctx->kfv[(size_t)j];
-                for (size_t u = p.d0; u < p.d1 && !need; u++) need = near_tie(fj, ctx->dips[u].D_min, mins[0]);
-                for (size_t u = p.d0; u < p.d1 && !need; u++) {
-                    if (!dip_meets_other[u]) continue;
-                    for (size_t v = u + 1; v < p.d1 && !need; v++) need = near_tie(fj, ctx->dips[v].D_min, ctx->dips[u].D_min);
-                }
-            }
-            if (need && !why) why = 4;
-            if (need) { why_count[why]++; pairs.push_back(std::move(p)); }
-        }
-    }
-    if (getenv("KGMA_CHAIN_DEBUG"))
-        fprintf(stderr, "chain replay: %zu pairs selected: %lld by a window in the threshold band, %lld by a dip with tied minima, %lld by a dip at the threshold, "
-                "%lld by a minimum equal to the running / first / an earlier minimum\n", pairs.size(), (long long)why_count[1], (long long)why_count[2],
-                (long long)why_count[3], (long long)why_count[4]);
-    ctx->dip_fmin.assign(ctx->dips.size(), 0.0);
-    ctx->dip_fexit.assign(ctx->dips.size(), 0.0);
-    ctx->chain_pair.assign((size_t)m * (size_t)nc, 0);
-    ctx->firstF.assign((size_t)m * (size_t)nc, 0.0);
-    if (pairs.empty()) { ctx->stats.chain_ms = now_ms() - t0; return KGMA_OK; }
 
-    // ---- sample windows of every pair: its dips (start .. exit) and its guard-band windows (+ the next) ----
-    for (Pair &p : pairs) {
+// (A) ties inside one dip are decided where that is provably independent of the chain's history
+// (no genome: kgma_replay_dips, residues through the source)
+static void resolve_local_ties(kgma_ctx *ctx, const kgma_genome *g)
+{
+    TieResolver tr{ctx, g, {}, {}, {}, nullptr, {}, {}};
+    if (g) tr.prefetch();
+    for (size_t i = 0; i < ctx->dips.size(); i++) {
+        kgma_dip &d = ctx->dips[i];
+        if (!(d.flags & KGMA_HIT_TIE)) continue;
+        const TieResolver::Result r = tr.replay(d.kfv - 1, d.contig, d.argmin, d.D_min, d.argmin, ctx->dip_argl[i], d.D_min, false,
+                                                g ? tr.prefetched(i) : nullptr);
+        if (r.ok && !r.sensitive) {
+            d.argmin = r.pos;
+            d.flags = (d.flags & ~(uint32_t)KGMA_HIT_TIE) | KGMA_HIT_TIE_RESOLVED;
+        }
+    }
+}
+
+// (cluster engine) does the widest candidate range of a dip meet that of another dip of its record?
+static std::vector<char> mark_dips_meeting_others(const kgma_ctx *ctx, int64_t buff)
+{
+    std::vector<char> dip_meets_other(ctx->dips.size(), 0);
+    struct Rg { int64_t lo, hi; size_t u; };
+    std::vector<Rg> rg;
+    size_t u0 = 0;
+    const size_t ndp = ctx->dips.size();
+    while (u0 < ndp) {
+        size_t u1 = u0;
+        rg.clear();
+        while (u1 < ndp && ctx->dips[u1].contig == ctx->dips[u0].contig) {
+            const kgma_dip &d = ctx->dips[u1];
+            const int64_t W = ctx->kfv[(size_t)(d.kfv - 1)].W;
+            rg.push_back(Rg{d.start - 1 - buff, d.end - 1 + W - 1 + buff, u1});     // CMI = best window - 1, anywhere in the dip
+            u1++;
+        }
+        std::sort(rg.begin(), rg.end(), [](const Rg &a, const Rg &b) { return a.lo < b.lo; });
+        int64_t reach = INT64_MIN;                                                 // farthest end among the ranges before
+        for (size_t i = 0; i < rg.size(); i++) {
+            if (reach >= rg[i].lo) dip_meets_other[rg[i].u] = 1;
+            if (i + 1 < rg.size() && rg[i + 1].lo <= rg[i].hi) dip_meets_other[rg[i].u] = 1;
+            reach = std::max(reach, rg[i].hi);
+        }
+        u0 = u1;
+    }
+    return dip_meets_other;
+}
+
+// Single engine: may a dip's minimum of pair `p` equal the running minimum?  The single engine's alignment does not feed back
+// (GenomeMiner.jl:96-99): with no other tie in the pair its state machine is a function of the dips alone, so "a dip's minimum
+// equals the running minimum" is found by running it (GenomeMiner.jl:82-104)
+static bool single_engine_may_tie(const kgma_ctx *ctx, const ChainPair &p, int64_t firstD)
+{
+    const int k = ctx->k;
+    const int64_t W = ctx->kfv[0].W;
+    int64_t currmin = firstD, CMI = 2, goal_ind = 0;
+    bool stop = true, need = false;
+    for (size_t u = p.d0; u < p.d1 && !need; u++) {
+        const kgma_dip &d = ctx->dips[u];
+        if (near_tie(ctx->kfv[0], d.D_min, currmin)) need = true;
+        if (d.D_min < currmin) { currmin = d.D_min; CMI = d.argmin + k - 2; stop = false; }
+        if (d.exit_pos == 0 || stop) continue;
+        stop = true;
+        CMI += 1;
+        if (CMI > goal_ind) { goal_ind = CMI + W - 1; currmin = d.D_exit; }
+    }
+    return need;
+}
+
+// Cluster engine: whether a hit is emitted (and the running minimum reset) depends on the alignment
+// callback (OmnGenomeMiner.jl:126,139,152), so its state machine cannot be run ahead.  What can tie:
+// a dip's minimum with the first window's value (curr_mins starts there, :73-74), or with the STALE
+// minimum an earlier dip A of the same KFV left behind -- and a dip only leaves one when it is
+// suppressed (:126 CMI in prev_hit_range, :139 aligned range not disjoint from it); the accepted hit's
+// range is a sub-range of its candidate range max(CMI-buff,1) : CMI+ws-1+buff, so A can only be suppressed
+// if its candidate range meets that of another dip of the record (any KFV).  Superset taken: equal minima
+// A before B where A's widest possible candidate range meets another dip's.
+static bool cluster_engine_may_tie(const kgma_ctx *ctx, const ChainPair &p, int64_t firstD, const std::vector<char> &dip_meets_other)
+{
+    const KfvInfo &fj = ctx->kfv[(size_t)p.j];
+    bool need = false;
+    for (size_t u = p.d0; u < p.d1 && !need; u++) need = near_tie(fj, ctx->dips[u].D_min, firstD);
+    for (size_t u = p.d0; u < p.d1 && !need; u++) {
+        if (!dip_meets_other[u]) continue;
+        for (size_t v = u + 1; v < p.d1 && !need; v++) need = near_tie(fj, ctx->dips[v].D_min, ctx->dips[u].D_min);
+    }
+    return need;
+}
+
+// The pairs the chain decides: a merge over the dips and the guard-band windows (both in (record, KFV) order).
+// why_count (KGMA_CHAIN_DEBUG): what selected them
+static std::vector<ChainPair> select_chain_pairs(const kgma_ctx *ctx, int32_t mode, const std::vector<char> &dip_meets_other, int64_t why_count[5])
+{
+    std::vector<ChainPair> pairs;
+    const int64_t nc = (int64_t)ctx->contig_len.size();
+    size_t di = 0, ai = 0;
+    const size_t nd = ctx->dips.size(), na = ctx->att.size();
+    while (di < nd || ai < na) {
+        int32_t c, j;
+        const bool dip_first = di < nd && (ai >= na || ctx->dips[di].contig < ctx->att[ai].contig ||
+                                           (ctx->dips[di].contig == ctx->att[ai].contig && ctx->dips[di].kfv - 1 <= ctx->att[ai].kfv));
+        if (dip_first) { c = ctx->dips[di].contig; j = ctx->dips[di].kfv - 1; }
+        else { c = ctx->att[ai].contig; j = ctx->att[ai].kfv; }
+        ChainPair p{c, j, di, di, ai, ai, {}, {}, 0};
+        while (p.d1 < nd && ctx->dips[p.d1].contig == c && ctx->dips[p.d1].kfv - 1 == j) p.d1++;
+        while (p.a1 < na && ctx->att[p.a1].contig == c && ctx->att[p.a1].kfv == j) p.a1++;
+        di = p.d1; ai = p.a1;
+        bool need = p.a1 > p.a0;
+        int why = need ? 1 : 0;
+        for (size_t u = p.d0; u < p.d1; u++)
+            if (ctx->dips[u].flags & (KGMA_HIT_TIE | KGMA_HIT_AT_THRESHOLD)) { need = true; if (!why) why = (ctx->dips[u].flags & KGMA_HIT_TIE) ? 2 : 3; }
+        const int64_t firstD = ctx->firstD[(size_t)j * (size_t)nc + (size_t)c];
+        if (!need) need = mode == KGMA_MODE_SINGLE ? single_engine_may_tie(ctx, p, firstD) : cluster_engine_may_tie(ctx, p, firstD, dip_meets_other);
+        if (need && !why) why = 4;
+        if (need) { why_count[why]++; pairs.push_back(std::move(p)); }
+    }
+    return pairs;
+}
+
+// ---- sample windows of every pair: its dips (start .. exit) and its guard-band windows (+ the next) ----
+static int sample_pair_windows(kgma_ctx *ctx, std::vector<ChainPair> &pairs)
+{
+    for (ChainPair &p : pairs) {
         const int64_t nwin = ctx->contig_nwin[(size_t)p.c];
         std::vector<ChainInterval> iv;
         iv.push_back(ChainInterval{1, 1});
@@ -4716,71 +4874,53 @@ static int chain_decide(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64
         p.last = p.iv.back().hi;
         if (p.iv.front().lo < 1 || p.last > nwin) return fail(ctx, KGMA_E_HIP, "internal: chain replay window outside record %d", p.c);
     }
+    return KGMA_OK;
+}
 
-    // ---- the chains: on the device where its kernel applies, the rest (and whatever failed a check there) on the host ----
-    std::vector<char> on_device(pairs.size(), 0);
-    ChainDevInfo dev;
-    const double t_selected = now_ms();
-    if (!g) {
-        // kgma_replay_dips: the residues are with the ranks that scanned them; the caller's source runs the chain there
-        // (kgma_chain_export per slice) and hands back the values at the wanted windows
-        if (!ctx->chain_src) return fail(ctx, KGMA_E_STATE, "chain replay without a genome needs a chain source (kgma_set_chain_source)");
-        std::vector<int32_t> pc(pairs.size()), pj(pairs.size());
-        std::vector<int64_t> ivb(pairs.size() + 1, 0), lo, hi;
-        size_t nv = 0;
-        for (size_t i = 0; i < pairs.size(); i++) {
-            pc[i] = pairs[i].c; pj[i] = pairs[i].j + 1;
-            for (const ChainInterval &x : pairs[i].iv) { lo.push_back(x.lo); hi.push_back(x.hi); }
-            ivb[i + 1] = (int64_t)lo.size();
-            nv += pairs[i].val.size();
-        }
-        std::vector<double> vals(nv, 0.0);
-        const int src = ctx->chain_src(ctx->chain_user, (int64_t)pairs.size(), pc.data(), pj.data(), ivb.data(), lo.data(), hi.data(), vals.data());
-        if (src != 0) return fail(ctx, KGMA_E_STATE, "the chain source failed (status %d)", src);
-        size_t off = 0;
-        for (size_t i = 0; i < pairs.size(); i++) {
-            std::copy(vals.begin() + (long)off, vals.begin() + (long)(off + pairs[i].val.size()), pairs[i].val.begin());
-            off += pairs[i].val.size();
-            on_device[i] = 1;
-            dev.pairs++;
-            dev.windows += pairs[i].last;
-        }
-    } else if (chain_device_enabled()) {
-        const int drc = chain_on_device(ctx, g, pairs, on_device, dev);
-        if (drc) return drc;
+// kgma_replay_dips: the residues are with the ranks that scanned them; the caller's source runs the chain there
+// (kgma_chain_export per slice) and hands back the values at the wanted windows
+static int chains_from_source(kgma_ctx *ctx, std::vector<ChainPair> &pairs, std::vector<char> &done, ChainDevInfo &dev)
+{
+    if (!ctx->chain_src) return fail(ctx, KGMA_E_STATE, "chain replay without a genome needs a chain source (kgma_set_chain_source)");
+    std::vector<int32_t> pc(pairs.size()), pj(pairs.size());
+    std::vector<int64_t> ivb(pairs.size() + 1, 0), lo, hi;
+    size_t nv = 0;
+    for (size_t i = 0; i < pairs.size(); i++) {
+        pc[i] = pairs[i].c; pj[i] = pairs[i].j + 1;
+        for (const ChainInterval &x : pairs[i].iv) { lo.push_back(x.lo); hi.push_back(x.hi); }
+        ivb[i + 1] = (int64_t)lo.size();
+        nv += pairs[i].val.size();
     }
-    ctx->stats.chain_device_pairs = dev.pairs;
-    ctx->stats.chain_device_ms = dev.kernel_ms;
-    ctx->stats.chain_raw_steps = dev.raw_steps;
-    ctx->stats.chain_max_drift = dev.max_drift;
-    if (getenv("KGMA_CHAIN_DEBUG"))
-        fprintf(stderr, "chain replay: local tie pass + pair selection %.2f ms, device chains %.2f ms (wall)\n", t_selected - t0, now_ms() - t_selected);
-    if (getenv("KGMA_CHAIN_DEBUG"))
-        fprintf(stderr, "chain on the device: %lld of %zu pairs, %lld windows in %lld streams / %lld chunks, setup %.2f ms, kernels %.2f ms (%d attempt(s)), download %.2f ms, host walk %.2f ms, %lld raw steps, drift <= %.3g\n",
-                (long long)dev.pairs, pairs.size(), (long long)dev.windows, (long long)dev.streams, (long long)dev.chunks, dev.setup_ms, dev.kernel_ms, dev.attempts,
-                dev.copy_ms, dev.walk_ms, (long long)dev.raw_steps, dev.max_drift);
-    std::vector<Pair *> hostp;
-    for (size_t i = 0; i < pairs.size(); i++)
-        if (!on_device[i]) hostp.push_back(&pairs[i]);
-    // ---- host chains, records in batches of bounded host memory ---------------------------
-    int n_threads = (int)std::thread::hardware_concurrency();
-    if (const char *e = getenv("KGMA_CHAIN_THREADS")) n_threads = atoi(e);
-    n_threads = std::max(1, std::min(n_threads, 64));
+    std::vector<double> vals(nv, 0.0);
+    const int src = ctx->chain_src(ctx->chain_user, (int64_t)pairs.size(), pc.data(), pj.data(), ivb.data(), lo.data(), hi.data(), vals.data());
+    if (src != 0) return fail(ctx, KGMA_E_STATE, "the chain source failed (status %d)", src);
+    size_t off = 0;
+    for (size_t i = 0; i < pairs.size(); i++) {
+        std::copy(vals.begin() + (long)off, vals.begin() + (long)(off + pairs[i].val.size()), pairs[i].val.begin());
+        off += pairs[i].val.size();
+        done[i] = 1;
+        dev.pairs++;
+        dev.windows += pairs[i].last;
+    }
+    return KGMA_OK;
+}
+
+// ---- host chains, records in batches of bounded host memory; *windows: the windows chained are added ----
+static int chains_on_host(kgma_ctx *ctx, const kgma_genome *g, const ChainEnv &env, const std::vector<ChainPair *> &hostp, int64_t *windows)
+{
+    const int k = ctx->k;
     (void)hipSetDevice(ctx->device);
-    int64_t BATCH_BYTES = (int64_t)2 << 30;         // of 2-bit codes: 8 G residues per batch (one batch for a GRCh38-size genome)
-    if (const char *e = getenv("KGMA_CHAIN_BATCH_MB")) BATCH_BYTES = std::max<int64_t>(1, atoll(e)) << 20;   // experiments
     size_t pi = 0;
-    int64_t windows = dev.windows;
     double copy_ms = 0, jobs_ms = 0;
     while (pi < hostp.size()) {
         // the records of this batch: their 2-bit codes (the device's interleaved copy: a quarter of the residue text)
         // are copied into one pinned buffer, kept by the context; all pairs of one record share its copy
-        struct Rec { int32_t c; size_t p0, p1; int64_t need; size_t dw_off, dw; };
-        std::vector<Rec> recs;
+        struct HostRecord { ChainBatch::RecordSlice codes; size_t p0, p1; int64_t need; };
+        std::vector<HostRecord> recs;
         std::vector<ChainJob> jobs;
         int64_t bytes = 0;
         size_t pj = pi, total_dw = 0;
-        while (pj < hostp.size() && (pj == pi || bytes < BATCH_BYTES)) {
+        while (pj < hostp.size() && (pj == pi || bytes < env.batch_bytes)) {
             const int32_t c = hostp[pj]->c;
             size_t pe = pj;
             int64_t need = 0;
@@ -4790,141 +4930,139 @@ static int chain_decide(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64
             }
             need = std::min(need, g->cd[(size_t)c].len);
             const size_t dw = (size_t)((need + 15) / 16);
-            recs.push_back(Rec{c, pj, pe, need, total_dw, dw});
+            recs.push_back(HostRecord{{c, total_dw, dw}, pj, pe, need});
             total_dw += dw;
             bytes += (int64_t)dw * 4;
             pj = pe;
         }
         const double tc0 = now_ms();
-        if (total_dw > ctx->chain_cap) {
-            if (ctx->h_chain) (void)hipHostFree(ctx->h_chain);
-            ctx->h_chain = nullptr; ctx->chain_cap = 0;
-            const size_t cap = total_dw + (total_dw >> 3) + 1024;
-            if (hipHostMalloc(reinterpret_cast<void **>(&ctx->h_chain), cap * 4, hipHostMallocDefault) != hipSuccess)
-                return fail(ctx, KGMA_E_NOMEM, "chain replay: cannot allocate %zu bytes of pinned host memory", cap * 4);
-            ctx->chain_cap = cap;
-        }
-        for (const Rec &r : recs)
-            if (hipMemcpyAsync(ctx->h_chain + r.dw_off, g->d_inter + 2 * g->cd[(size_t)r.c].word_off, r.dw * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-                return fail(ctx, KGMA_E_HIP, "chain replay: cannot read record %d", r.c);
+        const size_t spare = (total_dw >> 3) + 1024;
+        if (!grow_pinned(ctx->h_chain, ctx->chain_cap, total_dw, spare))
+            return fail(ctx, KGMA_E_NOMEM, "chain replay: cannot allocate %zu bytes of pinned host memory", (total_dw + spare) * 4);
+        for (const HostRecord &r : recs)
+            if (hipMemcpyAsync(ctx->h_chain + r.codes.dw_off, g->d_inter + 2 * g->cd[(size_t)r.codes.c].word_off, r.codes.dw * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+                return fail(ctx, KGMA_E_HIP, "chain replay: cannot read record %d", r.codes.c);
         if (sync_spin(ctx->stream) != hipSuccess) return fail(ctx, KGMA_E_HIP, "chain replay: cannot read the records");
         copy_ms += now_ms() - tc0;
-        for (const Rec &r : recs)
+        for (const HostRecord &r : recs)
             for (size_t u = r.p0; u < r.p1; u++) {
-                Pair &p = *hostp[u];
-                ChainJob J;
-                J.seq = nullptr; J.packed = ctx->h_chain + r.dw_off; J.n_res = r.need; ctx->kfv[(size_t)p.j].chain_ref(J); J.k = k;
-                J.W = ctx->kfv[(size_t)p.j].W; J.last_window = p.last; J.iv = p.iv.data(); J.n_iv = p.iv.size();
-                J.out = p.val.data(); J.n_out = 0; J.ok = false;
-                jobs.push_back(J);
-                windows += p.last;
+                ChainPair &p = *hostp[u];
+                jobs.push_back(chain_job(ctx->kfv[(size_t)p.j], k, ctx->h_chain + r.codes.dw_off, r.need, p.last, p.iv.data(), p.iv.size(), p.val.data()));
+                *windows += p.last;
             }
         const double tj0 = now_ms();
-        run_chain_jobs(jobs.data(), jobs.size(), n_threads);
+        run_chain_jobs(jobs.data(), jobs.size(), env.threads);
         jobs_ms += now_ms() - tj0;
         for (size_t u = 0; u < jobs.size(); u++)
             if (!jobs[u].ok || jobs[u].n_out != (int64_t)hostp[pi + u]->val.size())
                 return fail(ctx, KGMA_E_HIP, "internal: chain replay of record %d KFV %d failed", hostp[pi + u]->c, hostp[pi + u]->j + 1);
         pi = pj;
     }
+    if (env.debug) fprintf(stderr, "chain replay: residues copied in %.1f ms, chains %.1f ms, %d threads\n", copy_ms, jobs_ms, env.threads);
+    return KGMA_OK;
+}
 
-    if (getenv("KGMA_CHAIN_DEBUG")) fprintf(stderr, "chain replay: residues copied in %.1f ms, chains %.1f ms, %d threads\n", copy_ms, jobs_ms, n_threads);
-    // ---- rebuild the dips of the chain pairs from the chain values ---------------------------
-    struct DipX { kgma_dip d; int64_t argl, aux; double fmin, fexit; };
-    double worst_drift = 0;                                            // beyond the limit, over all pairs
-    std::vector<DipX> all;
-    all.reserve(ctx->dips.size() + 16);
-    {
-        std::vector<char> replaced(ctx->dips.size(), 0);
-        for (const Pair &p : pairs)
-            for (size_t u = p.d0; u < p.d1; u++) replaced[u] = 1;
-        for (size_t u = 0; u < ctx->dips.size(); u++)
-            if (!replaced[u]) all.push_back(DipX{ctx->dips[u], ctx->dip_argl[u], ctx->dip_aux[u], 0.0, 0.0});
-    }
-    for (const Pair &p : pairs) {
-        const KfvInfo &f = ctx->kfv[(size_t)p.j];
-        const double scale = 2.0 * (double)k * (double)f.N * (double)f.N;
-        const int64_t nwin = ctx->contig_nwin[(size_t)p.c];
-        ctx->chain_pair[(size_t)p.j * (size_t)nc + (size_t)p.c] = 1;
-        ctx->firstF[(size_t)p.j * (size_t)nc + (size_t)p.c] = p.val[0];
-        {
-            // The windows sampled above are the ones whose EXACT distance is under (or within 2^-30 of) the threshold: that
-            // covers every window the reference's value can be under thr at only while the chain stays within 2^-30 of the
-            // exact distance.  Checked where both are known -- the first window and every dip's minimum (the device chain
-            // has checked every stream start too): a chain that drifted further is an error, never a silent miss.
-            auto value_at = [&](int64_t w) -> const double * {
-                size_t off = 0;
-                for (const ChainInterval &x : p.iv) {
-                    if (w >= x.lo && w <= x.hi) return &p.val[off + (size_t)(w - x.lo)];
-                    off += (size_t)(x.hi - x.lo + 1);
-                }
-                return nullptr;
-            };
-            // What the band has to cover is the value's ABSOLUTE error where the distance is near thr: the error is measured
-            // against max(exact distance, thr) -- at a dip's minimum the distance can be tiny (near-identical reference
-            // sequences: D_min of a few units) and an error inherited from windows of ordinary distances says nothing about
-            // the threshold there.  (The device chain's binade decisions have their own guard: kgma_device.h, ChainArgs.)
-            const double limit = std::ldexp(1.0, -(ctx->band_log2 + 1));
-            double pair_drift = 0;
-            auto drifted = [&](int64_t w, int64_t D) {
-                const double *v = value_at(w);
-                if (!v || D < 0) return;
-                const double exact = (double)D / scale, dr = std::fabs(*v - exact) / std::max(exact, f.thr > 0 ? f.thr : exact);
-                if (!(dr >= 0)) return;
-                pair_drift = std::max(pair_drift, dr);
-            };
-            drifted(1, ctx->firstD[(size_t)p.j * (size_t)nc + (size_t)p.c]);
-            for (size_t u = p.d0; u < p.d1; u++) drifted(ctx->dips[u].argmin, ctx->dips[u].D_min);
-            ctx->stats.chain_max_drift = std::max(ctx->stats.chain_max_drift, pair_drift);
-            if (pair_drift > limit) {
-                if (!drift_out)
-                    return fail(ctx, KGMA_E_STATE, "chain replay: the running Float64 value of record %d KFV %d has drifted %.3g (relative to max(distance, thr)) from the "
-                                "exact distance; the threshold guard band (2^-%d) no longer covers it", p.c, p.j + 1, pair_drift, ctx->band_log2);
-                worst_drift = std::max(worst_drift, pair_drift);
-            }
-        }
-        bool in_run = false;
-        DipX cur{};
-        int64_t prev_w = 0;
-        size_t vi = 0;
-        auto close_run = [&](int64_t exit_pos, double fexit) {
-            cur.d.exit_pos = exit_pos;
-            cur.fexit = fexit;
-            cur.d.D_exit = exit_pos ? (int64_t)std::llround(fexit * scale) : 0;
-            cur.d.D_min = (int64_t)std::llround(cur.fmin * scale);
-            cur.argl = cur.d.argmin;
-            all.push_back(cur);
-            in_run = false;
-        };
+// The windows sampled are the ones whose EXACT distance is under (or within 2^-30 of) the threshold: that
+// covers every window the reference's value can be under thr at only while the chain stays within 2^-30 of the
+// exact distance.  Checked where both are known -- the first window and every dip's minimum (the device chain
+// has checked every stream start too): a chain that drifted further is an error, never a silent miss.
+// What the band has to cover is the value's ABSOLUTE error where the distance is near thr: the error is measured
+// against max(exact distance, thr) -- at a dip's minimum the distance can be tiny (near-identical reference
+// sequences: D_min of a few units) and an error inherited from windows of ordinary distances says nothing about
+// the threshold there.  (The device chain's binade decisions have their own guard: kgma_device.h, ChainArgs.)
+static double pair_drift(const kgma_ctx *ctx, const ChainPair &p)
+{
+    const KfvInfo &f = ctx->kfv[(size_t)p.j];
+    const double scale = chain_scale(ctx->k, f);
+    const int64_t nc = (int64_t)ctx->contig_len.size();
+    auto value_at = [&](int64_t w) -> const double * {
+        size_t off = 0;
         for (const ChainInterval &x : p.iv) {
-            for (int64_t w = x.lo; w <= x.hi; w++, vi++) {
-                const double v = p.val[vi];
-                const bool under = w >= 2 && v < f.thr;            // GenomeMiner.jl:82 / OmnGenomeMiner.jl:113 (the first window is never tested)
-                if (in_run && w != prev_w + 1)                     // a run never reaches the end of a sampled interval
-                    return fail(ctx, KGMA_E_HIP, "internal: chain replay lost the exit of a dip (record %d KFV %d window %lld)", p.c, p.j + 1, (long long)prev_w);
-                if (under) {
-                    if (!in_run) {
-                        in_run = true;
-                        memset(&cur.d, 0, sizeof cur.d);
-                        cur.d.contig = p.c; cur.d.kfv = p.j + 1; cur.d.start = w; cur.d.argmin = w;
-                        cur.d.flags = KGMA_HIT_CHAIN;
-                        cur.fmin = v; cur.aux = -1;
-                    } else if (v < cur.fmin) { cur.fmin = v; cur.d.argmin = w; }   // strict: the first window attaining the minimum
-                    cur.d.end = w;
-                } else if (in_run) {
-                    close_run(w, v);
-                }
-                prev_w = w;
-            }
+            if (w >= x.lo && w <= x.hi) return &p.val[off + (size_t)(w - x.lo)];
+            off += (size_t)(x.hi - x.lo + 1);
         }
-        if (in_run) {
-            if (prev_w != nwin)
+        return nullptr;
+    };
+    double drift = 0;
+    auto drifted = [&](int64_t w, int64_t D) {
+        const double *v = value_at(w);
+        if (!v || D < 0) return;
+        const double exact = (double)D / scale, dr = std::fabs(*v - exact) / std::max(exact, f.thr > 0 ? f.thr : exact);
+        if (!(dr >= 0)) return;
+        drift = std::max(drift, dr);
+    };
+    drifted(1, ctx->firstD[(size_t)p.j * (size_t)nc + (size_t)p.c]);
+    for (size_t u = p.d0; u < p.d1; u++) drifted(ctx->dips[u].argmin, ctx->dips[u].D_min);
+    return drift;
+}
+
+// a dip with what the hit state machine wants beside it (ctx->dip_argl / dip_aux / dip_fmin / dip_fexit)
+struct ChainDip { kgma_dip d; int64_t argl, aux; double fmin, fexit; };
+
+// The dips of pair `p` as the chain's values draw them: the runs of windows under the threshold, appended to `all`
+static int rebuild_pair_dips(kgma_ctx *ctx, const ChainPair &p, std::vector<ChainDip> &all)
+{
+    const KfvInfo &f = ctx->kfv[(size_t)p.j];
+    const double scale = chain_scale(ctx->k, f);
+    const int64_t nwin = ctx->contig_nwin[(size_t)p.c];
+    bool in_run = false;
+    ChainDip cur{};
+    int64_t prev_w = 0;
+    size_t vi = 0;
+    auto close_run = [&](int64_t exit_pos, double fexit) {
+        cur.d.exit_pos = exit_pos;
+        cur.fexit = fexit;
+        cur.d.D_exit = exit_pos ? (int64_t)std::llround(fexit * scale) : 0;
+        cur.d.D_min = (int64_t)std::llround(cur.fmin * scale);
+        cur.argl = cur.d.argmin;
+        all.push_back(cur);
+        in_run = false;
+    };
+    for (const ChainInterval &x : p.iv) {
+        for (int64_t w = x.lo; w <= x.hi; w++, vi++) {
+            const double v = p.val[vi];
+            const bool under = w >= 2 && v < f.thr;            // GenomeMiner.jl:82 / OmnGenomeMiner.jl:113 (the first window is never tested)
+            if (in_run && w != prev_w + 1)                     // a run never reaches the end of a sampled interval
                 return fail(ctx, KGMA_E_HIP, "internal: chain replay lost the exit of a dip (record %d KFV %d window %lld)", p.c, p.j + 1, (long long)prev_w);
-            close_run(0, 0.0);                                         // still open at the record end: dropped by the state machine
+            if (under) {
+                if (!in_run) {
+                    in_run = true;
+                    memset(&cur.d, 0, sizeof cur.d);
+                    cur.d.contig = p.c; cur.d.kfv = p.j + 1; cur.d.start = w; cur.d.argmin = w;
+                    cur.d.flags = KGMA_HIT_CHAIN;
+                    cur.fmin = v; cur.aux = -1;
+                } else if (v < cur.fmin) { cur.fmin = v; cur.d.argmin = w; }   // strict: the first window attaining the minimum
+                cur.d.end = w;
+            } else if (in_run) {
+                close_run(w, v);
+            }
+            prev_w = w;
         }
     }
-    if (worst_drift > 0) { *drift_out = worst_drift; return CHAIN_DRIFT_RETRY; }
-    std::stable_sort(all.begin(), all.end(), [](const DipX &a, const DipX &b) {
+    if (in_run) {
+        if (prev_w != nwin)
+            return fail(ctx, KGMA_E_HIP, "internal: chain replay lost the exit of a dip (record %d KFV %d window %lld)", p.c, p.j + 1, (long long)prev_w);
+        close_run(0, 0.0);                                         // still open at the record end: dropped by the state machine
+    }
+    return KGMA_OK;
+}
+
+// the dips no chain pair replaces, as they are
+static std::vector<ChainDip> dips_outside_pairs(const kgma_ctx *ctx, const std::vector<ChainPair> &pairs)
+{
+    std::vector<ChainDip> all;
+    all.reserve(ctx->dips.size() + 16);
+    std::vector<char> replaced(ctx->dips.size(), 0);
+    for (const ChainPair &p : pairs)
+        for (size_t u = p.d0; u < p.d1; u++) replaced[u] = 1;
+    for (size_t u = 0; u < ctx->dips.size(); u++)
+        if (!replaced[u]) all.push_back(ChainDip{ctx->dips[u], ctx->dip_argl[u], ctx->dip_aux[u], 0.0, 0.0});
+    return all;
+}
+
+static void store_chain_dips(kgma_ctx *ctx, std::vector<ChainDip> &all)
+{
+    std::stable_sort(all.begin(), all.end(), [](const ChainDip &a, const ChainDip &b) {
         if (a.d.contig != b.d.contig) return a.d.contig < b.d.contig;
         if (a.d.kfv != b.d.kfv) return a.d.kfv < b.d.kfv;
         return a.d.start < b.d.start;
@@ -4936,10 +5074,83 @@ static int chain_decide(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64
         ctx->dip_fmin[u] = all[u].fmin; ctx->dip_fexit[u] = all[u].fexit;
     }
     ctx->stats.n_dips = (int64_t)n;
+}
+
+// (*drift_out, when given: instead of failing on a chain that has drifted beyond the guard band's half width, the largest drift seen
+//  is returned there with status CHAIN_DRIFT_RETRY, and kgma_scan repeats the scan with a band that covers it)
+constexpr int CHAIN_DRIFT_RETRY = -77;
+static int chain_decide(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64_t buff, double *drift_out = nullptr)
+{
+    const double t0 = now_ms();
+    const ChainEnv env = read_chain_env();
+    const int m = ctx->m;
+    const int64_t nc = (int64_t)ctx->contig_len.size();
+    reset_chain_stats(ctx);
+    resolve_local_ties(ctx, g);
+    // ---- select the pairs ------------------------------------------------------------------
+    int64_t why_count[5] = {0, 0, 0, 0, 0};
+    const std::vector<char> dip_meets_other = mode == KGMA_MODE_OMN ? mark_dips_meeting_others(ctx, buff) : std::vector<char>(ctx->dips.size(), 0);
+    std::vector<ChainPair> pairs = select_chain_pairs(ctx, mode, dip_meets_other, why_count);
+    if (env.debug)
+        fprintf(stderr, "chain replay: %zu pairs selected: %lld by a window in the threshold band, %lld by a dip with tied minima, %lld by a dip at the threshold, "
+                "%lld by a minimum equal to the running / first / an earlier minimum\n", pairs.size(), (long long)why_count[1], (long long)why_count[2],
+                (long long)why_count[3], (long long)why_count[4]);
+    ctx->dip_fmin.assign(ctx->dips.size(), 0.0);
+    ctx->dip_fexit.assign(ctx->dips.size(), 0.0);
+    ctx->chain_pair.assign((size_t)m * (size_t)nc, 0);
+    ctx->firstF.assign((size_t)m * (size_t)nc, 0.0);
+    if (pairs.empty()) { ctx->stats.chain_ms = now_ms() - t0; return KGMA_OK; }
+    int rc = sample_pair_windows(ctx, pairs);
+    if (rc) return rc;
+
+    // ---- the chains: on the device where its kernel applies, the rest (and whatever failed a check there) on the host ----
+    std::vector<char> on_device(pairs.size(), 0);
+    ChainDevInfo dev;
+    const double t_selected = now_ms();
+    if (!g) rc = chains_from_source(ctx, pairs, on_device, dev);
+    else if (!env.host_only) rc = chain_on_device(ctx, g, env, pairs, on_device, dev);
+    if (rc) return rc;
+    ctx->stats.chain_device_pairs = dev.pairs;
+    ctx->stats.chain_device_ms = dev.kernel_ms;
+    ctx->stats.chain_raw_steps = dev.raw_steps;
+    ctx->stats.chain_max_drift = dev.max_drift;
+    if (env.debug) {
+        fprintf(stderr, "chain replay: local tie pass + pair selection %.2f ms, device chains %.2f ms (wall)\n", t_selected - t0, now_ms() - t_selected);
+        fprintf(stderr, "chain on the device: %lld of %zu pairs, %lld windows in %lld streams / %lld chunks, setup %.2f ms, kernels %.2f ms (%d attempt(s)), download %.2f ms, host walk %.2f ms, %lld raw steps, drift <= %.3g\n",
+                (long long)dev.pairs, pairs.size(), (long long)dev.windows, (long long)dev.streams, (long long)dev.chunks, dev.setup_ms, dev.kernel_ms, dev.attempts,
+                dev.copy_ms, dev.walk_ms, (long long)dev.raw_steps, dev.max_drift);
+    }
+    std::vector<ChainPair *> hostp;
+    for (size_t i = 0; i < pairs.size(); i++)
+        if (!on_device[i]) hostp.push_back(&pairs[i]);
+    int64_t windows = dev.windows;
+    rc = chains_on_host(ctx, g, env, hostp, &windows);
+    if (rc) return rc;
+
+    // ---- rebuild the dips of the chain pairs from the chain values ---------------------------
+    const double limit = std::ldexp(1.0, -(ctx->band_log2 + 1));
+    double worst_drift = 0;                                            // beyond the limit, over all pairs
+    std::vector<ChainDip> all = dips_outside_pairs(ctx, pairs);
+    for (const ChainPair &p : pairs) {
+        ctx->chain_pair[(size_t)p.j * (size_t)nc + (size_t)p.c] = 1;
+        ctx->firstF[(size_t)p.j * (size_t)nc + (size_t)p.c] = p.val[0];
+        const double drift = pair_drift(ctx, p);
+        ctx->stats.chain_max_drift = std::max(ctx->stats.chain_max_drift, drift);
+        if (drift > limit) {
+            if (!drift_out)
+                return fail(ctx, KGMA_E_STATE, "chain replay: the running Float64 value of record %d KFV %d has drifted %.3g (relative to max(distance, thr)) from the "
+                            "exact distance; the threshold guard band (2^-%d) no longer covers it", p.c, p.j + 1, drift, ctx->band_log2);
+            worst_drift = std::max(worst_drift, drift);
+        }
+        rc = rebuild_pair_dips(ctx, p, all);
+        if (rc) return rc;
+    }
+    if (worst_drift > 0) { *drift_out = worst_drift; return CHAIN_DRIFT_RETRY; }
+    store_chain_dips(ctx, all);
     ctx->stats.n_chain_pairs = (int64_t)pairs.size();
     ctx->stats.chain_windows = windows;
     ctx->stats.chain_ms = now_ms() - t0;
-    if (getenv("KGMA_CHAIN_DEBUG")) fprintf(stderr, "chain replay: %.2f ms in all\n", ctx->stats.chain_ms);
+    if (env.debug) fprintf(stderr, "chain replay: %.2f ms in all\n", ctx->stats.chain_ms);
     return KGMA_OK;
 }
 
@@ -4995,6 +5206,19 @@ int kgma_scan(kgma_ctx *ctx, const kgma_genome *g, int32_t mode, int64_t buff, i
     return replay_hits(ctx, g, mode, buff, genome_pos0, flags, align, align_user);
 }
 
+// The caller's window intervals as a request for one pair: sorted, disjoint, inside 1 .. bound.  false: they are not
+static bool pair_of_intervals(int64_t contig, int32_t kfv, const int64_t *win_lo, const int64_t *win_hi, int64_t n_intervals, int64_t bound, ChainPair &p)
+{
+    p.c = (int32_t)contig; p.j = kfv - 1; p.d0 = p.d1 = p.a0 = p.a1 = 0;
+    p.last = 0;                                                        // (here: the last window wanted)
+    for (int64_t i = 0; i < n_intervals; i++) {
+        if (win_lo[i] < 1 || win_hi[i] < win_lo[i] || win_lo[i] <= p.last || win_hi[i] > bound) return false;
+        p.iv.push_back(ChainInterval{win_lo[i], win_hi[i]});
+        p.last = win_hi[i];
+    }
+    return true;
+}
+
 int kgma_chain_values(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32_t kfv, const int64_t *win_lo, const int64_t *win_hi,
                       int64_t n_intervals, double *out, int64_t cap, int64_t *n_out)
 {
@@ -5006,14 +5230,10 @@ int kgma_chain_values(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32
     const int64_t L = g->cd[(size_t)contig].len, nwin = L - f.W + 1;
     std::vector<ChainPair> pairs(1);
     ChainPair &p = pairs[0];
-    p.c = (int32_t)contig; p.j = kfv - 1; p.d0 = p.d1 = p.a0 = p.a1 = 0;
-    int64_t total = 0, prev = 0;
-    for (int64_t i = 0; i < n_intervals; i++) {
-        if (win_lo[i] < 1 || win_hi[i] < win_lo[i] || win_lo[i] <= prev || win_hi[i] > nwin) return fail(ctx, KGMA_E_ARG, "window intervals must be sorted, disjoint and inside the record");
-        p.iv.push_back(ChainInterval{win_lo[i], win_hi[i]});
-        total += win_hi[i] - win_lo[i] + 1;
-        prev = win_hi[i];
-    }
+    if (!pair_of_intervals(contig, kfv, win_lo, win_hi, n_intervals, nwin, p)) return fail(ctx, KGMA_E_ARG, "window intervals must be sorted, disjoint and inside the record");
+    const int64_t prev = p.last;
+    int64_t total = 0;
+    for (const ChainInterval &x : p.iv) total += x.hi - x.lo + 1;
     *n_out = total;
     if (!out) return KGMA_OK;
     if (cap < total) return KGMA_E_ARG;
@@ -5025,7 +5245,6 @@ int kgma_chain_values(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32
         if (fb != NO_BAD && (int64_t)fb <= f.W + prev - 1)
             return fail(ctx, KGMA_E_BADBASE, "record %lld position %llu: residue is not one of A/C/G/T/N (KeyError, Consts.jl:22-28)", (long long)contig, fb);
     }
-    p.last = prev;
     p.val.assign((size_t)total, 0.0);
     if (prev == 1) {
         // only window 1 is wanted: its value is the first window's kmer_count! + sqeuclidean (GenomeMiner.jl:42-47), formed on the
@@ -5033,16 +5252,13 @@ int kgma_chain_values(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32
         const size_t dw = (size_t)((f.W + 15) / 16) + 2;
         std::vector<uint32_t> codes(dw, 0u);
         HIP_TRY(ctx, hipMemcpy(codes.data(), g->d_inter + 2 * g->cd[(size_t)contig].word_off, dw * 4, hipMemcpyDeviceToHost));
-        static const ChainInterval one{1, 1};
-        ChainJob J;
-        J.seq = nullptr; J.packed = codes.data(); J.n_res = f.W; f.chain_ref(J); J.k = ctx->k; J.W = f.W; J.last_window = 1;
-        J.iv = &one; J.n_iv = 1; J.out = out; J.n_out = 0; J.ok = false;
+        ChainJob J = first_window_job(f, ctx->k, codes.data(), out);
         run_chain_jobs(&J, 1, 1);
         return J.ok && J.n_out == 1 ? KGMA_OK : fail(ctx, KGMA_E_HIP, "internal: first window of record %lld", (long long)contig);
     }
     std::vector<char> done(1, 0);
     ChainDevInfo info;
-    const int rc = chain_on_device(ctx, g, pairs, done, info);
+    const int rc = chain_on_device(ctx, g, read_chain_env(), pairs, done, info);
     if (rc) return rc;
     if (!done[0])
         return fail(ctx, KGMA_E_UNSUPPORTED, "no chain kernel served this request (KGMA_CHAIN / KGMA_CHAIN_GENERIC switched them off, the buffers did not fit, or the walk failed a drift check)");
@@ -5072,18 +5288,7 @@ int kgma_resolve_ties_local(kgma_ctx *ctx, const kgma_genome *g)
     if (ctx && ctx->strobe) return fail(ctx, KGMA_E_UNSUPPORTED, "%s is not served for strobemer references (kgma_set_strobe_ref)", __func__);
     if (!ctx || !g) return KGMA_E_ARG;
     if (ctx->last_mode < 0) return fail(ctx, KGMA_E_STATE, "no scan has been run");
-    TieResolver tr{ctx, g, {}, {}, {}, nullptr, {}, {}};
-    tr.prefetch();
-    for (size_t i = 0; i < ctx->dips.size(); i++) {
-        kgma_dip &d = ctx->dips[i];
-        if (!(d.flags & KGMA_HIT_TIE)) continue;
-        const TieResolver::Result r = tr.replay(d.kfv - 1, d.contig, d.argmin, d.D_min, d.argmin, ctx->dip_argl[i], d.D_min, false,
-                                                tr.prefetched(i));
-        if (r.ok && !r.sensitive) {
-            d.argmin = r.pos;
-            d.flags = (d.flags & ~(uint32_t)KGMA_HIT_TIE) | KGMA_HIT_TIE_RESOLVED;
-        }
-    }
+    resolve_local_ties(ctx, g);
     return KGMA_OK;
 }
 
@@ -5629,25 +5834,22 @@ int kgma_chain_export(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32
     if (last_window < 2 || last_window > nwin) return fail(ctx, KGMA_E_ARG, "last window %lld outside 2 ... %lld", (long long)last_window, (long long)nwin);
     std::vector<ChainPair> pairs(1);
     ChainPair &p = pairs[0];
-    p.c = (int32_t)contig; p.j = kfv - 1; p.d0 = p.d1 = p.a0 = p.a1 = 0;
-    int64_t prev = 0;
-    for (int64_t i = 0; i < n_intervals; i++) {
-        if (win_lo[i] < 1 || win_hi[i] < win_lo[i] || win_lo[i] <= prev || win_hi[i] > last_window) return fail(ctx, KGMA_E_ARG, "window intervals must be sorted, disjoint and <= the last window");
-        p.iv.push_back(ChainInterval{win_lo[i], win_hi[i]});
-        prev = win_hi[i];
-    }
+    if (!pair_of_intervals(contig, kfv, win_lo, win_hi, n_intervals, last_window, p)) return fail(ctx, KGMA_E_ARG, "window intervals must be sorted, disjoint and <= the last window");
     p.last = last_window;
     {
         kgma_genome *gm = const_cast<kgma_genome *>(g);
         const int src = genome_sync(ctx, gm);
         if (src) return src;
     }
-    const int which = chain_kernel_for(ctx, f);
+    const ChainEnv env = read_chain_env();
+    const int which = chain_kernel_for(ctx, f, env);
     if (which == 0) return fail(ctx, KGMA_E_UNSUPPORTED, "no chain kernel serves this KFV");
     std::vector<char> done(1, 0);
     ChainDevInfo info;
     (void)hipSetDevice(ctx->device);
-    const int rc = chain_on_device_batch(ctx, g, pairs, std::vector<size_t>(1, 0), done, info, true, 0, nullptr, which == 2);
+    ChainBatch batch(ctx, g, env, pairs, done, info, std::vector<size_t>(1, 0), 0, which == 2);
+    batch.export_only = true;
+    const int rc = run_chain_batch(batch, false);
     if (rc) return rc;
     if (!done[0]) return fail(ctx, KGMA_E_NOMEM, "the chain kernel's buffers do not fit");
     *n_streams = (int64_t)ctx->cx_streams.size(); *n_chunks = (int64_t)ctx->cx_chunks.size(); *pool_units = (int64_t)ctx->cx_pool.size();

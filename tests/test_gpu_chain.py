@@ -238,7 +238,7 @@ def test_chain_replay_with_grouped_launches(ctx, alp_clusters, genes, group, mon
 
 
 def test_chain_replay_in_small_batches(ctx, alp_ref, genes, monkeypatch):
-    """The pairs of a scan are chained in batches of bounded size (2^36 windows by default); forced down to 10^5 windows here,
+    """The pairs of a scan are chained in batches of bounded size (2^35 windows by default); forced down to 10^5 windows here,
     so that three records become three batches: same hits as the oracle."""
     monkeypatch.setenv("KGMA_CHAIN_BATCH_WINDOWS", "100000")
     rng = np.random.default_rng(28)
