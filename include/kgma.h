@@ -349,6 +349,45 @@ int kgma_get_first_window(kgma_ctx *ctx, int32_t kfv, int64_t *out, int64_t cap,
  * (GenomeMiner.jl:79 / OmnGenomeMiner.jl:111); needs KGMA_F_RETURN_DISTS. */
 int kgma_get_dists(kgma_ctx *ctx, int32_t kfv, double *out, int64_t cap, int64_t *n);
 
+/* Distance landscape: reductions over the vector of kgma_get_dists on the device, where the scan left it (it stays there until the
+ * next scan), so that a genome's 8 B per window per KFV need not come to the host.
+ *
+ * Layout.  The vector holds record after record; a record with nwin evaluated windows has nwin - 1 values, and value i (0-based in
+ * the record) is the distance of window start i + 2 (window 1 is never tested).  kgma_dist_layout: record c's values are
+ * offset[c] .. offset[c + 1] of the vector, *n = records + 1 (two-call pattern).  Host only; valid after any scan, with or without
+ * KGMA_F_RETURN_DISTS (KGMA_E_STATE before the first).
+ *
+ * kgma_dist_bins: every record is cut into bins of `bin` consecutive values (the last bin of a record may be shorter, a record
+ * without values has none; bins never cross a record).  bin_min[b] is the smallest value of bin b, bit for bit as the scan wrote
+ * it (also for a Float64 KFV); bin_argmin[b] the window start (1-based, within the record) of the FIRST value attaining it.
+ * Record c's bins are bin_offset[c] .. bin_offset[c + 1] (records + 1 entries, or NULL).  Two-call pattern on bin_min / bin_argmin
+ * (both NULL: *n_bins and bin_offset alone, no device work; cap counts bins).
+ *
+ * kgma_dist_sweep: for n_thr finite, strictly increasing thresholds (1 .. KGMA_SWEEP_MAX_THRESHOLDS), windows_below[j] is the exact
+ * number of values d < thr[j], dips_below[j] the exact number of maximal runs of consecutive values of one record below thr[j]:
+ * the dips kgma_get_dips lists for a scan at that threshold when no window lies at the threshold itself.  Comparisons only (a value
+ * equal to a threshold is not below it), one pass for the whole list.
+ *
+ * All three: KGMA_E_UNSUPPORTED for strobemer references (their distance vector follows another window convention).  The two
+ * device calls: KGMA_E_STATE when the last scan kept no distances, KGMA_E_ARG for kfv outside the KFVs the last scan evaluated,
+ * bin < 1, n_thr out of range, or a threshold that is not finite or not above the one before it.  The values are taken as
+ * non-negative doubles, as every scan writes them.  Nothing stays allocated after a call; the results of the scan are untouched. */
+#define KGMA_SWEEP_MAX_THRESHOLDS 4096
+int kgma_dist_layout(kgma_ctx *ctx, int64_t *offset, int64_t cap, int64_t *n);
+int kgma_dist_bins(kgma_ctx *ctx, int32_t kfv, int64_t bin, double *bin_min, int64_t *bin_argmin, int64_t *bin_offset /* records + 1, or NULL */,
+                   int64_t cap, int64_t *n_bins);
+int kgma_dist_sweep(kgma_ctx *ctx, int32_t kfv, const double *thr, int64_t n_thr, int64_t *windows_below /* n_thr */,
+                    int64_t *dips_below /* n_thr */);
+/* The last kgma_dist_bins (bins_ms: the bin kernel, combine_ms: the pass that joins bins spread over workgroups, n_bins) and the
+ * last kgma_dist_sweep (sweep_ms; sweep_slots: threshold slots of the kernel form that ran: 64, 512 or 4096): device time by
+ * hipEvents.  n_values (values read per kernel) and n_launches describe the later of the two.  All zero before the first call. */
+typedef struct {
+    double bins_ms, combine_ms, sweep_ms;
+    int64_t n_values, n_bins;
+    int32_t n_launches, sweep_slots;
+} kgma_landscape_stats;
+int kgma_get_landscape_stats(kgma_ctx *ctx, kgma_landscape_stats *out);
+
 int kgma_get_stats(kgma_ctx *ctx, kgma_stats *out);
 
 /* Distance-bound prefilter of the last scan (one integer KFV, k = 5 or 6, 8-bit count-table kernel, no distance output).

@@ -37,6 +37,7 @@
 #include "kgma_chain.h"
 #include "kgma_twobit.h"
 #include "kgma_assign.h"
+#include "kgma_landscape.h"
 
 namespace kgma {
 hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs,
@@ -413,6 +414,7 @@ struct kgma_ctx {
     kgma_stats stats{};
     kgma_assign_stats assign_stats{};        // the last kgma_assign_seqs / kgma_assign_ranges (kgma_assign.cpp)
     kgma_kmat_stats kmat_stats{};            // the last kgma_kmer_dist_matrix / kgma_kmer_nearest (kgma_kmat.cpp)
+    kgma_landscape_stats landscape_stats{};  // the last kgma_dist_bins / kgma_dist_sweep (kgma_landscape.cpp)
     int64_t device_bytes = 0;
 };
 
@@ -428,6 +430,29 @@ int ctx_n_cus(const kgma_ctx *ctx) { return ctx->n_cus; }
 kgma_assign_stats *ctx_assign_stats(kgma_ctx *ctx) { return &ctx->assign_stats; }
 kgma_kmat_stats *ctx_kmat_stats(kgma_ctx *ctx) { return &ctx->kmat_stats; }
 GenomeText genome_text(const kgma_genome *g) { return GenomeText{g->d_ascii, g->d_cd, g->cd.data(), g->n_contigs}; }
+
+// kgma_landscape.h: the kept distances of the last scan as kgma_landscape.cpp sees them
+kgma_landscape_stats *ctx_landscape_stats(kgma_ctx *ctx) { return &ctx->landscape_stats; }
+int ctx_dist_view(kgma_ctx *ctx, const char *fn, int32_t kfv, bool need_dists, DistView *view)
+{
+    char buf[256];
+    if (ctx->strobe) {
+        snprintf(buf, sizeof buf, "%s is not served for strobemer references (kgma_set_strobe_ref)", fn);
+        return ctx_fail(ctx, KGMA_E_UNSUPPORTED, buf);
+    }
+    if (ctx->last_mode < 0) return ctx_fail(ctx, KGMA_E_STATE, need_dists ? "the last scan did not keep distances (KGMA_F_RETURN_DISTS)" : "no scan has been run");
+    view->nwin = &ctx->contig_nwin;
+    if (!need_dists) return KGMA_OK;
+    if (!ctx->have_dists) return ctx_fail(ctx, KGMA_E_STATE, "the last scan did not keep distances (KGMA_F_RETURN_DISTS)");
+    const int m_used = ctx->last_mode == KGMA_MODE_SINGLE ? 1 : ctx->m;
+    if (kfv < 1 || kfv > m_used) {
+        snprintf(buf, sizeof buf, "%s: kfv %d out of range", fn, kfv);
+        return ctx_fail(ctx, KGMA_E_ARG, buf);
+    }
+    view->d_dist = ctx->d_dist[(size_t)(kfv - 1)];
+    view->n = ctx->n_dists_per_kfv;
+    return KGMA_OK;
+}
 }  // namespace kgma
 
 namespace {

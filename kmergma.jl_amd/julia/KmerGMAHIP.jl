@@ -759,7 +759,43 @@ function assignGenes_screened(hits::Vector{FASTA.Record}, ref; prescreen::Intege
     return [Assignment[assignment(ids, out[t, i]) for t in 1:top] for i in eachindex(hits)]
 end
 
+# ---- distance landscape (kgma_dist_layout, kgma_dist_bins, kgma_dist_sweep): reductions over the distances the last scan kept ------
+# (like the rest of this shim these three calls have not been executed: no Julia on the build machines; the Python binding in
+#  _lib.py makes the same calls with the same argument types and is what the tests run)
+"dist_layout(ctx) -> offsets: record c's values are offset[c] + 1 : offset[c + 1] of the distance vector; value i is window start i + 1."
+function dist_layout(ctx::Context)
+    n = Ref{Int64}(0)
+    check(ctx, ccall((:kgma_dist_layout, libkgma), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Int64}), ctx.h, C_NULL, 0, n))
+    offset = Vector{Int64}(undef, n[])
+    check(ctx, ccall((:kgma_dist_layout, libkgma), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int64, Ptr{Int64}), ctx.h, offset, n[], n))
+    return offset
+end
+
+"""
+    dist_bins(ctx; kfv = 1, bin = 1) -> (bin_min, bin_argmin, bin_offset)
+Minimum and window start (1-based, within the record) of the first window attaining it, per `bin` consecutive windows of every
+record; record c's bins are bin_offset[c] + 1 : bin_offset[c + 1].  Needs a scan with the distances kept.
+"""
+function dist_bins(ctx::Context; kfv::Integer = 1, bin::Integer = 1)
+    offset = Vector{Int64}(undef, length(dist_layout(ctx)))
+    n = Ref{Int64}(0)
+    sig = (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64})
+    check(ctx, ccall((:kgma_dist_bins, libkgma), Cint, sig, ctx.h, kfv, bin, C_NULL, C_NULL, offset, 0, n))
+    bmin, barg = Vector{Float64}(undef, n[]), Vector{Int64}(undef, n[])
+    check(ctx, ccall((:kgma_dist_bins, libkgma), Cint, sig, ctx.h, kfv, bin, bmin, barg, offset, n[], n))
+    return bmin, barg, offset
+end
+
+"dist_sweep(ctx, thresholds; kfv = 1) -> (windows_below, dips_below) per threshold (finite, strictly increasing, at most 4096)."
+function dist_sweep(ctx::Context, thresholds::Vector{Float64}; kfv::Integer = 1)
+    below, dips = Vector{Int64}(undef, length(thresholds)), Vector{Int64}(undef, length(thresholds))
+    check(ctx, ccall((:kgma_dist_sweep, libkgma), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}),
+                     ctx.h, kfv, thresholds, length(thresholds), below, dips))
+    return below, dips
+end
+
 export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, HumanRSSV, HumanRSSD, Context
+export dist_layout, dist_bins, dist_sweep
 export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists, assignGenes, assign_ranges
 export kmer_dist_matrix, kmer_dist_matrix_ranges, nearest_refs, assignGenes_screened
 

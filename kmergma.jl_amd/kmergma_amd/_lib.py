@@ -42,7 +42,9 @@ EXPORTS = [
     "kgma_assign_seqs", "kgma_assign_ranges", "kgma_get_assign_stats",
     "kgma_kmer_dist_matrix", "kgma_kmer_dist_matrix_ranges", "kgma_kmer_nearest", "kgma_kmer_nearest_ranges", "kgma_get_kmat_stats",
     "kgma_assign_seqs_screened", "kgma_assign_ranges_screened",
+    "kgma_dist_layout", "kgma_dist_bins", "kgma_dist_sweep", "kgma_get_landscape_stats",
 ]
+SWEEP_MAX_THRESHOLDS = 4096          # KGMA_SWEEP_MAX_THRESHOLDS
 ASSIGN_MAX_LEN = 8191                # KGMA_ASSIGN_MAX_LEN
 KMAT_MAX_LEN = 32767                 # KGMA_KMAT_MAX_LEN
 KMAT_MAX_NEAR = 128                  # KGMA_KMAT_MAX_NEAR
@@ -109,6 +111,11 @@ class KgmaAssignStats(C.Structure):
 class KgmaKmatStats(C.Structure):
     _fields_ = [("kmat_ms", C.c_double), ("select_ms", C.c_double), ("n_pairs", C.c_int64), ("n_launches", C.c_int32),
                 ("form", C.c_int32), ("tile", C.c_int32), ("chunks", C.c_int32)]
+
+
+class KgmaLandscapeStats(C.Structure):
+    _fields_ = [("bins_ms", C.c_double), ("combine_ms", C.c_double), ("sweep_ms", C.c_double), ("n_values", C.c_int64),
+                ("n_bins", C.c_int64), ("n_launches", C.c_int32), ("sweep_slots", C.c_int32)]
 
 
 HIT_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("cmi", "<i8"), ("lo", "<i8"), ("hi", "<i8"),
@@ -249,6 +256,10 @@ def load():
     L.kgma_assign_seqs_screened.argtypes = [vp, C.c_char_p, P(i64), i32, C.c_char_p, P(i64), i64, i32, i32, i32, i32, i32, vp, P(i32), P(i32)]
     L.kgma_assign_ranges_screened.argtypes = [vp, vp, C.c_char_p, P(i64), i32, i64, P(i32), P(i64), P(i64), i32, i32, i32, i32, i32, vp,
                                               P(i32), P(i32)]
+    L.kgma_dist_layout.argtypes = [vp, P(i64), i64, P(i64)]
+    L.kgma_dist_bins.argtypes = [vp, i32, i64, P(dbl), P(i64), P(i64), i64, P(i64)]
+    L.kgma_dist_sweep.argtypes = [vp, i32, P(dbl), i64, P(i64), P(i64)]
+    L.kgma_get_landscape_stats.argtypes = [vp, P(KgmaLandscapeStats)]
     L.kgma_stream.argtypes = [vp]
     L.kgma_stream.restype = vp
     L.kgma_scan_kernel_name.argtypes = [vp]
@@ -678,6 +689,43 @@ class Context:
         out = np.zeros(max(n.value, 1), dtype=np.float64)
         self._check(load().kgma_get_dists(self._h, kfv, _np_ptr(out, C.c_double), out.size, C.byref(n)))
         return out[:n.value]
+
+    def dist_layout(self) -> np.ndarray:
+        """kgma_dist_layout: record c's values are offset[c] .. offset[c + 1] of dists(); value i of a record is window start i + 2."""
+        n = C.c_int64(0)
+        self._check(load().kgma_dist_layout(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.int64)
+        self._check(load().kgma_dist_layout(self._h, _np_ptr(out, C.c_int64), out.size, C.byref(n)))
+        return out[:n.value]
+
+    def dist_bins(self, kfv: int = 1, bin: int = 1):
+        """kgma_dist_bins over the distances the last scan kept on the device: (bin_min, bin_argmin, bin_offset).  Record c's bins
+        are bin_offset[c] .. bin_offset[c + 1]; bin_argmin is the window start (1-based, within the record) of the first value
+        attaining bin_min."""
+        n_rec = self.dist_layout().size - 1
+        n = C.c_int64(0)
+        off = np.zeros(n_rec + 1, dtype=np.int64)
+        self._check(load().kgma_dist_bins(self._h, int(kfv), int(bin), None, None, _np_ptr(off, C.c_int64), 0, C.byref(n)))
+        bmin = np.zeros(max(n.value, 1), dtype=np.float64)
+        barg = np.zeros(max(n.value, 1), dtype=np.int64)
+        self._check(load().kgma_dist_bins(self._h, int(kfv), int(bin), _np_ptr(bmin, C.c_double), _np_ptr(barg, C.c_int64),
+                                          _np_ptr(off, C.c_int64), bmin.size, C.byref(n)))
+        return bmin[:n.value], barg[:n.value], off
+
+    def dist_sweep(self, thresholds, kfv: int = 1):
+        """kgma_dist_sweep: (windows_below, dips_below) per threshold (finite, strictly increasing, at most SWEEP_MAX_THRESHOLDS)."""
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        below = np.zeros(max(thr.size, 1), dtype=np.int64)
+        dips = np.zeros(max(thr.size, 1), dtype=np.int64)
+        self._check(load().kgma_dist_sweep(self._h, int(kfv), _np_ptr(thr, C.c_double) if thr.size else None, thr.size,
+                                           _np_ptr(below, C.c_int64), _np_ptr(dips, C.c_int64)))
+        return below[:thr.size], dips[:thr.size]
+
+    def landscape_stats(self) -> dict:
+        """kgma_get_landscape_stats: device times, values read and launches of the last dist_bins / dist_sweep."""
+        s = KgmaLandscapeStats()
+        self._check(load().kgma_get_landscape_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in KgmaLandscapeStats._fields_}
 
     def dips_array(self) -> np.ndarray:
         """Dips of the last scan as a numpy structured array (DIP_DTYPE)."""

@@ -1174,6 +1174,159 @@ def nearest_refs(hits, ref_path_or_seqs, *, k: int = 6, n: int = 1, ctx=None) ->
     return [[(ids[int(r)], int(r), half_inv_k * float(d)) for r, d in zip(ri, di)] for ri, di in zip(index, D)]
 
 
+# ---- distance landscape: bin minima and threshold sweep of a scan, reduced on the device ----
+class LandscapeTrack(NamedTuple):
+    """One record of api.dist_landscape.  The first three fields are the track: bin b covers the windows whose starts, in the
+    scanned orientation, are b * bin + 2 .. min((b + 1) * bin + 1, L - W + 1) (window 1 is never tested); bin_argmin is the
+    FORWARD start of the first window, in scan order, that attains bin_min."""
+    identifier: str
+    bin_min: np.ndarray
+    bin_argmin: np.ndarray
+    strand: str
+    bin: int
+    windowsize: int
+    length: int
+
+
+class ThresholdSweep(NamedTuple):
+    thresholds: np.ndarray
+    windows_below: np.ndarray
+    dips_below: np.ndarray
+
+
+def _landscape_scan(genome_or_path, RV, windowsize, k, n_refs, strand, ctx, reduce) -> None:
+    """The single-engine scan with the distances kept on the device, per strand: reduce(view, strand) runs after each."""
+    _check_strand(strand)
+    # (any finite threshold serves: the distances do not depend on it, and only the device part of the scan runs)
+    ctx.set_refs(int(k), [np.asarray(RV, dtype=np.float64)], [int(windowsize)], [1.0], None if n_refs is None else [int(n_refs)])
+    owned = not isinstance(genome_or_path, _GenomeView)
+    view = genome_or_path if not owned else _GenomeView(ctx, genome_or_path)
+
+    def run(v, sd):
+        ctx.scan_device(v.genome, _lib.MODE_SINGLE, _lib.F_RETURN_DISTS)
+        reduce(v, sd)
+
+    try:
+        _for_strands(view, strand, run)
+    finally:
+        if owned:
+            view.free()
+
+
+def dist_landscape(genome_or_path, RV, windowsize: int, k: int, *, bin: Optional[int] = None, n_refs: Optional[int] = None,
+                   strand: str = "+", ctx=None) -> List[LandscapeTrack]:
+    """The distance landscape of a genome against the KFV `RV`: per record (identifier, bin_min, bin_argmin, ...), the smallest
+    window distance of every `bin` consecutive windows (default: windowsize) and the start of the first window attaining it.
+    The scan keeps its distances on the device and kgma_dist_bins reduces them there: 16 bytes per bin come to the host
+    instead of 8 per window.  `genome_or_path`: a FASTA or .2bit path, an open device genome (it stays open) or records.
+    strand "-": the reverse complement of every record is scanned and bin_argmin is mapped to the forward start of the same
+    window, L - s - W + 2 (strand_range of the window); the bins keep the scan's order, so bin 0 lies at the record's END.
+    "both": the plus tracks, then the minus tracks.  Sets the context's references."""
+    ctx = ctx or default_context()
+    W = int(windowsize)
+    width = W if bin is None else int(bin)
+    if width < 1:
+        raise ValueError(f"bin = {bin}")
+    out: List[LandscapeTrack] = []
+
+    def reduce(v, sd):
+        bmin, barg, off = ctx.dist_bins(1, width)
+        for c in range(v.genome.n_contigs):
+            L = v.genome.contig_len(c)
+            m, a = bmin[off[c]:off[c + 1]].copy(), barg[off[c]:off[c + 1]].copy()
+            if sd == "-":
+                a = L - a - W + 2
+            out.append(LandscapeTrack(v.identifier(c), m, a, sd, width, W, L))
+
+    _landscape_scan(genome_or_path, RV, W, k, n_refs, strand, ctx, reduce)
+    return out
+
+
+def default_sweep_thresholds(ctx, RV, windowsize: int, n: int = _lib.SWEEP_MAX_THRESHOLDS) -> np.ndarray:
+    """Up to `n` thresholds from 0 up to the mean distance of random sequences of `windowsize` residues to the KFV
+    (refprep.estimate_optimal_threshold with buffer 0).  S/N KFV: each lies halfway between two lattice points, (D + 0.5) / scale
+    (off_lattice_threshold), D spread evenly, so no window lies on a threshold; Float64 KFV: evenly spaced.  The context's
+    references must be set (kfv 1)."""
+    top = float(refprep.estimate_optimal_threshold(RV, int(windowsize), buffer=0, ctx=ctx))
+    if ctx.kfv_is_float(1):
+        return np.linspace(top / n, top, n)
+    scale = ctx.kfv_scale(1)
+    D = np.unique(np.round(np.linspace(0, math.floor(top * scale), n)).astype(np.int64))
+    return (D + 0.5) / scale
+
+
+def threshold_sweep(genome_or_path, RV, windowsize: int, k: int, thresholds=None, *, n_refs: Optional[int] = None,
+                    strand: str = "+", ctx=None) -> ThresholdSweep:
+    """(thresholds, windows_below, dips_below): for every threshold the exact number of tested windows whose distance lies
+    below it and the exact number of dips -- maximal runs of such windows, what a scan at that threshold would find -- in ONE
+    scan and one pass over its distances on the device (kgma_dist_sweep).  thresholds: finite, strictly increasing, at most
+    4096; None: default_sweep_thresholds.  strand "both" adds the two strands' counts.  Sets the context's references."""
+    ctx = ctx or default_context()
+    _check_strand(strand)
+    if thresholds is None:
+        ctx.set_refs(int(k), [np.asarray(RV, dtype=np.float64)], [int(windowsize)], [1.0], None if n_refs is None else [int(n_refs)])
+        thresholds = default_sweep_thresholds(ctx, RV, windowsize)
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    state = dict(thr=thr, below=np.zeros(thr.size, dtype=np.int64), dips=np.zeros(thr.size, dtype=np.int64))
+
+    def reduce(v, sd):
+        below, dips = ctx.dist_sweep(thr, 1)
+        state["below"] += below
+        state["dips"] += dips
+
+    _landscape_scan(genome_or_path, RV, windowsize, k, n_refs, strand, ctx, reduce)
+    return ThresholdSweep(state["thr"], state["below"], state["dips"])
+
+
+def threshold_for_dips(sweep, n: int) -> Optional[float]:
+    """The largest threshold of a sweep (thresholds, windows_below, dips_below) with at most `n` dips; None if every one has more.
+    (The dips need not grow with the threshold: neighbouring dips merge.)"""
+    thr, dips = np.asarray(sweep[0]), np.asarray(sweep[2])
+    ok = np.nonzero(dips <= int(n))[0]
+    return float(thr[ok[-1]]) if ok.size else None
+
+
+def best_loci(track, n: int, sep: Optional[int] = None) -> list:
+    """The `n` best loci of a track (api.dist_landscape), threshold-free: (record, window start, dist) with record the index
+    into `track`.  GREEDY OVER BIN MINIMA, not over all windows: the bins are sorted by (minimum, record, argmin) and taken in
+    that order; a bin is dropped when its argmin lies fewer than `sep` windows (default: the track's windowsize) from an
+    accepted locus of the same record.  A second locus inside one bin is therefore never seen; choose bin <= sep.  Host only."""
+    track = list(track)
+    if not track or int(n) <= 0:
+        return []
+    sep = int(track[0].windowsize if sep is None else sep)
+    rec = np.concatenate([np.full(len(t[1]), i, dtype=np.int64) for i, t in enumerate(track)])
+    mins = np.concatenate([np.asarray(t[1], dtype=np.float64) for t in track])
+    args = np.concatenate([np.asarray(t[2], dtype=np.int64) for t in track])
+    taken: dict = {}
+    out = []
+    for i in np.lexsort((args, rec, mins)):
+        r, a = int(rec[i]), int(args[i])
+        if any(abs(a - b) < sep for b in taken.get(r, ())):
+            continue
+        taken.setdefault(r, []).append(a)
+        out.append((r, a, float(mins[i])))
+        if len(out) == int(n):
+            break
+    return out
+
+
+def write_bedgraph(track, path) -> None:
+    """One line per bin: record identifier, 0-based start and end of the bin's window STARTS (forward coordinates, half-open),
+    minimum (repr of the double).  Lines of a record ascend; a minus-strand track is written in forward order."""
+    with open(path, "w") as f:
+        for t in track:
+            nwin = t.length - t.windowsize + 1
+            rows = []
+            for b, m in enumerate(t.bin_min):
+                lo, hi = b * t.bin + 2, min((b + 1) * t.bin + 1, nwin)            # window starts, 1-based inclusive, scan order
+                if t.strand == "-":
+                    lo, hi = t.length - hi - t.windowsize + 2, t.length - lo - t.windowsize + 2
+                rows.append((lo - 1, hi, m))
+            for lo0, hi0, m in (reversed(rows) if t.strand == "-" else rows):
+                f.write(f"{t.identifier}\t{lo0}\t{hi0}\t{float(m)!r}\n")
+
+
 def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
     """src/ExactMatch.jl:146-158: the full description line of every record -> the summed length of the records BEFORE it
     (what the scan reports as GenomePos).  Given an open device genome the headers and lengths come from its handle;
