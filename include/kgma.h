@@ -422,6 +422,14 @@ int kgma_get_filter_candidates(kgma_ctx *ctx, int32_t *contig, int64_t *granule,
  * the sum of S over the k-mers that start at 0-based positions 16 b ... 16 b + 15 of the record, b = first_block + i, and do not
  * pass the record's last k-mer.  A record has 2 * ceil(len / 32) blocks.  KGMA_E_STATE: no such step has run on this genome. */
 int kgma_get_block_sums(kgma_ctx *ctx, const kgma_genome *genome, int64_t contig, int64_t first_block, int64_t n, uint32_t *out);
+/* The sparse step pack (tests and KGMA_GEOM_DEBUG).  A step whose pack carries the block sums, on a genome without a bit-plane
+ * copy, does not write the device's 2-bit copy of the genome in full (KGMA_SPARSE_PACK=0: it does): it packs only the blocks of
+ * 32 768 bases that its own candidate streams and chained records read, and leaves the genome KGMA_INTER_PARTIAL.  Every other
+ * reader of the copy completes it first (one full pack) and leaves it KGMA_INTER_FULL, so no call ever sees the difference.
+ * *state: KGMA_INTER_*; *demand_blocks: the blocks the last step packed on demand (0 after any full pack).  Either may be null.
+ * KGMA_SPARSE_POISON=1 (tests): a sparse step fills the copy with a byte pattern before it packs its blocks. */
+enum { KGMA_INTER_FULL = 0, KGMA_INTER_PARTIAL = 1 };
+int kgma_genome_inter_state(const kgma_genome *genome, int32_t *state, int64_t *demand_blocks);
 
 /* HOST-side helper (not on the device path; a Julia host keeps using BioAlignments.jl): semi-global
  * affine-gap alignment of `a` (global; the consensus) against `b` (leading/trailing residues of b

@@ -43,6 +43,9 @@ namespace kgma {
 hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs,
                        int64_t total_words, const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st,
                        int64_t block0 = 0, int64_t n_blocks = -1);
+hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs,
+                       int64_t total_words, const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st,
+                       const int32_t *block_list, int64_t n_list);
 int pack_block_words();
 hipError_t launch_synth(uint8_t *ascii, const ContigDesc *cd, int n_contigs, int64_t total_words,
                         uint64_t seed, hipStream_t st);
@@ -51,7 +54,7 @@ hipError_t launch_stream(const ScanArgs &a, const GroupParams &gp, hipStream_t s
 bool filter_applies(int k, int64_t s_max);
 hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, int32_t *form, hipStream_t st);
 bool pack_sums_applies(int k, int64_t s_max);
-hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, hipStream_t st);
+hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, bool sums_only, hipStream_t st);
 int stream_waves(int k, int nk, int n_kfv, int n_sizes);
 int stream_slots_per_cu(int k, int nk, int nk_min, int n_longer, int n_kfv, int n_sizes, bool s16, int64_t n_ref, bool u8, int n_plus2, bool need_wide);
 bool stream8_derive_applies(int k, int nk_min, int nk_max, int n_kfv, int64_t n_ref, bool s16);
@@ -186,6 +189,11 @@ struct kgma_genome {
     uint8_t *d_ascii = nullptr;
     uint32_t *d_planes = nullptr;
     uint32_t *d_inter = nullptr;             // 2-bit interleaved copy (16 bases per dword), written by the pack kernel beside the planes
+    // INTER_FULL: d_inter is the text as of the last pack, every word of it.  INTER_PARTIAL: the last pack was a step's sums-only pack
+    // (pack_sums_kernel<K, false>), and only the blocks that step packed on demand are written.  Nothing but ensure_inter and the two
+    // in-step consumers (pack_candidate_blocks, pack_record_blocks) may hand d_inter on while it is PARTIAL.
+    int32_t inter_state = KGMA_INTER_FULL;
+    int64_t inter_demand_blocks = 0;         // pack blocks the last step packed on demand (kgma_genome_inter_state)
     ContigDesc *d_cd = nullptr;
     unsigned long long *d_first_bad = nullptr;
     int32_t *d_block_contig = nullptr;       // record of the first word of every pack block (pack_kernel)
@@ -348,6 +356,9 @@ struct kgma_ctx {
     std::vector<TileDesc> ftiles;            // sorted by (record, first window)
     std::vector<int64_t> fcontig_tile_base;  // per contig: index of its first candidate stream or -1
     TileDesc *d_ftiles = nullptr; int64_t ftiles_cap = 0;
+    // sparse step pack: the pack blocks the candidate streams read, sorted (pack_candidate_blocks)
+    std::vector<int32_t> blist;
+    int32_t *d_blist = nullptr; int64_t blist_cap = 0;
     unsigned int *d_fctl = nullptr;          // entries the filter kernel appended (left at zero by its publish kernel)
     uint8_t *h_fpin = nullptr, *h_fpin_dev = nullptr; size_t fpin_cap = 0;   // pinned: [count u32, pad][FilterEntry list]: the kernel writes it directly
     hipEvent_t evf0 = nullptr, evf1 = nullptr;
@@ -851,6 +862,7 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_diff) (void)hipFree(ctx->d_diff);
     if (ctx->d_tiles) (void)hipFree(ctx->d_tiles);
     if (ctx->d_ftiles) (void)hipFree(ctx->d_ftiles);
+    if (ctx->d_blist) (void)hipFree(ctx->d_blist);
     if (ctx->d_fctl) (void)hipFree(ctx->d_fctl);
     if (ctx->h_fpin) (void)hipHostFree(ctx->h_fpin);
     if (ctx->evf0) (void)hipEventDestroy(ctx->evf0);
@@ -1582,6 +1594,90 @@ static int genome_sync(kgma_ctx *ctx, kgma_genome *g)
     return KGMA_OK;
 }
 
+// ---- the state of the 2-bit copy (kgma_genome::inter_state) ------------------------------------------------
+// ensure_inter is the ONE way a reader gets a complete copy: every site that hands g->d_inter to a kernel or to a copy calls it
+// first (or is one of the two in-step consumers below), and everything that changes the resident text of an existing genome calls
+// it BEFORE the change -- so the copy is, as ever, the text as of the last pack.  PARTIAL: the full plain pack runs on ctx->stream
+// (planes too, if the genome has got them since) and the state is FULL; FULL: nothing.
+static int ensure_inter(kgma_ctx *ctx, kgma_genome *g)
+{
+    if (g->inter_state == KGMA_INTER_FULL) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    if (g->n_contigs > 0)
+        HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream));
+    g->inter_state = KGMA_INTER_FULL;
+    if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "sparse pack: the 2-bit copy completed by a full pack (%lld blocks had been packed on demand)\n", (long long)g->inter_demand_blocks);
+    g->inter_demand_blocks = 0;
+    return KGMA_OK;
+}
+
+// Words the stream and chain kernels LOAD of a stream that starts at plane word `word_base` and evaluates n_valid windows of nk
+// k-mers (stream8_kernel and gen_kernel alike): the stream's positions are n_pos = n_valid + nk - 1 (+ up to 2 for derived windows),
+// walked in n_blocks = ceil(n_pos / 64) steps of 64; step b loads the dword pair of its entering k-mers, dwords 4 b + (lane >> 4) and
+// the one behind it, i.e. up to 4 b + 4, and the pair of its leaving ones, nk positions back and never before dword 0 (the index
+// is clamped in the warm-up; nothing is read in front of word_base).  The loads run ONE step ahead of the walk, up to b = n_blocks,
+// and the steady steps go through a buffer descriptor of 16 (n_blocks + 2) bytes.  So a stream loads no dword at or past
+// 4 (n_blocks + 2): plane words word_base ... word_base + 2 (n_blocks + 2) - 1.  (export_kernel reads the residue text only.)
+static inline int64_t stream_words_loaded(int64_t n_valid, int64_t nk)
+{
+    const int64_t n_blocks = (n_valid + nk - 1 + 2 + 63) >> 6;
+    return 2 * (n_blocks + 2);
+}
+
+// In-step consumer 1 (PARTIAL only): the sorted, de-duplicated pack blocks that the candidate streams ctx->ftiles load, packed whole
+// by the list form of pack_kernel in front of the exact scan.  A block shared by two records is packed whole like any other.
+static int pack_candidate_blocks(kgma_ctx *ctx, kgma_genome *g, int64_t nk)
+{
+    if (g->inter_state != KGMA_INTER_PARTIAL) return KGMA_OK;
+    const int64_t PBW = pack_block_words();
+    const int64_t total_blocks = (g->total_words + PBW - 1) / PBW;
+    std::vector<int32_t> &bl = ctx->blist;
+    bl.clear();
+    for (const TileDesc &td : ctx->ftiles) {                           // (sorted by record and window: so are the blocks)
+        const int64_t w0 = td.word_base, w1 = std::min<int64_t>(g->total_words, w0 + stream_words_loaded(td.n_valid, nk)) - 1;
+        if (w0 < 0 || w0 >= g->total_words) return fail(ctx, KGMA_E_HIP, "internal: candidate stream outside the genome");
+        for (int64_t b = w0 / PBW; b <= w1 / PBW && b < total_blocks; b++)
+            if (bl.empty() || bl.back() < (int32_t)b) bl.push_back((int32_t)b);
+    }
+    if (!std::is_sorted(bl.begin(), bl.end())) { std::sort(bl.begin(), bl.end()); bl.erase(std::unique(bl.begin(), bl.end()), bl.end()); }
+    if (bl.empty()) return KGMA_OK;
+    const int rc = dev_reserve(ctx, ctx->d_blist, ctx->blist_cap, (int64_t)bl.size());
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_blist, bl.data(), bl.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream,
+                             ctx->d_blist, (int64_t)bl.size()));
+    g->inter_demand_blocks += (int64_t)bl.size();
+    if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "sparse pack: %zu of %lld blocks packed for %zu candidate streams\n", bl.size(), (long long)total_blocks, ctx->ftiles.size());
+    return KGMA_OK;
+}
+
+// In-step consumer 2 (PARTIAL only): the block range of every record in `records`, with the range form of the pack, in front of
+// a chain launch or a download of a record's codes.  A chain's streams start at the record's first word and the last one ends
+// with the record's last k-mer: by stream_words_loaded it loads fewer than 8 words past the record's last word, inside the
+// CONTIG_PAD_WORDS that are taken here (past the last record: the tail padding).
+static int pack_record_blocks(kgma_ctx *ctx, kgma_genome *g, std::vector<int32_t> records)
+{
+    if (g->inter_state != KGMA_INTER_PARTIAL) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    const int64_t PBW = pack_block_words();
+    const int64_t total_blocks = (g->total_words + PBW - 1) / PBW;
+    std::sort(records.begin(), records.end());
+    records.erase(std::unique(records.begin(), records.end()), records.end());
+    int64_t done_to = 0;                                               // blocks below it are packed already (a block two records share)
+    for (const int32_t c : records) {
+        if (c < 0 || c >= g->n_contigs) return fail(ctx, KGMA_E_HIP, "internal: chained record outside the genome");
+        const ContigDesc &d = g->cd[(size_t)c];
+        const int64_t w1 = std::min<int64_t>(g->total_words, d.word_off + (d.len + 31) / 32 + CONTIG_PAD_WORDS) - 1;
+        const int64_t b0 = std::max<int64_t>(done_to, d.word_off / PBW), b1 = std::min<int64_t>(total_blocks, w1 / PBW + 1);
+        if (b1 <= b0) continue;
+        HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream,
+                                 b0, b1 - b0));
+        g->inter_demand_blocks += b1 - b0;
+        done_to = b1;
+    }
+    return KGMA_OK;
+}
+
 // The bit-plane copy of the genome (read by the bit-sliced kernel, its window pass and the 16-bit stream kernel) is
 // made the first time a scan needs it and kept up to date by every later pack; genomes that only the 8-bit stream
 // kernel scans never have one.
@@ -1594,13 +1690,18 @@ static int ensure_planes(kgma_ctx *ctx, kgma_genome *g)
         HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream));
     else
         HIP_TRY(ctx, hipMemsetAsync(g->d_planes, 0, (size_t)g->total_words * 8, ctx->stream));
+    g->inter_state = KGMA_INTER_FULL;                                  // (a full pack: it writes the 2-bit copy beside the planes)
+    g->inter_demand_blocks = 0;
     return KGMA_OK;
 }
 
 // sums: the step's pack with the prefilter's block sums of KFV 0 (pack_sums_kernel; the caller has checked that it applies and
-// that g->d_bsum exists)
-static int genome_repack(kgma_ctx *ctx, kgma_genome *g, bool sums)
+// that g->d_bsum exists).  sparse (with sums, a genome without planes): the sums-only form -- the 2-bit copy is left PARTIAL and the
+// step packs the blocks it reads (pack_candidate_blocks, pack_record_blocks).  Every other pack is a full one: FULL
+static int genome_repack(kgma_ctx *ctx, kgma_genome *g, bool sums, bool sparse = false)
 {
+    sparse = sparse && sums && g->n_contigs > 0 && g->d_planes == nullptr;
+    g->inter_demand_blocks = 0;
     (void)hipSetDevice(ctx->device);
     // first_bad (smallest position of a residue outside A/C/G/T/N per record) is a function of the residue
     // text: re-encoding unchanged text finds the same minima, so the reset and the download of the table
@@ -1616,7 +1717,7 @@ static int genome_repack(kgma_ctx *ctx, kgma_genome *g, bool sums)
         a.S = ctx->d_Stab; a.n_contigs = (int32_t)g->n_contigs;
         const int bw = pack_block_words();
         a.block_shift = (bw & (bw - 1)) == 0 ? __builtin_ctz((unsigned)bw) : -1;
-        HIP_TRY(ctx, launch_pack_sums(a, ctx->k, ctx->kfv[0].Smax, ctx->n_cus, ctx->stream));
+        HIP_TRY(ctx, launch_pack_sums(a, ctx->k, ctx->kfv[0].Smax, ctx->n_cus, sparse, ctx->stream));
         g->bsum_fresh = true;
         g->bsum_k = ctx->k;
     } else if (g->n_contigs > 0)
@@ -1627,6 +1728,13 @@ static int genome_repack(kgma_ctx *ctx, kgma_genome *g, bool sums)
         HIP_TRY(ctx, hipMemsetAsync(g->d_inter, 0, (size_t)g->total_words * 8, ctx->stream));
     }
     HIP_TRY(ctx, hipEventRecord(ctx->evp1, ctx->stream));
+    g->inter_state = sparse ? KGMA_INTER_PARTIAL : KGMA_INTER_FULL;
+    if (sparse) {
+        // KGMA_SPARSE_POISON=1 (tests): every word of the copy is allocated memory, so a read of a block that nobody packed shows up
+        // as a wrong result, never as a fault
+        const char *pz = getenv("KGMA_SPARSE_POISON");
+        if (pz && atoi(pz) != 0) HIP_TRY(ctx, hipMemsetAsync(g->d_inter, 0x5A, (size_t)g->total_words * 8, ctx->stream));
+    }
     if (dirty) HIP_TRY(ctx, hipMemcpyAsync(g->first_bad, g->d_first_bad, std::max<size_t>(1, (size_t)g->n_contigs) * 8, hipMemcpyDeviceToHost, ctx->stream));
     g->text_dirty = false;
     g->pack_pending = true;     // completed by the next scan's single synchronisation (or genome_sync)
@@ -1751,6 +1859,10 @@ int kgma_genome_revcomp_into(kgma_ctx *ctx, const kgma_genome *g, kgma_genome *r
     for (int64_t c = 0; c < nc && same; c++) same = rc->cd[(size_t)c].len == g->cd[(size_t)c].len;
     if (!same) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: the genomes' record lengths differ");
     (void)hipSetDevice(ctx->device);
+    {
+        const int irc = ensure_inter(ctx, rc);                         // (rc's text is about to change: its 2-bit copy is completed from the old one first)
+        if (irc) return irc;
+    }
     // a record's slot in the text: its residues rounded up to 32 bytes + 32 (genome_layout); the kernel writes all of it
     const int64_t per_tile = revcomp_tile_bytes();
     std::vector<int64_t> prefix((size_t)nc + 1, 0);
@@ -2270,8 +2382,23 @@ int kgma_genome_poke(kgma_ctx *ctx, kgma_genome *g, int64_t contig, int64_t pos,
         return fail(ctx, KGMA_E_ARG, "kgma_genome_poke: range outside the record");
     if (len == 0) return KGMA_OK;
     (void)hipSetDevice(ctx->device);
+    if (g->inter_state != KGMA_INTER_FULL) {
+        // the 2-bit copy stays the text as of the last pack: completed, to the end, before the text changes (the copy below does
+        // not wait for the context's stream)
+        const int irc = ensure_inter(ctx, g);
+        if (irc) return irc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
     HIP_TRY(ctx, hipMemcpy(g->d_ascii + g->cd[(size_t)contig].ascii_off + (pos - 1), bytes, (size_t)len, hipMemcpyHostToDevice));
     g->text_dirty = true;
+    return KGMA_OK;
+}
+
+int kgma_genome_inter_state(const kgma_genome *g, int32_t *state, int64_t *demand_blocks)
+{
+    if (!g) return KGMA_E_ARG;
+    if (state) *state = g->inter_state;
+    if (demand_blocks) *demand_blocks = g->inter_demand_blocks;
     return KGMA_OK;
 }
 
@@ -2570,6 +2697,8 @@ static int launch_overlapped(kgma_ctx *ctx, kgma_genome *g, const ScanArgs &a0, 
     g->text_dirty = false;
     g->pack_pending = true;
     g->repack_deferred = false;
+    g->inter_state = KGMA_INTER_FULL;                                  // (the groups' packs cover every block)
+    g->inter_demand_blocks = 0;
     ctx->ov_groups = G;
     return KGMA_OK;
 }
@@ -2721,6 +2850,10 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_fctl, 0, 16, ctx->stream));
     }
     if (!ctx->evf0) { HIP_TRY(ctx, hipEventCreate(&ctx->evf0)); HIP_TRY(ctx, hipEventCreate(&ctx->evf1)); }
+    if (!g->bsum_fresh) {                                               // (only the form on this step's block sums leaves the 2-bit copy alone)
+        const int irc = ensure_inter(ctx, g);
+        if (irc) return irc;
+    }
     FilterArgs a;
     memset(&a, 0, sizeof a);
     a.inter = g->d_inter; a.n_dwords = 2 * g->total_words;
@@ -2818,6 +2951,8 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
     int rc = dev_reserve(ctx, ctx->d_ftiles, ctx->ftiles_cap, (int64_t)ctx->ftiles.size());
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ftiles, ctx->ftiles.data(), ctx->ftiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice, ctx->stream));
+    rc = pack_candidate_blocks(ctx, g, nk);                             // (a sparse step: the blocks these streams load, in front of the exact scan)
+    if (rc) return rc;
     *filtered = true;
     return KGMA_OK;
 }
@@ -2957,7 +3092,10 @@ int plan_deferred_pack(kgma_ctx *ctx, kgma_genome *g, ScanPlan &p)
             g->d_bsum = nullptr; g->bsum_failed = true; sums = false;
         } else g->device_bytes += g->total_words * 4;
     }
-    return genome_repack(ctx, g, sums);
+    // ... and, on a genome without planes, leaves the 2-bit copy to the blocks the step reads (KGMA_SPARSE_PACK=0: never)
+    const char *sp = getenv("KGMA_SPARSE_PACK");
+    const bool sparse = sums && g->d_planes == nullptr && !(sp && atoi(sp) == 0);
+    return genome_repack(ctx, g, sums, sparse);
 }
 
 // Launches that keep different numbers of streams resident (one KFV: 32 per CU; four: 22): all launches share one
@@ -3605,6 +3743,13 @@ int kgma_scan_device(kgma_ctx *ctx, const kgma_genome *gc, int32_t mode, uint32_
     ScanTables t;
     if (filter_wanted(ctx, plan, plan.overlap)) {
         rc = filter_candidate_table(ctx, g, (int)(ctx->kfv[0].W - plan.k + 1), n_tiles, &t.filtered);
+        if (rc) return rc;
+    }
+    // every scan but the one over a sparse step's candidate streams reads the 2-bit copy anywhere: the filter does not apply, did
+    // not run or fell back (one full pack, once: a fallback is remembered), or this is no step's scan at all
+    // (an overlapped step packs every block itself, group by group beside its launches)
+    if (!t.filtered && !(plan.overlap && g->repack_deferred)) {
+        rc = ensure_inter(ctx, g);
         if (rc) return rc;
     }
     t.n_tiles = n_tiles;
@@ -4701,6 +4846,14 @@ static int chain_on_device(kgma_ctx *ctx, const kgma_genome *g, const ChainEnv &
     }
     if (el8.empty() && elg.empty()) return KGMA_OK;
     (void)hipSetDevice(ctx->device);
+    {
+        // a sparse step: the chain kernels and the download of the first windows' codes read these records of the 2-bit copy
+        std::vector<int32_t> recs_read;
+        for (const std::vector<size_t> *el : {&el8, &elg})
+            for (const size_t i : *el) recs_read.push_back(pairs[i].c);
+        const int prc = pack_record_blocks(ctx, const_cast<kgma_genome *>(g), std::move(recs_read));
+        if (prc) return prc;
+    }
     NumaBind numa(ctx);                      // (the pinned download buffers and the walking threads on the GPU's NUMA node: gigabytes come back on dense inputs)
     // batches of bounded size (2^35 windows: a chunk array of 128 MiB), in record order; the host part of a batch overlaps
     // the device part of the next, so what stays exposed is the LAST batch's host part: smaller batches, shorter tail
@@ -4935,6 +5088,12 @@ static int chains_on_host(kgma_ctx *ctx, const kgma_genome *g, const ChainEnv &e
 {
     const int k = ctx->k;
     (void)hipSetDevice(ctx->device);
+    if (g && !hostp.empty()) {
+        std::vector<int32_t> recs_read;                                // (a sparse step: the records whose codes come down)
+        for (const ChainPair *p : hostp) recs_read.push_back(p->c);
+        const int prc = pack_record_blocks(ctx, const_cast<kgma_genome *>(g), std::move(recs_read));
+        if (prc) return prc;
+    }
     size_t pi = 0;
     double copy_ms = 0, jobs_ms = 0;
     while (pi < hostp.size()) {
@@ -5271,6 +5430,11 @@ int kgma_chain_values(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32
             return fail(ctx, KGMA_E_BADBASE, "record %lld position %llu: residue is not one of A/C/G/T/N (KeyError, Consts.jl:22-28)", (long long)contig, fb);
     }
     p.val.assign((size_t)total, 0.0);
+    {
+        const int irc = ensure_inter(ctx, const_cast<kgma_genome *>(g));   // (no step's reader: the whole copy)
+        if (irc) return irc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));               // (the blocking copy below does not wait for the context's stream)
+    }
     if (prev == 1) {
         // only window 1 is wanted: its value is the first window's kmer_count! + sqeuclidean (GenomeMiner.jl:42-47), formed on the
         // host from the window's 2-bit codes like the first value of every device chain
@@ -5872,6 +6036,11 @@ int kgma_chain_export(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int32
     std::vector<char> done(1, 0);
     ChainDevInfo info;
     (void)hipSetDevice(ctx->device);
+    {
+        // (a rank's part of a sharded step's chain: the record's blocks, like the step's own chain)
+        const int prc = pack_record_blocks(ctx, const_cast<kgma_genome *>(g), std::vector<int32_t>(1, (int32_t)contig));
+        if (prc) return prc;
+    }
     ChainBatch batch(ctx, g, env, pairs, done, info, std::vector<size_t>(1, 0), 0, which == 2);
     batch.export_only = true;
     const int rc = run_chain_batch(batch, false);
@@ -5994,7 +6163,9 @@ int kgma_exact_match(kgma_ctx *ctx, const kgma_genome *gc, const uint8_t *querie
         const int prc = kgma_genome_repack(ctx, g);
         if (prc) return prc;
     }
-    int rc = genome_sync(ctx, g);
+    int rc = ensure_inter(ctx, g);
+    if (rc) return rc;
+    rc = genome_sync(ctx, g);
     if (rc) return rc;
     bool clean = true;                       // no residue outside A/C/G/T/N anywhere: nothing to check, and the 2-bit copy is faithful up to N
     for (int64_t c = 0; c < g->n_contigs; c++) clean = clean && g->first_bad[(size_t)c] == NO_BAD;

@@ -66,9 +66,12 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ a
                                                    uint32_t *__restrict__ planes, uint32_t *__restrict__ inter,
                                                    const ContigDesc *__restrict__ cd, int n_contigs,
                                                    int64_t total_words, const int32_t *__restrict__ block_contig,
-                                                   unsigned long long *__restrict__ first_bad, int block0)
+                                                   unsigned long long *__restrict__ first_bad, int block0,
+                                                   const int32_t *__restrict__ block_list)
 {
-    const int blk = (int)blockIdx.x + block0;                         // (block0: a launch over a part of the genome)
+    // (block0: a launch over a part of the genome; block_list, when given: the launch's blocks by name -- the same body, so a
+    //  block packed from a list holds the words the full pack gives it)
+    const int blk = block_list != nullptr ? block_list[blockIdx.x] : (int)blockIdx.x + block0;
     const int64_t g0 = (int64_t)blk * PACK_BLOCK_WORDS;
     const int c0 = block_contig[blk];                                 // record of word g0 (or the one before its lead padding)
     const ContigDesc d0 = cd[c0];
@@ -1176,7 +1179,19 @@ hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, 
     if (block0 < 0 || block0 + n_blocks > blocks) return hipErrorInvalidValue;
     if (n_blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)n_blocks), dim3(256), 0, st, ascii, planes, inter, cd,
-                       n_contigs, total_words, block_contig, first_bad, (int)block0);
+                       n_contigs, total_words, block_contig, first_bad, (int)block0, (const int32_t *)nullptr);
+    return hipGetLastError();
+}
+
+// the blocks block_list[0 .. n_list) (device memory; every entry a block of the genome: the caller has checked them)
+hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs,
+                       int64_t total_words, const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st,
+                       const int32_t *block_list, int64_t n_list)
+{
+    if (total_words <= 0 || n_list <= 0) return hipSuccess;
+    if (block_list == nullptr || n_list > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)n_list), dim3(256), 0, st, ascii, planes, inter, cd,
+                       n_contigs, total_words, block_contig, first_bad, 0, block_list);
     return hipGetLastError();
 }
 

@@ -43,6 +43,7 @@ EXPORTS = [
     "kgma_kmer_dist_matrix", "kgma_kmer_dist_matrix_ranges", "kgma_kmer_nearest", "kgma_kmer_nearest_ranges", "kgma_get_kmat_stats",
     "kgma_assign_seqs_screened", "kgma_assign_ranges_screened",
     "kgma_dist_layout", "kgma_dist_bins", "kgma_dist_sweep", "kgma_get_landscape_stats",
+    "kgma_genome_inter_state",
 ]
 SWEEP_MAX_THRESHOLDS = 4096          # KGMA_SWEEP_MAX_THRESHOLDS
 ASSIGN_MAX_LEN = 8191                # KGMA_ASSIGN_MAX_LEN
@@ -52,6 +53,7 @@ KMAT_FORM_LDS, KMAT_FORM_GLOBAL = 0, 1   # kgma_kmat_stats.form
 TWOBIT_NOMASK = 1                    # KGMA_2BIT_NOMASK
 TWOBIT_SIGNATURE = b"\x43\x27\x41\x1a"  # the first four bytes of a .2bit file in this machine's byte order
 FILTER_FORM_PRESUMMED = 1 << 16      # kgma_filter_stats.form: the filter read the block sums the step's pack wrote (KGMA_FUSE_SUMS)
+INTER_FULL, INTER_PARTIAL = 0, 1     # kgma_genome_inter_state: the device's 2-bit copy of the genome (KGMA_SPARSE_PACK)
 FILTER_OK, FILTER_OVERFLOW, FILTER_STREAMS, FILTER_FRACTION, FILTER_REMEMBERED = 0, 1, 2, 3, 4
 
 
@@ -216,6 +218,7 @@ def load():
     L.kgma_get_filter_stats.argtypes = [vp, P(KgmaFilterStats)]
     L.kgma_get_filter_candidates.argtypes = [vp, P(i32), P(i64), i64, P(i64)]
     L.kgma_get_block_sums.argtypes = [vp, vp, i64, i64, i64, P(C.c_uint32)]
+    L.kgma_genome_inter_state.argtypes = [vp, P(i32), P(i64)]
     L.kgma_resolve_ties_local.argtypes = [vp, vp]
     L.kgma_repack_scan_hits.argtypes = [vp, vp, i32, i64, i64, C.c_uint32, P(KgmaHit), i64, P(i64)]
     L.kgma_align_hits_device.argtypes = [vp, vp, C.c_char_p, i64, i32, i32, i64, P(i32), P(i64), P(i64), P(i64), P(i64), P(i64)]
@@ -409,6 +412,12 @@ class Genome:
 
     def repack(self) -> None:
         self._ctx._check(load().kgma_genome_repack(self._ctx._h, self._h))
+
+    def inter_state(self) -> tuple:
+        """kgma_genome_inter_state: (INTER_FULL / INTER_PARTIAL, pack blocks the last step packed on demand)."""
+        st, nb = C.c_int32(0), C.c_int64(0)
+        self._ctx._check(load().kgma_genome_inter_state(self._h, C.byref(st), C.byref(nb)))
+        return int(st.value), int(nb.value)
 
     def revcomp(self) -> "Genome":
         """kgma_genome_revcomp: a new device genome whose record c is the reverse complement of this genome's record c
