@@ -11,7 +11,6 @@
 #include <fcntl.h>
 #include <pthread.h>
 #include <sched.h>
-#include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -25,6 +24,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
+#include <optional>
 #include <mutex>
 #include <functional>
 #include <thread>
@@ -35,26 +36,17 @@
 #include "../../include/kgma.h"
 #include "kgma_device.h"
 #include "kgma_chain.h"
-#include "kgma_twobit.h"
 #include "kgma_assign.h"
+#include "kgma_stage_fill.h"
+#include "kgma_twobit.h"
 #include "kgma_landscape.h"
 
 namespace kgma {
-hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs,
-                       int64_t total_words, const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st,
-                       int64_t block0 = 0, int64_t n_blocks = -1);
-hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs,
-                       int64_t total_words, const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st,
-                       const int32_t *block_list, int64_t n_list);
-int pack_block_words();
-hipError_t launch_synth(uint8_t *ascii, const ContigDesc *cd, int n_contigs, int64_t total_words,
-                        uint64_t seed, hipStream_t st);
 hipError_t launch_scan(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
 hipError_t launch_stream(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
 bool filter_applies(int k, int64_t s_max);
 hipError_t launch_filter(const FilterArgs &a, int k, int64_t s_max, int n_cus, unsigned int *host_count, int32_t *form, hipStream_t st);
 bool pack_sums_applies(int k, int64_t s_max);
-hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, bool sums_only, hipStream_t st);
 int stream_waves(int k, int nk, int n_kfv, int n_sizes);
 int stream_slots_per_cu(int k, int nk, int nk_min, int n_longer, int n_kfv, int n_sizes, bool s16, int64_t n_ref, bool u8, int n_plus2, bool need_wide);
 bool stream8_derive_applies(int k, int nk_min, int nk_max, int n_kfv, int64_t n_ref, bool s16);
@@ -79,14 +71,10 @@ int pos_tables_per_pass(int k);
 int64_t align_trace_bytes(int m, int n);
 hipError_t launch_align(const uint8_t *ascii, const AlignJob *jobs, int n_jobs, const uint8_t *cons, int m, int go, int ge,
                         uint8_t *trace, int64_t trace_stride, int max_n, int64_t *out, hipStream_t st);
-hipError_t launch_fasta_count(const uint8_t *raw, int64_t n, uint32_t *counts, hipStream_t st);
-hipError_t launch_fasta_blank(uint8_t *raw, const int64_t *ranges, int n_ranges, hipStream_t st);
 hipError_t launch_gather_ranges(const uint8_t *src, const int64_t *desc, int n, uint8_t *dst, hipStream_t st);
 hipError_t launch_export(uint8_t *res, uint8_t *host, int64_t d0_slots, int64_t d0_used, unsigned int rec_cap, unsigned int inline_recs,
                          int do_gather, const TileDesc *tiles, const ContigDesc *cd, const uint8_t *ascii, const int64_t *Wtab,
                          unsigned int *done, hipStream_t st);
-hipError_t launch_fasta_scatter(const uint8_t *raw, int64_t n, const int64_t *block_base, const int64_t *rec_start,
-                                const ContigDesc *cd, int n_rec, uint8_t *ascii, hipStream_t st);
 int scan_tile_stride_words(int nk);
 int scan_nblocks(int nk);
 int64_t exact_tile_starts(bool two_bit);
@@ -94,10 +82,6 @@ hipError_t launch_exact(const ExactArgs &a, int kind, int64_t n_tiles, hipStream
 int64_t motif_tile_starts();
 int motif_planes(int max_mm);
 hipError_t launch_motif(const MotifArgs &a, int P, int64_t n_tiles, hipStream_t st);
-int64_t revcomp_tile_bytes();
-hipError_t launch_revcomp(const RevcompArgs &a, int64_t n_tiles, hipStream_t st);
-int64_t twobit_tile_bytes();
-hipError_t launch_twobit_unpack(const TwobitArgs &a, int64_t n_tiles, hipStream_t st);
 int kdist_grid(int k, int64_t n_seqs);
 hipError_t launch_kdist(int mode, const uint8_t *seqs, const int64_t *off, int64_t n_seqs, int k, const double *ref,
                         uint32_t *scratch, double scale, double *out, unsigned long long *first_bad, hipStream_t st);
@@ -105,12 +89,174 @@ hipError_t launch_kdist(int mode, const uint8_t *seqs, const int64_t *off, int64
 
 using namespace kgma;
 
+struct kgma_genome {
+    int64_t n_contigs = 0;
+    int64_t total_bases = 0;
+    int64_t total_words = 0;      // plane words incl. padding
+    int64_t ascii_bytes = 0;
+    std::vector<kgma::ContigDesc> cd;
+    std::vector<std::string> headers;          // FASTA header lines (without '>') or .2bit record names; empty for genomes built otherwise
+    unsigned long long *first_bad = nullptr;   // pinned host copy, valid once pack_pending is cleared
+    bool pack_pending = false;
+    bool repack_deferred = false; // kgma_repack_scan_hits: the re-encoding is still to be launched -- by the next scan, group by group beside
+                                  // its scan launches when that scan qualifies (launch_overlapped), else as one launch in front of it
+    bool text_dirty = true;      // residue text changed since first_bad was last computed (new genome, poke)
+    uint64_t uid = 0;
+    uint8_t *d_ascii = nullptr;
+    uint32_t *d_planes = nullptr;
+    uint32_t *d_inter = nullptr;             // 2-bit interleaved copy (16 bases per dword), written by the pack kernel beside the planes
+    // INTER_FULL: d_inter is the text as of the last pack, every word of it.  INTER_PARTIAL: the last pack was a step's sums-only pack
+    // (pack_sums_kernel<K, false>), and only the blocks that step packed on demand are written.  Nothing but ensure_inter and the two
+    // in-step consumers (pack_candidate_blocks, pack_record_blocks) may hand d_inter on while it is PARTIAL.
+    int32_t inter_state = KGMA_INTER_FULL;
+    int64_t inter_demand_blocks = 0;         // pack blocks the last step packed on demand (kgma_genome_inter_state)
+    kgma::ContigDesc *d_cd = nullptr;
+    unsigned long long *d_first_bad = nullptr;
+    int32_t *d_block_contig = nullptr;       // record of the first word of every pack block (pack_kernel)
+    // the prefilter's block sums (pack_sums_kernel): one uint16 per dword of d_inter, allocated by the first step that fuses them into
+    // its pack.  bsum_fresh: written by the pack of the scan that is running (only that scan's filter reads them); bsum_k: the k of
+    // the last step that wrote them (0: none; kgma_get_block_sums); bsum_failed: the allocation failed once, plain path from then on
+    uint16_t *d_bsum = nullptr;
+    bool bsum_fresh = false, bsum_failed = false;
+    int bsum_k = 0;
+    int64_t device_bytes = 0;
+};
+
+// Two pinned staging buffers used alternately: the CPU fills one while the DMA engine drains the other
+// (host bytes -> device at the pace of the slower of memcpy and PCIe instead of their sum).
+struct StagePipe {
+    uint8_t *buf[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool busy[2] = {false, false};
+    int cur = 0;
+    size_t cap = 0;
+    hipStream_t st = nullptr;
+    bool init(size_t cap_, hipStream_t st_)
+    {
+        cap = cap_; st = st_;
+        for (int i = 0; i < 2; i++)
+            if (hipHostMalloc(reinterpret_cast<void **>(&buf[i]), cap, hipHostMallocDefault) != hipSuccess ||
+                hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) return false;
+        return true;
+    }
+    uint8_t *acquire()                        // buffer to fill next (waits for its previous copy)
+    {
+        if (busy[cur]) { (void)hipEventSynchronize(ev[cur]); busy[cur] = false; }
+        return buf[cur];
+    }
+    hipError_t submit(uint8_t *dst, size_t n) // copy the buffer just filled to the device, switch buffers
+    {
+        hipError_t e = hipMemcpyAsync(dst, buf[cur], n, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipEventRecord(ev[cur], st);
+        busy[cur] = true;
+        cur ^= 1;
+        return e;
+    }
+    void drain()
+    {
+        for (int i = 0; i < 2; i++)
+            if (busy[i]) { (void)hipEventSynchronize(ev[i]); busy[i] = false; }
+    }
+    ~StagePipe()
+    {
+        drain();
+        for (int i = 0; i < 2; i++) {
+            if (buf[i]) (void)hipHostFree(buf[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    }
+};
+
+namespace kgma { int pack_block_words(); }   // kgma_kernels.hip
 namespace {
 
 constexpr int64_t CONTIG_PAD_WORDS = 32;
 constexpr int64_t LEAD_PAD_WORDS = 8;
 constexpr int64_t TAIL_PAD_WORDS = KGMA_TILE_WORDS + 128;
 constexpr unsigned long long NO_BAD = ~0ull;
+
+// a record's slot in the residue text: its residues rounded up to 32 bytes, and 32 more
+inline int64_t record_slot_bytes(int64_t len) { return ((len + 31) & ~31ll) + 32; }
+
+// What a context keeps for building and packing its genomes (kgma_create / kgma_destroy call init / release)
+struct GenomeStore {
+    // ingest: pinned staging pair and device scratch, kept between genomes (allocating and pinning them cost a third of a
+    // 400 MB ingest); scratch beyond 2 GiB is given back after use
+    StagePipe *pipe = nullptr;
+    uint8_t *d_ingest = nullptr; int64_t ingest_cap = 0;                 // raw FASTA text on the device
+    uint32_t *d_icounts = nullptr; int64_t icounts_cap = 0;
+    uint64_t next_uid = 1;
+    hipEvent_t evp0 = nullptr, evp1 = nullptr;                           // around the last pack genome_repack queued
+    int numa_state = 0;                                  // 0: not looked up, 1: numa_cpus is the GPU's NUMA node, -1: none / not applicable
+    cpu_set_t numa_cpus;                                 // CPUs of the NUMA node the GPU hangs on (NumaBind)
+    // sparse step pack: the pack blocks the candidate streams read, sorted (pack_candidate_blocks)
+    std::vector<int32_t> blist;
+    int32_t *d_blist = nullptr; int64_t blist_cap = 0;
+    // reverse complement (kgma_genome_revcomp): the tile table of the last call, on the device and as uploaded
+    int64_t *d_rcprefix = nullptr; int64_t rcprefix_cap = 0;
+    std::vector<int64_t> rcprefix;
+    double twobit_ms = -1;                   // kgma_genome_from_2bit_file: device time of the last call's unpack kernel (-1: none yet)
+    bool init() { return hipEventCreate(&evp0) == hipSuccess && hipEventCreate(&evp1) == hipSuccess; }
+    void release()
+    {
+        delete pipe;
+        for (void *p : {(void *)d_ingest, (void *)d_icounts, (void *)d_blist, (void *)d_rcprefix}) if (p) (void)hipFree(p);
+        for (hipEvent_t e : {evp0, evp1}) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// The ingest moves the genome through pinned staging buffers with a few copying threads; on a two-socket host it matters which
+// socket they run on: measured on the GPU box (2 x EPYC 9575F, the GPU on node 0), a 1000 MB FASTA file: 45-46 GB/s with the
+// process on the GPU's node, 33 GB/s on the other, and either of the two from run to run when left to the scheduler.  NumaBind
+// narrows the CALLING thread's CPU affinity to the CPUs of the GPU's NUMA node (the PCI device's numa_node in sysfs) that it is
+// allowed to run on, for the duration of an ingest call: the staging buffers are then allocated and pinned from that node and the
+// copying threads, which inherit the mask, run there.  The previous mask is restored on return.  KGMA_NUMA_BIND=0: off.
+struct NumaBind {
+    bool bound = false;
+    cpu_set_t saved;
+    explicit NumaBind(kgma_ctx *ctx);
+    ~NumaBind();
+    NumaBind(const NumaBind &) = delete;
+    NumaBind &operator=(const NumaBind &) = delete;
+};
+
+// Host side of the ingest on a few threads: fn(t, begin, end) over [0, n) cut into equal ranges (one range: inline).
+int ingest_threads();
+template <class F>
+void parallel_ranges(int64_t n, int n_threads, int64_t min_per_thread, F fn)
+{
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n / std::max<int64_t>(1, min_per_thread)));
+    if (T <= 1) { fn(0, (int64_t)0, n); return; }
+    std::vector<std::thread> pool;
+    pool.reserve((size_t)T - 1);
+    const int64_t per = (n + T - 1) / T;
+    for (int t = 1; t < T; t++) pool.emplace_back([=]() { fn(t, std::min<int64_t>(n, t * per), std::min<int64_t>(n, (t + 1) * per)); });
+    fn(0, (int64_t)0, std::min<int64_t>(n, per));
+    for (std::thread &th : pool) th.join();
+}
+
+inline double now_ms()
+{
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// what a pack that carries the prefilter's block sums needs of the references (pack_sums_kernel)
+struct PackSums { const int32_t *S; int k; int64_t s_max; int n_cus; };
+
+// tiles of `per_tile` units over n records of len_of(c) residues, one record after the other: prefix[c] tiles lie before record c,
+// prefix[n] is their number.  by_slot: a record counts its whole slot of the text, else its residues
+template <class LenOf>
+std::vector<int64_t> tile_prefix(int64_t n, int64_t per_tile, bool by_slot, LenOf len_of)
+{
+    std::vector<int64_t> prefix((size_t)n + 1, 0);
+    for (int64_t c = 0; c < n; c++) prefix[(size_t)c + 1] = prefix[(size_t)c] + ((by_slot ? record_slot_bytes(len_of(c)) : len_of(c)) + per_tile - 1) / per_tile;
+    return prefix;
+}
+
+}  // namespace
+
+namespace {
 
 struct KfvInfo {
     int64_t W = 0;
@@ -173,84 +319,6 @@ struct Group {
 
 }  // namespace
 
-struct kgma_genome {
-    int64_t n_contigs = 0;
-    int64_t total_bases = 0;
-    int64_t total_words = 0;      // plane words incl. padding
-    int64_t ascii_bytes = 0;
-    std::vector<ContigDesc> cd;
-    std::vector<std::string> headers;          // FASTA header lines (without '>') or .2bit record names; empty for genomes built otherwise
-    unsigned long long *first_bad = nullptr;   // pinned host copy, valid once pack_pending is cleared
-    bool pack_pending = false;
-    bool repack_deferred = false; // kgma_repack_scan_hits: the re-encoding is still to be launched -- by the next scan, group by group beside
-                                  // its scan launches when that scan qualifies (launch_overlapped), else as one launch in front of it
-    bool text_dirty = true;      // residue text changed since first_bad was last computed (new genome, poke)
-    uint64_t uid = 0;
-    uint8_t *d_ascii = nullptr;
-    uint32_t *d_planes = nullptr;
-    uint32_t *d_inter = nullptr;             // 2-bit interleaved copy (16 bases per dword), written by the pack kernel beside the planes
-    // INTER_FULL: d_inter is the text as of the last pack, every word of it.  INTER_PARTIAL: the last pack was a step's sums-only pack
-    // (pack_sums_kernel<K, false>), and only the blocks that step packed on demand are written.  Nothing but ensure_inter and the two
-    // in-step consumers (pack_candidate_blocks, pack_record_blocks) may hand d_inter on while it is PARTIAL.
-    int32_t inter_state = KGMA_INTER_FULL;
-    int64_t inter_demand_blocks = 0;         // pack blocks the last step packed on demand (kgma_genome_inter_state)
-    ContigDesc *d_cd = nullptr;
-    unsigned long long *d_first_bad = nullptr;
-    int32_t *d_block_contig = nullptr;       // record of the first word of every pack block (pack_kernel)
-    // the prefilter's block sums (pack_sums_kernel): one uint16 per dword of d_inter, allocated by the first step that fuses them into
-    // its pack.  bsum_fresh: written by the pack of the scan that is running (only that scan's filter reads them); bsum_k: the k of
-    // the last step that wrote them (0: none; kgma_get_block_sums); bsum_failed: the allocation failed once, plain path from then on
-    uint16_t *d_bsum = nullptr;
-    bool bsum_fresh = false, bsum_failed = false;
-    int bsum_k = 0;
-    int64_t device_bytes = 0;
-};
-
-// Two pinned staging buffers used alternately: the CPU fills one while the DMA engine drains the other
-// (host bytes -> device at the pace of the slower of memcpy and PCIe instead of their sum).
-struct StagePipe {
-    uint8_t *buf[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool busy[2] = {false, false};
-    int cur = 0;
-    size_t cap = 0;
-    hipStream_t st = nullptr;
-    bool init(size_t cap_, hipStream_t st_)
-    {
-        cap = cap_; st = st_;
-        for (int i = 0; i < 2; i++)
-            if (hipHostMalloc(reinterpret_cast<void **>(&buf[i]), cap, hipHostMallocDefault) != hipSuccess ||
-                hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) return false;
-        return true;
-    }
-    uint8_t *acquire()                        // buffer to fill next (waits for its previous copy)
-    {
-        if (busy[cur]) { (void)hipEventSynchronize(ev[cur]); busy[cur] = false; }
-        return buf[cur];
-    }
-    hipError_t submit(uint8_t *dst, size_t n) // copy the buffer just filled to the device, switch buffers
-    {
-        hipError_t e = hipMemcpyAsync(dst, buf[cur], n, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipEventRecord(ev[cur], st);
-        busy[cur] = true;
-        cur ^= 1;
-        return e;
-    }
-    void drain()
-    {
-        for (int i = 0; i < 2; i++)
-            if (busy[i]) { (void)hipEventSynchronize(ev[i]); busy[i] = false; }
-    }
-    ~StagePipe()
-    {
-        drain();
-        for (int i = 0; i < 2; i++) {
-            if (buf[i]) (void)hipHostFree(buf[i]);
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    }
-};
-
 // kgma_step_begin / kgma_step_end: one findGenes step run by a helper thread of the context, so that the
 // caller's thread can queue other work (the hit exchange of the previous step) while the GPU scans.
 struct StepWorker {
@@ -279,11 +347,9 @@ struct ChainBufferSet {
 struct kgma_ctx {
     StepWorker *worker = nullptr;
     int device = 0;
-    int numa_state = 0;                                  // 0: not looked up, 1: numa_cpus is the GPU's NUMA node, -1: none / not applicable
-    cpu_set_t numa_cpus;                                 // CPUs of the NUMA node the GPU hangs on (NumaBind)
     int n_cus = 256;                                     // hipDeviceAttributeMultiprocessorCount (CPX / partitioned modes expose fewer)
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, evp0 = nullptr, evp1 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
     uint8_t *h_pin = nullptr; size_t h_pin_cap = 0;     // pinned mirror of the result block, written by export_kernel
     uint8_t *h_pin_dev = nullptr;                        // the same memory as the device addresses it
@@ -300,11 +366,7 @@ struct kgma_ctx {
     char kernel_name[48] = "";
     uint8_t *d_gath = nullptr, *h_gath = nullptr; size_t gath_cap = 0;   // tie-replay residue gather: [desc | residues]
     uint32_t *h_chain = nullptr; size_t chain_cap = 0;                   // chain replay: pinned copy of the records' 2-bit codes (dwords)
-    // ingest: pinned staging pair and device scratch, kept between genomes (allocating and pinning them cost a third of a
-    // 400 MB ingest); scratch beyond 2 GiB is given back after use
-    StagePipe *pipe = nullptr;
-    uint8_t *d_ingest = nullptr; int64_t ingest_cap = 0;                 // raw FASTA text on the device
-    uint32_t *d_icounts = nullptr; int64_t icounts_cap = 0;
+    GenomeStore genome;                                                  // what building and packing genomes keeps
     // chain on the device (stream8_kernel<..., CHAIN>): stream table, the two sets of output buffers, hot-chunk bits,
     // {raw cursor, status}
     TileDesc *d_ctiles = nullptr; int64_t ctiles_cap = 0;
@@ -315,7 +377,6 @@ struct kgma_ctx {
     uint64_t *d_chmask = nullptr; int64_t chmask_cap = 0;                // hot steps of each hot chunk
     double cpool_per_step = 0;                                           // pool units per step the last chain launches needed beyond their hot steps
     unsigned int *d_cctl = nullptr;
-    uint64_t next_uid = 1;
     // key of the tile table currently on the device
     uint64_t tk_uid = 0, tk_version = 0; int tk_mode = -1, tk_k = 0; int64_t tk_maxws = 0;
     // references
@@ -356,9 +417,6 @@ struct kgma_ctx {
     std::vector<TileDesc> ftiles;            // sorted by (record, first window)
     std::vector<int64_t> fcontig_tile_base;  // per contig: index of its first candidate stream or -1
     TileDesc *d_ftiles = nullptr; int64_t ftiles_cap = 0;
-    // sparse step pack: the pack blocks the candidate streams read, sorted (pack_candidate_blocks)
-    std::vector<int32_t> blist;
-    int32_t *d_blist = nullptr; int64_t blist_cap = 0;
     unsigned int *d_fctl = nullptr;          // entries the filter kernel appended (left at zero by its publish kernel)
     uint8_t *h_fpin = nullptr, *h_fpin_dev = nullptr; size_t fpin_cap = 0;   // pinned: [count u32, pad][FilterEntry list]: the kernel writes it directly
     hipEvent_t evf0 = nullptr, evf1 = nullptr;
@@ -414,10 +472,6 @@ struct kgma_ctx {
     uint8_t *d_cbtext = nullptr; int64_t cbtext_cap = 0;
     uint64_t *d_cbP = nullptr; int64_t cbP_cap = 0;
     unsigned long long *d_cbbad = nullptr; int64_t cbbad_cap = 0;
-    // reverse complement (kgma_genome_revcomp): the tile table of the last call, on the device and as uploaded
-    int64_t *d_rcprefix = nullptr; int64_t rcprefix_cap = 0;
-    std::vector<int64_t> rcprefix;
-    double twobit_ms = -1;                   // kgma_genome_from_2bit_file: device time of the last call's unpack kernel (-1: none yet)
     std::vector<int64_t> contig_len;
     int64_t n_dists_per_kfv = 0;
     int64_t tile_windows = KGMA_TILE_WINDOWS;
@@ -481,22 +535,23 @@ int fail(kgma_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                   \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess)                                                               \
-            return fail((ctx), KGMA_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__));  \
+#define HIP_TRY(ctx, expr)                                                                              \
+    do {                                                                                                \
+        hipError_t e__ = (expr);                                                                        \
+        if (e__ != hipSuccess)                                                                          \
+            return fail((ctx), KGMA_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
     } while (0)
 
 template <class T>
 int dev_reserve(kgma_ctx *ctx, T *&ptr, int64_t &cap, int64_t need)
 {
     if (need <= cap && ptr) return KGMA_OK;
-    if (ptr) { (void)hipFree(ptr); ctx->device_bytes -= cap * (int64_t)sizeof(T); ptr = nullptr; cap = 0; }
+    int64_t &device_bytes = ctx->device_bytes;
+    if (ptr) { (void)hipFree(ptr); device_bytes -= cap * (int64_t)sizeof(T); ptr = nullptr; cap = 0; }
     int64_t n = std::max<int64_t>(need, 16);
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ptr), (size_t)n * sizeof(T)));
     cap = n;
-    ctx->device_bytes += n * (int64_t)sizeof(T);
+    device_bytes += n * (int64_t)sizeof(T);
     return KGMA_OK;
 }
 
@@ -682,105 +737,6 @@ std::vector<Group> make_groups(const kgma_ctx *ctx, int mode, bool s8 = false)
     return gs;
 }
 
-// The ingest moves the genome through pinned staging buffers with a few copying threads; on a two-socket host it matters which
-// socket they run on: measured on the GPU box (2 x EPYC 9575F, the GPU on node 0), a 1000 MB FASTA file: 45-46 GB/s with the
-// process on the GPU's node, 33 GB/s on the other, and either of the two from run to run when left to the scheduler.  NumaBind
-// narrows the CALLING thread's CPU affinity to the CPUs of the GPU's NUMA node (the PCI device's numa_node in sysfs) that it is
-// allowed to run on, for the duration of an ingest call: the staging buffers are then allocated and pinned from that node and the
-// copying threads, which inherit the mask, run there.  The previous mask is restored on return.  KGMA_NUMA_BIND=0: off.
-static bool parse_cpulist(const char *txt, cpu_set_t *out)
-{
-    CPU_ZERO(out);
-    const char *p = txt;
-    bool any = false;
-    while (*p) {
-        while (*p == ',' || *p == ' ' || *p == '\n') p++;
-        if (!*p) break;
-        char *e = nullptr;
-        const long a = strtol(p, &e, 10);
-        if (e == p || a < 0) return false;
-        long b = a;
-        p = e;
-        if (*p == '-') { b = strtol(p + 1, &e, 10); if (e == p + 1 || b < a) return false; p = e; }
-        for (long c = a; c <= b && c < CPU_SETSIZE; c++) { CPU_SET((int)c, out); any = true; }
-    }
-    return any;
-}
-
-static void numa_lookup(kgma_ctx *ctx)
-{
-    ctx->numa_state = -1;
-    const char *env = getenv("KGMA_NUMA_BIND");
-    if (env && atoi(env) == 0) return;
-    char bdf[64] = {0};
-    if (hipDeviceGetPCIBusId(bdf, (int)sizeof bdf - 1, ctx->device) != hipSuccess) { (void)hipGetLastError(); return; }
-    for (char *q = bdf; *q; q++) if (*q >= 'A' && *q <= 'F') *q = (char)(*q - 'A' + 'a');
-    char path[256], buf[4096];
-    auto slurp = [&](const char *pth) -> bool {
-        FILE *f = fopen(pth, "r");
-        if (!f) return false;
-        const size_t got = fread(buf, 1, sizeof buf - 1, f);
-        fclose(f);
-        buf[got] = 0;
-        return got > 0;
-    };
-    snprintf(path, sizeof path, "/sys/bus/pci/devices/%s/numa_node", bdf);
-    if (!slurp(path)) return;
-    const int node = atoi(buf);
-    if (node < 0) return;
-    snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
-    if (!slurp(path)) return;
-    cpu_set_t node_cpus;
-    if (!parse_cpulist(buf, &node_cpus)) return;
-    ctx->numa_cpus = node_cpus;
-    ctx->numa_state = 1;
-}
-
-struct NumaBind {
-    bool bound = false;
-    cpu_set_t saved;
-    explicit NumaBind(kgma_ctx *ctx)
-    {
-        if (ctx->numa_state == 0) numa_lookup(ctx);
-        if (ctx->numa_state != 1) return;
-        if (pthread_getaffinity_np(pthread_self(), sizeof saved, &saved) != 0) return;
-        cpu_set_t want;
-        CPU_AND(&want, &saved, &ctx->numa_cpus);
-        const int n = CPU_COUNT(&want);
-        if (n < 1 || n == CPU_COUNT(&saved)) return;                  // (not allowed there, or already there)
-        bound = pthread_setaffinity_np(pthread_self(), sizeof want, &want) == 0;
-    }
-    ~NumaBind() { if (bound) (void)pthread_setaffinity_np(pthread_self(), sizeof saved, &saved); }
-    NumaBind(const NumaBind &) = delete;
-    NumaBind &operator=(const NumaBind &) = delete;
-};
-
-// Host side of the ingest on a few threads: fn(t, begin, end) over [0, n) cut into equal ranges (one range: inline).
-int ingest_threads()
-{
-    int t = (int)std::thread::hardware_concurrency() / 2;
-    if (const char *e = getenv("KGMA_INGEST_THREADS")) t = atoi(e);
-    return std::max(1, std::min(t, 8));
-}
-template <class F>
-void parallel_ranges(int64_t n, int n_threads, int64_t min_per_thread, F fn)
-{
-    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n / std::max<int64_t>(1, min_per_thread)));
-    if (T <= 1) { fn(0, (int64_t)0, n); return; }
-    std::vector<std::thread> pool;
-    pool.reserve((size_t)T - 1);
-    const int64_t per = (n + T - 1) / T;
-    for (int t = 1; t < T; t++) pool.emplace_back([=]() { fn(t, std::min<int64_t>(n, t * per), std::min<int64_t>(n, (t + 1) * per)); });
-    fn(0, (int64_t)0, std::min<int64_t>(n, per));
-    for (std::thread &th : pool) th.join();
-}
-
-double now_ms()
-{
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
 extern "C" {
@@ -826,8 +782,7 @@ int kgma_create(int device_ordinal, kgma_ctx **out)
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cus > 0) ctx->n_cus = cus;
     }
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
-        hipEventCreate(&ctx->evp0) != hipSuccess || hipEventCreate(&ctx->evp1) != hipSuccess) {
+        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess || !ctx->genome.init()) {
         kgma_destroy(ctx);
         return KGMA_E_HIP;
     }
@@ -862,7 +817,6 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_diff) (void)hipFree(ctx->d_diff);
     if (ctx->d_tiles) (void)hipFree(ctx->d_tiles);
     if (ctx->d_ftiles) (void)hipFree(ctx->d_ftiles);
-    if (ctx->d_blist) (void)hipFree(ctx->d_blist);
     if (ctx->d_fctl) (void)hipFree(ctx->d_fctl);
     if (ctx->h_fpin) (void)hipHostFree(ctx->h_fpin);
     if (ctx->evf0) (void)hipEventDestroy(ctx->evf0);
@@ -877,9 +831,7 @@ void kgma_destroy(kgma_ctx *ctx)
         for (hipEvent_t e : {ctx->ov_p0[i], ctx->ov_p1[i], ctx->ov_s0[i], ctx->ov_s1[i]}) if (e) (void)hipEventDestroy(e);
     if (ctx->h_gath) (void)hipHostFree(ctx->h_gath);
     if (ctx->h_chain) (void)hipHostFree(ctx->h_chain);
-    delete ctx->pipe;
-    if (ctx->d_ingest) (void)hipFree(ctx->d_ingest);
-    if (ctx->d_icounts) (void)hipFree(ctx->d_icounts);
+    ctx->genome.release();
     if (ctx->d_ctiles) (void)hipFree(ctx->d_ctiles);
     for (ChainBufferSet &cs : ctx->cset) {
         for (void *d : {(void *)cs.chunks, (void *)cs.pool, (void *)cs.D0}) if (d) (void)hipFree(d);
@@ -901,12 +853,9 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_mprefix) (void)hipFree(ctx->d_mprefix);
     if (ctx->d_mout) (void)hipFree(ctx->d_mout);
     if (ctx->d_mctl) (void)hipFree(ctx->d_mctl);
-    if (ctx->d_rcprefix) (void)hipFree(ctx->d_rcprefix);
     for (void *q : {(void *)ctx->d_cboff, (void *)ctx->d_cbD, (void *)ctx->d_cbdist, (void *)ctx->d_cbtab, (void *)ctx->d_cbtext,
                     (void *)ctx->d_cbP, (void *)ctx->d_cbbad})
         if (q) (void)hipFree(q);
-    if (ctx->evp0) (void)hipEventDestroy(ctx->evp0);
-    if (ctx->evp1) (void)hipEventDestroy(ctx->evp1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1460,10 +1409,6 @@ int kgma_set_refs_sparse(kgma_ctx *ctx, int32_t k, int32_t m, const int64_t *nnz
     return set_refs_sparse_core(ctx, k, m, kk, vv, windowsizes, thr, n_refs);
 }
 
-// ------------------------------------------------------------------------------------------
-// genomes
-// ------------------------------------------------------------------------------------------
-// the context's staging pair (2 x 32 MiB of pinned memory), made on first use
 // The strobemer method's reference (kgma.h): one KFV over the 4^(2s) randstrobe bins, S/N only.  kfv_from_nonzeros does the S/N
 // inference, the range checks (its "k-mers per window" W - k + 1 is the window's item count here: W - k sliding strobemers plus
 // the permanent one) and the threshold band; the tables stay in natural bin order, which is the order strobe_kernel forms.
@@ -1526,18 +1471,293 @@ int kgma_set_strobe_ref(kgma_ctx *ctx, int32_t s, int32_t w_min, int32_t w_max, 
     return KGMA_OK;
 }
 
-static StagePipe *ctx_pipe(kgma_ctx *ctx)
+}  // extern "C"
+
+// ---- genomes: layout, ingests, constructors, pack launches, the state of the 2-bit copy ------------------------------------------
+namespace kgma {
+hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs, int64_t total_words,
+                       const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st, int64_t block0 = 0, int64_t n_blocks = -1);
+hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs, int64_t total_words,
+                       const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st, const int32_t *block_list, int64_t n_list);
+hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, bool sums_only, hipStream_t st);
+hipError_t launch_synth(uint8_t *ascii, const ContigDesc *cd, int n_contigs, int64_t total_words, uint64_t seed, hipStream_t st);
+hipError_t launch_fasta_count(const uint8_t *raw, int64_t n, uint32_t *counts, hipStream_t st);
+hipError_t launch_fasta_blank(uint8_t *raw, const int64_t *ranges, int n_ranges, hipStream_t st);
+hipError_t launch_fasta_scatter(const uint8_t *raw, int64_t n, const int64_t *block_base, const int64_t *rec_start, const ContigDesc *cd, int n_rec,
+                                uint8_t *ascii, hipStream_t st);
+int64_t revcomp_tile_bytes();
+hipError_t launch_revcomp(const RevcompArgs &a, int64_t n_tiles, hipStream_t st);
+int64_t twobit_tile_bytes();
+hipError_t launch_twobit_unpack(const TwobitArgs &a, int64_t n_tiles, hipStream_t st);
+}  // namespace kgma
+
+namespace {
+
+bool parse_cpulist(const char *txt, cpu_set_t *out)
 {
-    if (ctx->pipe) { ctx->pipe->drain(); return ctx->pipe; }
+    CPU_ZERO(out);
+    const char *p = txt;
+    bool any = false;
+    while (*p) {
+        while (*p == ',' || *p == ' ' || *p == '\n') p++;
+        if (!*p) break;
+        char *e = nullptr;
+        const long a = strtol(p, &e, 10);
+        if (e == p || a < 0) return false;
+        long b = a;
+        p = e;
+        if (*p == '-') { b = strtol(p + 1, &e, 10); if (e == p + 1 || b < a) return false; p = e; }
+        for (long c = a; c <= b && c < CPU_SETSIZE; c++) { CPU_SET((int)c, out); any = true; }
+    }
+    return any;
+}
+
+void numa_lookup(kgma_ctx *ctx)
+{
+    ctx->genome.numa_state = -1;
+    const char *env = getenv("KGMA_NUMA_BIND");
+    if (env && atoi(env) == 0) return;
+    char bdf[64] = {0};
+    if (hipDeviceGetPCIBusId(bdf, (int)sizeof bdf - 1, ctx->device) != hipSuccess) { (void)hipGetLastError(); return; }
+    for (char *q = bdf; *q; q++) if (*q >= 'A' && *q <= 'F') *q = (char)(*q - 'A' + 'a');
+    char path[256], buf[4096];
+    auto slurp = [&](const char *pth) -> bool {
+        FILE *f = fopen(pth, "r");
+        if (!f) return false;
+        const size_t got = fread(buf, 1, sizeof buf - 1, f);
+        fclose(f);
+        buf[got] = 0;
+        return got > 0;
+    };
+    snprintf(path, sizeof path, "/sys/bus/pci/devices/%s/numa_node", bdf);
+    if (!slurp(path)) return;
+    const int node = atoi(buf);
+    if (node < 0) return;
+    snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
+    if (!slurp(path)) return;
+    cpu_set_t node_cpus;
+    if (!parse_cpulist(buf, &node_cpus)) return;
+    ctx->genome.numa_cpus = node_cpus;
+    ctx->genome.numa_state = 1;
+}
+
+NumaBind::NumaBind(kgma_ctx *ctx)
+{
+    if (ctx->genome.numa_state == 0) numa_lookup(ctx);
+    if (ctx->genome.numa_state != 1) return;
+    if (pthread_getaffinity_np(pthread_self(), sizeof saved, &saved) != 0) return;
+    cpu_set_t want;
+    CPU_AND(&want, &saved, &ctx->genome.numa_cpus);
+    const int n = CPU_COUNT(&want);
+    if (n < 1 || n == CPU_COUNT(&saved)) return;                  // (not allowed there, or already there)
+    bound = pthread_setaffinity_np(pthread_self(), sizeof want, &want) == 0;
+}
+NumaBind::~NumaBind() { if (bound) (void)pthread_setaffinity_np(pthread_self(), sizeof saved, &saved); }
+
+int ingest_threads()
+{
+    int t = (int)std::thread::hardware_concurrency() / 2;
+    if (const char *e = getenv("KGMA_INGEST_THREADS")) t = atoi(e);
+    return std::max(1, std::min(t, 8));
+}
+
+// the one place that spells out the pack kernel's arguments: one pack launch over all blocks (the default), over [block0, block0 + n_blocks),
+// or over a sorted list on the device; st null: the context's stream
+#define PACK_ARGS(g, st) (g)->d_ascii, (g)->d_planes, (g)->d_inter, (g)->d_cd, (int)(g)->n_contigs, (g)->total_words, (g)->d_block_contig, (g)->d_first_bad, (st)
+hipError_t pack_blocks(kgma_ctx *ctx, const kgma_genome *g, int64_t block0 = 0, int64_t n_blocks = -1, hipStream_t st = nullptr) { return launch_pack(PACK_ARGS(g, st ? st : ctx->stream), block0, n_blocks); }
+hipError_t pack_blocks(kgma_ctx *ctx, const kgma_genome *g, const int32_t *block_list, int64_t n_list) { return launch_pack(PACK_ARGS(g, ctx->stream), block_list, n_list); }
+
+// Waits for a pending pack of `g` (the pack kernel is launched asynchronously).
+int genome_sync(kgma_ctx *ctx, kgma_genome *g)
+{
+    if (!g->pack_pending) return KGMA_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->genome.evp0, ctx->genome.evp1);
+    ctx->stats.pack_ms = ms;
+    g->pack_pending = false;
+    return KGMA_OK;
+}
+
+// ---- the state of the 2-bit copy (kgma_genome::inter_state; DESIGN.md section 2) ------------------------------------------------
+// ensure_inter is the ONE way a reader gets a complete copy: every site that hands g->d_inter to a kernel or to a copy calls it
+// first (or is one of the two in-step consumers below), and everything that changes the resident text of an existing genome calls
+// it BEFORE the change -- so the copy is, as ever, the text as of the last pack.  PARTIAL: the full plain pack runs on the context's
+// stream (planes too, if the genome has got them since) and the state is FULL; FULL: nothing.
+int ensure_inter(kgma_ctx *ctx, kgma_genome *g)
+{
+    if (g->inter_state == KGMA_INTER_FULL) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    if (g->n_contigs > 0) HIP_TRY(ctx, pack_blocks(ctx, g));
+    g->inter_state = KGMA_INTER_FULL;
+    if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "sparse pack: the 2-bit copy completed by a full pack (%lld blocks had been packed on demand)\n", (long long)g->inter_demand_blocks);
+    g->inter_demand_blocks = 0;
+    return KGMA_OK;
+}
+
+// Words the stream and chain kernels LOAD of a stream that starts at plane word `word_base` and evaluates n_valid windows of nk
+// k-mers (stream8_kernel and gen_kernel alike): the stream's positions are n_pos = n_valid + nk - 1 (+ up to 2 for derived windows),
+// walked in n_blocks = ceil(n_pos / 64) steps of 64; step b loads the dword pair of its entering k-mers, dwords 4 b + (lane >> 4) and
+// the one behind it, i.e. up to 4 b + 4, and the pair of its leaving ones, nk positions back and never before dword 0 (the index
+// is clamped in the warm-up; nothing is read in front of word_base).  The loads run ONE step ahead of the walk, up to b = n_blocks,
+// and the steady steps go through a buffer descriptor of 16 (n_blocks + 2) bytes.  So a stream loads no dword at or past
+// 4 (n_blocks + 2): plane words word_base ... word_base + 2 (n_blocks + 2) - 1.  (export_kernel reads the residue text only.)
+static inline int64_t stream_words_loaded(int64_t n_valid, int64_t nk)
+{
+    const int64_t n_blocks = (n_valid + nk - 1 + 2 + 63) >> 6;
+    return 2 * (n_blocks + 2);
+}
+
+// In-step consumer 1 (PARTIAL only): the sorted, de-duplicated pack blocks that the candidate streams `streams` load, packed whole
+// by the list form of pack_kernel in front of the exact scan.  A block shared by two records is packed whole like any other.
+int pack_candidate_blocks(kgma_ctx *ctx, kgma_genome *g, const std::vector<TileDesc> &streams, int64_t nk)
+{
+    if (g->inter_state != KGMA_INTER_PARTIAL) return KGMA_OK;
+    const int64_t PBW = pack_block_words();
+    const int64_t total_blocks = (g->total_words + PBW - 1) / PBW;
+    std::vector<int32_t> &bl = ctx->genome.blist;
+    bl.clear();
+    for (const TileDesc &td : streams) {                               // (sorted by record and window: so are the blocks)
+        const int64_t w0 = td.word_base, w1 = std::min<int64_t>(g->total_words, w0 + stream_words_loaded(td.n_valid, nk)) - 1;
+        if (w0 < 0 || w0 >= g->total_words) return ctx_fail(ctx, KGMA_E_HIP, "internal: candidate stream outside the genome");
+        for (int64_t b = w0 / PBW; b <= w1 / PBW && b < total_blocks; b++)
+            if (bl.empty() || bl.back() < (int32_t)b) bl.push_back((int32_t)b);
+    }
+    if (!std::is_sorted(bl.begin(), bl.end())) { std::sort(bl.begin(), bl.end()); bl.erase(std::unique(bl.begin(), bl.end()), bl.end()); }
+    if (bl.empty()) return KGMA_OK;
+    const int rc = dev_reserve(ctx, ctx->genome.d_blist, ctx->genome.blist_cap, (int64_t)bl.size());
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->genome.d_blist, bl.data(), bl.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, pack_blocks(ctx, g, ctx->genome.d_blist, (int64_t)bl.size()));
+    g->inter_demand_blocks += (int64_t)bl.size();
+    if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "sparse pack: %zu of %lld blocks packed for %zu candidate streams\n", bl.size(), (long long)total_blocks, streams.size());
+    return KGMA_OK;
+}
+
+// In-step consumer 2 (PARTIAL only): the block range of every record in `records`, with the range form of the pack, in front of
+// a chain launch or a download of a record's codes.  A chain's streams start at the record's first word and the last one ends
+// with the record's last k-mer: by stream_words_loaded it loads fewer than 8 words past the record's last word, inside the
+// CONTIG_PAD_WORDS that are taken here (past the last record: the tail padding).
+int pack_record_blocks(kgma_ctx *ctx, kgma_genome *g, std::vector<int32_t> records)
+{
+    if (g->inter_state != KGMA_INTER_PARTIAL) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    const int64_t PBW = pack_block_words();
+    const int64_t total_blocks = (g->total_words + PBW - 1) / PBW;
+    std::sort(records.begin(), records.end());
+    records.erase(std::unique(records.begin(), records.end()), records.end());
+    int64_t done_to = 0;                                               // blocks below it are packed already (a block two records share)
+    for (const int32_t c : records) {
+        if (c < 0 || c >= g->n_contigs) return ctx_fail(ctx, KGMA_E_HIP, "internal: chained record outside the genome");
+        const ContigDesc &d = g->cd[(size_t)c];
+        const int64_t w1 = std::min<int64_t>(g->total_words, d.word_off + (d.len + 31) / 32 + CONTIG_PAD_WORDS) - 1;
+        const int64_t b0 = std::max<int64_t>(done_to, d.word_off / PBW), b1 = std::min<int64_t>(total_blocks, w1 / PBW + 1);
+        if (b1 <= b0) continue;
+        HIP_TRY(ctx, pack_blocks(ctx, g, b0, b1 - b0));
+        g->inter_demand_blocks += b1 - b0;
+        done_to = b1;
+    }
+    return KGMA_OK;
+}
+
+// The bit-plane copy of the genome (read by the bit-sliced kernel, its window pass and the 16-bit stream kernel) is
+// made the first time a scan needs it and kept up to date by every later pack; genomes that only the 8-bit stream
+// kernel scans never have one.
+int ensure_planes(kgma_ctx *ctx, kgma_genome *g)
+{
+    if (g->d_planes) return KGMA_OK;
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&g->d_planes), (size_t)g->total_words * 8));
+    g->device_bytes += g->total_words * 8;
+    if (g->n_contigs > 0)
+        HIP_TRY(ctx, pack_blocks(ctx, g));
+    else
+        HIP_TRY(ctx, hipMemsetAsync(g->d_planes, 0, (size_t)g->total_words * 8, ctx->stream));
+    g->inter_state = KGMA_INTER_FULL;                                  // (a full pack: it writes the 2-bit copy beside the planes)
+    g->inter_demand_blocks = 0;
+    return KGMA_OK;
+}
+
+// sums: the step's pack with the prefilter's block sums of KFV 0 (pack_sums_kernel; the caller has checked that it applies and
+// that g->d_bsum exists).  sparse (with sums, a genome without planes): the sums-only form -- the 2-bit copy is left PARTIAL and the
+// step packs the blocks it reads (pack_candidate_blocks, pack_record_blocks).  Every other pack is a full one: FULL
+int genome_repack(kgma_ctx *ctx, kgma_genome *g, const PackSums *sums, bool sparse = false)
+{
+    sparse = sparse && sums && g->n_contigs > 0 && g->d_planes == nullptr;
+    g->inter_demand_blocks = 0;
+    (void)hipSetDevice(ctx->device);
+    // first_bad (smallest position of a residue outside A/C/G/T/N per record) is a function of the residue
+    // text: re-encoding unchanged text finds the same minima, so the reset and the download of the table
+    // are only queued when the text changed (new genome, kgma_genome_poke)
+    const bool dirty = g->text_dirty;
+    if (dirty) HIP_TRY(ctx, hipMemsetAsync(g->d_first_bad, 0xFF, std::max<size_t>(1, (size_t)g->n_contigs) * 8, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->genome.evp0, ctx->stream));
+    if (g->n_contigs > 0 && sums) {
+        PackSumsArgs a;
+        memset(&a, 0, sizeof a);
+        a.ascii = g->d_ascii; a.planes = g->d_planes; a.inter = g->d_inter; a.bsum = g->d_bsum;
+        a.cd = g->d_cd; a.total_words = g->total_words; a.block_contig = g->d_block_contig; a.first_bad = g->d_first_bad;
+        a.S = sums->S; a.n_contigs = (int32_t)g->n_contigs;
+        const int bw = pack_block_words();
+        a.block_shift = (bw & (bw - 1)) == 0 ? __builtin_ctz((unsigned)bw) : -1;
+        HIP_TRY(ctx, launch_pack_sums(a, sums->k, sums->s_max, sums->n_cus, sparse, ctx->stream));
+        g->bsum_fresh = true;
+        g->bsum_k = sums->k;
+    } else if (g->n_contigs > 0)
+        HIP_TRY(ctx, pack_blocks(ctx, g));
+    else
+    {
+        if (g->d_planes) HIP_TRY(ctx, hipMemsetAsync(g->d_planes, 0, (size_t)g->total_words * 8, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(g->d_inter, 0, (size_t)g->total_words * 8, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->genome.evp1, ctx->stream));
+    g->inter_state = sparse ? KGMA_INTER_PARTIAL : KGMA_INTER_FULL;
+    if (sparse) {
+        // KGMA_SPARSE_POISON=1 (tests): every word of the copy is allocated memory, so a read of a block that nobody packed shows up
+        // as a wrong result, never as a fault
+        const char *pz = getenv("KGMA_SPARSE_POISON");
+        if (pz && atoi(pz) != 0) HIP_TRY(ctx, hipMemsetAsync(g->d_inter, 0x5A, (size_t)g->total_words * 8, ctx->stream));
+    }
+    if (dirty) HIP_TRY(ctx, hipMemcpyAsync(g->first_bad, g->d_first_bad, std::max<size_t>(1, (size_t)g->n_contigs) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    g->text_dirty = false;
+    g->pack_pending = true;     // completed by the next scan's single synchronisation (or genome_sync)
+    return KGMA_OK;
+}
+
+// What the pack kernel knows about the residues (first_bad) and the copy the caller reads must be current: a pack that is deferred,
+// or never queued since the text changed, runs now; then the copy is completed and the pack waited for.
+int genome_ready(kgma_ctx *ctx, kgma_genome *g, bool planes)   // planes: the reader needs the bit planes, else the 2-bit copy
+{
+    if (g->repack_deferred || g->text_dirty) {
+        g->repack_deferred = false;
+        const int prc = genome_repack(ctx, g, nullptr);
+        if (prc) return prc;
+    }
+    const int rc = planes ? ensure_planes(ctx, g) : ensure_inter(ctx, g);
+    if (rc) return rc;
+    return genome_sync(ctx, g);
+}
+
+// the context's staging pair (2 x 32 MiB of pinned memory), made on first use
+StagePipe *ctx_pipe(kgma_ctx *ctx)
+{
+    if (ctx->genome.pipe) { ctx->genome.pipe->drain(); return ctx->genome.pipe; }
     StagePipe *p = new (std::nothrow) StagePipe();
     if (!p) return nullptr;
     if (!p->init((size_t)32 << 20, ctx->stream)) { delete p; return nullptr; }
-    ctx->pipe = p;
+    ctx->genome.pipe = p;
     return p;
 }
 
-static int genome_layout(kgma_ctx *ctx, kgma_genome *g, const int64_t *contig_len, int64_t n_contigs)
+// ---- a genome under construction: one owner, one way in, one way out -------------------------------------------------------------
+struct GenomeRelease { kgma_ctx *ctx; void operator()(kgma_genome *g) const { kgma_genome_free(ctx, g); } };
+using GenomeOwner = std::unique_ptr<kgma_genome, GenomeRelease>;
+
+// in: a genome of records of these lengths, laid out and allocated, its text still to be written
+int genome_begin(kgma_ctx *ctx, const int64_t *contig_len, int64_t n_contigs, GenomeOwner &owner)
 {
+    owner = GenomeOwner(new (std::nothrow) kgma_genome(), GenomeRelease{ctx});
+    kgma_genome *g = owner.get();
+    if (!g) return ctx_fail(ctx, KGMA_E_NOMEM, "out of host memory");
     g->n_contigs = n_contigs;
     g->cd.resize((size_t)n_contigs);
     int64_t aoff = 0, woff = LEAD_PAD_WORDS, total = 0;
@@ -1545,7 +1765,7 @@ static int genome_layout(kgma_ctx *ctx, kgma_genome *g, const int64_t *contig_le
         const int64_t L = contig_len[c];
         if (L < 0) return fail(ctx, KGMA_E_ARG, "contig_len[%lld] < 0", (long long)c);
         g->cd[(size_t)c] = ContigDesc{aoff, woff, L};
-        aoff += ((L + 31) & ~31ll) + 32;
+        aoff += record_slot_bytes(L);
         woff += (L + 31) / 32 + CONTIG_PAD_WORDS;
         total += L;
     }
@@ -1559,7 +1779,7 @@ static int genome_layout(kgma_ctx *ctx, kgma_genome *g, const int64_t *contig_le
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&g->d_cd), std::max<size_t>(1, (size_t)n_contigs) * sizeof(ContigDesc)));
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&g->d_first_bad), std::max<size_t>(1, (size_t)n_contigs) * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&g->first_bad), std::max<size_t>(1, (size_t)n_contigs) * sizeof(unsigned long long), hipHostMallocDefault));
-    g->uid = ctx->next_uid++;
+    g->uid = ctx->genome.next_uid++;
     {
         // pack_kernel: record of the first plane word of every block (words before a record's first one -- lead /
         // inter-record padding -- belong to the record before; the kernel walks forward from there)
@@ -1582,169 +1802,68 @@ static int genome_layout(kgma_ctx *ctx, kgma_genome *g, const int64_t *contig_le
     return KGMA_OK;
 }
 
-// Waits for a pending pack of `g` (the pack kernel is launched asynchronously).
-static int genome_sync(kgma_ctx *ctx, kgma_genome *g)
+// out: the text is written (or queued on the context's stream); the first pack is queued behind it and the caller gets the genome
+int genome_finish(kgma_ctx *ctx, GenomeOwner &g, kgma_genome **out)
 {
-    if (!g->pack_pending) return KGMA_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->evp0, ctx->evp1);
-    ctx->stats.pack_ms = ms;
-    g->pack_pending = false;
-    return KGMA_OK;
+    const int rc = genome_repack(ctx, g.get(), nullptr);
+    if (rc == KGMA_OK) *out = g.release();
+    return rc;
 }
 
-// ---- the state of the 2-bit copy (kgma_genome::inter_state; DESIGN.md section 2) ------------------------------------------------
-// ensure_inter is the ONE way a reader gets a complete copy: every site that hands g->d_inter to a kernel or to a copy calls it
-// first (or is one of the two in-step consumers below), and everything that changes the resident text of an existing genome calls
-// it BEFORE the change -- so the copy is, as ever, the text as of the last pack.  PARTIAL: the full plain pack runs on ctx->stream
-// (planes too, if the genome has got them since) and the state is FULL; FULL: nothing.
-static int ensure_inter(kgma_ctx *ctx, kgma_genome *g)
-{
-    if (g->inter_state == KGMA_INTER_FULL) return KGMA_OK;
-    (void)hipSetDevice(ctx->device);
-    if (g->n_contigs > 0)
-        HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream));
-    g->inter_state = KGMA_INTER_FULL;
-    if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "sparse pack: the 2-bit copy completed by a full pack (%lld blocks had been packed on demand)\n", (long long)g->inter_demand_blocks);
-    g->inter_demand_blocks = 0;
-    return KGMA_OK;
-}
-
-// Words the stream and chain kernels LOAD of a stream that starts at plane word `word_base` and evaluates n_valid windows of nk
-// k-mers (stream8_kernel and gen_kernel alike): the stream's positions are n_pos = n_valid + nk - 1 (+ up to 2 for derived windows),
-// walked in n_blocks = ceil(n_pos / 64) steps of 64; step b loads the dword pair of its entering k-mers, dwords 4 b + (lane >> 4) and
-// the one behind it, i.e. up to 4 b + 4, and the pair of its leaving ones, nk positions back and never before dword 0 (the index
-// is clamped in the warm-up; nothing is read in front of word_base).  The loads run ONE step ahead of the walk, up to b = n_blocks,
-// and the steady steps go through a buffer descriptor of 16 (n_blocks + 2) bytes.  So a stream loads no dword at or past
-// 4 (n_blocks + 2): plane words word_base ... word_base + 2 (n_blocks + 2) - 1.  (export_kernel reads the residue text only.)
-static inline int64_t stream_words_loaded(int64_t n_valid, int64_t nk)
-{
-    const int64_t n_blocks = (n_valid + nk - 1 + 2 + 63) >> 6;
-    return 2 * (n_blocks + 2);
-}
-
-// In-step consumer 1 (PARTIAL only): the sorted, de-duplicated pack blocks that the candidate streams ctx->ftiles load, packed whole
-// by the list form of pack_kernel in front of the exact scan.  A block shared by two records is packed whole like any other.
-static int pack_candidate_blocks(kgma_ctx *ctx, kgma_genome *g, int64_t nk)
-{
-    if (g->inter_state != KGMA_INTER_PARTIAL) return KGMA_OK;
-    const int64_t PBW = pack_block_words();
-    const int64_t total_blocks = (g->total_words + PBW - 1) / PBW;
-    std::vector<int32_t> &bl = ctx->blist;
-    bl.clear();
-    for (const TileDesc &td : ctx->ftiles) {                           // (sorted by record and window: so are the blocks)
-        const int64_t w0 = td.word_base, w1 = std::min<int64_t>(g->total_words, w0 + stream_words_loaded(td.n_valid, nk)) - 1;
-        if (w0 < 0 || w0 >= g->total_words) return fail(ctx, KGMA_E_HIP, "internal: candidate stream outside the genome");
-        for (int64_t b = w0 / PBW; b <= w1 / PBW && b < total_blocks; b++)
-            if (bl.empty() || bl.back() < (int32_t)b) bl.push_back((int32_t)b);
-    }
-    if (!std::is_sorted(bl.begin(), bl.end())) { std::sort(bl.begin(), bl.end()); bl.erase(std::unique(bl.begin(), bl.end()), bl.end()); }
-    if (bl.empty()) return KGMA_OK;
-    const int rc = dev_reserve(ctx, ctx->d_blist, ctx->blist_cap, (int64_t)bl.size());
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_blist, bl.data(), bl.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream,
-                             ctx->d_blist, (int64_t)bl.size()));
-    g->inter_demand_blocks += (int64_t)bl.size();
-    if (getenv("KGMA_GEOM_DEBUG")) fprintf(stderr, "sparse pack: %zu of %lld blocks packed for %zu candidate streams\n", bl.size(), (long long)total_blocks, ctx->ftiles.size());
-    return KGMA_OK;
-}
-
-// In-step consumer 2 (PARTIAL only): the block range of every record in `records`, with the range form of the pack, in front of
-// a chain launch or a download of a record's codes.  A chain's streams start at the record's first word and the last one ends
-// with the record's last k-mer: by stream_words_loaded it loads fewer than 8 words past the record's last word, inside the
-// CONTIG_PAD_WORDS that are taken here (past the last record: the tail padding).
-static int pack_record_blocks(kgma_ctx *ctx, kgma_genome *g, std::vector<int32_t> records)
-{
-    if (g->inter_state != KGMA_INTER_PARTIAL) return KGMA_OK;
-    (void)hipSetDevice(ctx->device);
-    const int64_t PBW = pack_block_words();
-    const int64_t total_blocks = (g->total_words + PBW - 1) / PBW;
-    std::sort(records.begin(), records.end());
-    records.erase(std::unique(records.begin(), records.end()), records.end());
-    int64_t done_to = 0;                                               // blocks below it are packed already (a block two records share)
-    for (const int32_t c : records) {
-        if (c < 0 || c >= g->n_contigs) return fail(ctx, KGMA_E_HIP, "internal: chained record outside the genome");
-        const ContigDesc &d = g->cd[(size_t)c];
-        const int64_t w1 = std::min<int64_t>(g->total_words, d.word_off + (d.len + 31) / 32 + CONTIG_PAD_WORDS) - 1;
-        const int64_t b0 = std::max<int64_t>(done_to, d.word_off / PBW), b1 = std::min<int64_t>(total_blocks, w1 / PBW + 1);
-        if (b1 <= b0) continue;
-        HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream,
-                                 b0, b1 - b0));
-        g->inter_demand_blocks += b1 - b0;
-        done_to = b1;
-    }
-    return KGMA_OK;
-}
-
-// The bit-plane copy of the genome (read by the bit-sliced kernel, its window pass and the 16-bit stream kernel) is
-// made the first time a scan needs it and kept up to date by every later pack; genomes that only the 8-bit stream
-// kernel scans never have one.
-static int ensure_planes(kgma_ctx *ctx, kgma_genome *g)
-{
-    if (g->d_planes) return KGMA_OK;
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&g->d_planes), (size_t)g->total_words * 8));
-    g->device_bytes += g->total_words * 8;
-    if (g->n_contigs > 0)
-        HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream));
-    else
-        HIP_TRY(ctx, hipMemsetAsync(g->d_planes, 0, (size_t)g->total_words * 8, ctx->stream));
-    g->inter_state = KGMA_INTER_FULL;                                  // (a full pack: it writes the 2-bit copy beside the planes)
-    g->inter_demand_blocks = 0;
-    return KGMA_OK;
-}
-
-// sums: the step's pack with the prefilter's block sums of KFV 0 (pack_sums_kernel; the caller has checked that it applies and
-// that g->d_bsum exists).  sparse (with sums, a genome without planes): the sums-only form -- the 2-bit copy is left PARTIAL and the
-// step packs the blocks it reads (pack_candidate_blocks, pack_record_blocks).  Every other pack is a full one: FULL
-static int genome_repack(kgma_ctx *ctx, kgma_genome *g, bool sums, bool sparse = false)
-{
-    sparse = sparse && sums && g->n_contigs > 0 && g->d_planes == nullptr;
-    g->inter_demand_blocks = 0;
-    (void)hipSetDevice(ctx->device);
-    // first_bad (smallest position of a residue outside A/C/G/T/N per record) is a function of the residue
-    // text: re-encoding unchanged text finds the same minima, so the reset and the download of the table
-    // are only queued when the text changed (new genome, kgma_genome_poke)
-    const bool dirty = g->text_dirty;
-    if (dirty) HIP_TRY(ctx, hipMemsetAsync(g->d_first_bad, 0xFF, std::max<size_t>(1, (size_t)g->n_contigs) * 8, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->evp0, ctx->stream));
-    if (g->n_contigs > 0 && sums) {
-        PackSumsArgs a;
-        memset(&a, 0, sizeof a);
-        a.ascii = g->d_ascii; a.planes = g->d_planes; a.inter = g->d_inter; a.bsum = g->d_bsum;
-        a.cd = g->d_cd; a.total_words = g->total_words; a.block_contig = g->d_block_contig; a.first_bad = g->d_first_bad;
-        a.S = ctx->d_Stab; a.n_contigs = (int32_t)g->n_contigs;
-        const int bw = pack_block_words();
-        a.block_shift = (bw & (bw - 1)) == 0 ? __builtin_ctz((unsigned)bw) : -1;
-        HIP_TRY(ctx, launch_pack_sums(a, ctx->k, ctx->kfv[0].Smax, ctx->n_cus, sparse, ctx->stream));
-        g->bsum_fresh = true;
-        g->bsum_k = ctx->k;
-    } else if (g->n_contigs > 0)
-        HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)g->n_contigs, g->total_words, g->d_block_contig, g->d_first_bad, ctx->stream));
-    else
+// The transient device memory and events of one ingest (DeviceHold) and the staging pair it fills.  Destroyed (reset()) where the
+// ingest is done with them, in front of the first pack, and on every other path out: waits for the staging copies, frees the
+// transients and, fasta: gives the context's FASTA scratch back where it has grown beyond 2 GiB.
+struct IngestScratch : DeviceHold {
+    kgma_ctx *ctx; StagePipe &pipe; bool fasta;
+    IngestScratch(kgma_ctx *ctx_, StagePipe &pipe_, bool fasta_) : ctx(ctx_), pipe(pipe_), fasta(fasta_) {}
+    ~IngestScratch()
     {
-        if (g->d_planes) HIP_TRY(ctx, hipMemsetAsync(g->d_planes, 0, (size_t)g->total_words * 8, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(g->d_inter, 0, (size_t)g->total_words * 8, ctx->stream));
+        pipe.drain();
+        if (!fasta || ctx->genome.ingest_cap <= ((int64_t)2 << 30)) return;   // (large scratch is not kept)
+        (void)hipFree(ctx->genome.d_ingest); ctx->genome.d_ingest = nullptr; ctx->device_bytes -= ctx->genome.ingest_cap; ctx->genome.ingest_cap = 0;
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->evp1, ctx->stream));
-    g->inter_state = sparse ? KGMA_INTER_PARTIAL : KGMA_INTER_FULL;
-    if (sparse) {
-        // KGMA_SPARSE_POISON=1 (tests): every word of the copy is allocated memory, so a read of a block that nobody packed shows up
-        // as a wrong result, never as a fault
-        const char *pz = getenv("KGMA_SPARSE_POISON");
-        if (pz && atoi(pz) != 0) HIP_TRY(ctx, hipMemsetAsync(g->d_inter, 0x5A, (size_t)g->total_words * 8, ctx->stream));
+};
+
+struct IngestLap {   // KGMA_INGEST_DEBUG: the host's time from one point of an ingest to the next
+    const char *tag;
+    const bool on = getenv("KGMA_INGEST_DEBUG") != nullptr;
+    double tq = now_ms();
+    void operator()(const char *what) { const double t = now_ms(); if (on) fprintf(stderr, "  %s: %-28s %8.3f ms\n", tag, what, t - tq); tq = t; }
+};
+
+// One staged upload for every ingest: device bytes dst[0, bytes) are the segments `segs` (kgma_stage_fill.h) with `gap` between
+// them, moved window by window through the staging pair -- a few threads fill one buffer (at least min_per_thread bytes each) while
+// the DMA engine drains the other.  hook (optional) runs on the thread that has just filled bytes [b0, e0) of the window that
+// starts at device byte w0: the bytes are in its cache.  0, UPLOAD_UNREAD (a read failed), or the hipError_t of the copy that failed.
+constexpr int UPLOAD_UNREAD = -1;
+using RangeHook = std::function<void(int t, const uint8_t *stage, int64_t w0, int64_t b0, int64_t e0)>;
+int staged_upload(StagePipe &pipe, uint8_t *dst, int64_t bytes, const std::vector<StageSeg> &segs, uint8_t gap, int64_t min_per_thread,
+                  const RangeHook &hook = nullptr)
+{
+    const int64_t stage_cap = (int64_t)pipe.cap;
+    std::atomic<int> unread{0};
+    for (int64_t w0 = 0; w0 < bytes; w0 += stage_cap) {
+        uint8_t *stage = pipe.acquire();               // (the other buffer may still be on its way to the device)
+        const int64_t len = std::min<int64_t>(stage_cap, bytes - w0);
+        parallel_ranges(len, ingest_threads(), min_per_thread, [&](int t, int64_t b0, int64_t e0) {
+            if (!stage_fill(stage, w0, b0, e0, segs.data(), segs.size(), gap)) unread.store(1);
+            if (hook) hook(t, stage, w0, b0, e0);
+        });
+        if (unread.load()) return UPLOAD_UNREAD;
+        const hipError_t e = pipe.submit(dst + w0, (size_t)len);
+        if (e != hipSuccess) return (int)e;
     }
-    if (dirty) HIP_TRY(ctx, hipMemcpyAsync(g->first_bad, g->d_first_bad, std::max<size_t>(1, (size_t)g->n_contigs) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    g->text_dirty = false;
-    g->pack_pending = true;     // completed by the next scan's single synchronisation (or genome_sync)
-    return KGMA_OK;
+    return 0;
 }
+
+}  // namespace
+
+extern "C" {
 
 int kgma_genome_repack(kgma_ctx *ctx, kgma_genome *g)
 {
     if (!ctx || !g) return KGMA_E_ARG;
-    return genome_repack(ctx, g, false);
+    return genome_repack(ctx, g, nullptr);
 }
 
 int kgma_genome_from_host(kgma_ctx *ctx, const uint8_t *const *contig_ascii, const int64_t *contig_len,
@@ -1752,66 +1871,24 @@ int kgma_genome_from_host(kgma_ctx *ctx, const uint8_t *const *contig_ascii, con
 {
     if (!ctx) return KGMA_E_ARG;
     if (!out || n_contigs < 0 || (n_contigs > 0 && (!contig_ascii || !contig_len)))
-        return fail(ctx, KGMA_E_ARG, "null argument");
-    if (n_contigs > 0x7FFFFFF0ll) return fail(ctx, KGMA_E_UNSUPPORTED, "too many records");
+        return ctx_fail(ctx, KGMA_E_ARG, "null argument");
+    if (n_contigs > 0x7FFFFFF0ll) return ctx_fail(ctx, KGMA_E_UNSUPPORTED, "too many records");
     *out = nullptr;
     NumaBind numa(ctx);                                              // (staging buffers and copying threads on the GPU's NUMA node)
-    kgma_genome *g = new (std::nothrow) kgma_genome();
-    if (!g) return fail(ctx, KGMA_E_NOMEM, "out of host memory");
-    int rc = genome_layout(ctx, g, contig_len, n_contigs);
-    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
-    // stream the records through two pinned staging buffers (fill one while the other is copied)
-    StagePipe *pp = ctx_pipe(ctx);
-    if (!pp) {
-        kgma_genome_free(ctx, g);
-        return fail(ctx, KGMA_E_NOMEM, "cannot allocate the pinned staging buffers");
-    }
-    StagePipe &pipe = *pp;
-    const size_t stage_cap = pipe.cap;
-    uint8_t *stage = pipe.acquire();
-    int64_t win_base = 0;   // device offset of stage[0]
-    size_t fill = 0;        // bytes of the window in use
-    auto flush = [&]() -> hipError_t {
-        if (fill == 0) return hipSuccess;
-        hipError_t e = pipe.submit(g->d_ascii + win_base, fill);
-        win_base += (int64_t)fill;
-        fill = 0;
-        stage = pipe.acquire();
-        return e;
-    };
-    hipError_t he = hipSuccess;
-    const int n_thr = ingest_threads();                 // the staging copy runs on a few host threads
-    for (int64_t c = 0; c < n_contigs && he == hipSuccess; c++) {
-        const ContigDesc &d = g->cd[(size_t)c];
-        const int64_t region = ((d.len + 31) & ~31ll) + 32;
-        int64_t done = 0;   // bytes of this record's region already staged
-        while (done < region && he == hipSuccess) {
-            if (fill == stage_cap) { he = flush(); if (he != hipSuccess) break; }
-            const size_t room = stage_cap - fill;
-            const size_t take = (size_t)std::min<int64_t>((int64_t)room, region - done);
-            // part of [done, done+take) that is residue data
-            const int64_t data_hi = std::min<int64_t>(d.len, done + (int64_t)take);
-            size_t ndata = data_hi > done ? (size_t)(data_hi - done) : 0;
-            if (ndata) {
-                uint8_t *dst = stage + fill;
-                const uint8_t *src = contig_ascii[c] + done;
-                parallel_ranges((int64_t)ndata, n_thr, (int64_t)2 << 20, [=](int, int64_t b0, int64_t e0) { memcpy(dst + b0, src + b0, (size_t)(e0 - b0)); });
-            }
-            if (take > ndata) memset(stage + fill + ndata, 0, take - ndata);
-            fill += take;
-            done += (int64_t)take;
-        }
-    }
-    if (he == hipSuccess) he = flush();
-    pipe.drain();
-    if (he != hipSuccess) {
-        kgma_genome_free(ctx, g);
-        return fail(ctx, KGMA_E_HIP, "host-to-device copy failed: %s", hipGetErrorString(he));
-    }
-    rc = kgma_genome_repack(ctx, g);
-    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
-    *out = g;
-    return KGMA_OK;
+    GenomeOwner g;
+    const int rc = genome_begin(ctx, contig_len, n_contigs, g);
+    if (rc != KGMA_OK) return rc;
+    // stream the records through two pinned staging buffers (fill one while the other is copied): every record's residues at
+    // its place in the text, zeros in the padding behind them (the text's 64 tail bytes are not written)
+    StagePipe *pipe = ctx_pipe(ctx);
+    if (!pipe) return ctx_fail(ctx, KGMA_E_NOMEM, "cannot allocate the pinned staging buffers");
+    std::vector<StageSeg> segs;
+    for (int64_t c = 0; c < n_contigs; c++)
+        if (g->cd[(size_t)c].len > 0) segs.push_back(StageSeg{g->cd[(size_t)c].ascii_off, g->cd[(size_t)c].len, contig_ascii[c], -1, 0});
+    const int up = staged_upload(*pipe, g->d_ascii, g->ascii_bytes - 64, segs, 0, (int64_t)2 << 20);
+    pipe->drain();
+    if (up) return fail(ctx, KGMA_E_HIP, "host-to-device copy failed: %s", hipGetErrorString((hipError_t)up));
+    return genome_finish(ctx, g, out);
 }
 
 int kgma_genome_synthetic(kgma_ctx *ctx, const int64_t *contig_len, int64_t n_contigs, uint64_t seed,
@@ -1819,31 +1896,22 @@ int kgma_genome_synthetic(kgma_ctx *ctx, const int64_t *contig_len, int64_t n_co
                           const int64_t *plant_pos, int64_t n_plants, kgma_genome **out)
 {
     if (!ctx) return KGMA_E_ARG;
-    if (!out || !contig_len || n_contigs < 1) return fail(ctx, KGMA_E_ARG, "null argument");
-    if (n_plants > 0 && (!plant || !plant_contig || !plant_pos || plant_len < 1)) return fail(ctx, KGMA_E_ARG, "bad plant arguments");
+    if (!out || !contig_len || n_contigs < 1) return ctx_fail(ctx, KGMA_E_ARG, "null argument");
+    if (n_plants > 0 && (!plant || !plant_contig || !plant_pos || plant_len < 1)) return ctx_fail(ctx, KGMA_E_ARG, "bad plant arguments");
     *out = nullptr;
-    kgma_genome *g = new (std::nothrow) kgma_genome();
-    if (!g) return fail(ctx, KGMA_E_NOMEM, "out of host memory");
-    int rc = genome_layout(ctx, g, contig_len, n_contigs);
-    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
+    GenomeOwner g;
+    const int rc = genome_begin(ctx, contig_len, n_contigs, g);
+    if (rc != KGMA_OK) return rc;
     hipError_t he = launch_synth(g->d_ascii, g->d_cd, (int)n_contigs, g->total_words, seed, ctx->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
     for (int64_t i = 0; i < n_plants && he == hipSuccess; i++) {
         const int64_t c = plant_contig[i], pos = plant_pos[i];
-        if (c < 0 || c >= n_contigs || pos < 1 || pos + plant_len - 1 > contig_len[c]) {
-            kgma_genome_free(ctx, g);
+        if (c < 0 || c >= n_contigs || pos < 1 || pos + plant_len - 1 > contig_len[c])
             return fail(ctx, KGMA_E_ARG, "plant %lld does not fit its record", (long long)i);
-        }
         he = hipMemcpy(g->d_ascii + g->cd[(size_t)c].ascii_off + (pos - 1), plant, (size_t)plant_len, hipMemcpyHostToDevice);
     }
-    if (he != hipSuccess) {
-        kgma_genome_free(ctx, g);
-        return fail(ctx, KGMA_E_HIP, "synthetic genome generation failed: %s", hipGetErrorString(he));
-    }
-    rc = kgma_genome_repack(ctx, g);
-    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
-    *out = g;
-    return KGMA_OK;
+    if (he != hipSuccess) return fail(ctx, KGMA_E_HIP, "synthetic genome generation failed: %s", hipGetErrorString(he));
+    return genome_finish(ctx, g, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1852,37 +1920,32 @@ int kgma_genome_synthetic(kgma_ctx *ctx, const int64_t *contig_len, int64_t n_co
 int kgma_genome_revcomp_into(kgma_ctx *ctx, const kgma_genome *g, kgma_genome *rc)
 {
     if (!ctx) return KGMA_E_ARG;
-    if (!g || !rc) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: null argument");
-    if (g == rc) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: source and destination are the same genome");
+    if (!g || !rc) return ctx_fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: null argument");
+    if (g == rc) return ctx_fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: source and destination are the same genome");
     const int64_t nc = g->n_contigs;
     bool same = rc->n_contigs == nc && rc->ascii_bytes == g->ascii_bytes;
     for (int64_t c = 0; c < nc && same; c++) same = rc->cd[(size_t)c].len == g->cd[(size_t)c].len;
-    if (!same) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: the genomes' record lengths differ");
+    if (!same) return ctx_fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp_into: the genomes' record lengths differ");
     (void)hipSetDevice(ctx->device);
     {
         const int irc = ensure_inter(ctx, rc);                         // (rc's text is about to change: its 2-bit copy is completed from the old one first)
         if (irc) return irc;
     }
-    // a record's slot in the text: its residues rounded up to 32 bytes + 32 (genome_layout); the kernel writes all of it
-    const int64_t per_tile = revcomp_tile_bytes();
-    std::vector<int64_t> prefix((size_t)nc + 1, 0);
-    for (int64_t c = 0; c < nc; c++) {
-        const int64_t slot = ((g->cd[(size_t)c].len + 31) & ~31ll) + 32;
-        prefix[(size_t)c + 1] = prefix[(size_t)c] + (slot + per_tile - 1) / per_tile;
-    }
+    // the kernel writes all of a record's slot in the text
+    const std::vector<int64_t> prefix = tile_prefix(nc, revcomp_tile_bytes(), true, [&](int64_t c) { return g->cd[(size_t)c].len; });
     const int64_t n_tiles = prefix[(size_t)nc];
     if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_genome_revcomp: %lld tiles exceed one launch", (long long)n_tiles);
-    if (!ctx->d_rcprefix || prefix != ctx->rcprefix) {
+    if (!ctx->genome.d_rcprefix || prefix != ctx->genome.rcprefix) {
         // (a launch of an earlier call may still be reading the table it was given)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->rcprefix.clear();
-        int rc_ = dev_reserve(ctx, ctx->d_rcprefix, ctx->rcprefix_cap, nc + 1);
+        ctx->genome.rcprefix.clear();
+        int rc_ = dev_reserve(ctx, ctx->genome.d_rcprefix, ctx->genome.rcprefix_cap, nc + 1);
         if (rc_) return rc_;
-        HIP_TRY(ctx, hipMemcpy(ctx->d_rcprefix, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        ctx->rcprefix = prefix;
+        HIP_TRY(ctx, hipMemcpy(ctx->genome.d_rcprefix, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        ctx->genome.rcprefix = prefix;
     }
     RevcompArgs a{};
-    a.src = g->d_ascii; a.dst = rc->d_ascii; a.cd = rc->d_cd; a.tile_prefix = ctx->d_rcprefix; a.n_contigs = (int32_t)nc;
+    a.src = g->d_ascii; a.dst = rc->d_ascii; a.cd = rc->d_cd; a.tile_prefix = ctx->genome.d_rcprefix; a.n_contigs = (int32_t)nc;
     HIP_TRY(ctx, launch_revcomp(a, n_tiles, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(rc->d_ascii + (rc->ascii_bytes - 64), 0, 64, ctx->stream));      // the text's 64 tail bytes
     rc->text_dirty = true;
@@ -1892,21 +1955,17 @@ int kgma_genome_revcomp_into(kgma_ctx *ctx, const kgma_genome *g, kgma_genome *r
 int kgma_genome_revcomp(kgma_ctx *ctx, const kgma_genome *src, kgma_genome **out)
 {
     if (!ctx) return KGMA_E_ARG;
-    if (!src || !out) return fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp: null argument");
+    if (!src || !out) return ctx_fail(ctx, KGMA_E_ARG, "kgma_genome_revcomp: null argument");
     *out = nullptr;
-    kgma_genome *g = new (std::nothrow) kgma_genome();
-    if (!g) return fail(ctx, KGMA_E_NOMEM, "out of host memory");
     std::vector<int64_t> lens((size_t)src->n_contigs);
     for (int64_t c = 0; c < src->n_contigs; c++) lens[(size_t)c] = src->cd[(size_t)c].len;
-    int rc = genome_layout(ctx, g, lens.data(), src->n_contigs);
-    if (rc == KGMA_OK) {
-        g->headers = src->headers;
-        rc = kgma_genome_revcomp_into(ctx, src, g);
-    }
-    if (rc == KGMA_OK) rc = kgma_genome_repack(ctx, g);
-    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
-    *out = g;
-    return KGMA_OK;
+    GenomeOwner g;
+    int rc = genome_begin(ctx, lens.data(), src->n_contigs, g);
+    if (rc != KGMA_OK) return rc;
+    g->headers = src->headers;
+    rc = kgma_genome_revcomp_into(ctx, src, g.get());
+    if (rc != KGMA_OK) return rc;
+    return genome_finish(ctx, g, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1919,18 +1978,11 @@ int kgma_genome_revcomp(kgma_ctx *ctx, const kgma_genome *src, kgma_genome **out
 static int genome_from_fasta_impl(kgma_ctx *ctx, const uint8_t *text, int64_t n, int fd, kgma_genome **out)
 {
     if (!ctx) return KGMA_E_ARG;
-    if (!out || n < 0 || (n > 0 && !text)) return fail(ctx, KGMA_E_ARG, "null argument");
+    if (!out || n < 0 || (n > 0 && !text)) return ctx_fail(ctx, KGMA_E_ARG, "null argument");
     *out = nullptr;
+    IngestLap lap{"ingest"};
     (void)hipSetDevice(ctx->device);
     NumaBind numa(ctx);                                              // (staging buffers and copying threads on the GPU's NUMA node)
-    const bool dbg = getenv("KGMA_INGEST_DEBUG") != nullptr;
-    double tq = now_ms();
-    auto lap = [&](const char *what) {
-        if (!dbg) return;
-        const double t = now_ms();
-        fprintf(stderr, "  ingest: %-28s %8.3f ms\n", what, t - tq);
-        tq = t;
-    };
     constexpr int64_t FB = 4096;
     // ---- upload the raw text through the staging pair, padded with '\n' to a block multiple; the threads that fill a
     //      staging buffer also look for the header lines in the stretch they have just copied (a '>' at the start of a
@@ -1941,115 +1993,72 @@ static int genome_from_fasta_impl(kgma_ctx *ctx, const uint8_t *text, int64_t n,
     const int n_thr = ingest_threads();
     const int64_t nb = (n + FB - 1) / FB;
     const int64_t n_pad = std::max<int64_t>(nb, 1) * FB;
-    uint8_t *d_raw = nullptr;
-    uint32_t *d_counts = nullptr;
     int64_t *d_base = nullptr, *d_rs = nullptr, *d_ranges = nullptr;
-    kgma_genome *g = nullptr;
-    int rc = KGMA_OK;
-    StagePipe *pp = ctx_pipe(ctx);
-    if (!pp) return fail(ctx, KGMA_E_NOMEM, "cannot allocate the pinned staging buffers");
-    StagePipe &pipe = *pp;
-    auto cleanup = [&]() {
-        pipe.drain();
-        if (d_base) (void)hipFree(d_base);
-        if (d_rs) (void)hipFree(d_rs);
-        if (d_ranges) (void)hipFree(d_ranges);
-        if (ctx->ingest_cap > ((int64_t)2 << 30)) {                  // (large scratch is not kept)
-            (void)hipFree(ctx->d_ingest); ctx->d_ingest = nullptr; ctx->device_bytes -= ctx->ingest_cap; ctx->ingest_cap = 0;
-        }
-    };
-#define FA_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e__ = (expr);                                                                  \
-        if (e__ != hipSuccess) {                                                                  \
-            rc = fail(ctx, KGMA_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__));           \
-            cleanup();                                                                            \
-            if (g) kgma_genome_free(ctx, g);                                                      \
-            return rc;                                                                            \
-        }                                                                                         \
-    } while (0)
-    rc = dev_reserve(ctx, ctx->d_ingest, ctx->ingest_cap, n_pad);
+    StagePipe *pipe = ctx_pipe(ctx);
+    if (!pipe) return ctx_fail(ctx, KGMA_E_NOMEM, "cannot allocate the pinned staging buffers");
+    int rc = dev_reserve(ctx, ctx->genome.d_ingest, ctx->genome.ingest_cap, n_pad);
     if (rc) return rc;
-    rc = dev_reserve(ctx, ctx->d_icounts, ctx->icounts_cap, std::max<int64_t>(nb, 1));
+    rc = dev_reserve(ctx, ctx->genome.d_icounts, ctx->genome.icounts_cap, std::max<int64_t>(nb, 1));
     if (rc) return rc;
-    d_raw = ctx->d_ingest;
-    d_counts = ctx->d_icounts;
+    uint8_t *d_raw = ctx->genome.d_ingest;
+    std::optional<IngestScratch> scratch;
+    scratch.emplace(ctx, *pipe, true);
     lap("scratch + staging");
     {
-        const int64_t stage_cap = (int64_t)pipe.cap;
-        std::vector<std::vector<Hdr>> found((size_t)n_thr);
-        std::atomic<int> read_failed{0};
+        // (file: pread into the staging buffer.  Measured against the alternatives on a 400 MB file in the page cache:
+        //  memcpy from the mapping with a fault per page 17.0 ms per ingest, pread 13.7, MADV_POPULATE_READ of the
+        //  stretch + memcpy 14.8 -- KGMA_INGEST_POPULATE=1 keeps the last one reachable)
+        const bool from_mapping = fd < 0 || getenv("KGMA_INGEST_POPULATE");
+        std::vector<StageSeg> segs;
+        if (n > 0) segs.push_back(StageSeg{0, n, from_mapping ? text : nullptr, fd, 0});
+        // header lines found by thread t in the window at device byte w0: found[w0 / window * n_thr + t], in text order
+        const int64_t window = (int64_t)pipe->cap;
+        std::vector<std::vector<Hdr>> found((size_t)((n_pad + window - 1) / window) * (size_t)n_thr);
+        const RangeHook search = [&](int t, const uint8_t *stage, int64_t off, int64_t b0, int64_t e0) {
+            std::vector<Hdr> &mine = found[(size_t)(off / window) * (size_t)n_thr + (size_t)t];
+            const uint8_t *p = stage + b0, *e = stage + e0;
+            while (p < e) {
+                const uint8_t *q = static_cast<const uint8_t *>(memchr(p, '>', (size_t)(e - p)));
+                if (!q) break;
+                const int64_t pos = off + (q - stage);                   // position in the text
+                if (pos == 0 || text[pos - 1] == '\n') {
+                    const uint8_t *nl = static_cast<const uint8_t *>(memchr(text + pos, '\n', (size_t)(n - pos)));
+                    const int64_t he = nl ? (nl - text) + 1 : n;
+                    mine.push_back(Hdr{pos, he});
+                    if (he >= off + e0) break;                            // (the line runs past this thread's stretch)
+                    p = stage + (he - off);
+                } else {
+                    p = q + 1;
+                }
+            }
+        };
+        const int up = staged_upload(*pipe, d_raw, n_pad, segs, '\n', (int64_t)2 << 20, search);
+        if (up == UPLOAD_UNREAD) return ctx_fail(ctx, KGMA_E_ARG, "cannot read the FASTA file");
+        if (up) return fail(ctx, KGMA_E_HIP, "pipe.submit(d_raw + off, (size_t)len) failed: %s", hipGetErrorString((hipError_t)up));
         int64_t hdr_done = 0;                              // text before this offset belongs to a header line already found
-        for (int64_t off = 0; off < n_pad; off += stage_cap) {
-            uint8_t *stage = pipe.acquire();               // (the other buffer may still be on its way to the device)
-            const int64_t len = std::min<int64_t>(stage_cap, n_pad - off);
-            const int64_t data = std::max<int64_t>(0, std::min<int64_t>(len, n - off));
-            for (std::vector<Hdr> &f : found) f.clear();
-            if (data)
-                parallel_ranges(data, n_thr, (int64_t)2 << 20, [&](int t, int64_t b0, int64_t e0) {
-                    // (file: pread into the staging buffer.  Measured against the alternatives on a 400 MB file in the page cache:
-                    //  memcpy from the mapping with a fault per page 17.0 ms per ingest, pread 13.7, MADV_POPULATE_READ of the
-                    //  stretch + memcpy 14.8 -- KGMA_INGEST_POPULATE=1 keeps the last one reachable)
-                    bool mapped_copy = fd < 0;
-#ifdef MADV_POPULATE_READ
-                    if (fd >= 0 && getenv("KGMA_INGEST_POPULATE")) {
-                        const uintptr_t a0 = reinterpret_cast<uintptr_t>(text + off + b0) & ~(uintptr_t)4095;
-                        const uintptr_t a1 = reinterpret_cast<uintptr_t>(text + off + e0);
-                        mapped_copy = madvise(reinterpret_cast<void *>(a0), (size_t)(a1 - a0), MADV_POPULATE_READ) == 0;
-                    }
-#endif
-                    if (mapped_copy) {
-                        memcpy(stage + b0, text + off + b0, (size_t)(e0 - b0));
-                    } else if (fd >= 0) {
-                        for (int64_t done = b0; done < e0;) {
-                            const ssize_t got = pread(fd, stage + done, (size_t)(e0 - done), (off_t)(off + done));
-                            if (got <= 0) { read_failed.store(1); memset(stage + done, '\n', (size_t)(e0 - done)); break; }
-                            done += got;
-                        }
-                    }
-                    const uint8_t *p = stage + b0, *e = stage + e0;
-                    while (p < e) {
-                        const uint8_t *q = static_cast<const uint8_t *>(memchr(p, '>', (size_t)(e - p)));
-                        if (!q) break;
-                        const int64_t pos = off + (q - stage);                   // position in the text
-                        if (pos == 0 || text[pos - 1] == '\n') {
-                            const uint8_t *nl = static_cast<const uint8_t *>(memchr(text + pos, '\n', (size_t)(n - pos)));
-                            const int64_t he = nl ? (nl - text) + 1 : n;
-                            found[(size_t)t].push_back(Hdr{pos, he});
-                            if (he >= off + e0) break;                            // (the line runs past this thread's stretch)
-                            p = stage + (he - off);
-                        } else {
-                            p = q + 1;
-                        }
-                    }
-                });
-            if (len > data) memset(stage + data, '\n', (size_t)(len - data));
-            if (read_failed.load()) { cleanup(); return fail(ctx, KGMA_E_ARG, "cannot read the FASTA file"); }
-            for (const std::vector<Hdr> &f : found)
-                for (const Hdr &h : f)
-                    if (h.begin >= hdr_done) { hdrs.push_back(h); hdr_done = h.end; }   // (a '>' inside a header line found earlier is text)
-            FA_TRY(pipe.submit(d_raw + off, (size_t)len));
-        }
+        for (const std::vector<Hdr> &f : found)
+            for (const Hdr &h : f)
+                if (h.begin >= hdr_done) { hdrs.push_back(h); hdr_done = h.end; }   // (a '>' inside a header line found earlier is text)
     }
     lap("staged upload + header search");
     const int64_t n_rec = (int64_t)hdrs.size();
-    if (n_rec > 0x7FFFFFF0ll) { cleanup(); return fail(ctx, KGMA_E_UNSUPPORTED, "too many records"); }
+    if (n_rec > 0x7FFFFFF0ll) return ctx_fail(ctx, KGMA_E_UNSUPPORTED, "too many records");
     {
         const int64_t lead = n_rec > 0 ? hdrs[0].begin : n;
         for (int64_t i = 0; i < lead; i++)
-            if (text[i] > 0x20) { cleanup(); return fail(ctx, KGMA_E_ARG, "FASTA text has sequence data before the first '>' header"); }
+            if (text[i] > 0x20) return ctx_fail(ctx, KGMA_E_ARG, "FASTA text has sequence data before the first '>' header");
     }
     if (n_rec > 0) {
         static_assert(sizeof(Hdr) == 16, "header ranges are uploaded as int64 pairs");
-        FA_TRY(hipMalloc(reinterpret_cast<void **>(&d_ranges), (size_t)n_rec * sizeof(Hdr)));
-        FA_TRY(hipMemcpyAsync(d_ranges, hdrs.data(), (size_t)n_rec * sizeof(Hdr), hipMemcpyHostToDevice, ctx->stream));
-        FA_TRY(launch_fasta_blank(d_raw, d_ranges, (int)n_rec, ctx->stream));
+        HIP_TRY(ctx, scratch->alloc(d_ranges, (size_t)n_rec * 2));
+        HIP_TRY(ctx, hipMemcpyAsync(d_ranges, hdrs.data(), (size_t)n_rec * sizeof(Hdr), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, launch_fasta_blank(d_raw, d_ranges, (int)n_rec, ctx->stream));
     }
     // ---- kernel 1: residues per block; host prefix sum -> block bases --------------------------
-    FA_TRY(launch_fasta_count(d_raw, n_pad, d_counts, ctx->stream));
+    HIP_TRY(ctx, launch_fasta_count(d_raw, n_pad, ctx->genome.d_icounts, ctx->stream));
     std::vector<uint32_t> counts((size_t)std::max<int64_t>(nb, 1), 0);
-    FA_TRY(hipMemcpyAsync(counts.data(), d_counts, (size_t)std::max<int64_t>(nb, 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    FA_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(counts.data(), ctx->genome.d_icounts, (size_t)std::max<int64_t>(nb, 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     lap("upload drained + count kernel");
     std::vector<int64_t> base((size_t)std::max<int64_t>(nb, 1) + 1, 0);
     for (int64_t b = 0; b < nb; b++) base[(size_t)b + 1] = base[(size_t)b] + counts[(size_t)b];
@@ -2080,10 +2089,9 @@ static int genome_from_fasta_impl(kgma_ctx *ctx, const uint8_t *text, int64_t n,
     for (int64_t c = 0; c < n_rec; c++) lens[(size_t)c] = rs[(size_t)c + 1] - rs[(size_t)c];
     lap("record table (host)");
     // ---- layout, kernel 2 (scatter), pack ---------------------------------------------------------
-    g = new (std::nothrow) kgma_genome();
-    if (!g) { cleanup(); return fail(ctx, KGMA_E_NOMEM, "out of host memory"); }
-    rc = genome_layout(ctx, g, lens.data(), n_rec);
-    if (rc != KGMA_OK) { cleanup(); kgma_genome_free(ctx, g); return rc; }
+    GenomeOwner g;
+    rc = genome_begin(ctx, lens.data(), n_rec, g);
+    if (rc != KGMA_OK) return rc;
     g->headers.resize((size_t)n_rec);
     for (int64_t c = 0; c < n_rec; c++) {
         int64_t b = hdrs[(size_t)c].begin + 1, e = hdrs[(size_t)c].end;
@@ -2091,23 +2099,20 @@ static int genome_from_fasta_impl(kgma_ctx *ctx, const uint8_t *text, int64_t n,
         g->headers[(size_t)c].assign(reinterpret_cast<const char *>(text + b), (size_t)(e - b));
     }
     if (n_rec > 0) {
-        FA_TRY(hipMalloc(reinterpret_cast<void **>(&d_base), base.size() * sizeof(int64_t)));
-        FA_TRY(hipMalloc(reinterpret_cast<void **>(&d_rs), rs.size() * sizeof(int64_t)));
-        FA_TRY(hipMemcpy(d_base, base.data(), base.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        FA_TRY(hipMemcpy(d_rs, rs.data(), rs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        FA_TRY(hipMemsetAsync(g->d_ascii, 0, (size_t)g->ascii_bytes, ctx->stream));
-        FA_TRY(launch_fasta_scatter(d_raw, n_pad, d_base, d_rs, g->d_cd, (int)n_rec, g->d_ascii, ctx->stream));
-        FA_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, scratch->alloc(d_base, base.size()));
+        HIP_TRY(ctx, scratch->alloc(d_rs, rs.size()));
+        HIP_TRY(ctx, hipMemcpy(d_base, base.data(), base.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_rs, rs.data(), rs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemsetAsync(g->d_ascii, 0, (size_t)g->ascii_bytes, ctx->stream));
+        HIP_TRY(ctx, launch_fasta_scatter(d_raw, n_pad, d_base, d_rs, g->d_cd, (int)n_rec, g->d_ascii, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-#undef FA_TRY
     lap("layout + scatter kernel");
-    cleanup();
+    scratch.reset();
     lap("free scratch");
-    rc = kgma_genome_repack(ctx, g);
+    rc = genome_finish(ctx, g, out);
     lap("pack launched");
-    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
-    *out = g;
-    return KGMA_OK;
+    return rc;
 }
 
 int kgma_genome_from_fasta(kgma_ctx *ctx, const uint8_t *text, int64_t n, kgma_genome **out)
@@ -2118,7 +2123,7 @@ int kgma_genome_from_fasta(kgma_ctx *ctx, const uint8_t *text, int64_t n, kgma_g
 int kgma_genome_from_fasta_file(kgma_ctx *ctx, const char *path, kgma_genome **out)
 {
     if (!ctx) return KGMA_E_ARG;
-    if (!path || !out) return fail(ctx, KGMA_E_ARG, "null argument");
+    if (!path || !out) return ctx_fail(ctx, KGMA_E_ARG, "null argument");
     *out = nullptr;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return fail(ctx, KGMA_E_ARG, "cannot open %s", path);
@@ -2141,7 +2146,7 @@ int kgma_genome_from_fasta_file(kgma_ctx *ctx, const char *path, kgma_genome **o
 int kgma_genome_from_2bit_file(kgma_ctx *ctx, const char *path, uint32_t flags, kgma_genome **out)
 {
     if (!ctx) return KGMA_E_ARG;
-    if (!path || !out) return fail(ctx, KGMA_E_ARG, "null argument");
+    if (!path || !out) return ctx_fail(ctx, KGMA_E_ARG, "null argument");
     *out = nullptr;
     if (flags & ~(uint32_t)KGMA_2BIT_NOMASK) return fail(ctx, KGMA_E_ARG, "kgma_genome_from_2bit_file: unknown flags 0x%x", flags);
     const int fd = open(path, O_RDONLY);
@@ -2150,14 +2155,7 @@ int kgma_genome_from_2bit_file(kgma_ctx *ctx, const char *path, uint32_t flags, 
     struct stat sb;
     if (fstat(fd, &sb) != 0 || sb.st_size < 0) return fail(ctx, KGMA_E_ARG, "cannot stat %s", path);
     if (!S_ISREG(sb.st_mode)) return fail(ctx, KGMA_E_ARG, "%s is not a regular file", path);
-    const bool dbg = getenv("KGMA_INGEST_DEBUG") != nullptr;
-    double tq = now_ms();
-    auto lap = [&](const char *what) {
-        if (!dbg) return;
-        const double t = now_ms();
-        fprintf(stderr, "  2bit ingest: %-28s %8.3f ms\n", what, t - tq);
-        tq = t;
-    };
+    IngestLap lap{"2bit ingest"};
     // ---- the host reads and validates header, index and block tables: nothing below indexes with a value it has not checked ----
     TwoBitFile f;
     {
@@ -2170,16 +2168,18 @@ int kgma_genome_from_2bit_file(kgma_ctx *ctx, const char *path, uint32_t flags, 
     const bool masks = !(flags & KGMA_2BIT_NOMASK);
     const int64_t n_nblk = (int64_t)f.n_blocks.size(), n_mblk = masks ? (int64_t)f.m_blocks.size() : 0;
     static_assert(sizeof(TwoBitBlock) == sizeof(TwobitBlock) && sizeof(TwobitBlock) == 8, "the parser's blocks are uploaded as the kernel's");
+    std::vector<int64_t> lens((size_t)std::max<int64_t>(nc, 1), 0);
+    for (int64_t c = 0; c < nc; c++) lens[(size_t)c] = f.recs[(size_t)c].dna_size;
     // one table of int64 for the kernel: [tile_prefix: nc + 1][packed_off: nc][n_prefix: nc + 1][m_prefix: nc + 1]
-    std::vector<int64_t> lens((size_t)std::max<int64_t>(nc, 1), 0), tab((size_t)(4 * nc + 3), 0);
-    int64_t *tile_prefix = tab.data(), *packed_off = tile_prefix + (nc + 1), *n_prefix = packed_off + nc, *m_prefix = n_prefix + (nc + 1);
-    const int64_t per_tile = twobit_tile_bytes();
+    std::vector<int64_t> tab((size_t)(4 * nc + 3), 0);
+    int64_t *tile_prefix_ = tab.data(), *packed_off = tile_prefix_ + (nc + 1), *n_prefix = packed_off + nc, *m_prefix = n_prefix + (nc + 1);
+    {
+        const std::vector<int64_t> prefix = tile_prefix(nc, twobit_tile_bytes(), true, [&](int64_t c) { return lens[(size_t)c]; });   // (the kernel writes all of a record's slot)
+        std::copy(prefix.begin(), prefix.end(), tile_prefix_);
+    }
     int64_t packed_total = 0;
     for (int64_t c = 0; c < nc; c++) {
         const TwoBitRecord &R = f.recs[(size_t)c];
-        lens[(size_t)c] = R.dna_size;
-        const int64_t slot = ((R.dna_size + 31) & ~31ll) + 32;         // (genome_layout; the kernel writes all of it)
-        tile_prefix[c + 1] = tile_prefix[c] + (slot + per_tile - 1) / per_tile;
         packed_off[c] = packed_total;                                   // 16-byte aligned, whatever the byte it starts at in the file
         packed_total += (R.packed_bytes + 15) & ~15ll;
         n_prefix[c] = R.n_begin;
@@ -2187,93 +2187,43 @@ int kgma_genome_from_2bit_file(kgma_ctx *ctx, const char *path, uint32_t flags, 
     }
     n_prefix[nc] = n_nblk;
     m_prefix[nc] = n_nblk + n_mblk;
-    const int64_t n_tiles = tile_prefix[nc];
+    const int64_t n_tiles = tile_prefix_[nc];
     if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_genome_from_2bit_file: %lld tiles exceed one launch", (long long)n_tiles);
     (void)hipSetDevice(ctx->device);
     NumaBind numa(ctx);                                              // (staging buffers and reading threads on the GPU's NUMA node)
-    StagePipe *pp = ctx_pipe(ctx);
-    if (!pp) return fail(ctx, KGMA_E_NOMEM, "cannot allocate the pinned staging buffers");
-    StagePipe &pipe = *pp;
-    kgma_genome *g = new (std::nothrow) kgma_genome();
-    if (!g) return fail(ctx, KGMA_E_NOMEM, "out of host memory");
+    StagePipe *pipe = ctx_pipe(ctx);
+    if (!pipe) return ctx_fail(ctx, KGMA_E_NOMEM, "cannot allocate the pinned staging buffers");
+    GenomeOwner g;
+    int rc = genome_begin(ctx, lens.data(), nc, g);
+    if (rc != KGMA_OK) return rc;
+    g->headers.resize((size_t)nc);
+    for (int64_t c = 0; c < nc; c++) g->headers[(size_t)c] = f.recs[(size_t)c].name;
+    lap("layout (genome allocations)");
     // ONE transient device buffer, freed once the kernel is done: [table][N blocks][mask blocks][packed bytes, every record at a
     // 16-byte aligned offset].  It is filled as one byte stream through the pinned staging pair: the host's tables are copied,
     // the packed bytes are pread straight from the file, the gaps are zeros.
-    struct Seg { int64_t dev_off, len; const uint8_t *host; int64_t file_off; };   // host != nullptr: memory, else the file
-    std::vector<Seg> segs;
+    std::vector<StageSeg> segs;
     const int64_t tab_bytes = (int64_t)(tab.size() * sizeof(int64_t));
     const int64_t blk_off = (tab_bytes + 15) & ~15ll;
     const int64_t packed_base = (blk_off + (n_nblk + n_mblk) * (int64_t)sizeof(TwobitBlock) + 15) & ~15ll;
     const int64_t buf_bytes = std::max<int64_t>(packed_base + packed_total, 16);
-    segs.push_back(Seg{0, tab_bytes, reinterpret_cast<const uint8_t *>(tab.data()), 0});
-    if (n_nblk > 0) segs.push_back(Seg{blk_off, n_nblk * 8, reinterpret_cast<const uint8_t *>(f.n_blocks.data()), 0});
-    if (n_mblk > 0) segs.push_back(Seg{blk_off + n_nblk * 8, n_mblk * 8, reinterpret_cast<const uint8_t *>(f.m_blocks.data()), 0});
+    segs.push_back(StageSeg{0, tab_bytes, reinterpret_cast<const uint8_t *>(tab.data()), -1, 0});
+    if (n_nblk > 0) segs.push_back(StageSeg{blk_off, n_nblk * 8, reinterpret_cast<const uint8_t *>(f.n_blocks.data()), -1, 0});
+    if (n_mblk > 0) segs.push_back(StageSeg{blk_off + n_nblk * 8, n_mblk * 8, reinterpret_cast<const uint8_t *>(f.m_blocks.data()), -1, 0});
     for (int64_t c = 0; c < nc; c++)
         if (f.recs[(size_t)c].packed_bytes > 0)
-            segs.push_back(Seg{packed_base + packed_off[c], f.recs[(size_t)c].packed_bytes, nullptr, f.recs[(size_t)c].packed_off});
+            segs.push_back(StageSeg{packed_base + packed_off[c], f.recs[(size_t)c].packed_bytes, nullptr, fd, f.recs[(size_t)c].packed_off});
+    std::optional<IngestScratch> scratch;
+    scratch.emplace(ctx, *pipe, false);
     uint8_t *d_buf = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() {
-        pipe.drain();
-        if (d_buf) (void)hipFree(d_buf);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    int rc = genome_layout(ctx, g, lens.data(), nc);
-    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
-    g->headers.resize((size_t)nc);
-    for (int64_t c = 0; c < nc; c++) g->headers[(size_t)c] = f.recs[(size_t)c].name;
-    lap("layout (genome allocations)");
-#define TB_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e__ = (expr);                                                                  \
-        if (e__ != hipSuccess) {                                                                  \
-            rc = fail(ctx, KGMA_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__));           \
-            cleanup();                                                                            \
-            kgma_genome_free(ctx, g);                                                             \
-            return rc;                                                                            \
-        }                                                                                         \
-    } while (0)
-    TB_TRY(hipMalloc(reinterpret_cast<void **>(&d_buf), (size_t)buf_bytes));
-    TB_TRY(hipEventCreate(&e0));
-    TB_TRY(hipEventCreate(&e1));
+    hipEvent_t &e0 = scratch->ev[0], &e1 = scratch->ev[1];
+    HIP_TRY(ctx, scratch->alloc(d_buf, (size_t)buf_bytes));
+    HIP_TRY(ctx, hipEventCreate(&e0));
+    HIP_TRY(ctx, hipEventCreate(&e1));
     lap("transient buffer");
-    {
-        const int64_t stage_cap = (int64_t)pipe.cap;
-        const int n_thr = ingest_threads();
-        std::atomic<int> read_failed{0};
-        // bytes [b0, e0) of the staging buffer that holds device bytes w0 ... of the transient buffer
-        auto fill = [&](uint8_t *stage, int64_t w0, int64_t b0, int64_t e0_) {
-            int64_t at = w0 + b0;
-            const int64_t end = w0 + e0_;
-            size_t si = (size_t)(std::upper_bound(segs.begin(), segs.end(), at, [](int64_t x, const Seg &S) { return x < S.dev_off + S.len; }) - segs.begin());
-            while (at < end) {
-                if (si == segs.size() || segs[si].dev_off >= end) { memset(stage + (at - w0), 0, (size_t)(end - at)); break; }
-                const Seg &S = segs[si];
-                if (S.dev_off > at) { memset(stage + (at - w0), 0, (size_t)(S.dev_off - at)); at = S.dev_off; }
-                const int64_t n = std::min<int64_t>(end, S.dev_off + S.len) - at, rel = at - S.dev_off;
-                uint8_t *dst = stage + (at - w0);
-                if (S.host) {
-                    memcpy(dst, S.host + rel, (size_t)n);
-                } else {
-                    for (int64_t done = 0; done < n;) {
-                        const ssize_t got = pread(fd, dst + done, (size_t)(n - done), (off_t)(S.file_off + rel + done));
-                        if (got <= 0) { read_failed.store(1); memset(dst + done, 0, (size_t)(n - done)); break; }
-                        done += got;
-                    }
-                }
-                at += n;
-                if (at == S.dev_off + S.len) si++;
-            }
-        };
-        for (int64_t w0 = 0; w0 < buf_bytes; w0 += stage_cap) {
-            uint8_t *stage = pipe.acquire();               // (the other buffer may still be on its way to the device)
-            const int64_t len = std::min<int64_t>(stage_cap, buf_bytes - w0);
-            parallel_ranges(len, n_thr, (int64_t)1 << 20, [&](int, int64_t b0, int64_t e0_) { fill(stage, w0, b0, e0_); });
-            if (read_failed.load()) { cleanup(); kgma_genome_free(ctx, g); return fail(ctx, KGMA_E_ARG, "cannot read the packed bases of %s", path); }
-            TB_TRY(pipe.submit(d_buf + w0, (size_t)len));
-        }
-    }
+    const int up = staged_upload(*pipe, d_buf, buf_bytes, segs, 0, (int64_t)1 << 20);
+    if (up == UPLOAD_UNREAD) return fail(ctx, KGMA_E_ARG, "cannot read the packed bases of %s", path);
+    if (up) return fail(ctx, KGMA_E_HIP, "pipe.submit(d_buf + w0, (size_t)len) failed: %s", hipGetErrorString((hipError_t)up));
     lap("staged upload queued");
     // ---- kernel, tail ----
     const int64_t *d_tab = reinterpret_cast<const int64_t *>(d_buf);
@@ -2283,33 +2233,31 @@ int kgma_genome_from_2bit_file(kgma_ctx *ctx, const char *path, uint32_t flags, 
     a.packed = d_packed; a.dst = g->d_ascii; a.cd = g->d_cd;
     a.tile_prefix = d_tab; a.packed_off = d_tab + (nc + 1); a.n_prefix = d_tab + (2 * nc + 1); a.m_prefix = d_tab + (3 * nc + 2);
     a.blk = d_blk; a.n_contigs = (int32_t)nc;
-    TB_TRY(hipEventRecord(e0, ctx->stream));
-    TB_TRY(launch_twobit_unpack(a, n_tiles, ctx->stream));
-    TB_TRY(hipEventRecord(e1, ctx->stream));
-    TB_TRY(hipMemsetAsync(g->d_ascii + (g->ascii_bytes - 64), 0, 64, ctx->stream));              // the text's 64 tail bytes
-    TB_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
+    HIP_TRY(ctx, launch_twobit_unpack(a, n_tiles, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(g->d_ascii + (g->ascii_bytes - 64), 0, 64, ctx->stream));              // the text's 64 tail bytes
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     {
         float ms = 0;
-        TB_TRY(hipEventElapsedTime(&ms, e0, e1));
-        ctx->twobit_ms = n_tiles > 0 ? ms : 0.0;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, e0, e1));
+        ctx->genome.twobit_ms = n_tiles > 0 ? ms : 0.0;
     }
-#undef TB_TRY
     lap("upload drained + kernel");
-    cleanup();
+    scratch.reset();
     lap("free transients");
-    rc = kgma_genome_repack(ctx, g);
+    rc = genome_finish(ctx, g, out);
     lap("pack launched");
-    if (rc != KGMA_OK) { kgma_genome_free(ctx, g); return rc; }
-    *out = g;
-    return KGMA_OK;
+    return rc;
 }
 
 int kgma_get_2bit_unpack_ms(kgma_ctx *ctx, double *ms)
 {
     if (!ctx) return KGMA_E_ARG;
-    if (!ms) return fail(ctx, KGMA_E_ARG, "null argument");
-    if (ctx->twobit_ms < 0) return fail(ctx, KGMA_E_STATE, "kgma_get_2bit_unpack_ms: no kgma_genome_from_2bit_file has completed on this context");
-    *ms = ctx->twobit_ms;
+    if (!ms) return ctx_fail(ctx, KGMA_E_ARG, "null argument");
+    const double last = ctx->genome.twobit_ms;
+    if (last < 0) return ctx_fail(ctx, KGMA_E_STATE, "kgma_get_2bit_unpack_ms: no kgma_genome_from_2bit_file has completed on this context");
+    *ms = last;
     return KGMA_OK;
 }
 
@@ -2325,12 +2273,61 @@ int kgma_genome_fetch(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int64
 {
     if (!ctx || !g) return KGMA_E_ARG;
     if (contig < 0 || contig >= g->n_contigs || pos < 1 || len < 0 || pos + len - 1 > g->cd[(size_t)contig].len || (!outp && len > 0))
-        return fail(ctx, KGMA_E_ARG, "kgma_genome_fetch: range outside the record");
+        return ctx_fail(ctx, KGMA_E_ARG, "kgma_genome_fetch: range outside the record");
     if (len == 0) return KGMA_OK;
     (void)hipSetDevice(ctx->device);
     HIP_TRY(ctx, hipMemcpy(outp, g->d_ascii + g->cd[(size_t)contig].ascii_off + (pos - 1), (size_t)len, hipMemcpyDeviceToHost));
     return KGMA_OK;
 }
+
+int kgma_genome_poke(kgma_ctx *ctx, kgma_genome *g, int64_t contig, int64_t pos, int64_t len, const uint8_t *bytes)
+{
+    if (!ctx || !g) return KGMA_E_ARG;
+    if (contig < 0 || contig >= g->n_contigs || pos < 1 || len < 0 || pos + len - 1 > g->cd[(size_t)contig].len || (!bytes && len > 0))
+        return ctx_fail(ctx, KGMA_E_ARG, "kgma_genome_poke: range outside the record");
+    if (len == 0) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    if (g->inter_state != KGMA_INTER_FULL) {
+        // the 2-bit copy stays the text as of the last pack: completed, to the end, before the text changes (the copy below does
+        // not wait for the context's stream)
+        const int irc = ensure_inter(ctx, g);
+        if (irc) return irc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    HIP_TRY(ctx, hipMemcpy(g->d_ascii + g->cd[(size_t)contig].ascii_off + (pos - 1), bytes, (size_t)len, hipMemcpyHostToDevice));
+    g->text_dirty = true;
+    return KGMA_OK;
+}
+
+int kgma_genome_inter_state(const kgma_genome *g, int32_t *state, int64_t *demand_blocks)
+{
+    if (!g) return KGMA_E_ARG;
+    if (state) *state = g->inter_state;
+    if (demand_blocks) *demand_blocks = g->inter_demand_blocks;
+    return KGMA_OK;
+}
+
+int64_t kgma_genome_num_contigs(const kgma_genome *g) { return g ? g->n_contigs : 0; }
+int64_t kgma_genome_contig_len(const kgma_genome *g, int64_t c)
+{
+    return (g && c >= 0 && c < g->n_contigs) ? g->cd[(size_t)c].len : -1;
+}
+int64_t kgma_genome_total_bases(const kgma_genome *g) { return g ? g->total_bases : 0; }
+
+void kgma_genome_free(kgma_ctx *ctx, kgma_genome *g)
+{
+    if (!g) return;
+    if (ctx) (void)hipSetDevice(ctx->device);
+    for (void *p : {(void *)g->d_ascii, (void *)g->d_planes, (void *)g->d_inter, (void *)g->d_cd, (void *)g->d_first_bad, (void *)g->d_block_contig, (void *)g->d_bsum})
+        if (p) (void)hipFree(p);
+    if (g->first_bad) (void)hipHostFree(g->first_bad);
+    if (ctx && ctx->tk_uid == g->uid) ctx->tk_uid = 0;
+    delete g;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int kgma_genome_fetch_batch(kgma_ctx *ctx, const kgma_genome *g, int64_t n, const int64_t *contig, const int64_t *pos,
                             const int64_t *len, uint8_t *outp, int64_t out_cap)
@@ -2373,56 +2370,6 @@ int kgma_genome_fetch_batch(kgma_ctx *ctx, const kgma_genome *g, int64_t n, cons
     HIP_TRY(ctx, sync_spin(ctx->stream));
     memcpy(outp, ctx->h_gath + desc_bytes, (size_t)total);
     return KGMA_OK;
-}
-
-int kgma_genome_poke(kgma_ctx *ctx, kgma_genome *g, int64_t contig, int64_t pos, int64_t len, const uint8_t *bytes)
-{
-    if (!ctx || !g) return KGMA_E_ARG;
-    if (contig < 0 || contig >= g->n_contigs || pos < 1 || len < 0 || pos + len - 1 > g->cd[(size_t)contig].len || (!bytes && len > 0))
-        return fail(ctx, KGMA_E_ARG, "kgma_genome_poke: range outside the record");
-    if (len == 0) return KGMA_OK;
-    (void)hipSetDevice(ctx->device);
-    if (g->inter_state != KGMA_INTER_FULL) {
-        // the 2-bit copy stays the text as of the last pack: completed, to the end, before the text changes (the copy below does
-        // not wait for the context's stream)
-        const int irc = ensure_inter(ctx, g);
-        if (irc) return irc;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    HIP_TRY(ctx, hipMemcpy(g->d_ascii + g->cd[(size_t)contig].ascii_off + (pos - 1), bytes, (size_t)len, hipMemcpyHostToDevice));
-    g->text_dirty = true;
-    return KGMA_OK;
-}
-
-int kgma_genome_inter_state(const kgma_genome *g, int32_t *state, int64_t *demand_blocks)
-{
-    if (!g) return KGMA_E_ARG;
-    if (state) *state = g->inter_state;
-    if (demand_blocks) *demand_blocks = g->inter_demand_blocks;
-    return KGMA_OK;
-}
-
-int64_t kgma_genome_num_contigs(const kgma_genome *g) { return g ? g->n_contigs : 0; }
-int64_t kgma_genome_contig_len(const kgma_genome *g, int64_t c)
-{
-    return (g && c >= 0 && c < g->n_contigs) ? g->cd[(size_t)c].len : -1;
-}
-int64_t kgma_genome_total_bases(const kgma_genome *g) { return g ? g->total_bases : 0; }
-
-void kgma_genome_free(kgma_ctx *ctx, kgma_genome *g)
-{
-    if (!g) return;
-    if (ctx) (void)hipSetDevice(ctx->device);
-    if (g->d_ascii) (void)hipFree(g->d_ascii);
-    if (g->d_planes) (void)hipFree(g->d_planes);
-    if (g->d_inter) (void)hipFree(g->d_inter);
-    if (g->d_cd) (void)hipFree(g->d_cd);
-    if (g->d_first_bad) (void)hipFree(g->d_first_bad);
-    if (g->d_block_contig) (void)hipFree(g->d_block_contig);
-    if (g->d_bsum) (void)hipFree(g->d_bsum);
-    if (g->first_bad) (void)hipHostFree(g->first_bad);
-    if (ctx && ctx->tk_uid == g->uid) ctx->tk_uid = 0;
-    delete g;
 }
 
 }  // extern "C"
@@ -2671,8 +2618,7 @@ static int launch_overlapped(kgma_ctx *ctx, kgma_genome *g, const ScanArgs &a0, 
         const int64_t b1 = c_of[(size_t)gi + 1] >= nc ? total_blocks : (g->cd[(size_t)c_of[(size_t)gi + 1]].word_off + PBW - 1) / PBW;
         hipStream_t ps = gi == 0 ? ctx->stream : ctx->ov_pack;
         HIP_TRY(ctx, hipEventRecord(ctx->ov_p0[gi], ps));
-        HIP_TRY(ctx, launch_pack(g->d_ascii, g->d_planes, g->d_inter, g->d_cd, (int)nc, g->total_words, g->d_block_contig, g->d_first_bad, ps, b0,
-                                 std::max<int64_t>(0, b1 - b0)));
+        HIP_TRY(ctx, pack_blocks(ctx, g, b0, std::max<int64_t>(0, b1 - b0), ps));
         HIP_TRY(ctx, hipEventRecord(ctx->ov_p1[gi], ps));
     }
     for (int gi = 0; gi < G; gi++) {
@@ -2951,7 +2897,7 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
     int rc = dev_reserve(ctx, ctx->d_ftiles, ctx->ftiles_cap, (int64_t)ctx->ftiles.size());
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ftiles, ctx->ftiles.data(), ctx->ftiles.size() * sizeof(TileDesc), hipMemcpyHostToDevice, ctx->stream));
-    rc = pack_candidate_blocks(ctx, g, nk);                             // (a sparse step: the blocks these streams load, in front of the exact scan)
+    rc = pack_candidate_blocks(ctx, g, ctx->ftiles, nk);                             // (a sparse step: the blocks these streams load, in front of the exact scan)
     if (rc) return rc;
     *filtered = true;
     return KGMA_OK;
@@ -3095,7 +3041,8 @@ int plan_deferred_pack(kgma_ctx *ctx, kgma_genome *g, ScanPlan &p)
     // ... and, on a genome without planes, leaves the 2-bit copy to the blocks the step reads (KGMA_SPARSE_PACK=0: never)
     const char *sp = getenv("KGMA_SPARSE_PACK");
     const bool sparse = sums && g->d_planes == nullptr && !(sp && atoi(sp) == 0);
-    return genome_repack(ctx, g, sums, sparse);
+    const PackSums with_sums{ctx->d_Stab, ctx->k, ctx->kfv[0].Smax, ctx->n_cus};
+    return genome_repack(ctx, g, sums ? &with_sums : nullptr, sparse);
 }
 
 // Launches that keep different numbers of streams resident (one KFV: 32 per CU; four: 22): all launches share one
@@ -3623,7 +3570,7 @@ void note_pack_time(kgma_ctx *ctx, kgma_genome *g)
         // (an overlapped step: the sums of the groups' kernel times -- the pack launches of all but the first group ran on
         //  a few CUs beside the scan, so their times are long and mostly hidden)
         for (int gi = 0; gi < ctx->ov_groups; gi++) { float t = 0; (void)hipEventElapsedTime(&t, ctx->ov_p0[gi], ctx->ov_p1[gi]); pms += t; }
-    } else (void)hipEventElapsedTime(&pms, ctx->evp0, ctx->evp1);
+    } else (void)hipEventElapsedTime(&pms, ctx->genome.evp0, ctx->genome.evp1);
     ctx->stats.pack_ms = pms;
     g->pack_pending = false;
 }
@@ -6082,9 +6029,7 @@ static int exact_launch(kgma_ctx *ctx, const kgma_genome *g, int kind, const std
                         unsigned long long *bad_out, int *n_launches)
 {
     const int64_t nc = g->n_contigs;
-    const int64_t per_tile = exact_tile_starts(kind == 2);
-    std::vector<int64_t> prefix((size_t)nc + 1, 0);
-    for (int64_t c = 0; c < nc; c++) prefix[(size_t)c + 1] = prefix[(size_t)c] + (g->cd[(size_t)c].len + per_tile - 1) / per_tile;
+    const std::vector<int64_t> prefix = tile_prefix(nc, exact_tile_starts(kind == 2), false, [&](int64_t c) { return g->cd[(size_t)c].len; });
     const int64_t n_tiles = prefix[(size_t)nc];
     if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_exact_match: %lld tiles exceed one launch", (long long)n_tiles);
     int rc;
@@ -6156,16 +6101,7 @@ int kgma_exact_match(kgma_ctx *ctx, const kgma_genome *gc, const uint8_t *querie
         else { P.len = 0; q_2bit.push_back(P); }       // len 0: not a 2-bit query
     }
     (void)hipSetDevice(ctx->device);
-    // what the pack kernel knows about the residues (first_bad) and the 2-bit copy must be current: a pack that is deferred, or never
-    // queued since the text changed, runs now
-    if (g->repack_deferred || g->text_dirty) {
-        g->repack_deferred = false;
-        const int prc = kgma_genome_repack(ctx, g);
-        if (prc) return prc;
-    }
-    int rc = ensure_inter(ctx, g);
-    if (rc) return rc;
-    rc = genome_sync(ctx, g);
+    int rc = genome_ready(ctx, g, false);   // (first_bad and the 2-bit copy are current)
     if (rc) return rc;
     bool clean = true;                       // no residue outside A/C/G/T/N anywhere: nothing to check, and the 2-bit copy is faithful up to N
     for (int64_t c = 0; c < g->n_contigs; c++) clean = clean && g->first_bad[(size_t)c] == NO_BAD;
@@ -6565,16 +6501,8 @@ int kgma_motif_match(kgma_ctx *ctx, const kgma_genome *gc, const uint8_t *motifs
         descs.push_back(M);
     }
     (void)hipSetDevice(ctx->device);
-    // what the pack kernel knows about the residues (first_bad) and the plane copy must be current: a pack that is deferred, or never
-    // queued since the text changed, runs now
-    if (g->repack_deferred || g->text_dirty) {
-        g->repack_deferred = false;
-        const int prc = kgma_genome_repack(ctx, g);
-        if (prc) return prc;
-    }
-    int rc = ensure_planes(ctx, g);
+    int rc = genome_ready(ctx, g, true);   // (first_bad and the plane copy are current)
     if (rc) return rc;
-    if ((rc = genome_sync(ctx, g))) return rc;
     ctx->stats.bases_scanned = g->total_bases;
     ctx->stats.scan_ms = 0;
     ctx->stats.n_launches = 0;
@@ -6582,9 +6510,8 @@ int kgma_motif_match(kgma_ctx *ctx, const kgma_genome *gc, const uint8_t *motifs
         if (g->first_bad[(size_t)c] != NO_BAD) {
             return fail(ctx, KGMA_E_BADBASE, "record %lld: residue %llu is not one of A/C/G/T/N", (long long)c, g->first_bad[(size_t)c]);   // (first_bad is 1-based)
         }
-    const int64_t nc = g->n_contigs, per_tile = motif_tile_starts();
-    std::vector<int64_t> prefix((size_t)nc + 1, 0);
-    for (int64_t c = 0; c < nc; c++) prefix[(size_t)c + 1] = prefix[(size_t)c] + (g->cd[(size_t)c].len + per_tile - 1) / per_tile;
+    const int64_t nc = g->n_contigs;
+    const std::vector<int64_t> prefix = tile_prefix(nc, motif_tile_starts(), false, [&](int64_t c) { return g->cd[(size_t)c].len; });
     const int64_t n_tiles = prefix[(size_t)nc];
     if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_motif_match: %lld tiles exceed one launch", (long long)n_tiles);
     std::vector<kgma_motif_hit> found;
