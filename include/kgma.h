@@ -667,6 +667,55 @@ int kgma_motif_match(kgma_ctx *ctx, const kgma_genome *g, const uint8_t *motifs,
                      int32_t n_motifs, const int32_t *max_mismatch /* n_motifs */);
 int kgma_get_motif_matches(kgma_ctx *ctx, kgma_motif_hit *out, int64_t cap, int64_t *n);
 
+/* ---- approxMatch: semi-global edit-distance search on a resident genome (kernels: kgma_approx.hip) -----------------------------
+ * Query i is queries[offsets[i] .. offsets[i+1]): 1 ... 64 symbols of ACGTRYSWKMBDHVN in either case.  A genome residue MATCHES a
+ * symbol by kgma_motif_match's rule: case folded, its set must be a subset of the symbol's set -- a base A/C/G/T matches a symbol
+ * that contains it, a genome N matches only a query N.
+ * For a record t[1..L] and a query q[1..m], score(j) = min over 1 <= s <= j+1 of ed(q, t[s..j]): unit costs (substitution,
+ * insertion, deletion 1 each), the empty substring allowed -- Sellers' semi-global dynamic programme, the query global, the start
+ * in the text free.  Nothing spans two records.  Every end j with score(j) <= max_edits[i] is a MATCHING END.  Each carries a
+ * start: the largest s with ed(q, t[s..j]) == score(j), the shortest substring that attains the score; the covered range is
+ * start : j (start = j + 1 cannot occur under the limits below).  A RUN is a maximal set of consecutive matching ends of one
+ * (query, record).  best_only != 0 reports per run the end with the smallest score, on a tie the smallest end; best_only == 0
+ * reports every matching end.
+ * 0 <= max_edits[i] <= 15, and it must be smaller than the number of informative (non-N) symbols of query i -- otherwise every
+ * position would match.  The minus strand is served by passing the reverse-complemented query: it is searched on the same genome,
+ * start : end are forward coordinates and every canonical choice (shortest substring, smallest end of a run) is made on the
+ * forward text.
+ * All queries are served by ONE launch of the search kernel (Myers' bit vectors over the residue text, a lane per `tile` end
+ * positions, restarted m + max_edits columns before them) and one of the start kernel (the anchored recurrence backwards from each
+ * reported end); the search is repeated once when the ends outgrow the device buffer (KGMA_E_NOMEM, context still usable, if the
+ * larger buffer cannot be had; KGMA_E_OVERFLOW if it overflows again).  The bit vectors are one 32-bit word when no query of the
+ * batch is longer than 32 symbols, else two (the measuring switch KGMA_APPROX_WORDS=2 asks for two words in every case).
+ * KGMA_E_ARG: an empty query or one of more than 64 symbols, a symbol outside the 15 codes, a max_edits out of range;
+ * kgma_last_error names query and position.  KGMA_E_BADBASE: a genome residue outside A/C/G/T/N, in any record; kgma_last_error
+ * names the first such record and position.
+ * The call needs no references and leaves the KFVs, the hits, dips and distances of the last scan and the matches of the last
+ * kgma_exact_match / kgma_motif_match as they are; of kgma_stats it sets bases_scanned, scan_ms (hipEvents around the launches)
+ * and n_launches.  kgma_get_approx_matches returns the hits of the last call sorted by (query, contig, end), with the two-call
+ * pattern of kgma_get_hits; after a call that failed, for whatever reason, it returns none. */
+typedef struct {
+    int32_t query;       /* 0-based index of the query                                         */
+    int32_t contig;      /* 0-based index of the record                                        */
+    int64_t start, end;  /* 1-based, inclusive: the covered range                               */
+    int32_t edits;       /* score(end), <= max_edits of the query                              */
+    int32_t reserved;
+} kgma_approx_hit;
+typedef struct {
+    int32_t tile;        /* end positions a lane of the search kernel owns                     */
+    int32_t wg_bases;    /* end positions a workgroup owns                                     */
+    int32_t words;       /* 32-bit words of the bit vectors of the form that ran               */
+    int32_t n_launches;  /* kernel launches of the call (search, a repeated search, starts)    */
+    int64_t n_ends;      /* matching ends before the run reduction                             */
+    int64_t n_hits;      /* reported hits                                                      */
+    double search_ms;    /* hipEvents around the search launch(es)                             */
+    double starts_ms;    /* ... around the start kernel                                        */
+} kgma_approx_stats;
+int kgma_approx_match(kgma_ctx *ctx, const kgma_genome *g, const uint8_t *queries, const int64_t *offsets /* n_queries + 1 */,
+                      int32_t n_queries, const int32_t *max_edits /* n_queries */, int32_t best_only);
+int kgma_get_approx_matches(kgma_ctx *ctx, kgma_approx_hit *out, int64_t cap, int64_t *n);
+int kgma_get_approx_stats(kgma_ctx *ctx, kgma_approx_stats *out);
+
 /* Threshold calibration: the working form of src/DistanceTesting.jl on the device (kernels: kgma_calib.hip).  Both calls need
  * the references of kgma_set_refs (KGMA_E_STATE before it, or after kgma_set_strobe_ref), serve 1 <= k <= 10 (references at
  * k >= 11 are kept sparse: KGMA_E_UNSUPPORTED) and leave the references, the thresholds and the results of the last scan,

@@ -40,6 +40,7 @@
 #include "kgma_stage_fill.h"
 #include "kgma_twobit.h"
 #include "kgma_landscape.h"
+#include "kgma_approx.h"
 
 namespace kgma {
 hipError_t launch_scan(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
@@ -463,6 +464,7 @@ struct kgma_ctx {
     MotifHit *d_mout = nullptr; int64_t mout_cap = 0;
     unsigned long long *d_mctl = nullptr; int64_t mctl_cap = 0;
     std::vector<kgma_motif_hit> motif_hits;
+    ApproxState approx;                      // edit-distance search (kgma_approx_match; kgma_approx.cpp)
     // calibration (kgma_window_dists / kgma_mutation_dists; kgma_calib.hip): device buffers kept between calls.  d_cbtab is the
     // k >= 8 kernels' counter table, zeroed when allocated and left all-zero by every launch
     int64_t *d_cboff = nullptr; int64_t cboff_cap = 0;
@@ -852,6 +854,7 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_minfo) (void)hipFree(ctx->d_minfo);
     if (ctx->d_mprefix) (void)hipFree(ctx->d_mprefix);
     if (ctx->d_mout) (void)hipFree(ctx->d_mout);
+    if (ctx->approx.d_out) (void)hipFree(ctx->approx.d_out);
     if (ctx->d_mctl) (void)hipFree(ctx->d_mctl);
     for (void *q : {(void *)ctx->d_cboff, (void *)ctx->d_cbD, (void *)ctx->d_cbdist, (void *)ctx->d_cbtab, (void *)ctx->d_cbtext,
                     (void *)ctx->d_cbP, (void *)ctx->d_cbbad})
@@ -1857,6 +1860,27 @@ int staged_upload(StagePipe &pipe, uint8_t *dst, int64_t bytes, const std::vecto
 }
 
 }  // namespace
+
+// kgma_approx.h: the view kgma_approx.cpp has of a context and a genome
+namespace kgma {
+ApproxState *ctx_approx(kgma_ctx *ctx) { return &ctx->approx; }
+int64_t *ctx_device_bytes(kgma_ctx *ctx) { return &ctx->device_bytes; }
+kgma_stats *ctx_stats(kgma_ctx *ctx) { return &ctx->stats; }
+int genome_searchable(kgma_ctx *ctx, const kgma_genome *gc)
+{
+    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping is updated
+    (void)hipSetDevice(ctx->device);
+    const int rc = genome_ready(ctx, g, false);        // (first_bad is current)
+    if (rc) return rc;
+    ctx->stats.bases_scanned = g->total_bases;
+    ctx->stats.scan_ms = 0;
+    ctx->stats.n_launches = 0;
+    for (int64_t c = 0; c < g->n_contigs; c++)
+        if (g->first_bad[(size_t)c] != NO_BAD)
+            return fail(ctx, KGMA_E_BADBASE, "record %lld: residue %llu is not one of A/C/G/T/N", (long long)c, g->first_bad[(size_t)c]);   // (first_bad is 1-based)
+    return KGMA_OK;
+}
+}  // namespace kgma
 
 extern "C" {
 

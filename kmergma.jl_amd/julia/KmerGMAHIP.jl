@@ -561,6 +561,66 @@ end
 motifMatch(motif, genome::Union{String, DeviceGenome}; max_mismatch::Integer = 0, ctx::Context = default_context()) =
     motifMatch([motif], genome; max_mismatch = max_mismatch, ctx = ctx)[1]
 
+struct KgmaApproxHit      # kgma_approx_hit: 0-based query and contig, the 1-based inclusive range start:end
+    query::Int32
+    contig::Int32
+    start::Int64
+    stop::Int64
+    edits::Int32
+    reserved::Int32
+end
+
+struct KgmaApproxStats    # kgma_approx_stats
+    tile::Int32
+    wg_bases::Int32
+    words::Int32
+    n_launches::Int32
+    n_ends::Int64
+    n_hits::Int64
+    search_ms::Float64
+    starts_ms::Float64
+end
+
+function approx_stats(ctx::Context)
+    s = Ref{KgmaApproxStats}()
+    check(ctx, ccall((:kgma_get_approx_stats, libkgma), Cint, (Ptr{Cvoid}, Ref{KgmaApproxStats}), ctx.h, s))
+    return s[]
+end
+
+"""
+    approxMatch(queries, genome; max_edits = 1, all_ends = false)   -- `genome`: a FASTA path or an open DeviceGenome
+IUPAC queries (1 ... 64 symbols) within `max_edits` (one number, or one per query) substitutions, inserted and deleted bases of a
+substring of a record, all in one pass over the genome (kgma_approx_match): per query the vector of (record identifier, range,
+edits) -- per run of consecutive matching ends the best one, or every matching end with `all_ends`; the range is the shortest
+substring ending there that attains the edits.  Symbols match as in motifMatch.  For the minus strand pass the reverse
+complement of the query: its hits are in forward coordinates.
+"""
+function approxMatch(queries::Vector, genome::Union{String, DeviceGenome}; max_edits = 1, all_ends::Bool = false,
+                     ctx::Context = default_context())
+    g = genome isa String ? genome_from_fasta(ctx, genome) : genome
+    try
+        qs = String[query_text(q) for q in queries]
+        text = Vector{UInt8}(join(qs))
+        offsets = Int64[0; cumsum(Int64[ncodeunits(q) for q in qs])]
+        es = max_edits isa Integer ? fill(Int32(max_edits), length(qs)) : Int32.(max_edits)
+        check(ctx, ccall((:kgma_approx_match, libkgma), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int64}, Int32, Ptr{Int32}, Int32),
+                         ctx.h, g.h, text, offsets, length(qs), es, all_ends ? 0 : 1))
+        n = Ref{Int64}(0)
+        check(ctx, ccall((:kgma_get_approx_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaApproxHit}, Int64, Ref{Int64}), ctx.h, C_NULL, 0, n))
+        hits = Vector{KgmaApproxHit}(undef, n[])
+        check(ctx, ccall((:kgma_get_approx_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaApproxHit}, Int64, Ref{Int64}), ctx.h, hits, n[], n))
+        out = [Tuple{String, UnitRange{Int64}, Int}[] for _ in qs]
+        for h in hits
+            push!(out[h.query + 1], (identifier(g, h.contig), h.start:h.stop, Int(h.edits)))
+        end
+        return out
+    finally
+        genome isa String && free!(g)
+    end
+end
+approxMatch(query, genome::Union{String, DeviceGenome}; max_edits::Integer = 1, all_ends::Bool = false, ctx::Context = default_context()) =
+    approxMatch([query], genome; max_edits = max_edits, all_ends = all_ends, ctx = ctx)[1]
+
 # ---- threshold calibration (the working form of src/DistanceTesting.jl): kgma_window_dists, kgma_mutation_dists -------------
 
 """
@@ -794,7 +854,7 @@ function dist_sweep(ctx::Context, thresholds::Vector{Float64}; kfv::Integer = 1)
     return below, dips
 end
 
-export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, HumanRSSV, HumanRSSD, Context
+export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, approxMatch, HumanRSSV, HumanRSSD, Context
 export dist_layout, dist_bins, dist_sweep
 export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists, assignGenes, assign_ranges
 export kmer_dist_matrix, kmer_dist_matrix_ranges, nearest_refs, assignGenes_screened

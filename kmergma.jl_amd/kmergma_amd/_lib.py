@@ -36,6 +36,7 @@ EXPORTS = [
     "kgma_chain_export", "kgma_chain_export_copy", "kgma_kfv_scale", "kgma_kfv_is_float",
     "kgma_set_strobe_ref", "kgma_strobe_scan", "kgma_exact_match", "kgma_get_matches",
     "kgma_motif_match", "kgma_get_motif_matches",
+    "kgma_approx_match", "kgma_get_approx_matches", "kgma_get_approx_stats",
     "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
     "kgma_get_block_sums", "kgma_genome_from_2bit_file", "kgma_get_2bit_unpack_ms", "kgma_twobit_inspect",
     "kgma_window_dists", "kgma_mutation_dists", "kgma_strobe_window_dists", "kgma_strobe_mutation_dists",
@@ -81,6 +82,16 @@ class KgmaMatch(C.Structure):
 class KgmaMotifHit(C.Structure):
     _fields_ = [("motif", C.c_int32), ("contig", C.c_int32), ("start", C.c_int64), ("mismatches", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class KgmaApproxHit(C.Structure):
+    _fields_ = [("query", C.c_int32), ("contig", C.c_int32), ("start", C.c_int64), ("end", C.c_int64), ("edits", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class KgmaApproxStats(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("wg_bases", C.c_int32), ("words", C.c_int32), ("n_launches", C.c_int32),
+                ("n_ends", C.c_int64), ("n_hits", C.c_int64), ("search_ms", C.c_double), ("starts_ms", C.c_double)]
 
 
 class KgmaTwobitInfo(C.Structure):
@@ -129,6 +140,8 @@ DIP_DTYPE = np.dtype([("contig", "<i4"), ("kfv", "<i4"), ("start", "<i8"), ("end
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("contig", "<i4"), ("start", "<i8")])
 
 MOTIF_HIT_DTYPE = np.dtype([("motif", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("mismatches", "<i4"), ("reserved", "<i4")])
+
+APPROX_HIT_DTYPE = np.dtype([("query", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("end", "<i8"), ("edits", "<i4"), ("reserved", "<i4")])
 
 ASSIGNMENT_DTYPE = np.dtype([("ref", "<i4"), ("score", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"),
                              ("q_lo", "<i4"), ("q_hi", "<i4")])   # kgma_assignment
@@ -186,6 +199,9 @@ def load():
     L.kgma_get_matches.argtypes = [vp, P(KgmaMatch), i64, P(i64)]
     L.kgma_motif_match.argtypes = [vp, vp, C.c_char_p, P(i64), i32, P(i32)]
     L.kgma_get_motif_matches.argtypes = [vp, P(KgmaMotifHit), i64, P(i64)]
+    L.kgma_approx_match.argtypes = [vp, vp, C.c_char_p, P(i64), i32, P(i32), i32]
+    L.kgma_get_approx_matches.argtypes = [vp, P(KgmaApproxHit), i64, P(i64)]
+    L.kgma_get_approx_stats.argtypes = [vp, P(KgmaApproxStats)]
     L.kgma_genome_from_host.argtypes = [vp, P(C.c_char_p), P(i64), i64, P(vp)]
     L.kgma_genome_from_fasta.argtypes = [vp, vp, i64, P(vp)]
     L.kgma_genome_from_fasta_file.argtypes = [vp, C.c_char_p, P(vp)]
@@ -573,6 +589,35 @@ class Context:
         arr = np.zeros(max(n.value, 1), dtype=MOTIF_HIT_DTYPE)
         self._check(load().kgma_get_motif_matches(self._h, arr.ctypes.data_as(C.POINTER(KgmaMotifHit)), n.value, C.byref(n)))
         return arr[:n.value]
+
+    def approx_match(self, genome: Genome, queries: Sequence[bytes], max_edits: Sequence[int], best_only: bool = True) -> None:
+        """kgma_approx_match: every end in every record of `genome` at which query i (1 ... 64 IUPAC symbols, either case) lies
+        within max_edits[i] edits (substitutions, insertions, deletions) of a substring ending there; best_only keeps the best
+        end of every run of consecutive ends.  One pass over the genome for the whole batch.  Needs no references.
+        approx_matches() afterwards."""
+        text, off = self._concat(queries)
+        ed = np.ascontiguousarray(np.asarray(list(max_edits), dtype=np.int32).ravel())
+        if ed.size != off.size - 1:
+            raise ValueError("need one max_edits per query")
+        ed = np.concatenate([ed, np.zeros(1, np.int32)])          # (never empty: a pointer to take)
+        self._check(load().kgma_approx_match(self._h, genome._h, text, _np_ptr(off, C.c_int64), off.size - 1, _np_ptr(ed, C.c_int32),
+                                             1 if best_only else 0))
+
+    def approx_matches(self) -> np.ndarray:
+        """Hits of the last approx_match as a structured array (APPROX_HIT_DTYPE: 0-based query and contig, the 1-based
+        inclusive range start:end, edits), sorted by (query, contig, end)."""
+        n = C.c_int64(0)
+        self._check(load().kgma_get_approx_matches(self._h, None, 0, C.byref(n)))
+        arr = np.zeros(max(n.value, 1), dtype=APPROX_HIT_DTYPE)
+        self._check(load().kgma_get_approx_matches(self._h, arr.ctypes.data_as(C.POINTER(KgmaApproxHit)), n.value, C.byref(n)))
+        return arr[:n.value]
+
+    def approx_stats(self) -> dict:
+        """kgma_get_approx_stats: the search kernel's geometry and form, ends, hits, launches and device times of the last
+        approx_match."""
+        s = KgmaApproxStats()
+        self._check(load().kgma_get_approx_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in KgmaApproxStats._fields_}
 
     def set_thresholds(self, thr: Sequence[float]) -> None:
         th = np.asarray(list(thr)[:self.m], dtype=np.float64)

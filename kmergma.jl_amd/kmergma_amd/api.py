@@ -639,8 +639,8 @@ def RSS_dist(RSS1, RSS2=HumanRSSV) -> int:
     return sum(1 for i in range(len(a)) if a[i] != b[i])
 
 
-def _motif_bytes(motif, max_mismatch, which: str = "motif") -> bytes:
-    """The checks of kgma_motif_match, made before any device call."""
+def _motif_bytes(motif, max_mismatch, which: str = "motif", limit: str = "max_mismatch") -> bytes:
+    """The checks of kgma_motif_match (and, with limit="max_edits", of kgma_approx_match), made before any device call."""
     if isinstance(motif, Record):
         m = bytes(motif.sequence)
     elif isinstance(motif, str):
@@ -656,15 +656,15 @@ def _motif_bytes(motif, max_mismatch, which: str = "motif") -> bytes:
             raise ValueError(f"{which}, symbol {i + 1} ({m[i:i + 1]!r}) is not an IUPAC nucleotide code")
     d = int(max_mismatch)
     if not 0 <= d <= MOTIF_MAX_MISMATCH:
-        raise ValueError(f"{which}: max_mismatch {d} (0 ... {MOTIF_MAX_MISMATCH})")
+        raise ValueError(f"{which}: {limit} {d} (0 ... {MOTIF_MAX_MISMATCH})")
     informative = sum(1 for ch in m.upper() if ch != ord("N"))
     if d >= informative:
-        raise ValueError(f"{which}: max_mismatch {d} is not smaller than its {informative} informative (non-N) positions: "
+        raise ValueError(f"{which}: {limit} {d} is not smaller than its {informative} informative (non-N) positions: "
                          "every start would match")
     return m
 
 
-def _motif_args(motifs, max_mismatch, strand):
+def _motif_args(motifs, max_mismatch, strand, which: str = "motif", limit: str = "max_mismatch"):
     _check_strand(strand)
     motifs = list(motifs)
     if isinstance(max_mismatch, (int, np.integer)):
@@ -672,8 +672,8 @@ def _motif_args(motifs, max_mismatch, strand):
     else:
         ds = [int(d) for d in max_mismatch]
         if len(ds) != len(motifs):
-            raise ValueError("need one max_mismatch per motif")
-    ms = [_motif_bytes(m, d, f"motif {i}") for i, (m, d) in enumerate(zip(motifs, ds))]
+            raise ValueError(f"need one {limit} per {which}")
+    ms = [_motif_bytes(m, d, f"{which} {i}", limit) for i, (m, d) in enumerate(zip(motifs, ds))]
     # the minus strand: the reverse-complemented motif on the SAME genome, in the same pass
     sent, tags = [], []
     for i, (m, d) in enumerate(zip(ms, ds)):
@@ -742,6 +742,71 @@ def findRSS(genome_or_path, rss=HumanRSSD, max_mismatch: int = 1, strand: str = 
     """Recombination signal sequences on a genome: motifMatch with the 23-nt-spacer RSS, one mismatch and both strands as the
     defaults.  (The reference's Align_RSS / is_RSS are not mirrored: DESIGN.md, section 8.)"""
     return motifMatch(rss, genome_or_path, max_mismatch=max_mismatch, strand=strand, ctx=ctx)
+
+
+# ---- edit-distance search (kgma_approx_match): what motifMatch cannot express -- a base inserted or deleted -------------------
+
+def _approx_run(ctx, g, qs, sent, tags, all_ends: bool) -> list:
+    """Per query the hits (record, lo, hi, strand, edits), sorted by (record, lo, strand)."""
+    ctx.approx_match(g, [q for q, _ in sent], [e for _, e in sent], best_only=not all_ends)
+    out = [[] for _ in qs]
+    for query, contig, start, end, edits, _ in ctx.approx_matches().tolist():
+        i, st = tags[query]
+        out[i].append((contig, start, end, st, edits))
+    for lst in out:
+        lst.sort(key=lambda t: (t[0], t[1], t[3], t[2]))        # ("+" sorts before "-"; all_ends: several ends may share a lo)
+    return out
+
+
+def approxMatch_batch(queries, genome_or_path, *, max_edits=1, strand: str = "+", all_ends: bool = False, ctx=None) -> list:
+    """Many queries in ONE pass over the genome (kgma_approx_match): per query the list of
+    (record_index, identifier, lo, hi, strand, edits) -- 0-based record, 1-based inclusive lo:hi in forward coordinates --
+    sorted by (record, lo, strand).  `max_edits`: one number for all queries or one per query.  Semantics: approxMatch.
+    `genome_or_path`: a FASTA or .2bit path, or a device genome that is already open (it stays open)."""
+    qs, sent, tags = _motif_args(queries, max_edits, strand, "query", "max_edits")
+    if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
+        raise TypeError("Invalid subject sequence type")
+    ctx = ctx or default_context()
+    g, src, owned = _open_subject(ctx, genome_or_path)
+    try:
+        res = _approx_run(ctx, g, qs, sent, tags, all_ends)
+        ids = {c: _identifier(src, c) for c in {t[0] for lst in res for t in lst}}
+    finally:
+        if owned:
+            g.free()
+    return [[(c, ids[c], lo, hi, st, ed) for c, lo, hi, st, ed in lst] for lst in res]
+
+
+def approxMatch(query, subject_seq, *, max_edits: int = 1, strand: str = "+", all_ends: bool = False, ctx=None):
+    """Every place at which `query` -- 1 ... 64 IUPAC symbols (ACGTRYSWKMBDHVN, either case; bytes / str / Record) -- lies on the
+    subject within `max_edits` (0 ... 15) edits: substitutions, inserted and deleted bases, one each (Sellers' semi-global edit
+    distance: the whole query against any substring of one record).  Symbols match as in motifMatch: a genome base matches a
+    symbol whose set contains it, a genome N only a query N.  `max_edits` must be smaller than the number of non-N symbols of
+    the query.  The subject may hold A/C/G/T/N only (KgmaError KGMA_E_BADBASE otherwise).
+    An end position whose best substring is within max_edits is a matching end; consecutive matching ends form a run, and per
+    run the end with the fewest edits (the leftmost of them) is reported with lo:hi, the SHORTEST substring ending there that
+    attains its edits.  all_ends=True reports every matching end instead.
+    strand: "+" the query as given; "-" its reverse complement, searched on the same genome and reported at the forward lo:hi
+    it covers; "both" the two together.
+    A `subject_seq` of residues (bytes, or a Record) returns [(lo, hi, strand, edits)] sorted by (lo, strand); a FASTA path or
+    an open device genome returns approxMatch_batch(...)[0].  An empty list when there is no match."""
+    if isinstance(subject_seq, (Record, bytes, bytearray, memoryview)):
+        qs, sent, tags = _motif_args([query], max_edits, strand, "query", "max_edits")
+        seq = bytes(subject_seq.sequence if isinstance(subject_seq, Record) else subject_seq)
+        ctx = ctx or default_context()
+        g = ctx.genome_from_host([seq])
+        try:
+            res = _approx_run(ctx, g, qs, sent, tags, all_ends)[0]
+        finally:
+            g.free()
+        return [(lo, hi, st, ed) for _, lo, hi, st, ed in res]
+    return approxMatch_batch([query], subject_seq, max_edits=max_edits, strand=strand, all_ends=all_ends, ctx=ctx)[0]
+
+
+def findRSS_edits(genome_or_path, rss=HumanRSSD, max_edits: int = 1, strand: str = "both", ctx=None):
+    """Recombination signal sequences within `max_edits` edits: with the default, one substitution or a spacer one base longer
+    or shorter than the 23 (12) nt findRSS lays rigidly.  approxMatch's best end per run."""
+    return approxMatch(rss, genome_or_path, max_edits=max_edits, strand=strand, ctx=ctx)
 
 
 # ---- threshold calibration (kgma_window_dists, kgma_mutation_dists): the working form of src/DistanceTesting.jl --------------
