@@ -716,6 +716,52 @@ int kgma_approx_match(kgma_ctx *ctx, const kgma_genome *g, const uint8_t *querie
 int kgma_get_approx_matches(kgma_ctx *ctx, kgma_approx_hit *out, int64_t cap, int64_t *n);
 int kgma_get_approx_stats(kgma_ctx *ctx, kgma_approx_stats *out);
 
+/* ---- pwmMatch: position-weight-matrix search on a resident genome (kernel: kgma_pwm.hip) --------------------------------------
+ * Matrix i is rows row_offsets[i] .. row_offsets[i+1] - 1 of `weights`: m = 1 ... 64 rows of four integer weights in the order
+ * A, C, G, T, each in -32768 ... 32767 (the int16_t of the interface), the matrices back to back.  Every score fits an int32, its
+ * magnitude is at most 2^21.
+ * Laid at the 1-based start s of a record t[1..L], s + m - 1 <= L, score(s) = sum over the rows i = 0 ... m - 1 of
+ * W[i][t[s + i]].  Nothing spans two records.  Case is folded.  A genome N scores the row's minimum over A/C/G/T: an assembly gap
+ * never looks like a signal, and a row of four equal weights (a spacer) costs nothing.  Every s with score(s) >= threshold[i] is a
+ * hit, overlapping ones included.
+ * threshold[i] must exceed the sum of the row minima of matrix i -- otherwise every start would match; a threshold above the sum
+ * of the row maxima is legal and finds nothing.  The minus strand is served by passing the reverse-complemented matrix (rows
+ * reversed, A<->T and C<->G swapped): it is searched on the same genome, in the same pass, and its starts are forward
+ * coordinates.  The 0/1 matrix of an IUPAC motif (1 where the symbol's set holds the base, four 0 for N) with the threshold
+ * informative - d finds exactly the starts of kgma_motif_match with max_mismatch d, and score = informative - mismatches.
+ * All matrices are served by ONE launch (a workgroup per `wg_starts` consecutive starts of a record, a wave per `wave_starts` of
+ * them, `lane_starts` consecutive starts per lane; the host folds the constant rows into the threshold and every other row with
+ * the row behind it into a table indexed by two residues); the search is repeated once when the hits outgrow the device buffer,
+ * which starts at 64 Ki hits and is kept between calls (KGMA_E_NOMEM, context still usable, if the larger buffer cannot be had;
+ * KGMA_E_OVERFLOW if it overflows again).
+ * KGMA_E_ARG: a null pointer, a matrix of no rows or of more than 64, a threshold that does not exceed the sum of the row
+ * minima; kgma_last_error names the matrix.  KGMA_E_BADBASE: a genome residue outside A/C/G/T/N, in any record, exactly as in
+ * kgma_motif_match.
+ * The call needs no references and leaves the KFVs, the hits, dips and distances of the last scan and the matches of the last
+ * kgma_exact_match / kgma_motif_match / kgma_approx_match as they are; of kgma_stats it sets bases_scanned, scan_ms (hipEvents
+ * around the launches) and n_launches.  kgma_get_pwm_matches returns the hits of the last call sorted by (matrix, contig,
+ * start), with the two-call pattern of kgma_get_hits; after a call that failed, for whatever reason, it returns none. */
+typedef struct {
+    int32_t matrix;      /* 0-based index of the matrix                                        */
+    int32_t contig;      /* 0-based index of the record                                        */
+    int64_t start;       /* 1-based                                                            */
+    int32_t score;       /* score(start), >= threshold of the matrix                           */
+    int32_t reserved;
+} kgma_pwm_hit;          /* 24 bytes */
+typedef struct {
+    int32_t lane_starts; /* consecutive starts a lane owns                                     */
+    int32_t wave_starts; /* ... a wave owns                                                    */
+    int32_t wg_starts;   /* ... a workgroup owns                                               */
+    int32_t n_launches;  /* kernel launches of the call (the search, a repeated search)        */
+    int64_t n_candidates; /* starts the kernel emitted: it scores exactly, so = n_hits         */
+    int64_t n_hits;      /* reported hits                                                      */
+    double search_ms;    /* hipEvents around the search launch(es)                             */
+} kgma_pwm_stats;
+int kgma_pwm_match(kgma_ctx *ctx, const kgma_genome *g, const int16_t *weights /* rows of 4, matrices back to back */,
+                   const int64_t *row_offsets /* n_matrices + 1, in rows */, int32_t n_matrices, const int32_t *threshold /* n_matrices */);
+int kgma_get_pwm_matches(kgma_ctx *ctx, kgma_pwm_hit *out, int64_t cap, int64_t *n);
+int kgma_get_pwm_stats(kgma_ctx *ctx, kgma_pwm_stats *out);
+
 /* Threshold calibration: the working form of src/DistanceTesting.jl on the device (kernels: kgma_calib.hip).  Both calls need
  * the references of kgma_set_refs (KGMA_E_STATE before it, or after kgma_set_strobe_ref), serve 1 <= k <= 10 (references at
  * k >= 11 are kept sparse: KGMA_E_UNSUPPORTED) and leave the references, the thresholds and the results of the last scan,

@@ -41,6 +41,7 @@
 #include "kgma_twobit.h"
 #include "kgma_landscape.h"
 #include "kgma_approx.h"
+#include "kgma_pwm.h"
 
 namespace kgma {
 hipError_t launch_scan(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
@@ -465,6 +466,7 @@ struct kgma_ctx {
     unsigned long long *d_mctl = nullptr; int64_t mctl_cap = 0;
     std::vector<kgma_motif_hit> motif_hits;
     ApproxState approx;                      // edit-distance search (kgma_approx_match; kgma_approx.cpp)
+    PwmState pwm;                            // position-weight-matrix search (kgma_pwm_match; kgma_pwm.cpp)
     // calibration (kgma_window_dists / kgma_mutation_dists; kgma_calib.hip): device buffers kept between calls.  d_cbtab is the
     // k >= 8 kernels' counter table, zeroed when allocated and left all-zero by every launch
     int64_t *d_cboff = nullptr; int64_t cboff_cap = 0;
@@ -855,6 +857,7 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_mprefix) (void)hipFree(ctx->d_mprefix);
     if (ctx->d_mout) (void)hipFree(ctx->d_mout);
     if (ctx->approx.d_out) (void)hipFree(ctx->approx.d_out);
+    if (ctx->pwm.d_out) (void)hipFree(ctx->pwm.d_out);
     if (ctx->d_mctl) (void)hipFree(ctx->d_mctl);
     for (void *q : {(void *)ctx->d_cboff, (void *)ctx->d_cbD, (void *)ctx->d_cbdist, (void *)ctx->d_cbtab, (void *)ctx->d_cbtext,
                     (void *)ctx->d_cbP, (void *)ctx->d_cbbad})
@@ -1861,9 +1864,10 @@ int staged_upload(StagePipe &pipe, uint8_t *dst, int64_t bytes, const std::vecto
 
 }  // namespace
 
-// kgma_approx.h: the view kgma_approx.cpp has of a context and a genome
+// kgma_approx.h, kgma_pwm.h: the view kgma_approx.cpp and kgma_pwm.cpp have of a context and a genome
 namespace kgma {
 ApproxState *ctx_approx(kgma_ctx *ctx) { return &ctx->approx; }
+PwmState *ctx_pwm(kgma_ctx *ctx) { return &ctx->pwm; }
 int64_t *ctx_device_bytes(kgma_ctx *ctx) { return &ctx->device_bytes; }
 kgma_stats *ctx_stats(kgma_ctx *ctx) { return &ctx->stats; }
 int genome_searchable(kgma_ctx *ctx, const kgma_genome *gc)

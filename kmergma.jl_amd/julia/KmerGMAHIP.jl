@@ -621,6 +621,72 @@ end
 approxMatch(query, genome::Union{String, DeviceGenome}; max_edits::Integer = 1, all_ends::Bool = false, ctx::Context = default_context()) =
     approxMatch([query], genome; max_edits = max_edits, all_ends = all_ends, ctx = ctx)[1]
 
+struct KgmaPwmHit         # kgma_pwm_hit: 0-based matrix and contig, the 1-based start
+    matrix::Int32
+    contig::Int32
+    start::Int64
+    score::Int32
+    reserved::Int32
+end
+
+struct KgmaPwmStats       # kgma_pwm_stats
+    lane_starts::Int32
+    wave_starts::Int32
+    wg_starts::Int32
+    n_launches::Int32
+    n_candidates::Int64
+    n_hits::Int64
+    search_ms::Float64
+end
+
+function pwm_stats(ctx::Context)
+    s = Ref{KgmaPwmStats}()
+    check(ctx, ccall((:kgma_get_pwm_stats, libkgma), Cint, (Ptr{Cvoid}, Ref{KgmaPwmStats}), ctx.h, s))
+    return s[]
+end
+
+"The matrix of the other strand: rows reversed, A <-> T and C <-> G swapped (`matrix` is m x 4, columns A, C, G, T)."
+pwm_revcomp(matrix::AbstractMatrix{<:Integer}) = matrix[end:-1:1, end:-1:1]
+
+"""
+    pwmMatch(matrices, genome; threshold)   -- `genome`: a FASTA path or an open DeviceGenome
+Position weight matrices (m x 4 integer weights, columns A, C, G, T, 1 <= m <= 64, each weight an Int16) laid on every start of
+every record, all in one pass over the genome (kgma_pwm_match): per matrix the vector of (record identifier, range, score) with
+score = the sum of the weights of the residues under the rows >= `threshold` (one number, or one per matrix; it must exceed the
+sum of the row minima).  A genome N scores its row's minimum.  For the minus strand pass `pwm_revcomp(matrix)`: its hits are in
+forward coordinates.
+"""
+function pwmMatch(matrices::Vector{<:AbstractMatrix{<:Integer}}, genome::Union{String, DeviceGenome}; threshold,
+                  ctx::Context = default_context())
+    all(m -> size(m, 2) == 4, matrices) || throw(ArgumentError("a matrix has four columns: A, C, G, T"))
+    g = genome isa String ? genome_from_fasta(ctx, genome) : genome
+    try
+        weights = Int16[]
+        for m in matrices, i in 1:size(m, 1), b in 1:4
+            push!(weights, Int16(m[i, b]))                    # rows of four, matrices back to back (InexactError: a weight out of range)
+        end
+        offsets = Int64[0; cumsum(Int64[size(m, 1) for m in matrices])]
+        ts = threshold isa Integer ? fill(Int32(threshold), length(matrices)) : Int32.(threshold)
+        length(ts) == length(matrices) || throw(ArgumentError("need one threshold per matrix"))
+        check(ctx, ccall((:kgma_pwm_match, libkgma), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int16}, Ptr{Int64}, Int32, Ptr{Int32}),
+                         ctx.h, g.h, weights, offsets, length(matrices), ts))
+        n = Ref{Int64}(0)
+        check(ctx, ccall((:kgma_get_pwm_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaPwmHit}, Int64, Ref{Int64}), ctx.h, C_NULL, 0, n))
+        hits = Vector{KgmaPwmHit}(undef, n[])
+        check(ctx, ccall((:kgma_get_pwm_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaPwmHit}, Int64, Ref{Int64}), ctx.h, hits, n[], n))
+        out = [Tuple{String, UnitRange{Int64}, Int}[] for _ in matrices]
+        for h in hits
+            m = size(matrices[h.matrix + 1], 1)
+            push!(out[h.matrix + 1], (identifier(g, h.contig), h.start:(h.start + m - 1), Int(h.score)))
+        end
+        return out
+    finally
+        genome isa String && free!(g)
+    end
+end
+pwmMatch(matrix::AbstractMatrix{<:Integer}, genome::Union{String, DeviceGenome}; threshold::Integer, ctx::Context = default_context()) =
+    pwmMatch([matrix], genome; threshold = threshold, ctx = ctx)[1]
+
 # ---- threshold calibration (the working form of src/DistanceTesting.jl): kgma_window_dists, kgma_mutation_dists -------------
 
 """
@@ -854,7 +920,7 @@ function dist_sweep(ctx::Context, thresholds::Vector{Float64}; kfv::Integer = 1)
     return below, dips
 end
 
-export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, approxMatch, HumanRSSV, HumanRSSD, Context
+export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, approxMatch, pwmMatch, pwm_revcomp, HumanRSSV, HumanRSSD, Context
 export dist_layout, dist_bins, dist_sweep
 export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists, assignGenes, assign_ranges
 export kmer_dist_matrix, kmer_dist_matrix_ranges, nearest_refs, assignGenes_screened

@@ -37,6 +37,7 @@ EXPORTS = [
     "kgma_set_strobe_ref", "kgma_strobe_scan", "kgma_exact_match", "kgma_get_matches",
     "kgma_motif_match", "kgma_get_motif_matches",
     "kgma_approx_match", "kgma_get_approx_matches", "kgma_get_approx_stats",
+    "kgma_pwm_match", "kgma_get_pwm_matches", "kgma_get_pwm_stats",
     "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
     "kgma_get_block_sums", "kgma_genome_from_2bit_file", "kgma_get_2bit_unpack_ms", "kgma_twobit_inspect",
     "kgma_window_dists", "kgma_mutation_dists", "kgma_strobe_window_dists", "kgma_strobe_mutation_dists",
@@ -94,6 +95,15 @@ class KgmaApproxStats(C.Structure):
                 ("n_ends", C.c_int64), ("n_hits", C.c_int64), ("search_ms", C.c_double), ("starts_ms", C.c_double)]
 
 
+class KgmaPwmHit(C.Structure):
+    _fields_ = [("matrix", C.c_int32), ("contig", C.c_int32), ("start", C.c_int64), ("score", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgmaPwmStats(C.Structure):
+    _fields_ = [("lane_starts", C.c_int32), ("wave_starts", C.c_int32), ("wg_starts", C.c_int32), ("n_launches", C.c_int32),
+                ("n_candidates", C.c_int64), ("n_hits", C.c_int64), ("search_ms", C.c_double)]
+
+
 class KgmaTwobitInfo(C.Structure):
     _fields_ = [("version", C.c_int32), ("reserved", C.c_int32), ("n_records", C.c_int64), ("total_bases", C.c_int64),
                 ("n_blocks", C.c_int64), ("mask_blocks", C.c_int64), ("packed_bytes", C.c_int64)]
@@ -142,6 +152,8 @@ MATCH_DTYPE = np.dtype([("query", "<i4"), ("contig", "<i4"), ("start", "<i8")])
 MOTIF_HIT_DTYPE = np.dtype([("motif", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("mismatches", "<i4"), ("reserved", "<i4")])
 
 APPROX_HIT_DTYPE = np.dtype([("query", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("end", "<i8"), ("edits", "<i4"), ("reserved", "<i4")])
+
+PWM_HIT_DTYPE = np.dtype([("matrix", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("score", "<i4"), ("reserved", "<i4")])
 
 ASSIGNMENT_DTYPE = np.dtype([("ref", "<i4"), ("score", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"),
                              ("q_lo", "<i4"), ("q_hi", "<i4")])   # kgma_assignment
@@ -202,6 +214,9 @@ def load():
     L.kgma_approx_match.argtypes = [vp, vp, C.c_char_p, P(i64), i32, P(i32), i32]
     L.kgma_get_approx_matches.argtypes = [vp, P(KgmaApproxHit), i64, P(i64)]
     L.kgma_get_approx_stats.argtypes = [vp, P(KgmaApproxStats)]
+    L.kgma_pwm_match.argtypes = [vp, vp, P(C.c_int16), P(i64), i32, P(i32)]
+    L.kgma_get_pwm_matches.argtypes = [vp, P(KgmaPwmHit), i64, P(i64)]
+    L.kgma_get_pwm_stats.argtypes = [vp, P(KgmaPwmStats)]
     L.kgma_genome_from_host.argtypes = [vp, P(C.c_char_p), P(i64), i64, P(vp)]
     L.kgma_genome_from_fasta.argtypes = [vp, vp, i64, P(vp)]
     L.kgma_genome_from_fasta_file.argtypes = [vp, C.c_char_p, P(vp)]
@@ -618,6 +633,45 @@ class Context:
         s = KgmaApproxStats()
         self._check(load().kgma_get_approx_stats(self._h, C.byref(s)))
         return {name: getattr(s, name) for name, _ in KgmaApproxStats._fields_}
+
+    def pwm_match(self, genome: Genome, matrices: Sequence, thresholds: Sequence[int]) -> None:
+        """kgma_pwm_match: every start in every record of `genome` at which matrix i -- (m, 4) integer weights in the order
+        A, C, G, T, 1 <= m <= 64, each in -32768 ... 32767 -- scores at least thresholds[i]; a genome N scores its row's minimum.
+        One pass over the genome for the whole batch.  Needs no references.  pwm_matches() afterwards."""
+        mats = [np.asarray(m) for m in matrices]
+        for i, m in enumerate(mats):
+            if m.ndim != 2 or m.shape[1] != 4 or not np.issubdtype(m.dtype, np.integer):
+                raise ValueError(f"matrix {i}: need an (m, 4) array of integers")
+            bad = np.argwhere((m < -32768) | (m > 32767))
+            if bad.size:
+                raise ValueError(f"matrix {i}, row {int(bad[0][0]) + 1}: weight {int(m[tuple(bad[0])])} is outside -32768 ... 32767")
+        thr = [int(t) for t in thresholds]
+        if len(thr) != len(mats):
+            raise ValueError("need one threshold per matrix")
+        for i, t in enumerate(thr):
+            if not -2 ** 31 <= t < 2 ** 31:
+                raise ValueError(f"matrix {i}: threshold {t} does not fit an int32")
+        w = np.ascontiguousarray(np.concatenate([m.reshape(-1, 4) for m in mats] + [np.zeros((1, 4), np.int64)]).astype(np.int16))
+        off = np.zeros(len(mats) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([m.shape[0] for m in mats])
+        th = np.asarray(thr + [0], dtype=np.int32)                  # (never empty: a pointer to take)
+        self._check(load().kgma_pwm_match(self._h, genome._h, _np_ptr(w, C.c_int16), _np_ptr(off, C.c_int64), len(mats),
+                                          _np_ptr(th, C.c_int32)))
+
+    def pwm_matches(self) -> np.ndarray:
+        """Hits of the last pwm_match as a structured array (PWM_HIT_DTYPE: 0-based matrix and contig, 1-based start, score),
+        sorted by (matrix, contig, start)."""
+        n = C.c_int64(0)
+        self._check(load().kgma_get_pwm_matches(self._h, None, 0, C.byref(n)))
+        arr = np.zeros(max(n.value, 1), dtype=PWM_HIT_DTYPE)
+        self._check(load().kgma_get_pwm_matches(self._h, arr.ctypes.data_as(C.POINTER(KgmaPwmHit)), n.value, C.byref(n)))
+        return arr[:n.value]
+
+    def pwm_stats(self) -> dict:
+        """kgma_get_pwm_stats: the kernel's geometry, candidates, hits, launches and device time of the last pwm_match."""
+        s = KgmaPwmStats()
+        self._check(load().kgma_get_pwm_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in KgmaPwmStats._fields_}
 
     def set_thresholds(self, thr: Sequence[float]) -> None:
         th = np.asarray(list(thr)[:self.m], dtype=np.float64)

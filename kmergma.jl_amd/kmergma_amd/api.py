@@ -809,6 +809,209 @@ def findRSS_edits(genome_or_path, rss=HumanRSSD, max_edits: int = 1, strand: str
     return approxMatch(rss, genome_or_path, max_edits=max_edits, strand=strand, ctx=ctx)
 
 
+# ---- position-weight-matrix search (kgma_pwm_match): positions weighted by how much they matter -----------------------------
+
+PWM_MAX_ROWS, PWM_WEIGHT_MIN, PWM_WEIGHT_MAX = 64, -32768, 32767
+_UNIFORM = (0.25, 0.25, 0.25, 0.25)
+_IUPAC_SETS = {"A": 1, "C": 2, "G": 4, "T": 8, "R": 5, "Y": 10, "S": 6, "W": 9, "K": 12, "M": 3, "B": 14, "D": 13, "H": 11, "V": 7,
+               "N": 15}          # bit 0 A, 1 C, 2 G, 3 T
+
+
+def _background(background) -> np.ndarray:
+    bg = np.asarray(background, dtype=np.float64)
+    if bg.shape != (4,) or not np.isfinite(bg).all() or (bg <= 0).any() or not math.isclose(float(bg.sum()), 1.0, rel_tol=0, abs_tol=1e-9):
+        raise ValueError("background: four positive probabilities (A, C, G, T) that sum to 1")
+    return bg
+
+
+def _pwm_matrix(matrix, which: str = "matrix") -> np.ndarray:
+    """The checks of kgma_pwm_match on one matrix, made before any device call: an (m, 4) int64 array."""
+    if isinstance(matrix, (str, bytes, bytearray, memoryview, Record)) or matrix is None:
+        raise TypeError("Invalid matrix type")
+    a = np.asarray(matrix)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"{which}: the weights must be integers (scale and round a log-odds matrix: pwm_from_sequences)")
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"{which}: need rows of four weights (A, C, G, T), got shape {a.shape}")
+    if not 1 <= a.shape[0] <= PWM_MAX_ROWS:
+        raise ValueError(f"{which} has {a.shape[0]} rows (1 ... {PWM_MAX_ROWS})")
+    a = a.astype(np.int64)
+    bad = np.argwhere((a < PWM_WEIGHT_MIN) | (a > PWM_WEIGHT_MAX))
+    if bad.size:
+        raise ValueError(f"{which}, row {int(bad[0][0]) + 1}: weight {int(a[tuple(bad[0])])} is outside {PWM_WEIGHT_MIN} ... {PWM_WEIGHT_MAX}")
+    return a
+
+
+def pwm_from_sequences(seqs, *, pseudocount: float = 1.0, background=_UNIFORM, scale: float = 100) -> np.ndarray:
+    """Log-odds position weight matrix of equal-length example sites (A/C/G/T, either case; bytes / str / Record): the (m, 4)
+    int64 array np.rint(scale * log2(((count + pseudocount * bg) / (n + pseudocount)) / bg)), columns in the order A, C, G, T.
+    With scale = 100 the weights are centibits.  ValueError when a weight leaves the int16 range of kgma_pwm_match (a count of 0
+    without a pseudocount, a scale too large)."""
+    rows = [_query_bytes(q).upper() for q in seqs]
+    if not rows:
+        raise ValueError("need at least one sequence")
+    m = len(rows[0])
+    if not 1 <= m <= PWM_MAX_ROWS:
+        raise ValueError(f"the sequences have {m} symbols (1 ... {PWM_MAX_ROWS})")
+    if any(len(r) != m for r in rows):
+        raise ValueError("the sequences differ in length")
+    bg = _background(background)
+    if not (math.isfinite(pseudocount) and pseudocount >= 0 and math.isfinite(scale) and scale > 0):
+        raise ValueError("pseudocount must be >= 0 and scale > 0")
+    text = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), m)
+    count = np.stack([(text == ch).sum(axis=0) for ch in b"ACGT"], axis=1).astype(np.float64)
+    if (count.sum(axis=1) != len(rows)).any():
+        raise ValueError("the sequences may hold A, C, G and T only")
+    with np.errstate(divide="ignore"):
+        w = np.rint(scale * np.log2(((count + pseudocount * bg) / (len(rows) + pseudocount)) / bg))
+    if not np.isfinite(w).all() or (w < PWM_WEIGHT_MIN).any() or (w > PWM_WEIGHT_MAX).any():
+        i = int(np.argwhere(~np.isfinite(w) | (w < PWM_WEIGHT_MIN) | (w > PWM_WEIGHT_MAX))[0][0])
+        raise ValueError(f"row {i + 1}: a weight leaves {PWM_WEIGHT_MIN} ... {PWM_WEIGHT_MAX} (give a pseudocount or a smaller scale)")
+    return w.astype(np.int64)
+
+
+def pwm_from_motif(motif):
+    """The 0/1 matrix of an IUPAC motif and its number of informative (non-N) symbols: weight 1 where the symbol's set holds
+    the base, all four weights 0 for N.  With threshold = informative - d, pwmMatch finds exactly motifMatch(max_mismatch=d)'s
+    starts, and score = informative - mismatches."""
+    m = _motif_bytes(motif, 0)
+    sets = [_IUPAC_SETS[chr(ch).upper()] for ch in m]
+    w = np.array([[0, 0, 0, 0] if s == 15 else [(s >> b) & 1 for b in range(4)] for s in sets], dtype=np.int64)
+    return w, sum(1 for s in sets if s != 15)
+
+
+def pwm_revcomp(matrix) -> np.ndarray:
+    """The matrix of the other strand: rows reversed, A <-> T and C <-> G swapped."""
+    return _pwm_matrix(matrix)[::-1, ::-1].copy()
+
+
+def pwm_score_distribution(matrix, background=_UNIFORM):
+    """(lowest, p): p[k] is the probability that m independent bases drawn from `background` score lowest + k, exactly on the
+    integer lattice -- one convolution per row; lowest is the sum of the row minima, lowest + len(p) - 1 that of the maxima."""
+    w, bg = _pwm_matrix(matrix), _background(background)
+    lo = w.min(axis=1)
+    p = np.ones(1, dtype=np.float64)
+    for row, base in zip(w, lo):
+        shift = (row - base).tolist()
+        q = np.zeros(p.size + max(shift), dtype=np.float64)
+        for b in range(4):
+            q[shift[b]:shift[b] + p.size] += bg[b] * p
+        p = q
+    return int(lo.sum()), p
+
+
+def pwm_threshold(matrix, pvalue: float, background=_UNIFORM) -> int:
+    """The smallest integer t with P(score >= t) <= pvalue for independent bases drawn from `background` (A, C, G, T), from
+    the exact score distribution (pwm_score_distribution).  One above the highest score when even that one is likelier than
+    pvalue."""
+    if not 0 < float(pvalue) < 1:
+        raise ValueError("pvalue must lie strictly between 0 and 1")
+    lowest, p = pwm_score_distribution(matrix, background)
+    tail = np.cumsum(p[::-1])[::-1]                               # tail[k] = P(score >= lowest + k), summed from the top
+    ok = np.flatnonzero(tail <= float(pvalue))
+    return lowest + (int(ok[0]) if ok.size else p.size)
+
+
+def _pwm_args(matrices, threshold, pvalue, strand):
+    _check_strand(strand)
+    if (threshold is None) == (pvalue is None):
+        raise ValueError("give exactly one of threshold and pvalue")
+    ms = [_pwm_matrix(m, f"matrix {i}") for i, m in enumerate(matrices)]
+    if pvalue is not None:
+        ps = [float(pvalue)] * len(ms) if isinstance(pvalue, (int, float, np.integer, np.floating)) else [float(x) for x in pvalue]
+        if len(ps) != len(ms):
+            raise ValueError("need one pvalue per matrix")
+        ts = [pwm_threshold(m, x) for m, x in zip(ms, ps)]
+    elif isinstance(threshold, (int, np.integer)):
+        ts = [int(threshold)] * len(ms)
+    else:
+        ts = [int(t) for t in threshold]
+        if len(ts) != len(ms):
+            raise ValueError("need one threshold per matrix")
+    for i, (m, t) in enumerate(zip(ms, ts)):
+        lowest = int(m.min(axis=1).sum())
+        if t <= lowest:
+            raise ValueError(f"matrix {i}: threshold {t} does not exceed the sum of its row minima, {lowest}: every start would match")
+        if not t < 2 ** 31:
+            raise ValueError(f"matrix {i}: threshold {t} does not fit an int32")
+    # the minus strand: the reverse-complemented matrix on the SAME genome, in the same pass
+    sent, tags = [], []
+    for i, (m, t) in enumerate(zip(ms, ts)):
+        if strand != "-":
+            sent.append((m, t)); tags.append((i, "+"))
+        if strand != "+":
+            sent.append((pwm_revcomp(m), t)); tags.append((i, "-"))
+    return ms, sent, tags
+
+
+def _pwm_run(ctx, g, ms, sent, tags) -> list:
+    """Per matrix the hits (record, lo, hi, strand, score), sorted by (record, lo, strand)."""
+    ctx.pwm_match(g, [m for m, _ in sent], [t for _, t in sent])
+    out = [[] for _ in ms]
+    for h in ctx.pwm_matches().tolist():
+        i, st = tags[h[0]]
+        out[i].append((h[1], h[2], h[2] + ms[i].shape[0] - 1, st, h[3]))
+    for lst in out:
+        lst.sort(key=lambda t: (t[0], t[1], t[3]))              # ("+" sorts before "-")
+    return out
+
+
+def pwmMatch_batch(matrices, genome_or_path, *, threshold=None, pvalue=None, strand: str = "+", ctx=None) -> list:
+    """Many matrices in ONE pass over the genome (kgma_pwm_match): per matrix the list of
+    (record_index, identifier, lo, hi, strand, score) -- 0-based record, 1-based inclusive lo:hi in forward coordinates --
+    sorted by (record, lo, strand).  `threshold` / `pvalue`: one number for all matrices or one per matrix.  Semantics: pwmMatch.
+    `genome_or_path`: a FASTA or .2bit path, or a device genome that is already open (it stays open)."""
+    ms, sent, tags = _pwm_args(list(matrices), threshold, pvalue, strand)
+    if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
+        raise TypeError("Invalid subject sequence type")
+    ctx = ctx or default_context()
+    g, src, owned = _open_subject(ctx, genome_or_path)
+    try:
+        res = _pwm_run(ctx, g, ms, sent, tags)
+        ids = {c: _identifier(src, c) for c in {t[0] for lst in res for t in lst}}
+    finally:
+        if owned:
+            g.free()
+    return [[(c, ids[c], lo, hi, st, sc) for c, lo, hi, st, sc in lst] for lst in res]
+
+
+def pwmMatch(matrix, subject_seq, *, threshold=None, pvalue=None, strand: str = "+", ctx=None):
+    """Every place at which `matrix` -- 1 ... 64 rows of four integer weights (A, C, G, T; each -32768 ... 32767) -- laid on the
+    subject scores at least the threshold: score(s) = sum over the rows i of matrix[i][t[s + i]], overlapping places included,
+    none spanning two records.  Case is folded; a genome N scores its row's minimum, so an assembly gap never looks like a signal
+    and a row of four equal weights (a spacer) costs nothing.  Give exactly one of `threshold` (an integer that exceeds the sum of
+    the row minima) and `pvalue` (the threshold becomes pwm_threshold(matrix, pvalue), uniform background).  The subject may hold
+    A/C/G/T/N only (KgmaError KGMA_E_BADBASE otherwise).
+    strand: "+" the matrix as given; "-" its reverse complement (pwm_revcomp), searched on the same genome and reported at the
+    forward lo:hi it covers; "both" the two together (a matrix equal to its own reverse complement is reported on both strands).
+    A `subject_seq` of residues (bytes, or a Record) returns [(lo, hi, strand, score)] sorted by (lo, strand); a FASTA path or
+    an open device genome returns pwmMatch_batch(...)[0].  An empty list when there is no hit."""
+    if isinstance(subject_seq, (Record, bytes, bytearray, memoryview)):
+        ms, sent, tags = _pwm_args([matrix], threshold, pvalue, strand)
+        seq = bytes(subject_seq.sequence if isinstance(subject_seq, Record) else subject_seq)
+        ctx = ctx or default_context()
+        g = ctx.genome_from_host([seq])
+        try:
+            res = _pwm_run(ctx, g, ms, sent, tags)[0]
+        finally:
+            g.free()
+        return [(lo, hi, st, sc) for _, lo, hi, st, sc in res]
+    return pwmMatch_batch([matrix], subject_seq, threshold=threshold, pvalue=pvalue, strand=strand, ctx=ctx)[0]
+
+
+def findRSS_pwm(genome_or_path, sites_or_matrix, *, pvalue: float = 1e-6, strand: str = "both", ctx=None):
+    """Recombination signal sequences by a position weight matrix: `sites_or_matrix` is a list of example sites (equal-length
+    A/C/G/T sequences, made into a log-odds matrix by pwm_from_sequences) or a ready matrix; every place of the genome that
+    scores at least the exact p <= pvalue threshold is returned as pwmMatch does.  Unlike findRSS's mismatch count it weighs
+    the all but invariant CAC of the heptamer above the positions that drift."""
+    first = sites_or_matrix[0] if isinstance(sites_or_matrix, (list, tuple)) and len(sites_or_matrix) else None
+    if isinstance(first, (str, bytes, bytearray, memoryview, Record)):
+        matrix = pwm_from_sequences(sites_or_matrix)
+    else:
+        matrix = sites_or_matrix
+    return pwmMatch(matrix, genome_or_path, pvalue=pvalue, strand=strand, ctx=ctx)
+
+
 # ---- threshold calibration (kgma_window_dists, kgma_mutation_dists): the working form of src/DistanceTesting.jl --------------
 
 _M64 = (1 << 64) - 1
