@@ -621,7 +621,9 @@ int kgma_strobe_scan(kgma_ctx *ctx, const kgma_genome *g, int64_t buff, uint32_t
  * does not depend on n_queries (queries of A/C/G/T only are filtered on the 2-bit copy of the genome and verified against the
  * residue text, the others -- and every query when a record holds a symbol outside A/C/G/T/N, or under the testing switch
  * KGMA_EXACT_ASCII=1 -- are compared on the residue text: at most one launch of each kind, repeated once when the matches outgrow
- * the device buffer; KGMA_E_OVERFLOW if they do so again).
+ * the device buffer, which starts at 64 Ki matches and is kept between calls; KGMA_E_NOMEM, the buffer it had still in place and
+ * the context usable, if the larger buffer cannot be had, as in the three searches below; KGMA_E_OVERFLOW if the matches outgrow
+ * the regrown buffer).
  * KGMA_E_ARG: an empty query, or a query symbol outside the 16-symbol alphabet.  KGMA_E_BADBASE: a genome residue outside it, in any
  * record (the reference decodes every record before it searches, getSeq at src/ExactMatch.jl:109); kgma_last_error names the first
  * such record and position.

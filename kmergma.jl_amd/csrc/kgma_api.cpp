@@ -40,6 +40,8 @@
 #include "kgma_stage_fill.h"
 #include "kgma_twobit.h"
 #include "kgma_landscape.h"
+#include "kgma_exact.h"
+#include "kgma_motif.h"
 #include "kgma_approx.h"
 #include "kgma_pwm.h"
 
@@ -79,11 +81,6 @@ hipError_t launch_export(uint8_t *res, uint8_t *host, int64_t d0_slots, int64_t 
                          unsigned int *done, hipStream_t st);
 int scan_tile_stride_words(int nk);
 int scan_nblocks(int nk);
-int64_t exact_tile_starts(bool two_bit);
-hipError_t launch_exact(const ExactArgs &a, int kind, int64_t n_tiles, hipStream_t st);
-int64_t motif_tile_starts();
-int motif_planes(int max_mm);
-hipError_t launch_motif(const MotifArgs &a, int P, int64_t n_tiles, hipStream_t st);
 int kdist_grid(int k, int64_t n_seqs);
 hipError_t launch_kdist(int mode, const uint8_t *seqs, const int64_t *off, int64_t n_seqs, int k, const double *ref,
                         uint32_t *scratch, double scale, double *out, unsigned long long *first_bad, hipStream_t st);
@@ -177,9 +174,6 @@ constexpr int64_t LEAD_PAD_WORDS = 8;
 constexpr int64_t TAIL_PAD_WORDS = KGMA_TILE_WORDS + 128;
 constexpr unsigned long long NO_BAD = ~0ull;
 
-// a record's slot in the residue text: its residues rounded up to 32 bytes, and 32 more
-inline int64_t record_slot_bytes(int64_t len) { return ((len + 31) & ~31ll) + 32; }
-
 // What a context keeps for building and packing its genomes (kgma_create / kgma_destroy call init / release)
 struct GenomeStore {
     // ingest: pinned staging pair and device scratch, kept between genomes (allocating and pinning them cost a third of a
@@ -245,16 +239,6 @@ inline double now_ms()
 
 // what a pack that carries the prefilter's block sums needs of the references (pack_sums_kernel)
 struct PackSums { const int32_t *S; int k; int64_t s_max; int n_cus; };
-
-// tiles of `per_tile` units over n records of len_of(c) residues, one record after the other: prefix[c] tiles lie before record c,
-// prefix[n] is their number.  by_slot: a record counts its whole slot of the text, else its residues
-template <class LenOf>
-std::vector<int64_t> tile_prefix(int64_t n, int64_t per_tile, bool by_slot, LenOf len_of)
-{
-    std::vector<int64_t> prefix((size_t)n + 1, 0);
-    for (int64_t c = 0; c < n; c++) prefix[(size_t)c + 1] = prefix[(size_t)c] + ((by_slot ? record_slot_bytes(len_of(c)) : len_of(c)) + per_tile - 1) / per_tile;
-    return prefix;
-}
 
 }  // namespace
 
@@ -451,20 +435,8 @@ struct kgma_ctx {
     std::vector<ChainStream> cx_streams; std::vector<ChainChunk> cx_chunks, cx_pool; double cx_first = 0;
     std::vector<kgma_alignment> aligns;      // alignments the hit state machine consumed (kgma_scan_aligned), in order
     int64_t n_align_device = 0, n_align_host = 0;
-    // exact search (kgma_exact_match): device buffers kept between calls, and the matches of the last call
-    ExactQuery *d_xq = nullptr; int64_t xq_cap = 0;
-    uint8_t *d_xtext = nullptr; int64_t xtext_cap = 0;
-    int64_t *d_xprefix = nullptr; int64_t xprefix_cap = 0;
-    ExactMatch *d_xout = nullptr; int64_t xout_cap = 0;
-    unsigned long long *d_xctl = nullptr; int64_t xctl_cap = 0;
-    std::vector<kgma_match> matches;
-    // motif search (kgma_motif_match): likewise
-    MotifDesc *d_mq = nullptr; int64_t mq_cap = 0;
-    uint32_t *d_minfo = nullptr; int64_t minfo_cap = 0;
-    int64_t *d_mprefix = nullptr; int64_t mprefix_cap = 0;
-    MotifHit *d_mout = nullptr; int64_t mout_cap = 0;
-    unsigned long long *d_mctl = nullptr; int64_t mctl_cap = 0;
-    std::vector<kgma_motif_hit> motif_hits;
+    ExactState exact;                        // exact search (kgma_exact.cpp)
+    MotifState motif;                        // IUPAC motif search with mismatches (kgma_motif.cpp)
     ApproxState approx;                      // edit-distance search (kgma_approx_match; kgma_approx.cpp)
     PwmState pwm;                            // position-weight-matrix search (kgma_pwm_match; kgma_pwm.cpp)
     // calibration (kgma_window_dists / kgma_mutation_dists; kgma_calib.hip): device buffers kept between calls.  d_cbtab is the
@@ -487,7 +459,7 @@ struct kgma_ctx {
     int64_t device_bytes = 0;
 };
 
-// kgma_assign.h: the view kgma_assign.cpp and kgma_kmat.cpp have of the two structs above
+// kgma_search.h, kgma_assign.h: the view the other host files have of the two structs above
 namespace kgma {
 int ctx_fail(kgma_ctx *ctx, int code, const char *message)
 {
@@ -495,10 +467,13 @@ int ctx_fail(kgma_ctx *ctx, int code, const char *message)
     return code;
 }
 void ctx_device(const kgma_ctx *ctx, int *device, hipStream_t *stream) { *device = ctx->device; *stream = ctx->stream; }
+void ctx_events(const kgma_ctx *ctx, hipEvent_t *ev0, hipEvent_t *ev1) { *ev0 = ctx->ev0; *ev1 = ctx->ev1; }
+kgma_stats *ctx_stats(kgma_ctx *ctx) { return &ctx->stats; }
+int64_t *ctx_device_bytes(kgma_ctx *ctx) { return &ctx->device_bytes; }
 int ctx_n_cus(const kgma_ctx *ctx) { return ctx->n_cus; }
 kgma_assign_stats *ctx_assign_stats(kgma_ctx *ctx) { return &ctx->assign_stats; }
 kgma_kmat_stats *ctx_kmat_stats(kgma_ctx *ctx) { return &ctx->kmat_stats; }
-GenomeText genome_text(const kgma_genome *g) { return GenomeText{g->d_ascii, g->d_cd, g->cd.data(), g->n_contigs}; }
+GenomeText genome_text(const kgma_genome *g) { return GenomeText{g->d_ascii, g->d_cd, g->cd.data(), g->n_contigs, g->d_planes, g->d_inter}; }
 
 // kgma_landscape.h: the kept distances of the last scan as kgma_landscape.cpp sees them
 kgma_landscape_stats *ctx_landscape_stats(kgma_ctx *ctx) { return &ctx->landscape_stats; }
@@ -545,19 +520,6 @@ int fail(kgma_ctx *ctx, int code, const char *fmt, ...)
         if (e__ != hipSuccess)                                                                          \
             return fail((ctx), KGMA_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
     } while (0)
-
-template <class T>
-int dev_reserve(kgma_ctx *ctx, T *&ptr, int64_t &cap, int64_t need)
-{
-    if (need <= cap && ptr) return KGMA_OK;
-    int64_t &device_bytes = ctx->device_bytes;
-    if (ptr) { (void)hipFree(ptr); device_bytes -= cap * (int64_t)sizeof(T); ptr = nullptr; cap = 0; }
-    int64_t n = std::max<int64_t>(need, 16);
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ptr), (size_t)n * sizeof(T)));
-    cap = n;
-    device_bytes += n * (int64_t)sizeof(T);
-    return KGMA_OK;
-}
 
 // Grow a pinned host buffer to `need` elements and `spare` more; false: no memory (the buffer is gone)
 template <class T>
@@ -847,18 +809,10 @@ void kgma_destroy(kgma_ctx *ctx)
     if (ctx->d_chot) (void)hipFree(ctx->d_chot);
     if (ctx->d_cctl) (void)hipFree(ctx->d_cctl);
     if (ctx->d_gath) (void)hipFree(ctx->d_gath);
-    if (ctx->d_xq) (void)hipFree(ctx->d_xq);
-    if (ctx->d_xtext) (void)hipFree(ctx->d_xtext);
-    if (ctx->d_xprefix) (void)hipFree(ctx->d_xprefix);
-    if (ctx->d_xout) (void)hipFree(ctx->d_xout);
-    if (ctx->d_xctl) (void)hipFree(ctx->d_xctl);
-    if (ctx->d_mq) (void)hipFree(ctx->d_mq);
-    if (ctx->d_minfo) (void)hipFree(ctx->d_minfo);
-    if (ctx->d_mprefix) (void)hipFree(ctx->d_mprefix);
-    if (ctx->d_mout) (void)hipFree(ctx->d_mout);
-    if (ctx->approx.d_out) (void)hipFree(ctx->approx.d_out);
-    if (ctx->pwm.d_out) (void)hipFree(ctx->pwm.d_out);
-    if (ctx->d_mctl) (void)hipFree(ctx->d_mctl);
+    ctx->exact.release();
+    ctx->motif.release();
+    ctx->approx.release();
+    ctx->pwm.release();
     for (void *q : {(void *)ctx->d_cboff, (void *)ctx->d_cbD, (void *)ctx->d_cbdist, (void *)ctx->d_cbtab, (void *)ctx->d_cbtext,
                     (void *)ctx->d_cbP, (void *)ctx->d_cbbad})
         if (q) (void)hipFree(q);
@@ -1864,24 +1818,27 @@ int staged_upload(StagePipe &pipe, uint8_t *dst, int64_t bytes, const std::vecto
 
 }  // namespace
 
-// kgma_approx.h, kgma_pwm.h: the view kgma_approx.cpp and kgma_pwm.cpp have of a context and a genome
+// kgma_search.h and the headers of the four searches: their states in the context, and the genome made ready for a search
 namespace kgma {
+ExactState *ctx_exact(kgma_ctx *ctx) { return &ctx->exact; }
+MotifState *ctx_motif(kgma_ctx *ctx) { return &ctx->motif; }
 ApproxState *ctx_approx(kgma_ctx *ctx) { return &ctx->approx; }
 PwmState *ctx_pwm(kgma_ctx *ctx) { return &ctx->pwm; }
-int64_t *ctx_device_bytes(kgma_ctx *ctx) { return &ctx->device_bytes; }
-kgma_stats *ctx_stats(kgma_ctx *ctx) { return &ctx->stats; }
-int genome_searchable(kgma_ctx *ctx, const kgma_genome *gc)
+int genome_searchable(kgma_ctx *ctx, const kgma_genome *gc, PackedCopy copy, bool *clean)
 {
-    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping is updated
+    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping and its lazily made plane copy are updated
     (void)hipSetDevice(ctx->device);
-    const int rc = genome_ready(ctx, g, false);        // (first_bad is current)
+    const int rc = genome_ready(ctx, g, copy == PackedCopy::Planes);   // (first_bad is current)
     if (rc) return rc;
     ctx->stats.bases_scanned = g->total_bases;
     ctx->stats.scan_ms = 0;
     ctx->stats.n_launches = 0;
+    if (clean) *clean = true;
     for (int64_t c = 0; c < g->n_contigs; c++)
-        if (g->first_bad[(size_t)c] != NO_BAD)
-            return fail(ctx, KGMA_E_BADBASE, "record %lld: residue %llu is not one of A/C/G/T/N", (long long)c, g->first_bad[(size_t)c]);   // (first_bad is 1-based)
+        if (g->first_bad[(size_t)c] != NO_BAD) {
+            if (!clean) return fail(ctx, KGMA_E_BADBASE, "record %lld: residue %llu is not one of A/C/G/T/N", (long long)c, g->first_bad[(size_t)c]);   // (first_bad is 1-based)
+            *clean = false;
+        }
     return KGMA_OK;
 }
 }  // namespace kgma
@@ -6038,159 +5995,6 @@ int kgma_chain_export_copy(kgma_ctx *ctx, int64_t *win0, int32_t *n_valid, int64
 }
 
 // ------------------------------------------------------------------------------------------
-// exact sequence search (exactMatch, src/ExactMatch.jl:89-121; kernels: kgma_exact.hip)
-// ------------------------------------------------------------------------------------------
-static_assert(sizeof(kgma_match) == sizeof(ExactMatch), "kgma_match is the device record");
-
-// the 16 symbols of DNAAlphabet{4}, either case
-static bool exact_symbol(uint8_t ch)
-{
-    static const char sym[] = "ACGTMRWSYKVHDBN";
-    if (ch == '-') return true;
-    const uint8_t u = (uint8_t)(ch & 0xDFu);
-    return u >= 'A' && u <= 'Z' && strchr(sym, (int)u) != nullptr;
-}
-
-// One launch over the whole genome for the queries `qs` (kind: kgma_exact.hip, launch_exact); appends the matches to `found`.
-// A launch whose matches do not fit the device buffer is repeated once with a buffer of the size it counted.
-static int exact_launch(kgma_ctx *ctx, const kgma_genome *g, int kind, const std::vector<ExactQuery> &qs, std::vector<kgma_match> &found,
-                        unsigned long long *bad_out, int *n_launches)
-{
-    const int64_t nc = g->n_contigs;
-    const std::vector<int64_t> prefix = tile_prefix(nc, exact_tile_starts(kind == 2), false, [&](int64_t c) { return g->cd[(size_t)c].len; });
-    const int64_t n_tiles = prefix[(size_t)nc];
-    if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_exact_match: %lld tiles exceed one launch", (long long)n_tiles);
-    int rc;
-    if ((rc = dev_reserve(ctx, ctx->d_xq, ctx->xq_cap, (int64_t)qs.size()))) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_xprefix, ctx->xprefix_cap, nc + 1))) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_xctl, ctx->xctl_cap, 2))) return rc;
-    if ((rc = dev_reserve(ctx, ctx->d_xout, ctx->xout_cap, (int64_t)1 << 16))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xq, qs.data(), qs.size() * sizeof(ExactQuery), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xprefix, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    unsigned long long ctl[2] = {0, 0};
-    for (int attempt = 0;; attempt++) {
-        ExactArgs a{};
-        a.ascii = g->d_ascii; a.inter = g->d_inter; a.cd = g->d_cd; a.tile_prefix = ctx->d_xprefix;
-        a.n_contigs = (int32_t)nc; a.n_queries = (int32_t)qs.size();
-        a.queries = ctx->d_xq; a.qtext = ctx->d_xtext; a.out = ctx->d_xout; a.ctl = ctx->d_xctl; a.cap = (unsigned long long)ctx->xout_cap;
-        const unsigned long long init[2] = {0ull, NO_BAD};
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xctl, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, launch_exact(a, kind, n_tiles, ctx->stream));
-        (*n_launches)++;
-        HIP_TRY(ctx, hipMemcpyAsync(ctl, ctx->d_xctl, sizeof ctl, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctl[1] != NO_BAD) { *bad_out = ctl[1]; return KGMA_OK; }     // (the caller reports it; the matches are not wanted)
-        if (ctl[0] <= (unsigned long long)ctx->xout_cap) break;
-        if (attempt == 1) return fail(ctx, KGMA_E_OVERFLOW, "kgma_exact_match: %llu matches overflowed the regrown buffer", ctl[0]);
-        if (ctl[0] > (1ull << 40)) return fail(ctx, KGMA_E_NOMEM, "kgma_exact_match: %llu matches", ctl[0]);
-        if ((rc = dev_reserve(ctx, ctx->d_xout, ctx->xout_cap, (int64_t)ctl[0]))) return rc;
-    }
-    const size_t n0 = found.size();
-    found.resize(n0 + (size_t)ctl[0]);
-    if (ctl[0]) HIP_TRY(ctx, hipMemcpy(found.data() + n0, ctx->d_xout, (size_t)ctl[0] * sizeof(kgma_match), hipMemcpyDeviceToHost));
-    return KGMA_OK;
-}
-
-int kgma_exact_match(kgma_ctx *ctx, const kgma_genome *gc, const uint8_t *queries, const int64_t *offsets, int32_t n_queries, int32_t overlap)
-{
-    if (!ctx || !gc) return KGMA_E_ARG;
-    if (n_queries < 0 || (n_queries > 0 && (!queries || !offsets))) return fail(ctx, KGMA_E_ARG, "kgma_exact_match: no queries");
-    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping is updated
-    std::vector<uint8_t> text;
-    std::vector<ExactQuery> q_ascii, q_2bit;
-    std::vector<int64_t> qlen((size_t)n_queries);
-    for (int32_t i = 0; i < n_queries; i++) {
-        const int64_t b = offsets[i], m = offsets[i + 1] - b;
-        if (m < 1) return fail(ctx, KGMA_E_ARG, "kgma_exact_match: query %d is empty", i);
-        qlen[(size_t)i] = m;
-        ExactQuery Q{};
-        Q.text_off = (int64_t)text.size(); Q.len = m; Q.id = i;
-        bool acgt = true;
-        for (int64_t j = 0; j < m; j++) {
-            const uint8_t ch = queries[b + j];
-            if (!exact_symbol(ch)) return fail(ctx, KGMA_E_ARG, "kgma_exact_match: query %d, symbol %lld (0x%02x) is outside the DNA alphabet", i, (long long)j + 1, ch);
-            const uint8_t u = (uint8_t)(ch & 0xDFu);
-            acgt = acgt && (u == 'A' || u == 'C' || u == 'G' || u == 'T');
-            text.push_back(u);
-        }
-        ExactQuery P = Q;      // the same query for the 2-bit kernel
-        for (int64_t j = 0; j < std::min<int64_t>(m, 8); j++) {
-            Q.pat[j >> 2] |= (uint32_t)text[(size_t)(Q.text_off + j)] << (8 * (j & 3));
-            Q.mask[j >> 2] |= 0xFFu << (8 * (j & 3));
-        }
-        if (acgt)
-            for (int64_t j = 0; j < std::min<int64_t>(m, 16); j++) {
-                const uint8_t u = text[(size_t)(Q.text_off + j)];
-                P.pat[0] |= (u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : 3u) << (2 * j);
-                P.mask[0] |= 3u << (2 * j);
-            }
-        q_ascii.push_back(Q);
-        if (acgt) q_2bit.push_back(P);
-        else { P.len = 0; q_2bit.push_back(P); }       // len 0: not a 2-bit query
-    }
-    (void)hipSetDevice(ctx->device);
-    int rc = genome_ready(ctx, g, false);   // (first_bad and the 2-bit copy are current)
-    if (rc) return rc;
-    bool clean = true;                       // no residue outside A/C/G/T/N anywhere: nothing to check, and the 2-bit copy is faithful up to N
-    for (int64_t c = 0; c < g->n_contigs; c++) clean = clean && g->first_bad[(size_t)c] == NO_BAD;
-    const char *sw = getenv("KGMA_EXACT_ASCII");     // testing only: every query through the residue-text kernel
-    const bool allow_2bit = clean && !(sw && atoi(sw) != 0);
-    std::vector<ExactQuery> la, lb;
-    for (int32_t i = 0; i < n_queries; i++) {
-        if (allow_2bit && q_2bit[(size_t)i].len > 0) lb.push_back(q_2bit[(size_t)i]);
-        else la.push_back(q_ascii[(size_t)i]);
-    }
-    if ((rc = dev_reserve(ctx, ctx->d_xtext, ctx->xtext_cap, (int64_t)text.size() + 8))) return rc;
-    if (!text.empty()) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xtext, text.data(), text.size(), hipMemcpyHostToDevice, ctx->stream));
-    std::vector<kgma_match> found;
-    unsigned long long bad = NO_BAD;
-    int n_launches = 0;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    if (!la.empty() && (rc = exact_launch(ctx, g, clean ? 0 : 1, la, found, &bad, &n_launches))) return rc;
-    if (bad == NO_BAD && !lb.empty() && (rc = exact_launch(ctx, g, 2, lb, found, &bad, &n_launches))) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->stats.bases_scanned = g->total_bases;
-    ctx->stats.scan_ms = ms;
-    ctx->stats.n_launches = n_launches;
-    if (bad != NO_BAD) {
-        ctx->matches.clear();
-        return fail(ctx, KGMA_E_BADBASE, "record %lld: residue %lld is outside the DNA alphabet", (long long)(bad >> 40),
-                    (long long)(bad & ((1ull << 40) - 1)) + 1);
-    }
-    std::sort(found.begin(), found.end(), [](const kgma_match &x, const kgma_match &y) {
-        return x.query != y.query ? x.query < y.query : x.contig != y.contig ? x.contig < y.contig : x.start < y.start;
-    });
-    if (!overlap) {
-        // FindAll (src/ExactMatch.jl:20-30): the leftmost match, then the leftmost one that starts behind its end
-        size_t w = 0;
-        int64_t last_end = 0;
-        for (size_t i = 0; i < found.size(); i++) {
-            const kgma_match &mt = found[i];
-            const bool fresh = w == 0 || found[w - 1].query != mt.query || found[w - 1].contig != mt.contig;
-            if (!fresh && mt.start <= last_end) continue;
-            last_end = mt.start + qlen[(size_t)mt.query] - 1;
-            found[w++] = mt;
-        }
-        found.resize(w);
-    }
-    ctx->matches.swap(found);
-    return KGMA_OK;
-}
-
-int kgma_get_matches(kgma_ctx *ctx, kgma_match *out, int64_t cap, int64_t *n)
-{
-    if (!ctx || !n) return KGMA_E_ARG;
-    *n = (int64_t)ctx->matches.size();
-    if (!out) return KGMA_OK;
-    if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_matches: capacity %lld < %lld", (long long)cap, (long long)*n);
-    if (*n) memcpy(out, ctx->matches.data(), (size_t)*n * sizeof(kgma_match));
-    return KGMA_OK;
-}
-
-// ------------------------------------------------------------------------------------------
 // threshold calibration: distances of chosen windows of a genome and of mutated copies of sequences (the working form of
 // src/DistanceTesting.jl; kernels: kgma_calib.hip)
 // ------------------------------------------------------------------------------------------
@@ -6481,150 +6285,16 @@ int kgma_strobe_mutation_dists(kgma_ctx *ctx, const uint8_t *seqs, const int64_t
 }
 
 // ------------------------------------------------------------------------------------------
-// IUPAC motif search with mismatches (the working form of src/RSS.jl; kernel: kgma_motif.hip)
-// ------------------------------------------------------------------------------------------
-static_assert(sizeof(kgma_motif_hit) == sizeof(MotifHit), "kgma_motif_hit is the device record");
-
-// base set of an IUPAC symbol (bit 0 A, 1 C, 2 G, 3 T), either case; 0: not one of the 15 symbols
-static uint32_t iupac_set(uint8_t ch)
-{
-    switch (ch & 0xDFu) {
-    case 'A': return 1;  case 'C': return 2;  case 'G': return 4;  case 'T': return 8;
-    case 'R': return 5;  case 'Y': return 10; case 'S': return 6;  case 'W': return 9;
-    case 'K': return 12; case 'M': return 3;  case 'B': return 14; case 'D': return 13;
-    case 'H': return 11; case 'V': return 7;  case 'N': return 15;
-    default: return 0;
-    }
-}
-
-int kgma_motif_match(kgma_ctx *ctx, const kgma_genome *gc, const uint8_t *motifs, const int64_t *offsets, int32_t n_motifs,
-                     const int32_t *max_mismatch)
-{
-    if (!ctx || !gc) return KGMA_E_ARG;
-    ctx->motif_hits.clear();                           // (whatever happens below: a failed call leaves no hits of an earlier one behind)
-    if (n_motifs < 0 || (n_motifs > 0 && (!motifs || !offsets || !max_mismatch))) return fail(ctx, KGMA_E_ARG, "kgma_motif_match: no motifs");
-    kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping and its lazily made plane copy are updated
-    std::vector<MotifDesc> descs;
-    std::vector<uint32_t> info;
-    int P = 0;
-    for (int32_t i = 0; i < n_motifs; i++) {
-        const int64_t b = offsets[i], m = offsets[i + 1] - b;
-        if (m < 1 || m > 64) return fail(ctx, KGMA_E_ARG, "kgma_motif_match: motif %d has %lld symbols (1 ... 64)", i, (long long)m);
-        const int32_t d = max_mismatch[i];
-        if (d < 0 || d > 15) return fail(ctx, KGMA_E_ARG, "kgma_motif_match: motif %d: max_mismatch %d (0 ... 15)", i, d);
-        MotifDesc M{};
-        M.info_off = (int32_t)info.size(); M.len = (int32_t)m; M.max_mm = d; M.id = i;
-        for (int64_t j = 0; j < m; j++) {
-            const uint32_t set = iupac_set(motifs[b + j]);
-            if (!set) return fail(ctx, KGMA_E_ARG, "kgma_motif_match: motif %d, symbol %lld (0x%02x) is not an IUPAC nucleotide code", i, (long long)j + 1, motifs[b + j]);
-            if (set == 15u) continue;
-            info.push_back((uint32_t)j | (set << 8));          // (offsets ascend: those below 32 come first)
-            if (j < 32) M.n_lo++; else M.n_hi++;
-        }
-        if (d >= M.n_lo + M.n_hi)
-            return fail(ctx, KGMA_E_ARG, "kgma_motif_match: motif %d: max_mismatch %d is not smaller than its %d informative (non-N) positions: every start would match",
-                        i, d, M.n_lo + M.n_hi);
-        info.push_back(0x0F00u);                               // the spare entry the kernel's read-ahead touches
-        P = std::max(P, motif_planes(d));
-        descs.push_back(M);
-    }
-    (void)hipSetDevice(ctx->device);
-    int rc = genome_ready(ctx, g, true);   // (first_bad and the plane copy are current)
-    if (rc) return rc;
-    ctx->stats.bases_scanned = g->total_bases;
-    ctx->stats.scan_ms = 0;
-    ctx->stats.n_launches = 0;
-    for (int64_t c = 0; c < g->n_contigs; c++)
-        if (g->first_bad[(size_t)c] != NO_BAD) {
-            return fail(ctx, KGMA_E_BADBASE, "record %lld: residue %llu is not one of A/C/G/T/N", (long long)c, g->first_bad[(size_t)c]);   // (first_bad is 1-based)
-        }
-    const int64_t nc = g->n_contigs;
-    const std::vector<int64_t> prefix = tile_prefix(nc, motif_tile_starts(), false, [&](int64_t c) { return g->cd[(size_t)c].len; });
-    const int64_t n_tiles = prefix[(size_t)nc];
-    if (n_tiles > 0x7FFFFFFFll) return fail(ctx, KGMA_E_UNSUPPORTED, "kgma_motif_match: %lld tiles exceed one launch", (long long)n_tiles);
-    std::vector<kgma_motif_hit> found;
-    if (n_motifs > 0 && n_tiles > 0) {
-        if ((rc = dev_reserve(ctx, ctx->d_mq, ctx->mq_cap, (int64_t)descs.size()))) return rc;
-        if ((rc = dev_reserve(ctx, ctx->d_minfo, ctx->minfo_cap, (int64_t)info.size()))) return rc;
-        if ((rc = dev_reserve(ctx, ctx->d_mprefix, ctx->mprefix_cap, nc + 1))) return rc;
-        if ((rc = dev_reserve(ctx, ctx->d_mctl, ctx->mctl_cap, 2))) return rc;
-        if ((rc = dev_reserve(ctx, ctx->d_mout, ctx->mout_cap, (int64_t)1 << 16))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mq, descs.data(), descs.size() * sizeof(MotifDesc), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_minfo, info.data(), info.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mprefix, prefix.data(), prefix.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        unsigned long long ctl[2] = {0, 0};
-        int n_launches = 0;
-        // one launch for the whole batch; hits that do not fit the device buffer: once more with a buffer of the size it counted
-        for (int attempt = 0;; attempt++) {
-            MotifArgs a{};
-            a.planes = reinterpret_cast<const uint32_t *>(g->d_planes); a.ascii = g->d_ascii; a.cd = g->d_cd; a.tile_prefix = ctx->d_mprefix;
-            a.n_contigs = (int32_t)nc; a.n_motifs = (int32_t)descs.size();
-            a.motifs = ctx->d_mq; a.info = ctx->d_minfo; a.out = ctx->d_mout; a.ctl = ctx->d_mctl; a.cap = (unsigned long long)ctx->mout_cap;
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_mctl, 0, 2 * sizeof(unsigned long long), ctx->stream));
-            HIP_TRY(ctx, launch_motif(a, P, n_tiles, ctx->stream));
-            n_launches++;
-            HIP_TRY(ctx, hipMemcpyAsync(ctl, ctx->d_mctl, sizeof ctl, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctl[0] <= (unsigned long long)ctx->mout_cap) break;
-            if (attempt == 1) return fail(ctx, KGMA_E_OVERFLOW, "kgma_motif_match: %llu hits overflowed the regrown buffer", ctl[0]);
-            // the larger buffer is taken before the old one is given up: without room for it the context stays as it was
-            MotifHit *fresh = nullptr;
-            if (ctl[0] > (1ull << 40) || hipMalloc(reinterpret_cast<void **>(&fresh), (size_t)ctl[0] * sizeof(MotifHit)) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(ctx, KGMA_E_NOMEM, "kgma_motif_match: no device memory for %llu hits", ctl[0]);
-            }
-            (void)hipFree(ctx->d_mout);
-            ctx->device_bytes += ((int64_t)ctl[0] - ctx->mout_cap) * (int64_t)sizeof(MotifHit);
-            ctx->d_mout = fresh; ctx->mout_cap = (int64_t)ctl[0];
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-        ctx->stats.scan_ms = ms;
-        ctx->stats.n_launches = n_launches;
-        found.resize((size_t)ctl[0]);
-        if (ctl[0]) HIP_TRY(ctx, hipMemcpy(found.data(), ctx->d_mout, (size_t)ctl[0] * sizeof(kgma_motif_hit), hipMemcpyDeviceToHost));
-        std::sort(found.begin(), found.end(), [](const kgma_motif_hit &x, const kgma_motif_hit &y) {
-            return x.motif != y.motif ? x.motif < y.motif : x.contig != y.contig ? x.contig < y.contig : x.start < y.start;
-        });
-    }
-    ctx->motif_hits.swap(found);
-    return KGMA_OK;
-}
-
-int kgma_get_motif_matches(kgma_ctx *ctx, kgma_motif_hit *out, int64_t cap, int64_t *n)
-{
-    if (!ctx || !n) return KGMA_E_ARG;
-    *n = (int64_t)ctx->motif_hits.size();
-    if (!out) return KGMA_OK;
-    if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_motif_matches: capacity %lld < %lld", (long long)cap, (long long)*n);
-    if (*n) memcpy(out, ctx->motif_hits.data(), (size_t)*n * sizeof(kgma_motif_hit));
-    return KGMA_OK;
-}
-
-// ------------------------------------------------------------------------------------------
 // results
 // ------------------------------------------------------------------------------------------
 int kgma_get_hits(kgma_ctx *ctx, kgma_hit *out, int64_t cap, int64_t *n)
 {
-    if (!ctx || !n) return KGMA_E_ARG;
-    *n = (int64_t)ctx->hits.size();
-    if (!out) return KGMA_OK;
-    if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_hits: capacity %lld < %lld", (long long)cap, (long long)*n);
-    if (*n) memcpy(out, ctx->hits.data(), (size_t)*n * sizeof(kgma_hit));
-    return KGMA_OK;
+    return ctx ? copy_out(ctx, "kgma_get_hits", ctx->hits, out, cap, n) : KGMA_E_ARG;
 }
 
 int kgma_get_dips(kgma_ctx *ctx, kgma_dip *out, int64_t cap, int64_t *n)
 {
-    if (!ctx || !n) return KGMA_E_ARG;
-    *n = (int64_t)ctx->dips.size();
-    if (!out) return KGMA_OK;
-    if (cap < *n) return fail(ctx, KGMA_E_ARG, "kgma_get_dips: capacity %lld < %lld", (long long)cap, (long long)*n);
-    if (*n) memcpy(out, ctx->dips.data(), (size_t)*n * sizeof(kgma_dip));
-    return KGMA_OK;
+    return ctx ? copy_out(ctx, "kgma_get_dips", ctx->dips, out, cap, n) : KGMA_E_ARG;
 }
 
 int kgma_get_first_window(kgma_ctx *ctx, int32_t kfv, int64_t *out, int64_t cap, int64_t *n)

@@ -9,8 +9,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -22,36 +20,6 @@ using namespace kgma;
 static_assert(sizeof(kgma_approx_hit) == sizeof(ApproxHit), "kgma_approx_hit is the device record");
 
 namespace {
-
-constexpr int64_t FIRST_CAP = (int64_t)1 << 16;
-
-int failf(kgma_ctx *ctx, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return ctx_fail(ctx, code, buf);
-}
-
-#define A_TRY(expr)                                                                                          \
-    do {                                                                                                     \
-        const hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) return failf(ctx, KGMA_E_HIP, "%s: %s failed: %s", fn, #expr, hipGetErrorString(e__)); \
-    } while (0)
-
-// base set of an IUPAC symbol (bit 0 A, 1 C, 2 G, 3 T), either case; 0: not one of the 15 symbols
-uint32_t iupac_set(uint8_t ch)
-{
-    switch (ch & 0xDFu) {
-    case 'A': return 1;  case 'C': return 2;  case 'G': return 4;  case 'T': return 8;
-    case 'R': return 5;  case 'Y': return 10; case 'S': return 6;  case 'W': return 9;
-    case 'K': return 12; case 'M': return 3;  case 'B': return 14; case 'D': return 13;
-    case 'H': return 11; case 'V': return 7;  case 'N': return 15;
-    default: return 0;
-    }
-}
 
 // residue class (kgma_approx.h) of the bases A C G T, and of N
 constexpr int BASE_CLASS[4] = {('A' >> 1) & 7, ('C' >> 1) & 7, ('G' >> 1) & 7, ('T' >> 1) & 7};
@@ -122,10 +90,9 @@ int kgma_approx_match(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *q
     int rc = genome_searchable(ctx, genome);
     if (rc) return rc;
     const GenomeText g = genome_text(genome);
-    std::vector<int64_t> prefix((size_t)g.n_contigs + 1, 0);
-    for (int64_t c = 0; c < g.n_contigs; c++) prefix[(size_t)c + 1] = prefix[(size_t)c] + (g.cd[c].len + AP_WG_BASES - 1) / AP_WG_BASES;
+    const std::vector<int64_t> prefix = tile_prefix(g.n_contigs, AP_WG_BASES, false, [&](int64_t c) { return g.cd[c].len; });
     const int64_t n_wg = prefix[(size_t)g.n_contigs];
-    if (n_wg > 0x7FFFFFFFll) return failf(ctx, KGMA_E_UNSUPPORTED, "%s: %lld workgroups exceed one launch", fn, (long long)n_wg);
+    if ((rc = one_launch(ctx, fn, n_wg, "workgroups"))) return rc;
     kgma_approx_stats T{};
     T.tile = AP_TILE; T.wg_bases = AP_WG_BASES; T.words = words;
     if (n_queries == 0 || n_wg == 0) { S->stats = T; return KGMA_OK; }
@@ -135,52 +102,29 @@ int kgma_approx_match(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *q
     ctx_device(ctx, &device, &st);
     (void)hipSetDevice(device);
     DeviceHold hold;
-    if (!S->d_out) {
-        if (hipMalloc(reinterpret_cast<void **>(&S->d_out), (size_t)FIRST_CAP * sizeof(ApproxHit)) != hipSuccess) {
-            (void)hipGetLastError();
-            S->d_out = nullptr;
-            return failf(ctx, KGMA_E_NOMEM, "%s: no device memory for the hit buffer", fn);
-        }
-        S->out_cap = FIRST_CAP;
-        *ctx_device_bytes(ctx) += FIRST_CAP * (int64_t)sizeof(ApproxHit);
-    }
+    if ((rc = S->out.reserve(ctx, fn))) return rc;
     ApproxArgs a;
     memset(&a, 0, sizeof a);
     ApproxQuery *d_q = nullptr;
     int64_t *d_prefix = nullptr;
-    A_TRY(hold.upload(d_q, Q.data(), Q.size(), st));
-    A_TRY(hold.upload(d_prefix, prefix.data(), prefix.size(), st));
-    A_TRY(hold.alloc(a.ctl, 2));
-    for (int e = 0; e < 4; e++) A_TRY(hipEventCreate(&hold.ev[e]));
+    KGMA_TRY(hold.upload(d_q, Q.data(), Q.size(), st));
+    KGMA_TRY(hold.upload(d_prefix, prefix.data(), prefix.size(), st));
+    KGMA_TRY(hold.alloc(a.ctl, 2));
+    for (int e = 0; e < 4; e++) KGMA_TRY(hipEventCreate(&hold.ev[e]));
     a.ascii = g.d_ascii; a.cd = g.d_cd; a.wg_prefix = d_prefix; a.n_contigs = (int32_t)g.n_contigs; a.n_queries = n_queries;
     a.queries = d_q;
 
-    // one launch for the whole batch; ends that do not fit the device buffer: once more with a buffer of the size it counted
     unsigned long long ctl[2] = {0, 0};
-    A_TRY(hipEventRecord(hold.ev[0], st));
-    for (int attempt = 0;; attempt++) {
-        a.out = S->d_out; a.cap = (unsigned long long)S->out_cap;
-        A_TRY(hipMemsetAsync(a.ctl, 0, 2 * sizeof(unsigned long long), st));
-        A_TRY(launch_approx(a, words, n_wg, st));
-        T.n_launches++;
-        A_TRY(hipMemcpyAsync(ctl, a.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-        A_TRY(hipStreamSynchronize(st));
-        if (ctl[0] <= (unsigned long long)S->out_cap) break;
-        if (attempt == 1) return failf(ctx, KGMA_E_OVERFLOW, "%s: %llu hits overflowed the regrown buffer", fn, ctl[0]);
-        // the larger buffer is taken before the old one is given up: without room for it the context stays as it was
-        ApproxHit *fresh = nullptr;
-        if (ctl[0] > (1ull << 40) || hipMalloc(reinterpret_cast<void **>(&fresh), (size_t)ctl[0] * sizeof(ApproxHit)) != hipSuccess) {
-            (void)hipGetLastError();
-            return failf(ctx, KGMA_E_NOMEM, "%s: no device memory for %llu hits", fn, ctl[0]);
-        }
-        (void)hipFree(S->d_out);
-        *ctx_device_bytes(ctx) += ((int64_t)ctl[0] - S->out_cap) * (int64_t)sizeof(ApproxHit);
-        S->d_out = fresh; S->out_cap = (int64_t)ctl[0];
-    }
-    A_TRY(hipEventRecord(hold.ev[1], st));
-    std::vector<kgma_approx_hit> found((size_t)ctl[0]);
-    if (ctl[0]) A_TRY(hipMemcpyAsync(found.data(), S->d_out, found.size() * sizeof(kgma_approx_hit), hipMemcpyDeviceToHost, st));
-    A_TRY(hipStreamSynchronize(st));
+    KGMA_TRY(hipEventRecord(hold.ev[0], st));
+    rc = S->out.fill(ctx, fn, "hits", st, a.ctl, ctl, [&](ApproxHit *out, unsigned long long cap, unsigned long long *) {
+        a.out = out; a.cap = cap;
+        return launch_approx(a, words, n_wg, st);
+    }, &T.n_launches);
+    if (rc) return rc;
+    KGMA_TRY(hipEventRecord(hold.ev[1], st));
+    std::vector<kgma_approx_hit> found;
+    if ((rc = S->out.fetch(ctx, fn, ctl[0], found))) return rc;
+    KGMA_TRY(hipStreamSynchronize(st));            // (the second event has been reached)
     std::sort(found.begin(), found.end(), [](const kgma_approx_hit &x, const kgma_approx_hit &y) {
         return x.query != y.query ? x.query < y.query : x.contig != y.contig ? x.contig < y.contig : x.end < y.end;
     });
@@ -192,21 +136,21 @@ int kgma_approx_match(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *q
     float ms = 0;
     if (!found.empty()) {
         a.n_hits = (int64_t)found.size();
-        A_TRY(hipMemcpyAsync(S->d_out, found.data(), found.size() * sizeof(kgma_approx_hit), hipMemcpyHostToDevice, st));
-        A_TRY(hipEventRecord(hold.ev[2], st));
-        A_TRY(launch_approx_starts(a, st));
+        KGMA_TRY(hipMemcpyAsync(S->out.d, found.data(), found.size() * sizeof(kgma_approx_hit), hipMemcpyHostToDevice, st));
+        KGMA_TRY(hipEventRecord(hold.ev[2], st));
+        KGMA_TRY(launch_approx_starts(a, st));
         T.n_launches++;
-        A_TRY(hipEventRecord(hold.ev[3], st));
-        A_TRY(hipMemcpyAsync(found.data(), S->d_out, found.size() * sizeof(kgma_approx_hit), hipMemcpyDeviceToHost, st));
-        A_TRY(hipStreamSynchronize(st));
-        A_TRY(hipEventElapsedTime(&ms, hold.ev[2], hold.ev[3]));
+        KGMA_TRY(hipEventRecord(hold.ev[3], st));
+        KGMA_TRY(hipMemcpyAsync(found.data(), S->out.d, found.size() * sizeof(kgma_approx_hit), hipMemcpyDeviceToHost, st));
+        KGMA_TRY(hipStreamSynchronize(st));
+        KGMA_TRY(hipEventElapsedTime(&ms, hold.ev[2], hold.ev[3]));
         T.starts_ms = ms;
         for (const kgma_approx_hit &h : found)
             if (h.start < 1 || h.start > h.end)
                 return failf(ctx, KGMA_E_STATE, "%s: query %d, record %d, end %lld: no start attains %d edits", fn, h.query, h.contig,
                              (long long)h.end, h.edits);
     }
-    A_TRY(hipEventElapsedTime(&ms, hold.ev[0], hold.ev[1]));
+    KGMA_TRY(hipEventElapsedTime(&ms, hold.ev[0], hold.ev[1]));
     T.search_ms = ms;
     kgma_stats *stats = ctx_stats(ctx);
     stats->scan_ms = T.search_ms + T.starts_ms;
@@ -218,13 +162,7 @@ int kgma_approx_match(kgma_ctx *ctx, const kgma_genome *genome, const uint8_t *q
 
 int kgma_get_approx_matches(kgma_ctx *ctx, kgma_approx_hit *out, int64_t cap, int64_t *n)
 {
-    if (!ctx || !n) return KGMA_E_ARG;
-    const std::vector<kgma_approx_hit> &hits = ctx_approx(ctx)->hits;
-    *n = (int64_t)hits.size();
-    if (!out) return KGMA_OK;
-    if (cap < *n) return failf(ctx, KGMA_E_ARG, "kgma_get_approx_matches: capacity %lld < %lld", (long long)cap, (long long)*n);
-    if (*n) memcpy(out, hits.data(), (size_t)*n * sizeof(kgma_approx_hit));
-    return KGMA_OK;
+    return ctx ? copy_out(ctx, "kgma_get_approx_matches", ctx_approx(ctx)->hits, out, cap, n) : KGMA_E_ARG;
 }
 
 int kgma_get_approx_stats(kgma_ctx *ctx, kgma_approx_stats *out)

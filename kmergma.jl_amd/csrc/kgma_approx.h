@@ -1,14 +1,8 @@
-// kgma_approx.h -- what kgma_approx.cpp (host) and kgma_approx.hip (kernels) share, and the view the host file has of a context
-// and a genome (defined in kgma_api.cpp, which owns the structs).
+// kgma_approx.h -- what kgma_approx.cpp (host) and kgma_approx.hip (kernels) share, and what the context keeps for the search.
 #ifndef KGMA_APPROX_H
 #define KGMA_APPROX_H
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <vector>
-
-#include "kgma_assign.h"
+#include "kgma_search.h"
 
 namespace kgma {
 
@@ -61,20 +55,14 @@ hipError_t launch_approx_starts(const ApproxArgs &a, hipStream_t st);
 // What the context keeps for kgma_approx_match: the device buffer of the hits (kept between calls), the hits and the stats of the
 // last call
 struct ApproxState {
-    ApproxHit *d_out = nullptr;
-    int64_t out_cap = 0;
+    HitBuffer<ApproxHit> out;
     std::vector<kgma_approx_hit> hits;
     kgma_approx_stats stats{};
+    void release() { out.release(); }
 };
 
-// kgma_api.cpp.  ctx_approx: the state above (released by kgma_destroy).  ctx_device_bytes: the context's account of its device
-// memory.  ctx_stats: its kgma_stats.  genome_searchable: what the searches do before they launch -- the pack's residue check is
-// made current, bases_scanned is set and scan_ms / n_launches are zeroed in kgma_stats, and a residue outside A/C/G/T/N in any
-// record is KGMA_E_BADBASE.
+// kgma_api.cpp: the state above (released by kgma_destroy)
 ApproxState *ctx_approx(kgma_ctx *ctx);
-int64_t *ctx_device_bytes(kgma_ctx *ctx);
-kgma_stats *ctx_stats(kgma_ctx *ctx);
-int genome_searchable(kgma_ctx *ctx, const kgma_genome *g);
 
 }  // namespace kgma
 

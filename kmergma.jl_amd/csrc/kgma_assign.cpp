@@ -12,7 +12,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <numeric>
@@ -26,16 +25,6 @@ static_assert(sizeof(kgma_assignment) == 8 * sizeof(int32_t), "assign_trace_kern
 static_assert(KGMA_ASSIGN_MAX_LEN == kgma::KGMA_ASSIGN_LEN_MAX, "kgma.h and kgma_device.h agree on the longest sequence");
 
 namespace {
-
-int failf(kgma_ctx *ctx, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return ctx_fail(ctx, code, buf);
-}
 
 int check_refs(kgma_ctx *ctx, const char *fn, const uint8_t *refs, const int64_t *ref_offsets, int32_t n_refs, int32_t go, int32_t ge,
                int32_t top, int64_t n_queries, const void *out)

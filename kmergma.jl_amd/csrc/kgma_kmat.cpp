@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -23,16 +22,6 @@ namespace {
 
 constexpr unsigned long long NO_BAD = ~0ull;
 constexpr int64_t MAX_PAIRS = (int64_t)1 << 30;
-
-int failf(kgma_ctx *ctx, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return ctx_fail(ctx, code, buf);
-}
 
 #define K_TRY(expr)                                                                                          \
     do {                                                                                                     \

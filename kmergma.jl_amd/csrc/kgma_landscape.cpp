@@ -8,7 +8,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -20,16 +19,6 @@ using namespace kgma;
 namespace {
 
 constexpr int64_t MAX_VALUES = (int64_t)1 << 40;      // a workgroup's 32-bit counters and the grids hold far more than any device does
-
-int failf(kgma_ctx *ctx, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return ctx_fail(ctx, code, buf);
-}
 
 #define L_TRY(expr)                                                                                          \
     do {                                                                                                     \

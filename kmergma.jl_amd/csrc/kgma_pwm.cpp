@@ -4,14 +4,11 @@
 // One call: check the arguments, fold each matrix (the rows of four equal weights become a constant that moves into the threshold,
 // every other row and the row behind it one table of 64 sums indexed by two residue classes; a matrix whose threshold lies above
 // the sum of its row maxima is not sent at all), upload the matrices, their tables and the per-record prefix of workgroup counts,
-// run the kernel -- once more with a buffer of the size it counted when the hits outgrow the buffer -- bring the hits down and
-// sort them by (matrix, contig, start).  The hit buffer belongs to the context and is kept between calls; everything else is
-// freed before the call returns.
+// run the kernel by the protocol of kgma_search.h and sort the hits by (matrix, contig, start).  The hit buffer belongs to the
+// context and is kept between calls; everything else is freed before the call returns.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -22,24 +19,6 @@ using namespace kgma;
 static_assert(sizeof(kgma_pwm_hit) == sizeof(PwmHit), "kgma_pwm_hit is the device record");
 
 namespace {
-
-constexpr int64_t FIRST_CAP = (int64_t)1 << 16;
-
-int failf(kgma_ctx *ctx, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return ctx_fail(ctx, code, buf);
-}
-
-#define P_TRY(expr)                                                                                          \
-    do {                                                                                                     \
-        const hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) return failf(ctx, KGMA_E_HIP, "%s: %s failed: %s", fn, #expr, hipGetErrorString(e__)); \
-    } while (0)
 
 // weight of a row (A, C, G, T) for a residue class of the text (kgma_approx.h: A 0, C 1, T 2, G 3, N 7): a genome N scores the
 // row's minimum; the classes no residue of a checked genome has, and the one the kernel puts where there is no residue, score 0
@@ -108,13 +87,9 @@ int kgma_pwm_match(kgma_ctx *ctx, const kgma_genome *genome, const int16_t *weig
     if (rc) return rc;
     const GenomeText g = genome_text(genome);
     // workgroups of a record: over the starts its shortest matrix has there
-    std::vector<int64_t> prefix((size_t)g.n_contigs + 1, 0);
-    for (int64_t c = 0; c < g.n_contigs; c++) {
-        const int64_t starts = std::max<int64_t>(0, g.cd[c].len - m_min + 1);
-        prefix[(size_t)c + 1] = prefix[(size_t)c] + (starts + PW_WG_STARTS - 1) / PW_WG_STARTS;
-    }
+    const std::vector<int64_t> prefix = tile_prefix(g.n_contigs, PW_WG_STARTS, false, [&](int64_t c) { return g.cd[c].len; }, m_min);
     const int64_t n_wg = prefix[(size_t)g.n_contigs];
-    if (n_wg > 0x7FFFFFFFll) return failf(ctx, KGMA_E_UNSUPPORTED, "%s: %lld workgroups exceed one launch", fn, (long long)n_wg);
+    if ((rc = one_launch(ctx, fn, n_wg, "workgroups"))) return rc;
     kgma_pwm_stats T{};
     T.lane_starts = PW_LANE_STARTS; T.wave_starts = PW_WAVE_STARTS; T.wg_starts = PW_WG_STARTS;
     if (Q.empty() || n_wg == 0) { S->stats = T; return KGMA_OK; }
@@ -124,60 +99,37 @@ int kgma_pwm_match(kgma_ctx *ctx, const kgma_genome *genome, const int16_t *weig
     ctx_device(ctx, &device, &st);
     (void)hipSetDevice(device);
     DeviceHold hold;
-    if (!S->d_out) {
-        if (hipMalloc(reinterpret_cast<void **>(&S->d_out), (size_t)FIRST_CAP * sizeof(PwmHit)) != hipSuccess) {
-            (void)hipGetLastError();
-            S->d_out = nullptr;
-            return failf(ctx, KGMA_E_NOMEM, "%s: no device memory for the hit buffer", fn);
-        }
-        S->out_cap = FIRST_CAP;
-        *ctx_device_bytes(ctx) += FIRST_CAP * (int64_t)sizeof(PwmHit);
-    }
+    if ((rc = S->out.reserve(ctx, fn))) return rc;
     PwmArgs a;
     memset(&a, 0, sizeof a);
     PwmMatrix *d_q = nullptr;
     int32_t *d_tab = nullptr;
     int64_t *d_prefix = nullptr;
-    P_TRY(hold.upload(d_q, Q.data(), Q.size(), st));
-    P_TRY(hold.upload(d_tab, tables.data(), tables.size(), st));
-    P_TRY(hold.upload(d_prefix, prefix.data(), prefix.size(), st));
-    P_TRY(hold.alloc(a.ctl, 2));
-    for (int e = 0; e < 2; e++) P_TRY(hipEventCreate(&hold.ev[e]));
+    KGMA_TRY(hold.upload(d_q, Q.data(), Q.size(), st));
+    KGMA_TRY(hold.upload(d_tab, tables.data(), tables.size(), st));
+    KGMA_TRY(hold.upload(d_prefix, prefix.data(), prefix.size(), st));
+    KGMA_TRY(hold.alloc(a.ctl, 2));
+    for (int e = 0; e < 2; e++) KGMA_TRY(hipEventCreate(&hold.ev[e]));
     a.ascii = g.d_ascii; a.cd = g.d_cd; a.wg_prefix = d_prefix; a.n_contigs = (int32_t)g.n_contigs; a.n_matrices = (int32_t)Q.size();
     a.matrices = d_q; a.tables = d_tab;
 
-    // one launch for the whole batch; hits that do not fit the device buffer: once more with a buffer of the size it counted
     unsigned long long ctl[2] = {0, 0};
-    P_TRY(hipEventRecord(hold.ev[0], st));
-    for (int attempt = 0;; attempt++) {
-        a.out = S->d_out; a.cap = (unsigned long long)S->out_cap;
-        P_TRY(hipMemsetAsync(a.ctl, 0, 2 * sizeof(unsigned long long), st));
-        P_TRY(launch_pwm(a, n_wg, st));
-        T.n_launches++;
-        P_TRY(hipMemcpyAsync(ctl, a.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-        P_TRY(hipStreamSynchronize(st));
-        if (ctl[0] <= (unsigned long long)S->out_cap) break;
-        if (attempt == 1) return failf(ctx, KGMA_E_OVERFLOW, "%s: %llu hits overflowed the regrown buffer", fn, ctl[0]);
-        // the larger buffer is taken before the old one is given up: without room for it the context stays as it was
-        PwmHit *fresh = nullptr;
-        if (ctl[0] > (1ull << 40) || hipMalloc(reinterpret_cast<void **>(&fresh), (size_t)ctl[0] * sizeof(PwmHit)) != hipSuccess) {
-            (void)hipGetLastError();
-            return failf(ctx, KGMA_E_NOMEM, "%s: no device memory for %llu hits", fn, ctl[0]);
-        }
-        (void)hipFree(S->d_out);
-        *ctx_device_bytes(ctx) += ((int64_t)ctl[0] - S->out_cap) * (int64_t)sizeof(PwmHit);
-        S->d_out = fresh; S->out_cap = (int64_t)ctl[0];
-    }
-    P_TRY(hipEventRecord(hold.ev[1], st));
-    std::vector<kgma_pwm_hit> found((size_t)ctl[0]);
-    if (ctl[0]) P_TRY(hipMemcpyAsync(found.data(), S->d_out, found.size() * sizeof(kgma_pwm_hit), hipMemcpyDeviceToHost, st));
-    P_TRY(hipStreamSynchronize(st));
+    KGMA_TRY(hipEventRecord(hold.ev[0], st));
+    rc = S->out.fill(ctx, fn, "hits", st, a.ctl, ctl, [&](PwmHit *out, unsigned long long cap, unsigned long long *) {
+        a.out = out; a.cap = cap;
+        return launch_pwm(a, n_wg, st);
+    }, &T.n_launches);
+    if (rc) return rc;
+    KGMA_TRY(hipEventRecord(hold.ev[1], st));
+    std::vector<kgma_pwm_hit> found;
+    if ((rc = S->out.fetch(ctx, fn, ctl[0], found))) return rc;
+    KGMA_TRY(hipStreamSynchronize(st));            // (the second event has been reached)
     std::sort(found.begin(), found.end(), [](const kgma_pwm_hit &x, const kgma_pwm_hit &y) {
         return x.matrix != y.matrix ? x.matrix < y.matrix : x.contig != y.contig ? x.contig < y.contig : x.start < y.start;
     });
     T.n_candidates = T.n_hits = (int64_t)found.size();
     float ms = 0;
-    P_TRY(hipEventElapsedTime(&ms, hold.ev[0], hold.ev[1]));
+    KGMA_TRY(hipEventElapsedTime(&ms, hold.ev[0], hold.ev[1]));
     T.search_ms = ms;
     kgma_stats *stats = ctx_stats(ctx);
     stats->scan_ms = T.search_ms;
@@ -189,13 +141,7 @@ int kgma_pwm_match(kgma_ctx *ctx, const kgma_genome *genome, const int16_t *weig
 
 int kgma_get_pwm_matches(kgma_ctx *ctx, kgma_pwm_hit *out, int64_t cap, int64_t *n)
 {
-    if (!ctx || !n) return KGMA_E_ARG;
-    const std::vector<kgma_pwm_hit> &hits = ctx_pwm(ctx)->hits;
-    *n = (int64_t)hits.size();
-    if (!out) return KGMA_OK;
-    if (cap < *n) return failf(ctx, KGMA_E_ARG, "kgma_get_pwm_matches: capacity %lld < %lld", (long long)cap, (long long)*n);
-    if (*n) memcpy(out, hits.data(), (size_t)*n * sizeof(kgma_pwm_hit));
-    return KGMA_OK;
+    return ctx ? copy_out(ctx, "kgma_get_pwm_matches", ctx_pwm(ctx)->hits, out, cap, n) : KGMA_E_ARG;
 }
 
 int kgma_get_pwm_stats(kgma_ctx *ctx, kgma_pwm_stats *out)

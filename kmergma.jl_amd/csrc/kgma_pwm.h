@@ -1,14 +1,8 @@
-// kgma_pwm.h -- what kgma_pwm.cpp (host) and kgma_pwm.hip (kernel) share, and the view the host file has of a context and a
-// genome (defined in kgma_api.cpp, which owns the structs).
+// kgma_pwm.h -- what kgma_pwm.cpp (host) and kgma_pwm.hip (kernel) share, and what the context keeps for the search.
 #ifndef KGMA_PWM_H
 #define KGMA_PWM_H
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <vector>
-
-#include "kgma_approx.h"
+#include "kgma_approx.h"   // (the residue classes of the text)
 
 namespace kgma {
 
@@ -63,10 +57,10 @@ hipError_t launch_pwm(const PwmArgs &a, int64_t n_wg, hipStream_t st);
 // What the context keeps for kgma_pwm_match: the device buffer of the hits (kept between calls), the hits and the stats of the
 // last call
 struct PwmState {
-    PwmHit *d_out = nullptr;
-    int64_t out_cap = 0;
+    HitBuffer<PwmHit> out;
     std::vector<kgma_pwm_hit> hits;
     kgma_pwm_stats stats{};
+    void release() { out.release(); }
 };
 
 // kgma_api.cpp: the state above (released by kgma_destroy)
