@@ -954,6 +954,45 @@ int kgma_assign_ranges_screened(kgma_ctx *ctx, const kgma_genome *genome, const 
                                 int32_t gap_extend_score, int32_t top, int32_t screen_k, int32_t n_near, kgma_assignment *out,
                                 int32_t *cand, int32_t *scores);
 
+/* ---- k-mer counts of the resident genome (kgma_spectrum.hip, kgma_spectrum.cpp) ----
+ * counts[r * 4^k + x] = how often the k-mer of value x (first base most significant: the order of kgma_kmer_count_batch and of
+ * kgma_set_refs) begins at a considered start of range r: residues lo[r] .. hi[r] (1-based inclusive) of record contig[r] (0-based)
+ * of length L; hi = lo - 1 is an empty range.  Ranges may be unsorted, overlapping or duplicated; each has its own row.
+ *
+ * Considered starts: every p with lo <= p and p + k - 1 <= hi -- the row is kmer_count(view(seq, lo:hi), k) (src/Kmers.jl:14-28).
+ * With KGMA_COUNT_BY_START: every p in lo .. hi with p + k - 1 <= L: a k-mer belongs to the range it starts in, so the rows of
+ * ranges that tile a record sum to the record's whole count.
+ *
+ * flags == 0 (or BY_START alone): residues go through the reference's code table, A0 C1 G2 T3 and N -> 3, in either case.  Every
+ * residue the range covers is looked up, also when the range is shorter than k (BY_START: lo .. min(hi + k - 1, L)); a byte
+ * outside A/C/G/T/N among them is KGMA_E_BADBASE (the reference's KeyError) and kgma_last_error names the smallest (record,
+ * position) among such bytes; such a byte outside every requested range is no error.  For a whole record (lo = 1, hi = L) the row
+ * equals kgma_kmer_count_batch of the same bytes, value for value.
+ * KGMA_COUNT_SKIP_N: a considered start whose k residues hold a byte outside A/C/G/T (either case) is not counted but counted in
+ * n_skipped[r]; there is no KGMA_E_BADBASE in this mode, IUPAC codes are skipped like N.
+ * KGMA_COUNT_SKIP_MASKED: a considered start whose k residues hold a lower-case byte (the soft-mask of a .2bit genome) is not
+ * counted either and goes to n_skipped[r] too.  The flags combine freely; without SKIP_N an N in either case still counts as T and
+ * a byte outside A/C/G/T/N is still KGMA_E_BADBASE, masked or not.
+ * INVARIANT: the sum of row r plus n_skipped[r] is the number of considered starts of range r.
+ *
+ * 1 <= k <= 10.  KGMA_E_UNSUPPORTED: k > 10; n_ranges * 4^k > 2^28 (2 GiB of counts).  KGMA_E_ARG: a null pointer (n_skipped may
+ * be NULL), k < 1, unknown flag bits, a record out of range, lo < 1, hi > L or hi < lo - 1 (kgma_last_error names the range).
+ * n_ranges == 0: KGMA_OK.  KGMA_E_NOMEM leaves the context usable.  The call needs no kgma_set_refs; nothing stays allocated after
+ * it; it leaves references, thresholds, hits, dips, distances, alignments and the matches of the four searches untouched.  Of
+ * kgma_stats it sets scan_ms and n_launches only; kgma_scan_kernel_name afterwards names the form that ran,
+ * "spectrum_kernel<wg>", "spectrum_kernel<wave>" or "spectrum_kernel<global>". */
+enum { KGMA_COUNT_SKIP_N = 1u << 0, KGMA_COUNT_SKIP_MASKED = 1u << 1, KGMA_COUNT_BY_START = 1u << 2 };
+int kgma_genome_kmer_count(kgma_ctx *ctx, const kgma_genome *g, int32_t k, uint32_t flags, int64_t n_ranges,
+                           const int32_t *contig /* 0-based */, const int64_t *lo, const int64_t *hi /* 1-based inclusive */,
+                           int64_t *counts /* n_ranges * 4^k, row-major */, int64_t *n_skipped /* n_ranges, or NULL */);
+/* The last kgma_genome_kmer_count on the context: device time of the rows' memset and the launch (hipEvents), the ranges, the
+ * considered starts, and the form that ran: 0 = `wg` (4^k counters in a workgroup's LDS, k <= 7), 1 = `wave` (a table per wave,
+ * k <= 4, chosen when the mean range is shorter than a unit of `wg`), 2 = `global` (atomic adds straight into the rows, k >= 8);
+ * span = considered starts of a unit of work, n_workgroups = workgroups launched.  All zero before the first call and after a call
+ * that failed or had no range. */
+typedef struct { double count_ms; int64_t n_ranges, n_positions; int32_t form, span, n_workgroups, n_launches; } kgma_spectrum_stats;
+int kgma_get_spectrum_stats(kgma_ctx *ctx, kgma_spectrum_stats *out);
+
 /* kgma_repack_scan_hits in two halves, for step loops that have other work to queue while the GPU scans
  * (bench.py with several ranks: the hit exchange of step i overlaps the scan of step i+1).  kgma_step_begin
  * hands the step to a helper thread owned by the context and returns at once; kgma_step_end waits for it

@@ -456,6 +456,7 @@ struct kgma_ctx {
     kgma_assign_stats assign_stats{};        // the last kgma_assign_seqs / kgma_assign_ranges (kgma_assign.cpp)
     kgma_kmat_stats kmat_stats{};            // the last kgma_kmer_dist_matrix / kgma_kmer_nearest (kgma_kmat.cpp)
     kgma_landscape_stats landscape_stats{};  // the last kgma_dist_bins / kgma_dist_sweep (kgma_landscape.cpp)
+    kgma_spectrum_stats spectrum_stats{};    // the last kgma_genome_kmer_count (kgma_spectrum.cpp)
     int64_t device_bytes = 0;
 };
 
@@ -473,6 +474,8 @@ int64_t *ctx_device_bytes(kgma_ctx *ctx) { return &ctx->device_bytes; }
 int ctx_n_cus(const kgma_ctx *ctx) { return ctx->n_cus; }
 kgma_assign_stats *ctx_assign_stats(kgma_ctx *ctx) { return &ctx->assign_stats; }
 kgma_kmat_stats *ctx_kmat_stats(kgma_ctx *ctx) { return &ctx->kmat_stats; }
+kgma_spectrum_stats *ctx_spectrum_stats(kgma_ctx *ctx) { return &ctx->spectrum_stats; }
+void ctx_set_kernel_name(kgma_ctx *ctx, const char *name) { snprintf(ctx->kernel_name, sizeof ctx->kernel_name, "%s", name); }
 GenomeText genome_text(const kgma_genome *g) { return GenomeText{g->d_ascii, g->d_cd, g->cd.data(), g->n_contigs, g->d_planes, g->d_inter}; }
 
 // kgma_landscape.h: the kept distances of the last scan as kgma_landscape.cpp sees them

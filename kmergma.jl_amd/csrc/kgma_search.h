@@ -39,6 +39,8 @@ void ctx_device(const kgma_ctx *ctx, int *device, hipStream_t *stream);
 void ctx_events(const kgma_ctx *ctx, hipEvent_t *ev0, hipEvent_t *ev1);   // the context's pair of timing events
 kgma_stats *ctx_stats(kgma_ctx *ctx);
 int64_t *ctx_device_bytes(kgma_ctx *ctx);                     // the context's account of its device memory
+kgma_spectrum_stats *ctx_spectrum_stats(kgma_ctx *ctx);       // the last kgma_genome_kmer_count (kgma_spectrum.cpp)
+void ctx_set_kernel_name(kgma_ctx *ctx, const char *name);    // what kgma_scan_kernel_name answers
 GenomeText genome_text(const kgma_genome *g);
 // What a search does before it launches: the device is made current, the pack's residue check and the packed copy the kernel reads
 // are made current, bases_scanned is set and scan_ms / n_launches are zeroed in kgma_stats.  clean == nullptr: a residue outside

@@ -920,9 +920,36 @@ function dist_sweep(ctx::Context, thresholds::Vector{Float64}; kfv::Integer = 1)
     return below, dips
 end
 
+# ---- k-mer counts of the resident genome (kgma_genome_kmer_count) ---------------------------------------------------------------
+# (not executed either; _lib.py's Context.genome_kmer_count makes the same call with the same argument types)
+const KGMA_COUNT_SKIP_N = UInt32(1)
+const KGMA_COUNT_SKIP_MASKED = UInt32(2)
+const KGMA_COUNT_BY_START = UInt32(4)
+
+"""
+    genome_kmer_count(g, k, contig, lo, hi; skip_n = false, skip_masked = false, by_start = false) -> (counts, skipped)
+`counts[:, r]` is `kmer_count(view(seq, lo[r]:hi[r]), k)` of record `contig[r]` (0-based; lo:hi 1-based inclusive, hi = lo - 1 is
+empty) of the resident genome -- 4^k Int64, k-mer value + 1 as the row index, first base most significant --, `skipped[r]` the
+considered starts the flags left out.  skip_n: a k-mer with a byte outside A/C/G/T is skipped (default: N counts as T, anything
+else is the reference's KeyError); skip_masked: so is one with a lower-case byte; by_start: a k-mer belongs to the range it
+starts in.  1 <= k <= 10.
+"""
+function genome_kmer_count(g::DeviceGenome, k::Integer, contig::Vector{Int32}, lo::Vector{Int64}, hi::Vector{Int64};
+                           skip_n::Bool = false, skip_masked::Bool = false, by_start::Bool = false)
+    flags = (skip_n ? KGMA_COUNT_SKIP_N : UInt32(0)) | (skip_masked ? KGMA_COUNT_SKIP_MASKED : UInt32(0)) |
+            (by_start ? KGMA_COUNT_BY_START : UInt32(0))
+    counts = Matrix{Int64}(undef, 4^k, length(contig))
+    skipped = Vector{Int64}(undef, length(contig))
+    check(g.ctx, ccall((:kgma_genome_kmer_count, libkgma), Cint,
+                       (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt32, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                       g.ctx.h, g.h, k, flags, length(contig), contig, lo, hi, counts, skipped))
+    return counts, skipped
+end
+
 export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, approxMatch, pwmMatch, pwm_revcomp, HumanRSSV, HumanRSSD, Context
 export dist_layout, dist_bins, dist_sweep
 export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists, assignGenes, assign_ranges
 export kmer_dist_matrix, kmer_dist_matrix_ranges, nearest_refs, assignGenes_screened
+export genome_kmer_count
 
 end # module

@@ -46,12 +46,16 @@ EXPORTS = [
     "kgma_assign_seqs_screened", "kgma_assign_ranges_screened",
     "kgma_dist_layout", "kgma_dist_bins", "kgma_dist_sweep", "kgma_get_landscape_stats",
     "kgma_genome_inter_state",
+    "kgma_genome_kmer_count", "kgma_get_spectrum_stats",
 ]
 SWEEP_MAX_THRESHOLDS = 4096          # KGMA_SWEEP_MAX_THRESHOLDS
 ASSIGN_MAX_LEN = 8191                # KGMA_ASSIGN_MAX_LEN
 KMAT_MAX_LEN = 32767                 # KGMA_KMAT_MAX_LEN
 KMAT_MAX_NEAR = 128                  # KGMA_KMAT_MAX_NEAR
 KMAT_FORM_LDS, KMAT_FORM_GLOBAL = 0, 1   # kgma_kmat_stats.form
+COUNT_SKIP_N, COUNT_SKIP_MASKED, COUNT_BY_START = 1, 2, 4   # kgma_genome_kmer_count flags
+SPECTRUM_FORM_WG, SPECTRUM_FORM_WAVE, SPECTRUM_FORM_GLOBAL = 0, 1, 2   # kgma_spectrum_stats.form
+SPECTRUM_MAX_COUNTS = 1 << 28        # n_ranges * 4^k of one kgma_genome_kmer_count at most
 TWOBIT_NOMASK = 1                    # KGMA_2BIT_NOMASK
 TWOBIT_SIGNATURE = b"\x43\x27\x41\x1a"  # the first four bytes of a .2bit file in this machine's byte order
 FILTER_FORM_PRESUMMED = 1 << 16      # kgma_filter_stats.form: the filter read the block sums the step's pack wrote (KGMA_FUSE_SUMS)
@@ -134,6 +138,11 @@ class KgmaAssignStats(C.Structure):
 class KgmaKmatStats(C.Structure):
     _fields_ = [("kmat_ms", C.c_double), ("select_ms", C.c_double), ("n_pairs", C.c_int64), ("n_launches", C.c_int32),
                 ("form", C.c_int32), ("tile", C.c_int32), ("chunks", C.c_int32)]
+
+
+class KgmaSpectrumStats(C.Structure):
+    _fields_ = [("count_ms", C.c_double), ("n_ranges", C.c_int64), ("n_positions", C.c_int64), ("form", C.c_int32),
+                ("span", C.c_int32), ("n_workgroups", C.c_int32), ("n_launches", C.c_int32)]
 
 
 class KgmaLandscapeStats(C.Structure):
@@ -294,6 +303,8 @@ def load():
     L.kgma_dist_bins.argtypes = [vp, i32, i64, P(dbl), P(i64), P(i64), i64, P(i64)]
     L.kgma_dist_sweep.argtypes = [vp, i32, P(dbl), i64, P(i64), P(i64)]
     L.kgma_get_landscape_stats.argtypes = [vp, P(KgmaLandscapeStats)]
+    L.kgma_genome_kmer_count.argtypes = [vp, vp, i32, C.c_uint32, i64, P(i32), P(i64), P(i64), P(i64), P(i64)]
+    L.kgma_get_spectrum_stats.argtypes = [vp, P(KgmaSpectrumStats)]
     L.kgma_stream.argtypes = [vp]
     L.kgma_stream.restype = vp
     L.kgma_scan_kernel_name.argtypes = [vp]
@@ -1191,6 +1202,27 @@ class Context:
         s = KgmaKmatStats()
         self._check(load().kgma_get_kmat_stats(self._h, C.byref(s)))
         return {name: getattr(s, name) for name, _ in KgmaKmatStats._fields_}
+
+    def genome_kmer_count(self, genome: "Genome", k: int, contig, lo, hi, flags: int = 0):
+        """kgma_genome_kmer_count: (counts, skipped): counts int64 [n, 4^k], row r the k-mer counts (natural k-mer value, first
+        base most significant) of residues lo[r] .. hi[r] (1-based inclusive; hi = lo - 1: empty) of record contig[r] (0-based)
+        of the resident genome; skipped int64 [n]: the considered starts the flags (COUNT_SKIP_N, COUNT_SKIP_MASKED) left out.
+        COUNT_BY_START: a k-mer belongs to the range it starts in."""
+        n, ptrs, _keep = self._ranges(contig, lo, hi)
+        k = int(k)
+        served = 1 <= k <= 10 and (n << (2 * k)) <= SPECTRUM_MAX_COUNTS          # (else the call is refused: no rows needed)
+        counts = np.zeros((n, 4 ** k if served else 1), dtype=np.int64)
+        skipped = np.zeros(n, dtype=np.int64)
+        self._check(load().kgma_genome_kmer_count(self._h, genome._h, k, int(flags), n, *ptrs,
+                                                  _np_ptr(counts, C.c_int64) if n else None, _np_ptr(skipped, C.c_int64) if n else None))
+        return counts, skipped
+
+    def spectrum_stats(self) -> dict:
+        """kgma_get_spectrum_stats: device time, ranges, considered starts, form, span, workgroups and launches of the last
+        genome_kmer_count."""
+        s = KgmaSpectrumStats()
+        self._check(load().kgma_get_spectrum_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in KgmaSpectrumStats._fields_}
 
     def assign_seqs_screened(self, refs, queries, gap_open: int = -69, gap_extend: int = -1, top: int = 1, screen_k: int = 6,
                              n_near: int = 8):

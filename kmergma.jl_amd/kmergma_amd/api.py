@@ -912,7 +912,7 @@ def pwm_threshold(matrix, pvalue: float, background=_UNIFORM) -> int:
     return lowest + (int(ok[0]) if ok.size else p.size)
 
 
-def _pwm_args(matrices, threshold, pvalue, strand):
+def _pwm_args(matrices, threshold, pvalue, strand, background=None):
     _check_strand(strand)
     if (threshold is None) == (pvalue is None):
         raise ValueError("give exactly one of threshold and pvalue")
@@ -921,7 +921,7 @@ def _pwm_args(matrices, threshold, pvalue, strand):
         ps = [float(pvalue)] * len(ms) if isinstance(pvalue, (int, float, np.integer, np.floating)) else [float(x) for x in pvalue]
         if len(ps) != len(ms):
             raise ValueError("need one pvalue per matrix")
-        ts = [pwm_threshold(m, x) for m, x in zip(ms, ps)]
+        ts = [pwm_threshold(m, x) if background is None else pwm_threshold(m, x, background) for m, x in zip(ms, ps)]
     elif isinstance(threshold, (int, np.integer)):
         ts = [int(threshold)] * len(ms)
     else:
@@ -956,17 +956,34 @@ def _pwm_run(ctx, g, ms, sent, tags) -> list:
     return out
 
 
-def pwmMatch_batch(matrices, genome_or_path, *, threshold=None, pvalue=None, strand: str = "+", ctx=None) -> list:
+def _pwm_background(background, threshold):
+    """background= of the searches, checked: None (uniform, as pwm_threshold's default), four probabilities, or the string
+    "genome" (the base composition of the open subject, measured on the device by genome_background once it is open)."""
+    if background is None:
+        return None
+    if threshold is not None:
+        raise ValueError("background has an effect only together with pvalue: give pvalue, not threshold")
+    if isinstance(background, str):
+        if background != "genome":
+            raise ValueError(f"background must be four probabilities or 'genome', not {background!r}")
+        return background
+    return _background(background)
+
+
+def pwmMatch_batch(matrices, genome_or_path, *, threshold=None, pvalue=None, strand: str = "+", background=None, ctx=None) -> list:
     """Many matrices in ONE pass over the genome (kgma_pwm_match): per matrix the list of
     (record_index, identifier, lo, hi, strand, score) -- 0-based record, 1-based inclusive lo:hi in forward coordinates --
     sorted by (record, lo, strand).  `threshold` / `pvalue`: one number for all matrices or one per matrix.  Semantics: pwmMatch.
-    `genome_or_path`: a FASTA or .2bit path, or a device genome that is already open (it stays open)."""
-    ms, sent, tags = _pwm_args(list(matrices), threshold, pvalue, strand)
+    `genome_or_path`: a FASTA or .2bit path, or a device genome that is already open (it stays open).  `background`: pwmMatch."""
+    matrices, bg = list(matrices), _pwm_background(background, threshold)
+    ms, sent, tags = _pwm_args(matrices, threshold, pvalue, strand, None if isinstance(bg, str) else bg)
     if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
         raise TypeError("Invalid subject sequence type")
     ctx = ctx or default_context()
     g, src, owned = _open_subject(ctx, genome_or_path)
     try:
+        if isinstance(bg, str):
+            ms, sent, tags = _pwm_args(matrices, threshold, pvalue, strand, genome_background(g, ctx=ctx))
         res = _pwm_run(ctx, g, ms, sent, tags)
         ids = {c: _identifier(src, c) for c in {t[0] for lst in res for t in lst}}
     finally:
@@ -975,31 +992,36 @@ def pwmMatch_batch(matrices, genome_or_path, *, threshold=None, pvalue=None, str
     return [[(c, ids[c], lo, hi, st, sc) for c, lo, hi, st, sc in lst] for lst in res]
 
 
-def pwmMatch(matrix, subject_seq, *, threshold=None, pvalue=None, strand: str = "+", ctx=None):
+def pwmMatch(matrix, subject_seq, *, threshold=None, pvalue=None, strand: str = "+", background=None, ctx=None):
     """Every place at which `matrix` -- 1 ... 64 rows of four integer weights (A, C, G, T; each -32768 ... 32767) -- laid on the
     subject scores at least the threshold: score(s) = sum over the rows i of matrix[i][t[s + i]], overlapping places included,
     none spanning two records.  Case is folded; a genome N scores its row's minimum, so an assembly gap never looks like a signal
     and a row of four equal weights (a spacer) costs nothing.  Give exactly one of `threshold` (an integer that exceeds the sum of
-    the row minima) and `pvalue` (the threshold becomes pwm_threshold(matrix, pvalue), uniform background).  The subject may hold
-    A/C/G/T/N only (KgmaError KGMA_E_BADBASE otherwise).
+    the row minima) and `pvalue` (the threshold becomes pwm_threshold(matrix, pvalue, background)).  `background` has an effect only
+    together with `pvalue` (ValueError with `threshold`): None is the uniform one, four probabilities (A, C, G, T) are handed to
+    pwm_threshold, and the string "genome" is genome_background(subject), the subject's own base composition measured on the
+    device.  The subject may hold A/C/G/T/N only (KgmaError KGMA_E_BADBASE otherwise).
     strand: "+" the matrix as given; "-" its reverse complement (pwm_revcomp), searched on the same genome and reported at the
     forward lo:hi it covers; "both" the two together (a matrix equal to its own reverse complement is reported on both strands).
     A `subject_seq` of residues (bytes, or a Record) returns [(lo, hi, strand, score)] sorted by (lo, strand); a FASTA path or
     an open device genome returns pwmMatch_batch(...)[0].  An empty list when there is no hit."""
     if isinstance(subject_seq, (Record, bytes, bytearray, memoryview)):
-        ms, sent, tags = _pwm_args([matrix], threshold, pvalue, strand)
+        bg = _pwm_background(background, threshold)
+        ms, sent, tags = _pwm_args([matrix], threshold, pvalue, strand, None if isinstance(bg, str) else bg)
         seq = bytes(subject_seq.sequence if isinstance(subject_seq, Record) else subject_seq)
         ctx = ctx or default_context()
         g = ctx.genome_from_host([seq])
         try:
+            if isinstance(bg, str):
+                ms, sent, tags = _pwm_args([matrix], threshold, pvalue, strand, genome_background(g, ctx=ctx))
             res = _pwm_run(ctx, g, ms, sent, tags)[0]
         finally:
             g.free()
         return [(lo, hi, st, sc) for _, lo, hi, st, sc in res]
-    return pwmMatch_batch([matrix], subject_seq, threshold=threshold, pvalue=pvalue, strand=strand, ctx=ctx)[0]
+    return pwmMatch_batch([matrix], subject_seq, threshold=threshold, pvalue=pvalue, strand=strand, background=background, ctx=ctx)[0]
 
 
-def findRSS_pwm(genome_or_path, sites_or_matrix, *, pvalue: float = 1e-6, strand: str = "both", ctx=None):
+def findRSS_pwm(genome_or_path, sites_or_matrix, *, pvalue: float = 1e-6, strand: str = "both", background=None, ctx=None):
     """Recombination signal sequences by a position weight matrix: `sites_or_matrix` is a list of example sites (equal-length
     A/C/G/T sequences, made into a log-odds matrix by pwm_from_sequences) or a ready matrix; every place of the genome that
     scores at least the exact p <= pvalue threshold is returned as pwmMatch does.  Unlike findRSS's mismatch count it weighs
@@ -1009,7 +1031,7 @@ def findRSS_pwm(genome_or_path, sites_or_matrix, *, pvalue: float = 1e-6, strand
         matrix = pwm_from_sequences(sites_or_matrix)
     else:
         matrix = sites_or_matrix
-    return pwmMatch(matrix, genome_or_path, pvalue=pvalue, strand=strand, ctx=ctx)
+    return pwmMatch(matrix, genome_or_path, pvalue=pvalue, strand=strand, background=background, ctx=ctx)
 
 
 # ---- threshold calibration (kgma_window_dists, kgma_mutation_dists): the working form of src/DistanceTesting.jl --------------
@@ -1593,6 +1615,168 @@ def write_bedgraph(track, path) -> None:
                 rows.append((lo - 1, hi, m))
             for lo0, hi0, m in (reversed(rows) if t.strand == "-" else rows):
                 f.write(f"{t.identifier}\t{lo0}\t{hi0}\t{float(m)!r}\n")
+
+
+# ---- k-mer counts of the resident genome (kgma_genome_kmer_count): spectra, backgrounds, composition tracks ----
+class CompositionTrack(NamedTuple):
+    """One record of api.composition_track: bin b holds the k-mers that START at the 0-based residues b * bin ..
+    min((b + 1) * bin, length) - 1; counts[b] are their 4^k counts (natural k-mer value), skipped[b] the starts left out."""
+    identifier: str
+    counts: np.ndarray
+    skipped: np.ndarray
+    bin: int
+    k: int
+    length: int
+
+
+def _count_flags(skip_n: bool, skip_masked: bool, by_start: bool) -> int:
+    return ((_lib.COUNT_SKIP_N if skip_n else 0) | (_lib.COUNT_SKIP_MASKED if skip_masked else 0)
+            | (_lib.COUNT_BY_START if by_start else 0))
+
+
+def _count_view(ctx, genome_or_path):
+    """(view, owned) of a FASTA or .2bit path, an open device genome (it stays open), a _GenomeView or records."""
+    if isinstance(genome_or_path, _GenomeView):
+        return genome_or_path, False
+    if genome_or_path is None or isinstance(genome_or_path, (bytes, bytearray, memoryview, Record, int, float)):
+        raise TypeError("Invalid subject sequence type")
+    return _GenomeView(ctx, genome_or_path), True
+
+
+def _check_count_k(k) -> int:
+    if not 1 <= int(k) <= 10:
+        raise ValueError(f"k = {k}: the k-mer count serves k = 1 ... 10")
+    return int(k)
+
+
+def genome_kmer_count(genome_or_path, k: int, ranges=None, *, skip_n: bool = False, skip_masked: bool = False,
+                      by_start: bool = False, ctx=None):
+    """(counts, skipped) of kgma_genome_kmer_count: counts int64 [n, 4^k], row r = kmer_count(view(seq, lo:hi), k)
+    (src/Kmers.jl:14-28; index = natural k-mer value, first base most significant) of the r-th of `ranges`, (record, lo, hi)
+    triples with a 0-based record and 1-based inclusive lo:hi; None: one whole-record range per record.  The residues are read
+    where they lie on the device.  skip_n: a k-mer with a byte outside A/C/G/T is left out and counted in skipped[r] (default:
+    N counts as T, anything else is a BadBaseError); skip_masked: so is a k-mer with a lower-case (soft-masked) byte;
+    by_start: a k-mer belongs to the range it starts in, also when it ends behind hi, so ranges that tile a record sum to the
+    record's count.  `genome_or_path`: a FASTA or .2bit path, an open device genome (it stays open) or records."""
+    k = _check_count_k(k)
+    ctx = ctx or default_context()
+    view, owned = _count_view(ctx, genome_or_path)
+    try:
+        g = view.genome
+        if ranges is None:
+            ranges = [(c, 1, g.contig_len(c)) for c in range(g.n_contigs)]
+        ranges = [(int(c), int(lo), int(hi)) for c, lo, hi in ranges]
+        return ctx.genome_kmer_count(g, k, [r[0] for r in ranges], [r[1] for r in ranges], [r[2] for r in ranges],
+                                     _count_flags(skip_n, skip_masked, by_start))
+    finally:
+        if owned:
+            view.free()
+
+
+def revcomp_kmer_permutation(k: int) -> np.ndarray:
+    """perm[x] = the natural value of the reverse complement of the k-mer of value x: the spectrum of the minus strand is
+    spectrum[perm]."""
+    x = np.arange(4 ** int(k), dtype=np.int64)
+    y = np.zeros_like(x)
+    for _ in range(int(k)):
+        y = (y << 2) | (3 - (x & 3))
+        x = x >> 2
+    return y
+
+
+def genome_spectrum(genome_or_path, k: int, *, skip_n: bool = True, skip_masked: bool = False, strand: str = "+", ctx=None) -> np.ndarray:
+    """The k-mer spectrum of a genome: int64 [4^k], the whole-record counts summed over the records (no k-mer spans two).
+    strand "-": the spectrum of the reverse complements, formed on the host by the reverse-complement permutation of the index
+    (no second pass, no reversed genome); "both": the sum of the two."""
+    _check_strand(strand)
+    counts, _ = genome_kmer_count(genome_or_path, k, skip_n=skip_n, skip_masked=skip_masked, ctx=ctx)
+    plus = np.asarray(counts, dtype=np.int64).reshape(-1, 4 ** int(k)).sum(axis=0)
+    if strand == "+":
+        return plus
+    minus = plus[revcomp_kmer_permutation(k)]
+    return minus if strand == "-" else plus + minus
+
+
+def genome_background(genome_or_path, *, skip_masked: bool = False, strand: str = "both", ctx=None) -> np.ndarray:
+    """The base composition of a genome as four probabilities (A, C, G, T), measured on the device: usable wherever
+    `background=` is accepted (pwm_threshold, pwm_score_distribution, pwm_from_sequences, pwmMatch).  N and other codes are
+    left out; "both" symmetrises A/T and C/G.  ValueError when a base does not occur (a background needs positive
+    probabilities)."""
+    n = genome_spectrum(genome_or_path, 1, skip_n=True, skip_masked=skip_masked, strand=strand, ctx=ctx).astype(np.float64)
+    if (n <= 0).any():
+        raise ValueError(f"genome_background: base {'ACGT'[int(np.argmin(n))]} does not occur: a background needs four positive probabilities")
+    return n / n.sum()
+
+
+def composition_track(genome_or_path, bin: int, k: int = 1, *, skip_n: bool = True, skip_masked: bool = False, ctx=None) -> List[CompositionTrack]:
+    """Per record a CompositionTrack: the k-mer counts of every `bin` consecutive starts (the last bin of a record may be
+    shorter), a k-mer belonging to the bin it starts in (by_start) -- the material of GC, CpG and N / masked-share tracks
+    (gc_fraction, cpg_obs_exp, track.skipped).  One device call, split where ranges * 4^k would pass the call's cap."""
+    k = _check_count_k(k)
+    width = int(bin)
+    if width < 1:
+        raise ValueError(f"bin = {bin}")
+    ctx = ctx or default_context()
+    view, owned = _count_view(ctx, genome_or_path)
+    try:
+        g = view.genome
+        lens = [g.contig_len(c) for c in range(g.n_contigs)]
+        nbins = [(L + width - 1) // width for L in lens]
+        contig = np.repeat(np.arange(len(lens), dtype=np.int32), nbins)
+        lo = np.concatenate([np.arange(n, dtype=np.int64) * width + 1 for n in nbins]) if lens else np.zeros(0, dtype=np.int64)
+        hi = np.minimum(lo + width - 1, np.repeat(np.asarray(lens, dtype=np.int64), nbins))
+        flags = _count_flags(skip_n, skip_masked, True)
+        per_call = max(1, _lib.SPECTRUM_MAX_COUNTS >> (2 * k))
+        parts = [ctx.genome_kmer_count(g, k, contig[i:i + per_call], lo[i:i + per_call], hi[i:i + per_call], flags)
+                 for i in range(0, contig.size, per_call)]
+        counts = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 4 ** k), dtype=np.int64)
+        skipped = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.int64)
+        off = np.concatenate(([0], np.cumsum(nbins))).astype(np.int64)
+        return [CompositionTrack(view.identifier(c), counts[off[c]:off[c + 1]], skipped[off[c]:off[c + 1]], width, k, lens[c])
+                for c in range(len(lens))]
+    finally:
+        if owned:
+            view.free()
+
+
+def _first_base_counts(track) -> np.ndarray:
+    """[n_bins, 4]: the counted k-mers of every bin by their first base."""
+    c = np.asarray(track.counts, dtype=np.float64)
+    return c.reshape(c.shape[0], 4, -1).sum(axis=2)
+
+
+def gc_fraction(track) -> np.ndarray:
+    """(C + G) / counted per bin of a CompositionTrack; at k > 1 the base is the k-mer's first.  NaN where nothing was counted."""
+    m = _first_base_counts(track)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (m[:, 1] + m[:, 2]) / m.sum(axis=1)
+
+
+def cpg_obs_exp(track) -> np.ndarray:
+    """CpG observed / expected per bin of a k = 2 CompositionTrack: n_CG * counted / (n_C* * n_G*), the marginals being those
+    of the first base.  NaN where a factor of the denominator is 0."""
+    if track.k != 2:
+        raise ValueError("cpg_obs_exp needs a k = 2 track")
+    m = _first_base_counts(track)
+    c = np.asarray(track.counts, dtype=np.float64)
+    den = m[:, 1] * m[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, c[:, 4 * 1 + 2] * m.sum(axis=1) / den, np.nan)
+
+
+def write_composition_bedgraph(tracks, values, path) -> None:
+    """One line per bin: record identifier, 0-based half-open range of the bin's starts, value (repr of the double).  `values`:
+    one array per track (gc_fraction(track), cpg_obs_exp(track), track.skipped / bin, ...).  The analogue of write_bedgraph."""
+    tracks, values = list(tracks), list(values)
+    if len(tracks) != len(values):
+        raise ValueError("need one array of values per track")
+    with open(path, "w") as f:
+        for t, v in zip(tracks, values):
+            v = np.asarray(v, dtype=np.float64).reshape(-1)
+            if v.size != len(t.counts):
+                raise ValueError(f"{t.identifier}: {v.size} values for {len(t.counts)} bins")
+            for b, x in enumerate(v.tolist()):
+                f.write(f"{t.identifier}\t{b * t.bin}\t{min((b + 1) * t.bin, t.length)}\t{float(x)!r}\n")
 
 
 def fasta_id_to_cumulative_len_dict(fasta_file_path) -> dict:
