@@ -429,6 +429,21 @@ int kgma_get_block_sums(kgma_ctx *ctx, const kgma_genome *genome, int64_t contig
  * *state: KGMA_INTER_*; *demand_blocks: the blocks the last step packed on demand (0 after any full pack).  Either may be null.
  * KGMA_SPARSE_POISON=1 (tests): a sparse step fills the copy with a byte pattern before it packs its blocks. */
 enum { KGMA_INTER_FULL = 0, KGMA_INTER_PARTIAL = 1 };
+/* The block sums of a genome: none yet; written by the last step's pack; or DEFERRED -- that step's pack made the prefilter's test
+ * itself and stored none: kgma_get_block_sums (and whatever changes the resident text) has them written first, for the text and
+ * the reference of that step. */
+enum { KGMA_BSUM_NONE = 0, KGMA_BSUM_WRITTEN = 1, KGMA_BSUM_DEFERRED = 2 };
+/* The last step (kgma_repack_scan_hits): did its pack make the prefilter's granule test itself (no filter kernel, no block sums
+ * stored; KGMA_PACK_TEST=0: never), and if so: the units (128 plane words) a wave took at a time, the units in all, those that went
+ * word by word, and the chunks (half units) encoded a second time to prime a run. */
+typedef struct kgma_pack_test_stats {
+    int32_t tested;
+    int32_t run;
+    int64_t units;
+    int64_t slow_units;
+    int64_t primed_chunks;
+} kgma_pack_test_stats;
+int kgma_get_pack_test_stats(kgma_ctx *ctx, kgma_pack_test_stats *out);
 int kgma_genome_inter_state(const kgma_genome *genome, int32_t *state, int64_t *demand_blocks);
 
 /* HOST-side helper (not on the device path; a Julia host keeps using BioAlignments.jl): semi-global

@@ -118,6 +118,15 @@ struct kgma_genome {
     uint16_t *d_bsum = nullptr;
     bool bsum_fresh = false, bsum_failed = false;
     int bsum_k = 0;
+    // The last step's pack made the prefilter's test itself (pack_sums_kernel<K, false, true>) and stored no sum: bsum_state is
+    // DEFERRED and ensure_bsum writes them when somebody asks (kgma_get_block_sums), or before the text changes -- with the S table
+    // of that step, kept in d_bsum_S (copied when the reference set changed since the last copy).  pack_tested: the pack of the
+    // scan that is running tested; its entries are in the context's pinned list (filter_candidate_table).
+    int bsum_state = KGMA_BSUM_NONE;
+    bool pack_tested = false;
+    int32_t *d_bsum_S = nullptr;
+    uint64_t bsum_S_refs = ~(uint64_t)0;
+    int64_t bsum_smax = 0;
     int64_t device_bytes = 0;
 };
 
@@ -170,6 +179,12 @@ namespace kgma { int pack_block_words(); }   // kgma_kernels.hip
 namespace {
 
 constexpr int64_t CONTIG_PAD_WORDS = 32;
+// (the step's pack tests granules on sums of up to 63 consecutive blocks of ONE global block array: the 62 blocks behind a granule's
+//  first one must not reach the next record -- pack_sums_kernel<K, false, true>, launch_filter's nblk <= 63)
+static_assert(2 * CONTIG_PAD_WORDS >= 62, "a granule's blocks must end inside the padding behind its record");
+// the step's pack that makes the prefilter's test: units a wave takes at a time, and the runs per wave below which it is not used
+constexpr int PACK_TEST_RUN = 32;
+constexpr int64_t PACK_TEST_MIN_RUNS = 4;
 constexpr int64_t LEAD_PAD_WORDS = 8;
 constexpr int64_t TAIL_PAD_WORDS = KGMA_TILE_WORDS + 128;
 constexpr unsigned long long NO_BAD = ~0ull;
@@ -238,7 +253,8 @@ inline double now_ms()
 }
 
 // what a pack that carries the prefilter's block sums needs of the references (pack_sums_kernel)
-struct PackSums { const int32_t *S; int k; int64_t s_max; int n_cus; };
+// test: the pack makes the prefilter's granule test itself, with this bound, geometry, run length and list capacity
+struct PackSums { const int32_t *S; int k; int64_t s_max; int n_cus; bool test = false; uint32_t U = 0; int nblk = 0, nk = 0, run = 0; int64_t cap = 0; };
 
 }  // namespace
 
@@ -404,6 +420,10 @@ struct kgma_ctx {
     std::vector<int64_t> fcontig_tile_base;  // per contig: index of its first candidate stream or -1
     TileDesc *d_ftiles = nullptr; int64_t ftiles_cap = 0;
     unsigned int *d_fctl = nullptr;          // entries the filter kernel appended (left at zero by its publish kernel)
+    // the step's pack that makes the test itself (plan_deferred_pack): the bound and capacity it was launched with, and what
+    // kgma_get_pack_test_stats reports of the last step
+    uint32_t ptest_U = 0; int64_t ptest_cap = 0;
+    kgma_pack_test_stats ptest = {};
     uint8_t *h_fpin = nullptr, *h_fpin_dev = nullptr; size_t fpin_cap = 0;   // pinned: [count u32, pad][FilterEntry list]: the kernel writes it directly
     hipEvent_t evf0 = nullptr, evf1 = nullptr;
     std::vector<FilterEntry> fentries;       // the last scan's entries, sorted (kgma_get_filter_candidates)
@@ -959,6 +979,7 @@ int kgma_repack_scan_hits(kgma_ctx *ctx, kgma_genome *g, int32_t mode, int64_t b
     if (!ctx || !g || !n) return KGMA_E_ARG;
     // a large genome's re-encoding is left to the scan, which may run it beside its own launches (launch_overlapped)
     int rc = KGMA_OK;
+    ctx->ptest = kgma_pack_test_stats{};                               // (of the last step, whatever its pack turns out to be)
     // ... or put the prefilter's block sums into it (pack_sums_kernel), which only the scan can decide
     if (mode == KGMA_MODE_SINGLE && g->n_contigs >= 4 && g->total_bases >= overlap_min_bases() && overlap_setup(ctx)) g->repack_deferred = true;
     else if (fuse_sums_possible(ctx, mode)) g->repack_deferred = true;
@@ -991,6 +1012,7 @@ static void step_worker_main(kgma_ctx *ctx)
         }
         if (st == -1) return;
         int rc = KGMA_OK;
+        ctx->ptest = kgma_pack_test_stats{};
         if (w->mode == KGMA_MODE_SINGLE && w->g->n_contigs >= 4 && w->g->total_bases >= overlap_min_bases() && overlap_setup(ctx)) w->g->repack_deferred = true;
         else if (fuse_sums_possible(ctx, w->mode)) w->g->repack_deferred = true;
         else rc = kgma_genome_repack(ctx, w->g);
@@ -1442,7 +1464,8 @@ hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, 
                        const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st, int64_t block0 = 0, int64_t n_blocks = -1);
 hipError_t launch_pack(const uint8_t *ascii, uint32_t *planes, uint32_t *inter, const ContigDesc *cd, int n_contigs, int64_t total_words,
                        const int32_t *block_contig, unsigned long long *first_bad, hipStream_t st, const int32_t *block_list, int64_t n_list);
-hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, bool sums_only, hipStream_t st);
+hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, bool sums_only, hipStream_t st, unsigned int *host_count = nullptr);
+int64_t pack_sums_waves(int n_cus);
 hipError_t launch_synth(uint8_t *ascii, const ContigDesc *cd, int n_contigs, int64_t total_words, uint64_t seed, hipStream_t st);
 hipError_t launch_fasta_count(const uint8_t *raw, int64_t n, uint32_t *counts, hipStream_t st);
 hipError_t launch_fasta_blank(uint8_t *raw, const int64_t *ranges, int n_ranges, hipStream_t st);
@@ -1640,8 +1663,45 @@ int ensure_planes(kgma_ctx *ctx, kgma_genome *g)
     return KGMA_OK;
 }
 
+static void pack_sums_args(const kgma_genome *g, const int32_t *S, PackSumsArgs &a)
+{
+    a.ascii = g->d_ascii; a.planes = g->d_planes; a.inter = g->d_inter; a.bsum = g->d_bsum;
+    a.cd = g->d_cd; a.total_words = g->total_words; a.block_contig = g->d_block_contig; a.first_bad = g->d_first_bad;
+    a.S = S; a.n_contigs = (int32_t)g->n_contigs;
+    const int bw = pack_block_words();
+    a.block_shift = (bw & (bw - 1)) == 0 ? __builtin_ctz((unsigned)bw) : -1;
+}
+
+// The state of the block sums (kgma_genome::bsum_state).  DEFERRED: the storing sums-only pack runs now, on the
+// resident text and the S table of the step that deferred them, and the state is WRITTEN.  Called by whoever reads the sums and,
+// like ensure_inter, BEFORE anything changes the resident text of an existing genome: the sums are those of the text the step packed.
+// must: the caller reads the sums (a failed allocation is its error); else the text is about to change, and a failed allocation
+// only drops the sums (state NONE: kgma_get_block_sums then says that no step has left any) -- the change itself goes on.
+int ensure_bsum(kgma_ctx *ctx, kgma_genome *g, bool must)
+{
+    if (g->bsum_state != KGMA_BSUM_DEFERRED) return KGMA_OK;
+    (void)hipSetDevice(ctx->device);
+    if (!g->d_bsum) {
+        if (hipMalloc(reinterpret_cast<void **>(&g->d_bsum), (size_t)g->total_words * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            g->d_bsum = nullptr;
+            if (must) return fail(ctx, KGMA_E_NOMEM, "kgma_get_block_sums: no device memory for the block sums (%lld bytes)", (long long)g->total_words * 4);
+            g->bsum_state = KGMA_BSUM_NONE;
+            return KGMA_OK;
+        }
+        g->device_bytes += g->total_words * 4;
+    }
+    PackSumsArgs a;
+    memset(&a, 0, sizeof a);
+    pack_sums_args(g, g->d_bsum_S, a);
+    a.planes = nullptr; a.inter = nullptr;                             // (the sums-only form writes neither)
+    HIP_TRY(ctx, launch_pack_sums(a, g->bsum_k, g->bsum_smax, ctx->n_cus, true, ctx->stream));
+    g->bsum_state = KGMA_BSUM_WRITTEN;
+    return KGMA_OK;
+}
+
 // sums: the step's pack with the prefilter's block sums of KFV 0 (pack_sums_kernel; the caller has checked that it applies and
-// that g->d_bsum exists).  sparse (with sums, a genome without planes): the sums-only form -- the 2-bit copy is left PARTIAL and the
+// that g->d_bsum exists, or that the pack tests).  sparse (with sums, a genome without planes): the sums-only form -- the 2-bit copy is left PARTIAL and the
 // step packs the blocks it reads (pack_candidate_blocks, pack_record_blocks).  Every other pack is a full one: FULL
 int genome_repack(kgma_ctx *ctx, kgma_genome *g, const PackSums *sums, bool sparse = false)
 {
@@ -1657,14 +1717,20 @@ int genome_repack(kgma_ctx *ctx, kgma_genome *g, const PackSums *sums, bool spar
     if (g->n_contigs > 0 && sums) {
         PackSumsArgs a;
         memset(&a, 0, sizeof a);
-        a.ascii = g->d_ascii; a.planes = g->d_planes; a.inter = g->d_inter; a.bsum = g->d_bsum;
-        a.cd = g->d_cd; a.total_words = g->total_words; a.block_contig = g->d_block_contig; a.first_bad = g->d_first_bad;
-        a.S = sums->S; a.n_contigs = (int32_t)g->n_contigs;
-        const int bw = pack_block_words();
-        a.block_shift = (bw & (bw - 1)) == 0 ? __builtin_ctz((unsigned)bw) : -1;
-        HIP_TRY(ctx, launch_pack_sums(a, sums->k, sums->s_max, sums->n_cus, sparse, ctx->stream));
-        g->bsum_fresh = true;
+        const bool test = sums->test && sparse;
+        pack_sums_args(g, sums->S, a);
+        if (test) {
+            a.bsum = nullptr;
+            a.U = sums->U; a.nblk = sums->nblk; a.nk = sums->nk; a.run = sums->run; a.cap = (unsigned int)sums->cap;
+            a.list = reinterpret_cast<FilterEntry *>(ctx->h_fpin_dev + 16);
+            a.ctl = ctx->d_fctl;
+        }
+        HIP_TRY(ctx, launch_pack_sums(a, sums->k, sums->s_max, sums->n_cus, sparse, ctx->stream, test ? reinterpret_cast<unsigned int *>(ctx->h_fpin_dev) : nullptr));
+        g->bsum_fresh = !test;
+        g->pack_tested = test;
+        g->bsum_state = test ? KGMA_BSUM_DEFERRED : KGMA_BSUM_WRITTEN;
         g->bsum_k = sums->k;
+        g->bsum_smax = sums->s_max;
     } else if (g->n_contigs > 0)
         HIP_TRY(ctx, pack_blocks(ctx, g));
     else
@@ -1918,6 +1984,8 @@ int kgma_genome_revcomp_into(kgma_ctx *ctx, const kgma_genome *g, kgma_genome *r
     {
         const int irc = ensure_inter(ctx, rc);                         // (rc's text is about to change: its 2-bit copy is completed from the old one first)
         if (irc) return irc;
+        const int brc = ensure_bsum(ctx, rc, false);                       // (and its block sums, where a step left them to be written)
+        if (brc) return brc;
     }
     // the kernel writes all of a record's slot in the text
     const std::vector<int64_t> prefix = tile_prefix(nc, revcomp_tile_bytes(), true, [&](int64_t c) { return g->cd[(size_t)c].len; });
@@ -2275,6 +2343,11 @@ int kgma_genome_poke(kgma_ctx *ctx, kgma_genome *g, int64_t contig, int64_t pos,
         return ctx_fail(ctx, KGMA_E_ARG, "kgma_genome_poke: range outside the record");
     if (len == 0) return KGMA_OK;
     (void)hipSetDevice(ctx->device);
+    if (g->bsum_state == KGMA_BSUM_DEFERRED) {                         // (so do the block sums)
+        const int brc = ensure_bsum(ctx, g, false);
+        if (brc) return brc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
     if (g->inter_state != KGMA_INTER_FULL) {
         // the 2-bit copy stays the text as of the last pack: completed, to the end, before the text changes (the copy below does
         // not wait for the context's stream)
@@ -2306,7 +2379,7 @@ void kgma_genome_free(kgma_ctx *ctx, kgma_genome *g)
 {
     if (!g) return;
     if (ctx) (void)hipSetDevice(ctx->device);
-    for (void *p : {(void *)g->d_ascii, (void *)g->d_planes, (void *)g->d_inter, (void *)g->d_cd, (void *)g->d_first_bad, (void *)g->d_block_contig, (void *)g->d_bsum})
+    for (void *p : {(void *)g->d_ascii, (void *)g->d_planes, (void *)g->d_inter, (void *)g->d_cd, (void *)g->d_first_bad, (void *)g->d_block_contig, (void *)g->d_bsum, (void *)g->d_bsum_S})
         if (p) (void)hipFree(p);
     if (g->first_bad) (void)hipHostFree(g->first_bad);
     if (ctx && ctx->tk_uid == g->uid) ctx->tk_uid = 0;
@@ -2749,6 +2822,29 @@ static bool fuse_sums_possible(const kgma_ctx *ctx, int32_t mode)
     return mode == KGMA_MODE_SINGLE && !ctx->strobe && ctx->m >= 1 && !ctx->kfv[0].fp && pack_sums_applies(ctx->k, ctx->kfv[0].Smax);
 }
 
+// The candidate list's buffers, for whichever kernel appends to it (the filter's, or the step's pack when it tests): the list lives
+// in pinned host memory (the kernel appends a few thousand 16-byte entries), its counters on the device.  *cap: entries it holds
+static int filter_reserve_list(kgma_ctx *ctx, int64_t *cap_out)
+{
+    int64_t cap = 1 << 18;
+    if (const char *e = getenv("KGMA_FILTER_CAP")) cap = std::min<int64_t>(std::max<int64_t>(1, atoll(e)), 1 << 24);
+    const size_t pin_need = 16 + (size_t)cap * sizeof(FilterEntry);
+    if (pin_need > ctx->fpin_cap) {
+        if (ctx->h_fpin) (void)hipHostFree(ctx->h_fpin);
+        ctx->h_fpin = nullptr; ctx->fpin_cap = 0;
+        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_fpin), pin_need, hipHostMallocDefault));
+        ctx->fpin_cap = pin_need;
+        HIP_TRY(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_fpin_dev), ctx->h_fpin, 0));
+    }
+    if (!ctx->d_fctl) {
+        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_fctl), 16));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_fctl, 0, 16, ctx->stream));
+    }
+    if (!ctx->evf0) { HIP_TRY(ctx, hipEventCreate(&ctx->evf0)); HIP_TRY(ctx, hipEventCreate(&ctx->evf1)); }
+    *cap_out = cap;
+    return KGMA_OK;
+}
+
 static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t n_tiles, bool *filtered)
 {
     *filtered = false;
@@ -2768,50 +2864,47 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
         if (geom_debug) fprintf(stderr, "scan filter: skipped, this genome fell back before\n");
         return KGMA_OK;
     }
-    // ---- buffers: the list lives in pinned host memory (the kernel appends a few thousand 16-byte entries), its counter on the device
-    int64_t cap = 1 << 18;
-    if (const char *e = getenv("KGMA_FILTER_CAP")) cap = std::min<int64_t>(std::max<int64_t>(1, atoll(e)), 1 << 24);
-    const size_t pin_need = 16 + (size_t)cap * sizeof(FilterEntry);
-    if (pin_need > ctx->fpin_cap) {
-        if (ctx->h_fpin) (void)hipHostFree(ctx->h_fpin);
-        ctx->h_fpin = nullptr; ctx->fpin_cap = 0;
-        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_fpin), pin_need, hipHostMallocDefault));
-        ctx->fpin_cap = pin_need;
-        HIP_TRY(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->h_fpin_dev), ctx->h_fpin, 0));
-    }
-    if (!ctx->d_fctl) {
-        HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_fctl), 16));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_fctl, 0, 16, ctx->stream));
-    }
-    if (!ctx->evf0) { HIP_TRY(ctx, hipEventCreate(&ctx->evf0)); HIP_TRY(ctx, hipEventCreate(&ctx->evf1)); }
-    if (!g->bsum_fresh) {                                               // (only the form on this step's block sums leaves the 2-bit copy alone)
-        const int irc = ensure_inter(ctx, g);
-        if (irc) return irc;
-    }
-    FilterArgs a;
-    memset(&a, 0, sizeof a);
-    a.inter = g->d_inter; a.n_dwords = 2 * g->total_words;
-    a.tiles = ctx->d_tiles; a.n_tiles = (int32_t)n_tiles;
-    a.nblk = (nk + 14) / 16 + 1;
-    a.cd = g->d_cd;
-    a.S = ctx->d_Stab;
-    a.U = U;
-    a.cap = (unsigned int)cap;
-    a.list = reinterpret_cast<FilterEntry *>(ctx->h_fpin_dev + 16);
-    a.ctl = ctx->d_fctl;
-    a.bsum = g->bsum_fresh ? g->d_bsum : nullptr;                       // (this scan's pack wrote the block sums: the PRESUMMED form)
-    HIP_TRY(ctx, hipEventRecord(ctx->evf0, ctx->stream));
+    int64_t cap = 0;
     int32_t form = 0;
-    HIP_TRY(ctx, launch_filter(a, ctx->k, f.Smax, ctx->n_cus, reinterpret_cast<unsigned int *>(ctx->h_fpin_dev), &form, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->evf1, ctx->stream));
-    HIP_TRY(ctx, sync_spin(ctx->stream));
-    fs.ran = 1;
-    fs.form = form;
-    {
+    if (g->pack_tested) {
+        // ---- this scan's pack has made the test (plan_deferred_pack): no kernel here, its list is waited for and read like the filter's
+        if (U != ctx->ptest_U) return fail(ctx, KGMA_E_HIP, "internal: the pack tested against bound %u, the scan's is %u", ctx->ptest_U, U);
+        cap = ctx->ptest_cap;
+        HIP_TRY(ctx, hipEventRecord(ctx->evf0, ctx->stream));           // (kgma_stats::scan_ms runs from here: read-back, table, exact launch)
+        HIP_TRY(ctx, sync_spin(ctx->stream));
+        form = 1 | (32 << 8) | (1 << 16);                               // (what launch_filter reports for the form on the block sums)
+        fs.filter_ms = 0;                                               // (the time is the pack's: kgma_stats::pack_ms)
+        const unsigned int *hc = reinterpret_cast<const unsigned int *>(ctx->h_fpin);
+        ctx->ptest.slow_units = hc[1]; ctx->ptest.primed_chunks = hc[2];     // (both counted by the kernel)
+    } else {
+        const int lrc = filter_reserve_list(ctx, &cap);
+        if (lrc) return lrc;
+        if (!g->bsum_fresh) {                                           // (only the form on this step's block sums leaves the 2-bit copy alone)
+            const int irc = ensure_inter(ctx, g);
+            if (irc) return irc;
+        }
+        FilterArgs a;
+        memset(&a, 0, sizeof a);
+        a.inter = g->d_inter; a.n_dwords = 2 * g->total_words;
+        a.tiles = ctx->d_tiles; a.n_tiles = (int32_t)n_tiles;
+        a.nblk = (nk + 14) / 16 + 1;
+        a.cd = g->d_cd;
+        a.S = ctx->d_Stab;
+        a.U = U;
+        a.cap = (unsigned int)cap;
+        a.list = reinterpret_cast<FilterEntry *>(ctx->h_fpin_dev + 16);
+        a.ctl = ctx->d_fctl;
+        a.bsum = g->bsum_fresh ? g->d_bsum : nullptr;                   // (this scan's pack wrote the block sums: the PRESUMMED form)
+        HIP_TRY(ctx, hipEventRecord(ctx->evf0, ctx->stream));
+        HIP_TRY(ctx, launch_filter(a, ctx->k, f.Smax, ctx->n_cus, reinterpret_cast<unsigned int *>(ctx->h_fpin_dev), &form, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->evf1, ctx->stream));
+        HIP_TRY(ctx, sync_spin(ctx->stream));
         float fms = 0;
         (void)hipEventElapsedTime(&fms, ctx->evf0, ctx->evf1);
         fs.filter_ms = fms;
     }
+    fs.ran = 1;
+    fs.form = form;
     const unsigned int count = *reinterpret_cast<const unsigned int *>(ctx->h_fpin);
     const size_t n_e = (size_t)std::min<int64_t>(count, cap);
     const FilterEntry *he = reinterpret_cast<const FilterEntry *>(ctx->h_fpin + 16);
@@ -2874,7 +2967,7 @@ static int filter_candidate_table(kgma_ctx *ctx, kgma_genome *g, int nk, int64_t
     fs.streams = (int64_t)ctx->ftiles.size();
     if (reason == KGMA_FILTER_OK && fs.streams > n_tiles) reason = KGMA_FILTER_STREAMS;
     if (geom_debug)
-        fprintf(stderr, "scan filter: U %u, %lld granules, %lld regions, %lld candidate streams, %lld of %lld windows, %.3f ms%s%s\n", U, (long long)fs.granules,
+        fprintf(stderr, "scan filter (%s): U %u, %lld granules, %lld regions, %lld candidate streams, %lld of %lld windows, %.3f ms%s%s\n", g->pack_tested ? "tested in the pack" : g->bsum_fresh ? "filter kernel on the pack's sums" : "filter kernel", U, (long long)fs.granules,
                 (long long)fs.regions, (long long)fs.streams, (long long)fs.windows, (long long)total_nwin, fs.filter_ms, reason ? ", fallback: " : "",
                 reason == KGMA_FILTER_OVERFLOW ? "list overflow" : reason == KGMA_FILTER_STREAMS ? "too many streams" : reason == KGMA_FILTER_FRACTION ? "too many windows" : "");
     if (reason != KGMA_FILTER_OK) {
@@ -3005,6 +3098,7 @@ bool filter_wanted(const kgma_ctx *ctx, const ScanPlan &p, bool ovl)
 int plan_deferred_pack(kgma_ctx *ctx, kgma_genome *g, ScanPlan &p)
 {
     g->bsum_fresh = false;                                             // (block sums are only good inside the scan whose pack wrote them)
+    g->pack_tested = false;
     if (!g->repack_deferred) return KGMA_OK;
     p.overlap = p.use_stream && !p.generic_all && p.groups.size() == 1 && p.groups[0].gr.kfvs.size() == 1 && p.m_used == 1 && p.groups[0].s8 &&
                 g->d_planes == nullptr && overlap_setup(ctx);
@@ -3013,23 +3107,50 @@ int plan_deferred_pack(kgma_ctx *ctx, kgma_genome *g, ScanPlan &p)
     // the pack carries the filter's block sums when the filter is going to run on byte entries (else: the plain pack, and
     // the filter, if it runs after all, cuts its k-mers itself)
     bool sums = false;
+    uint32_t U = 0;
+    const int nk0 = (int)(ctx->kfv[0].W - p.k + 1);
     if (fuse_sums_possible(ctx, p.mode) && !g->bsum_failed && filter_wanted(ctx, p, false) && !filter_remembered(ctx, g)) {
         const int64_t W0 = ctx->kfv[0].W;
         int64_t total_nwin = 0;
         for (const ContigDesc &d : g->cd) total_nwin += d.len >= W0 ? d.len - W0 + 1 : 0;
-        uint32_t U = 0;
-        sums = filter_bound(ctx, (int)(W0 - p.k + 1), total_nwin, &U);
+        sums = filter_bound(ctx, nk0, total_nwin, &U);
     }
-    if (sums && !g->d_bsum) {
+    // ... and makes the filter's test itself where the pack is going to be the sums-only one and the genome gives every wave a few
+    // runs (KGMA_PACK_TEST=0: never; KGMA_PACK_RUN: units per run; KGMA_PACK_TEST_MIN_UNITS: the gate, for tests).  Below the gate
+    // the runs would leave waves idle, and the filter kernel on a small genome's sums costs next to nothing.
+    const char *sp = getenv("KGMA_SPARSE_PACK"), *pt = getenv("KGMA_PACK_TEST");
+    PackSums with_sums{ctx->d_Stab, ctx->k, ctx->kfv[0].Smax, ctx->n_cus};
+    if (sums && g->d_planes == nullptr && g->n_contigs > 0 && !(sp && atoi(sp) == 0) && !(pt && atoi(pt) == 0)) {
+        int run = PACK_TEST_RUN;
+        if (const char *e = getenv("KGMA_PACK_RUN")) run = std::min(std::max(1, atoi(e)), 4096);
+        const int64_t units = (g->total_words + 127) / 128;
+        int64_t min_units = pack_sums_waves(ctx->n_cus) * run * PACK_TEST_MIN_RUNS;
+        if (const char *e = getenv("KGMA_PACK_TEST_MIN_UNITS")) min_units = std::max<int64_t>(1, atoll(e));
+        const int nblk = (nk0 + 14) / 16 + 1;
+        if (units >= min_units && units < ((int64_t)1 << 29) && run <= 4096 && nblk >= 1 && nblk <= 63) {
+            int64_t cap = 0;
+            const int lrc = filter_reserve_list(ctx, &cap);
+            if (lrc) return lrc;
+            if (g->bsum_S_refs != ctx->refs_version || !g->d_bsum_S) {  // (ensure_bsum may run after the context's references changed)
+                const size_t nb = ((size_t)1 << (2 * p.k)) * sizeof(int32_t);
+                if (!g->d_bsum_S) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&g->d_bsum_S), (size_t)4096 * sizeof(int32_t)));
+                HIP_TRY(ctx, hipMemcpyAsync(g->d_bsum_S, ctx->d_Stab, nb, hipMemcpyDeviceToDevice, ctx->stream));
+                g->bsum_S_refs = ctx->refs_version;
+            }
+            with_sums.test = true; with_sums.U = U; with_sums.nblk = nblk; with_sums.nk = nk0; with_sums.run = run; with_sums.cap = cap;
+            ctx->ptest_U = U; ctx->ptest_cap = cap;
+            ctx->ptest.tested = 1; ctx->ptest.run = run;
+            ctx->ptest.units = units;
+        }
+    }
+    if (sums && !with_sums.test && !g->d_bsum) {
         if (hipMalloc(reinterpret_cast<void **>(&g->d_bsum), (size_t)g->total_words * 4) != hipSuccess) {
             (void)hipGetLastError();
             g->d_bsum = nullptr; g->bsum_failed = true; sums = false;
         } else g->device_bytes += g->total_words * 4;
     }
     // ... and, on a genome without planes, leaves the 2-bit copy to the blocks the step reads (KGMA_SPARSE_PACK=0: never)
-    const char *sp = getenv("KGMA_SPARSE_PACK");
     const bool sparse = sums && g->d_planes == nullptr && !(sp && atoi(sp) == 0);
-    const PackSums with_sums{ctx->d_Stab, ctx->k, ctx->kfv[0].Smax, ctx->n_cus};
     return genome_repack(ctx, g, sums ? &with_sums : nullptr, sparse);
 }
 
@@ -6335,15 +6456,26 @@ int kgma_get_filter_stats(kgma_ctx *ctx, kgma_filter_stats *out)
     return KGMA_OK;
 }
 
+int kgma_get_pack_test_stats(kgma_ctx *ctx, kgma_pack_test_stats *out)
+{
+    if (!ctx || !out) return KGMA_E_ARG;
+    *out = ctx->ptest;
+    return KGMA_OK;
+}
+
 int kgma_get_block_sums(kgma_ctx *ctx, const kgma_genome *g, int64_t contig, int64_t first_block, int64_t n, uint32_t *out)
 {
     if (!ctx || !g) return KGMA_E_ARG;
-    if (!g->d_bsum || g->bsum_k == 0) return fail(ctx, KGMA_E_STATE, "kgma_get_block_sums: no step has put block sums into this genome's pack");
+    if (g->bsum_state == KGMA_BSUM_NONE || g->bsum_k == 0) return fail(ctx, KGMA_E_STATE, "kgma_get_block_sums: no step has put block sums into this genome's pack");
     if (contig < 0 || contig >= g->n_contigs || first_block < 0 || n < 0 || (!out && n > 0)) return fail(ctx, KGMA_E_ARG, "kgma_get_block_sums: bad argument");
     const ContigDesc &d = g->cd[(size_t)contig];
     if (first_block + n > 2 * ((d.len + 31) / 32)) return fail(ctx, KGMA_E_ARG, "kgma_get_block_sums: blocks outside the record");
     if (n == 0) return KGMA_OK;
     (void)hipSetDevice(ctx->device);
+    {
+        const int brc = ensure_bsum(ctx, const_cast<kgma_genome *>(g), true);   // (a step whose pack tested left them to be written)
+        if (brc) return brc;
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<uint16_t> tmp((size_t)n);
     HIP_TRY(ctx, hipMemcpy(tmp.data(), g->d_bsum + 2 * d.word_off + first_block, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost));

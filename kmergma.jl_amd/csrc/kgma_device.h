@@ -271,6 +271,15 @@ struct PackSumsArgs {
     const int32_t *S;             // the KFV's S table as FilterArgs::S, every entry below 256
     int32_t n_contigs;
     int32_t block_shift;
+    // the form that makes the prefilter's granule test itself (pack_sums_kernel<K, false, true>; else list is null): FilterArgs' U,
+    // nblk, cap, list and ctl -- ctl[1] counts the units that went word by word, ctl[2] the chunks primed -- and
+    int32_t nblk;
+    int32_t nk;                   // k-mers of a window (a record has len - (nk + K - 1) + 1 windows)
+    int32_t run;                  // consecutive units a wave takes at a time
+    uint32_t U;
+    unsigned int cap;
+    FilterEntry *list;
+    unsigned int *ctl;
 };
 
 // Aux region of the result block: residues under tied minima, gathered on the device (export_kernel)

@@ -338,9 +338,20 @@ __device__ __forceinline__ void ps_stage_tables(uint32_t *fsm, const int32_t *S)
 // COPY = false, the sums-only form of a sparse step: the same encoding, sums and first_bad, but no word of
 // the 2-bit copy is stored (nor a plane: the form is only chosen for genomes without planes) -- the step packs the blocks it reads
 // with pack_kernel afterwards.  A fast unit then issues two stores per lane, not four, and the kernel moves 1.125 B per base.
-template <int K, bool COPY>
+//
+// TEST = true (only with COPY = false), the form that makes the prefilter's granule test itself and stores nothing in its steady
+// loop.  bsum is ONE array over all blocks of the genome, 0 in the padding, and records lie 2 *
+// CONTIG_PAD_WORDS = 64 zero blocks apart while nblk - 1 <= 62: the sum of the nblk blocks from a granule's first block on never
+// reaches the next record, so the candidate set is a prefix-sum difference over the GLOBAL block array, and only the label
+// (record, granule) and the test 0 <= granule < ceil(nwin / 16) are per record.  A chunk (64 plane words = 128 blocks, two per
+// lane, the sums of the storing form's layout) is one iteration of filter_sums_kernel's scheme with two blocks per lane.  The carry
+// wants consecutive units: a wave takes RUNS of a.run units, the runs dealt round-robin over the waves, and PRIMES a run with the
+// second chunk of the unit in front of it (128 blocks >= nblk - 1), of which nothing is emitted.  In a clean fast unit the
+// record is the wave's (scalar registers); elsewhere each candidate lane looks its block's record up and appends one granule.
+template <int K, bool COPY, bool TEST = false>
 __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
 {
+    static_assert(!TEST || !COPY, "the testing form stores nothing");
     extern __shared__ uint32_t fsm[];
     ps_stage_tables<K>(fsm, a.S);
     const int lane = (int)(threadIdx.x & 63);
@@ -356,7 +367,9 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
     uint32_t *outs = reinterpret_cast<uint32_t *>(a.bsum);             // one dword per plane word: its two sums
 
     // a unit's record and path (wave-uniform), and on the fast path its loads
-    struct Unit { int c; bool fast; u32x4_t v[4]; uint2 halo; };
+    // (TEST: u, the unit; rel: the unit's first block in the record's numbering; ng: the record's granules, or -1 in a PRIMING
+    //  visit: only the unit's second chunk is wanted, and nothing emitted)
+    struct Unit { int c; bool fast; u32x4_t v[4]; uint2 halo; int u, rel, ng; __device__ bool prime() const { return ng < 0; } };
     // The record of the wave's latest unit, in scalar registers: c = the last record that starts at or before the unit's first word
     // (record 0 in the lead padding), and `next`, the word at which record c + 1 starts (INT64_MAX behind the last).  A wave's units
     // only move forward, so the record stands until a unit starts at or past `next`; only then it is looked up again, from the
@@ -365,7 +378,7 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
     int64_t r_word_off = 0, r_len = 0, r_ascii_off = 0, r_next = 0;    // (r_next = 0: the wave's first unit looks its record up)
     auto prepare = [&](const int64_t u, Unit &n) {
         const int64_t g0 = u * PS_UNIT;
-        if (g0 >= r_next) {
+        if (TEST ? __builtin_expect(g0 >= r_next, 0) : g0 >= r_next) {
             int c = a.block_contig[g0 >> a.block_shift];
             while (c + 1 < a.n_contigs && a.cd[c + 1].word_off <= g0) c++;
             const ContigDesc d = a.cd[c];
@@ -376,12 +389,19 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
         }
         const int64_t w0 = g0 - r_word_off;
         n.c = rc;
+        if constexpr (TEST) {
+            const int64_t nwin = r_len - (a.nk + K - 1) + 1, ng = nwin > 0 ? (nwin + 15) >> 4 : 0;
+            n.rel = (int)(2 * w0);
+            if (!n.prime()) n.ng = (int)(ng > 0x7FFFFFFF ? 0x7FFFFFFF : ng);
+        }
         n.fast = w0 >= 0 && g0 + PS_UNIT <= a.total_words && (w0 + PS_UNIT) * 32 + (K - 1) <= r_len;
         if (n.fast) {
             const uint8_t *base = a.ascii + r_ascii_off + w0 * 32;
             const u32x4_t *p = reinterpret_cast<const u32x4_t *>(base) + 2 * lane;
-            n.v[0] = __builtin_nontemporal_load(p);
-            n.v[1] = __builtin_nontemporal_load(p + 1);
+            if (!TEST || !n.prime()) {
+                n.v[0] = __builtin_nontemporal_load(p);
+                n.v[1] = __builtin_nontemporal_load(p + 1);
+            }
             n.v[2] = __builtin_nontemporal_load(p + 128);
             n.v[3] = __builtin_nontemporal_load(p + 129);
             n.halo = make_uint2(0u, 0u);
@@ -413,7 +433,10 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
             uint32_t bad0, bad1;
             const uint4 a0 = make_uint4(cu.v[0].x, cu.v[0].y, cu.v[0].z, cu.v[0].w), b0 = make_uint4(cu.v[1].x, cu.v[1].y, cu.v[1].z, cu.v[1].w);
             const uint4 a1 = make_uint4(cu.v[2].x, cu.v[2].y, cu.v[2].z, cu.v[2].w), b1 = make_uint4(cu.v[3].x, cu.v[3].y, cu.v[3].z, cu.v[3].w);
-            if (!COPY || a.planes == nullptr) {                        // (no planes kept: straight to the 2-bit codes)
+            if (TEST && cu.prime()) {
+                bad0 = 0u;
+                i1 = pack_word_2bit(a1, b1, &bad1);
+            } else if (!COPY || a.planes == nullptr) {                 // (no planes kept: straight to the 2-bit codes)
                 i0 = pack_word_2bit(a0, b0, &bad0);
                 i1 = pack_word_2bit(a1, b1, &bad1);
             } else {
@@ -426,14 +449,18 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
         if (clean) {
             // the first dword of the next word: lane l + 1's; lane 63 reads lane 0, which offers the other chunk's / the halo's
             const uint32_t h = ps_halo_clean<K>(cu.halo);
-            const uint32_t n0 = (uint32_t)__builtin_amdgcn_ds_bpermute(next_idx, (int)(lane == 0 ? i1.x : i0.x));
+            uint32_t n0 = 0u;                                          // (a priming visit has no first chunk)
+            if (!TEST || !cu.prime()) n0 = (uint32_t)__builtin_amdgcn_ds_bpermute(next_idx, (int)(lane == 0 ? i1.x : i0.x));
             const uint32_t n1 = (uint32_t)__builtin_amdgcn_ds_bpermute(next_idx, (int)(lane == 0 ? h : i1.x));
             // (one sum's 16 lookups at a time: the other waves of the SIMD cover their latency, interleaving all 64 only costs registers)
+            uint32_t s00 = 0u, s01 = 0u;
             __builtin_amdgcn_sched_barrier(0);
-            const uint32_t s00 = ps_sum16_pairs<K>(i0.x, i0.y, ptab);
-            __builtin_amdgcn_sched_barrier(0);
-            const uint32_t s01 = ps_sum16_pairs<K>(i0.y, n0, ptab);
-            __builtin_amdgcn_sched_barrier(0);
+            if (!TEST || !cu.prime()) {
+                s00 = ps_sum16_pairs<K>(i0.x, i0.y, ptab);
+                __builtin_amdgcn_sched_barrier(0);
+                s01 = ps_sum16_pairs<K>(i0.y, n0, ptab);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             const uint32_t s10 = ps_sum16_pairs<K>(i1.x, i1.y, ptab);
             __builtin_amdgcn_sched_barrier(0);
             const uint32_t s11 = ps_sum16_pairs<K>(i1.y, n1, ptab);
@@ -443,10 +470,12 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
         e.r0 = r0; e.r1 = r1; e.i0 = i0; e.i1 = i1;
         return clean;
     };
-    auto by_word = [&](const int64_t u, const int c0) {
+    // (TEST: nothing is stored; the chunks' sums go to e.s0, e.s1, 0 for a word outside the genome; from chunk q0 on)
+    auto by_word = [&](const int64_t u, const int c0, Enc &e, const int q0) {
         const int64_t g0 = u * PS_UNIT;
+        if constexpr (TEST) e.s0 = e.s1 = 0u;
 #pragma unroll 1
-        for (int q = 0; q < PS_UNIT / 64; q++) {
+        for (int q = q0; q < PS_UNIT / 64; q++) {
             const int64_t g = g0 + q * 64 + lane;
             if (g >= a.total_words) continue;
             int c = c0;
@@ -470,7 +499,8 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
                 s0 = ps_sum16_masked<K>(iw.x, iw.y, tab, nv0);
                 s1 = ps_sum16_masked<K>(iw.y, h, tab, nv1);
             }
-            store(g0 + q * 64, lane, r, iw, s0 | (s1 << 16));
+            if constexpr (TEST) (q == 0 ? e.s0 : e.s1) = s0 | (s1 << 16);
+            else store(g0 + q * 64, lane, r, iw, s0 | (s1 << 16));
         }
     };
 
@@ -480,6 +510,112 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
     // are those of the unit before u, a whole encode old, and u's own go out behind the new loads with nothing waiting on them.
     // (Taking nx over behind u's stores, as `cu = nx` at the loop's head did, made every unit wait for its predecessor's stores to
     // drain with no load in flight: EXPERIMENTS.md section 16.)  A record lookup, where one runs, waits at the same place.
+    if constexpr (TEST) {
+        // The same loop over the wave's VISITS: the units of its runs, each run behind its priming visit.  Nothing is stored; a
+        // chunk's sums go through the scan, the two lower ends and the test where the storing form stores them.
+        // (the host launches this form with fewer than 2^30 units: units, runs and the visit cursor are 32-bit scalars)
+        const int R = a.run, nu = (int)n_units, nw = (int)n_waves;
+        if (wave0 * R >= n_units) return;
+        const int nblk = a.nblk, hb = nblk & 1;                        // nblk = 2 ha + hb
+        int lo_idx[2];                                                 // (bpermute takes byte addresses)
+        int offer_cur[2];                                              // lanes below it have their reader in this chunk (else in the next)
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const int back = (nblk >> 1) + (q < hb ? 1 : 0);
+            lo_idx[q] = ((lane - back) & 63) << 2;
+            offer_cur[q] = 64 - back;                                  // (a scalar and a compare per use: a lane mask held across the loop costs two)
+        }
+        uint32_t carry = 0, prevR[2] = {0u, 0u};                       // (block 0 of the genome has nothing in front: 0)
+        unsigned int n_primed = 0;
+        int v_u0 = (int)wave0 * R, v_i = wave0 == 0 ? 0 : -1;          // the next visit: unit v_u0 + v_i of the run from v_u0 (-1: the priming one)
+        auto next = [&](Unit &n) {
+            if (v_u0 >= nu) { n.u = -1; n.fast = false; n.ng = 0; return; }
+            n.u = v_u0 + v_i;
+            n.ng = v_i < 0 ? -1 : 0;
+            prepare(n.u, n);
+            v_i++;
+            if (v_i == R || v_u0 + v_i >= nu) { v_u0 += nw * R; v_i = -1; }
+        };
+        auto append = [&](const int32_t c, const int32_t gbase, const uint64_t mask) {
+            const unsigned int idx = atomicAdd(a.ctl, 1u);
+            if (idx < a.cap) {
+                FilterEntry fe;
+                fe.contig = c; fe.gbase = gbase; fe.mask = mask;
+                a.list[idx] = fe;
+            }
+        };
+        // chunk q of the unit: s01 = the lane's two block sums; own: the unit lies in the record the unit names
+        auto test = [&](const Unit &un, const bool own, const uint32_t s01, const int q) {
+            const uint32_t s1 = s01 >> 16;
+            const uint32_t I1 = f_incl_scan((s01 & 0xFFFFu) + s1) + carry;   // (mod 2^32: only differences nblk blocks apart are used)
+            carry = (uint32_t)__builtin_amdgcn_readlane((int)I1, 63);
+            const uint32_t I[2] = {I1 - s1, I1};
+            const uint32_t Rq[2] = {hb ? I[1] : I[0], hb ? I[0] : I[1]};     // the lower end of element q is element (q - hb) & 1 of its source lane
+            bool cand[2];
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(lo_idx[e], (int)(lane < offer_cur[e] ? Rq[e] : prevR[e]));
+                prevR[e] = Rq[e];
+                cand[e] = I[e] - lo >= a.U;
+            }
+            if (un.prime()) return;
+            const int back = q * 128 - (nblk - 1);                     // from the unit's first block to the granule of lane 0's element 0
+            if (own) {
+                const int gl = un.rel + back + 2 * lane;
+                const uint64_t m0 = __ballot(cand[0] & ((uint32_t)gl < (uint32_t)un.ng));
+                const uint64_t m1 = __ballot(cand[1] & ((uint32_t)(gl + 1) < (uint32_t)un.ng));
+                if (__builtin_expect((m0 | m1) != 0, 0)) {             // rare: entry e holds the blocks 64 e ... 64 e + 63 of the chunk
+                    const uint64_t mine = (lane & 1) ? m1 : m0;
+#pragma unroll 1
+                    for (int e = 0; e < 2; e++) {
+                        const uint64_t me = __ballot(((mine >> (32 * e + (lane >> 1))) & 1u) != 0);
+                        if (me != 0 && lane == 0) append(un.c, un.rel + back + 64 * e, me);
+                    }
+                }
+            } else if (__builtin_expect(cand[0] | cand[1], 0)) {       // rare: every candidate lane finds its block's record
+#pragma unroll 1
+                for (int e = 0; e < 2; e++) {
+                    const int64_t B = (int64_t)un.u * (2 * PS_UNIT) + back + 2 * lane + e, w = B >> 1;
+                    if (!cand[e] || B < 0 || w >= a.total_words) continue;
+                    int c = a.block_contig[w >> a.block_shift];
+                    while (c + 1 < a.n_contigs && a.cd[c + 1].word_off <= w) c++;
+                    const ContigDesc d = a.cd[c];
+                    const int64_t g = B - 2 * d.word_off, nwin = d.len - (a.nk + K - 1) + 1;
+                    if (g >= 0 && nwin > 0 && g < ((nwin + 15) >> 4)) append(c, (int32_t)g, 1u);
+                }
+            }
+        };
+        Unit cu, nx;
+        cu.c = nx.c = 0; cu.fast = nx.fast = false; cu.u = nx.u = -1; cu.rel = nx.rel = cu.ng = nx.ng = 0;
+        nx.halo = cu.halo = make_uint2(0u, 0u);
+#pragma unroll
+        for (int i = 0; i < 4; i++) nx.v[i] = cu.v[i] = u32x4_t{0u, 0u, 0u, 0u};
+        next(cu);
+        next(nx);
+#pragma unroll
+        for (int i = 0; i < 4; i++) asm volatile("" : "+v"(cu.v[i]));
+        asm volatile("" : "+v"(cu.halo.x), "+v"(cu.halo.y));
+        while (cu.u >= 0) {
+            Enc e;
+            const bool clean = encode(cu, e);
+            if (__builtin_expect(!clean, 0)) {
+                by_word(cu.u, cu.c, e, cu.prime() ? 1 : 0);
+                if (!cu.prime() && lane == 0) atomicAdd(a.ctl + 1, 1u);  // units that went word by word (kgma_get_pack_test_stats)
+            }
+            if (!cu.prime()) test(cu, clean, e.s0, 0);
+            else n_primed++;
+            test(cu, clean, e.s1, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            cu = nx;
+#pragma unroll
+            for (int i = 0; i < 4; i++) asm volatile("" : "+v"(cu.v[i]));
+            asm volatile("" : "+v"(cu.halo.x), "+v"(cu.halo.y));
+            next(nx);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (lane == 0 && n_primed != 0) atomicAdd(a.ctl + 2, n_primed);   // chunks primed (kgma_get_pack_test_stats)
+        return;
+    }
     if (wave0 >= n_units) return;
     Unit cu, nx;
     nx.c = 0; nx.fast = false; nx.halo = cu.halo = make_uint2(0u, 0u);
@@ -496,7 +632,7 @@ __global__ __launch_bounds__(1024) void pack_sums_kernel(PackSumsArgs a)
         Enc e;
         const int c0 = cu.c;
         const bool clean = encode(cu, e);
-        if (!clean) by_word(u, c0);                                    // (with its own loads and stores, and one buffer less alive)
+        if (!clean) by_word(u, c0, e, 0);                              // (with its own loads and stores, and one buffer less alive)
         __builtin_amdgcn_sched_barrier(0);
         cu = nx;
         // (the copy is pinned here: left to the compiler it sinks to the back-edge, behind the stores)
@@ -518,6 +654,15 @@ __global__ void filter_publish_kernel(unsigned int *ctl, unsigned int *host)
     if (threadIdx.x == 0) {
         host[0] = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(ctl, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the testing pack's three counters (entries, units that went word by word, chunks primed) to the pinned mirror, and back to zero
+__global__ void pack_test_publish_kernel(unsigned int *ctl, unsigned int *host)
+{
+    if (threadIdx.x < 3) {
+        host[threadIdx.x] = __hip_atomic_load(ctl + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ctl + threadIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -558,11 +703,11 @@ static hipError_t filter_sums_launch(const FilterArgs &a, int k, int n_cus, hipS
 
 bool pack_sums_applies(int k, int64_t s_max) { return (k == 5 || k == 6) && s_max >= 0 && s_max < 256; }
 
-template <int K, bool COPY>
+template <int K, bool COPY, bool TEST = false>
 static hipError_t pack_sums_launch(const PackSumsArgs &a, int n_cus, hipStream_t st)
 {
     constexpr size_t lds = ((size_t)1 << (2 * K)) * 9;                 // 4^(K+1) uint16 + 4^K bytes
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&pack_sums_kernel<K, COPY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&pack_sums_kernel<K, COPY, TEST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     // persistent waves: one 16-wave workgroup per CU (at up to 128 VGPRs a second one would not be resident beside it)
     int64_t grid = n_cus;
@@ -570,18 +715,39 @@ static hipError_t pack_sums_launch(const PackSumsArgs &a, int n_cus, hipStream_t
         const int64_t n = atoll(w);
         grid = n < 1 ? 1 : n < n_cus ? n : n_cus;
     }
-    const int64_t need = ((a.total_words + PS_UNIT - 1) / PS_UNIT + 15) / 16;
+    const int64_t units = (a.total_words + PS_UNIT - 1) / PS_UNIT;
+    const int64_t need = ((TEST ? (units + a.run - 1) / a.run : units) + 15) / 16;     // (TEST: a wave takes whole runs)
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((pack_sums_kernel<K, COPY>), dim3((unsigned)grid), dim3(1024), lds, st, a);
+    hipLaunchKernelGGL((pack_sums_kernel<K, COPY, TEST>), dim3((unsigned)grid), dim3(1024), lds, st, a);
     return hipGetLastError();
 }
 
+// waves the sums-only pack runs on a device of n_cus CUs (the in-pack test's size gate counts runs per wave)
+int64_t pack_sums_waves(int n_cus)
+{
+    int64_t grid = n_cus;
+    if (const char *w = getenv("KGMA_PACK_WGS")) {
+        const int64_t n = atoll(w);
+        grid = n < 1 ? 1 : n < n_cus ? n : n_cus;
+    }
+    return 16 * grid;
+}
+
 // sums_only: the form that stores no word of the 2-bit copy (a genome that keeps planes has no such form: they are written with it)
-hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, bool sums_only, hipStream_t st)
+hipError_t launch_pack_sums(const PackSumsArgs &a, int k, int64_t s_max, int n_cus, bool sums_only, hipStream_t st, unsigned int *host_count)
 {
     if (!pack_sums_applies(k, s_max) || a.total_words <= 0 || a.block_shift < 0 || ((int64_t)1 << a.block_shift) % PS_UNIT != 0) return hipErrorInvalidValue;
     if (sums_only && a.planes != nullptr) return hipErrorInvalidValue;
+    if (a.list != nullptr) {                                           // the testing form: host_count gets its four counters
+        const int64_t units = (a.total_words + PS_UNIT - 1) / PS_UNIT;
+        if (units + (int64_t)n_cus * 16 * a.run >= ((int64_t)1 << 30)) return hipErrorInvalidValue;
+        if (!sums_only || a.nblk < 1 || a.nblk > 63 || a.run < 1 || a.nk < 1 || a.ctl == nullptr || host_count == nullptr) return hipErrorInvalidValue;
+        const hipError_t e = k == 5 ? pack_sums_launch<5, false, true>(a, n_cus, st) : pack_sums_launch<6, false, true>(a, n_cus, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(pack_test_publish_kernel, dim3(1), dim3(64), 0, st, a.ctl, host_count);
+        return hipGetLastError();
+    }
     if (sums_only) return k == 5 ? pack_sums_launch<5, false>(a, n_cus, st) : pack_sums_launch<6, false>(a, n_cus, st);
     return k == 5 ? pack_sums_launch<5, true>(a, n_cus, st) : pack_sums_launch<6, true>(a, n_cus, st);
 }

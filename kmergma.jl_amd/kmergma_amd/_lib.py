@@ -47,6 +47,7 @@ EXPORTS = [
     "kgma_dist_layout", "kgma_dist_bins", "kgma_dist_sweep", "kgma_get_landscape_stats",
     "kgma_genome_inter_state",
     "kgma_genome_kmer_count", "kgma_get_spectrum_stats",
+    "kgma_get_pack_test_stats",
 ]
 SWEEP_MAX_THRESHOLDS = 4096          # KGMA_SWEEP_MAX_THRESHOLDS
 ASSIGN_MAX_LEN = 8191                # KGMA_ASSIGN_MAX_LEN
@@ -128,6 +129,11 @@ class KgmaFilterStats(C.Structure):
     _fields_ = [("ran", C.c_int32), ("fell_back", C.c_int32), ("reason", C.c_int32), ("form", C.c_int32),
                 ("granules", C.c_int64), ("regions", C.c_int64), ("streams", C.c_int64), ("windows", C.c_int64),
                 ("positions", C.c_int64), ("total_windows", C.c_int64), ("bound", C.c_int64), ("filter_ms", C.c_double)]
+
+
+class KgmaPackTestStats(C.Structure):
+    _fields_ = [("tested", C.c_int32), ("run", C.c_int32), ("units", C.c_int64), ("slow_units", C.c_int64),
+                ("primed_chunks", C.c_int64)]
 
 
 class KgmaAssignStats(C.Structure):
@@ -256,6 +262,7 @@ def load():
     L.kgma_get_dists.argtypes = [vp, i32, P(dbl), i64, P(i64)]
     L.kgma_get_stats.argtypes = [vp, P(KgmaStats)]
     L.kgma_get_filter_stats.argtypes = [vp, P(KgmaFilterStats)]
+    L.kgma_get_pack_test_stats.argtypes = [vp, P(KgmaPackTestStats)]
     L.kgma_get_filter_candidates.argtypes = [vp, P(i32), P(i64), i64, P(i64)]
     L.kgma_get_block_sums.argtypes = [vp, vp, i64, i64, i64, P(C.c_uint32)]
     L.kgma_genome_inter_state.argtypes = [vp, P(i32), P(i64)]
@@ -1308,6 +1315,12 @@ class Context:
         s = KgmaFilterStats()
         self._check(load().kgma_get_filter_stats(self._h, C.byref(s)))
         return {f: getattr(s, f) for f, _ in KgmaFilterStats._fields_}
+
+    def pack_test_stats(self) -> dict:
+        """kgma_get_pack_test_stats: whether the last step's pack made the prefilter's granule test itself, and on how many units."""
+        s = KgmaPackTestStats()
+        self._check(load().kgma_get_pack_test_stats(self._h, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in KgmaPackTestStats._fields_}
 
     def get_block_sums(self, genome: "Genome", contig: int, first_block: int = 0, n: int = -1) -> np.ndarray:
         """kgma_get_block_sums: record `contig`'s block sums (one per 16 positions) of the last step whose pack computed them."""
