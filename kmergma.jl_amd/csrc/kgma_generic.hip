@@ -138,7 +138,16 @@ template <> struct Ops<double> {
 //   start-of-step counts; (B) the returning add / subtract of the direct tables; (C) a leaving lane whose entry went to 0 leaves a
 //   tombstone.  Every insertion may consume a never-used entry, so the table is rebuilt from the window (clear + re-insert its n
 //   k-mers) every `rebuild` steps, chosen by the host so that an eighth of the table is never-used at all times: probes stay
-//   short and every search ends.  A search that does not end in 8 x buckets iterations reports a fault instead of hanging.
+//   short and every search ends.
+// The probe loop's iteration limit.  Per iteration an unfinished entering search ends, moves on one bucket, or loses its swap to
+//   another k-mer and starts over.  A lane loses on an entry at most once (the entry is live from then on) and every entry it loses
+//   on was won by a different lane, so it starts over at most 63 times; a pass reads at most every bucket once (some bucket holds a
+//   never-used entry): the entering searches end within 64 x buckets iterations.  A leaving k-mer is present by then (it was at the
+//   loop's start, or a lower lane of this step has entered it) and its search needs at most two more passes.  A loop that runs
+//   longer than 66 x buckets iterations has met a table without a never-used entry or a leaving k-mer that is in no entry --
+//   neither can come from a legal input -- and reports a fault instead of hanging.  (The bound is not slack: colliding k-mers
+//   computed from the hash reach 8.5 x buckets at k = 11, n = 2048 -- DESIGN.md, "Colliding k-mers".)
+constexpr int PROBE_LIMIT_PASSES = 66;
 constexpr uint32_t H_LIVE = 0x80000000u, H_TOMB = 1u, H_CNT = 0x7FFu, H_NONE = 0xFFFFFFFFu;
 
 template <int CM>
@@ -208,7 +217,7 @@ struct Counts {
     // the searches of a step: the entering k-mers (inserted when absent), then the leaving ones (present)
     __device__ __forceinline__ void probe2(Probe &e, Probe &l)
     {
-        const int limit = 8 * (int)(bmask + 1u);
+        const int limit = PROBE_LIMIT_PASSES * (int)(bmask + 1u);
         int it = 0;
         while (__ballot(!e.done || !l.done) != 0) {
             probe_step<true>(e);
@@ -288,8 +297,8 @@ struct Counts {
 // entries is three arrays: keys[M] (0 never used, 1 tombstone, H_LIVE | k-mer), counts[M] (32 bits) and vals[M] (64 bits: the KFV's
 // value of the entry's k-mer, looked up in the sparse KFV table -- GenParams::sp_keys -- when the k-mer is inserted, so that a k-mer
 // that stays or leaves costs no lookup).  Buckets of four keys (one 16-byte read per probe), linear probing over buckets, the never-
-// used suffix per bucket, tombstones and the periodic rebuild exactly as CM 2; a search that does not end in 8 x buckets iterations
-// reports a fault instead of hanging.  Counts and keys are separate words: a claimed entry's count is 0 (never-used entries are cleared
+// used suffix per bucket, tombstones, the periodic rebuild and the probe loop's iteration limit (PROBE_LIMIT_PASSES) exactly as
+// CM 2.  Counts and keys are separate words: a claimed entry's count is 0 (never-used entries are cleared
 // and an entry becomes a tombstone only at count 0), phase B adds to the count word, phase C turns a key at count 0 into a tombstone.
 // Windows shorter than a step (nk < 64): a lane's leaving k-mer may be entered by a lower lane IN THIS STEP, i.e. not be present yet
 // when its search starts -- a leaving search that reaches a bucket with a never-used entry without finding it starts over from its
@@ -420,7 +429,7 @@ struct WCounts {
     }
     __device__ __forceinline__ void probe2(Probe &e, Probe &l)
     {
-        const int limit = 8 * (int)(bmask + 1u);
+        const int limit = PROBE_LIMIT_PASSES * (int)(bmask + 1u);
         int it = 0;
         while (__ballot(!e.done || !l.done) != 0) {
             probe_step<true>(e);
@@ -579,7 +588,7 @@ __global__ __launch_bounds__(1024) void gen_kernel(ScanArgs a, GenParams g)
                 cnt.step(kp, ks, actE, actL, cp, cs, oldp, olds);
             }
             if constexpr (CM == 2 || WIDE) {
-                if (cnt.fault) {                                      // (wave-uniform; cannot happen: the host's rebuild period keeps never-used entries)
+                if (cnt.fault) {                                      // (wave-uniform; no legal input gets here: PROBE_LIMIT_PASSES is derived, not measured)
                     if (lane == 0) {
                         DevRecord rec;
                         rec.tile = tile; rec.kind_kfv = REC_FAULT | REC_WIDE | (kid << 8);
@@ -966,7 +975,7 @@ __global__ __launch_bounds__(1024) void gen_chain_kernel(ScanArgs a, GenParams g
                 cnt.step(kp, ks, actE, actL, cp, cs, oldp, olds);
             }
             if constexpr (CM == 2 || WIDE) {
-                if (cnt.fault) {                                      // (wave-uniform; cannot happen, see Counts)
+                if (cnt.fault) {                                      // (wave-uniform; no legal input gets here, see Counts)
                     if (lane == 0) atomicOr(a.chain.status, 2u);
                     break;
                 }
