@@ -779,6 +779,71 @@ int kgma_pwm_match(kgma_ctx *ctx, const kgma_genome *g, const int16_t *weights /
 int kgma_get_pwm_matches(kgma_ctx *ctx, kgma_pwm_hit *out, int64_t cap, int64_t *n);
 int kgma_get_pwm_stats(kgma_ctx *ctx, kgma_pwm_stats *out);
 
+/* ---- protMatch: codon-weight-matrix search on a resident genome, all three reading frames (kernel: kgma_codon.hip) -------------
+ * The device searches with a CODON WEIGHT MATRIX.  Matrix i is rows row_offsets[i] .. row_offsets[i+1] - 1 of `weights`:
+ * m = 1 ... 64 rows of KGMA_CODON_ENTRIES = 65 integer weights, each in -32768 ... 32767 (the int16_t of the interface), the
+ * matrices back to back.  Entry 16 b0 + 4 b1 + b2 of a row (A 0, C 1, G 2, T 3) is the weight of the codon b0 b1 b2 read left to
+ * right on the plus strand; entry 64 is the weight of a codon that holds any residue other than A/C/G/T -- an N, that is.  Case is
+ * folded as everywhere else.
+ * Laid at the 1-based NUCLEOTIDE start s of a record t[1..L], s + 3m - 1 <= L,
+ *     score(s) = sum over the rows i = 0 ... m - 1 of row_i[codon(t[s + 3i], t[s + 3i + 1], t[s + 3i + 2])].
+ * Every start is scored, so the three reading frames of the strand are searched in one pass; nothing spans two records.  Every
+ * score fits an int32, its magnitude is at most 64 * 32768 = 2^21.  Every s with score(s) >= threshold[i] is a hit, overlapping
+ * ones included.
+ * threshold[i] must exceed the sum of the row minima of matrix i (each over the 65 entries) -- otherwise every start would
+ * match; a threshold above the sum of the row maxima is legal and finds nothing.
+ * The kernel knows nothing of genetic codes or strands: kgma_codon_fold (below) turns an amino-acid profile into the codon
+ * matrix of one strand, and a minus-strand search is a plus-strand search with another matrix, on the same genome, in the same
+ * pass, its starts in forward coordinates.
+ * All matrices are served by ONE launch (a workgroup per `wg_starts` consecutive starts of a record, a wave per `wave_starts` of
+ * them, `lane_starts` consecutive starts per lane; the workgroup keeps one codon code per residue position in LDS; the host takes
+ * the rows of 65 equal weights out and into the threshold); the search is repeated once when the hits outgrow the device buffer,
+ * which starts at 64 Ki hits and is kept between calls (KGMA_E_NOMEM, context still usable, if the larger buffer cannot be had;
+ * KGMA_E_OVERFLOW if it overflows again).
+ * KGMA_E_ARG: a null pointer, a matrix of no rows or of more than 64, a threshold that does not exceed the sum of the row
+ * minima; kgma_last_error names the matrix.  KGMA_E_BADBASE: a genome residue outside A/C/G/T/N, in any record, exactly as in
+ * kgma_motif_match; kgma_last_error names the first such record and residue.
+ * The call needs no references and leaves the KFVs, the hits, dips and distances of the last scan and the matches of the last
+ * kgma_exact_match / kgma_motif_match / kgma_approx_match / kgma_pwm_match as they are; of kgma_stats it sets bases_scanned,
+ * scan_ms (hipEvents around the launches) and n_launches.  kgma_get_codon_matches returns the hits of the last call sorted by
+ * (matrix, contig, start), with the two-call pattern of kgma_get_hits; after a call that failed, for whatever reason, it returns
+ * none.
+ *
+ * kgma_codon_fold (host only: it needs no context and no GPU) makes the codon matrix of one strand from an amino-acid profile.
+ * aa_weights: m rows of KGMA_CODON_AA_COLUMNS = 21 weights, the columns in the order ACDEFGHIKLMNPQRSTVWY*, '*' the stop.
+ * code: the genetic code, 64 bytes: code[16 b0 + 4 b1 + b2] is the column (0 ... 20) the codon b0 b1 b2 translates to.
+ * x_weight: per row the weight of a codon that holds a residue other than A/C/G/T (entry 64).
+ * minus == 0:  out[i][c] = aa_weights[i][code[c]],                          out[i][64] = x_weight[i];
+ * minus != 0:  out[i][c] = aa_weights[m - 1 - i][code[revcomp(c)]],         out[i][64] = x_weight[m - 1 - i],
+ * where revcomp(b0 b1 b2) = (3 - b2)(3 - b1)(3 - b0): the rows are reversed and each codon is read as its reverse complement, so
+ * that a hit of the folded matrix at the forward start s is the profile read on the minus strand over s .. s + 3m - 1.
+ * KGMA_E_ARG: a null pointer, m outside 1 ... 64, a code entry above 20. */
+#define KGMA_CODON_ENTRIES 65
+#define KGMA_CODON_MAX_ROWS 64
+#define KGMA_CODON_AA_COLUMNS 21
+typedef struct {
+    int32_t matrix;      /* 0-based index of the matrix                                        */
+    int32_t contig;      /* 0-based index of the record                                        */
+    int64_t start;       /* 1-based nucleotide position of the first codon's first residue     */
+    int32_t score;       /* score(start), >= threshold of the matrix                           */
+    int32_t reserved;
+} kgma_codon_hit;        /* 24 bytes */
+typedef struct {
+    int32_t lane_starts; /* consecutive starts a lane owns                                     */
+    int32_t wave_starts; /* ... a wave owns                                                    */
+    int32_t wg_starts;   /* ... a workgroup owns                                               */
+    int32_t n_launches;  /* kernel launches of the call (the search, a repeated search)        */
+    int64_t n_candidates; /* starts the kernel emitted: it scores exactly, so = n_hits         */
+    int64_t n_hits;      /* reported hits                                                      */
+    double search_ms;    /* hipEvents around the search launch(es)                             */
+} kgma_codon_stats;
+int kgma_codon_match(kgma_ctx *ctx, const kgma_genome *g, const int16_t *weights /* rows of 65, matrices back to back */,
+                     const int64_t *row_offsets /* n_matrices + 1, in rows */, int32_t n_matrices, const int32_t *threshold /* n_matrices */);
+int kgma_get_codon_matches(kgma_ctx *ctx, kgma_codon_hit *out, int64_t cap, int64_t *n);
+int kgma_get_codon_stats(kgma_ctx *ctx, kgma_codon_stats *out);
+int kgma_codon_fold(const int16_t *aa_weights /* m rows of 21 */, int32_t m, const uint8_t *code /* 64 */, const int16_t *x_weight /* m */,
+                    int32_t minus, int16_t *out /* m rows of 65 */);
+
 /* Threshold calibration: the working form of src/DistanceTesting.jl on the device (kernels: kgma_calib.hip).  Both calls need
  * the references of kgma_set_refs (KGMA_E_STATE before it, or after kgma_set_strobe_ref), serve 1 <= k <= 10 (references at
  * k >= 11 are kept sparse: KGMA_E_UNSUPPORTED) and leave the references, the thresholds and the results of the last scan,

@@ -44,6 +44,7 @@
 #include "kgma_motif.h"
 #include "kgma_approx.h"
 #include "kgma_pwm.h"
+#include "kgma_codon.h"
 
 namespace kgma {
 hipError_t launch_scan(const ScanArgs &a, const GroupParams &gp, hipStream_t st);
@@ -459,6 +460,7 @@ struct kgma_ctx {
     MotifState motif;                        // IUPAC motif search with mismatches (kgma_motif.cpp)
     ApproxState approx;                      // edit-distance search (kgma_approx_match; kgma_approx.cpp)
     PwmState pwm;                            // position-weight-matrix search (kgma_pwm_match; kgma_pwm.cpp)
+    CodonState codon;                        // codon-weight-matrix search (kgma_codon_match; kgma_codon.cpp)
     // calibration (kgma_window_dists / kgma_mutation_dists; kgma_calib.hip): device buffers kept between calls.  d_cbtab is the
     // k >= 8 kernels' counter table, zeroed when allocated and left all-zero by every launch
     int64_t *d_cboff = nullptr; int64_t cboff_cap = 0;
@@ -836,6 +838,7 @@ void kgma_destroy(kgma_ctx *ctx)
     ctx->motif.release();
     ctx->approx.release();
     ctx->pwm.release();
+    ctx->codon.release();
     for (void *q : {(void *)ctx->d_cboff, (void *)ctx->d_cbD, (void *)ctx->d_cbdist, (void *)ctx->d_cbtab, (void *)ctx->d_cbtext,
                     (void *)ctx->d_cbP, (void *)ctx->d_cbbad})
         if (q) (void)hipFree(q);
@@ -1893,6 +1896,7 @@ ExactState *ctx_exact(kgma_ctx *ctx) { return &ctx->exact; }
 MotifState *ctx_motif(kgma_ctx *ctx) { return &ctx->motif; }
 ApproxState *ctx_approx(kgma_ctx *ctx) { return &ctx->approx; }
 PwmState *ctx_pwm(kgma_ctx *ctx) { return &ctx->pwm; }
+CodonState *ctx_codon(kgma_ctx *ctx) { return &ctx->codon; }
 int genome_searchable(kgma_ctx *ctx, const kgma_genome *gc, PackedCopy copy, bool *clean)
 {
     kgma_genome *g = const_cast<kgma_genome *>(gc);   // only its pack bookkeeping and its lazily made plane copy are updated

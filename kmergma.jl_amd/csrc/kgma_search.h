@@ -1,6 +1,6 @@
 // kgma_search.h -- what the host files beside kgma_api.cpp share (host side only): the view they have of a context and a genome,
 // whose structs are kgma_api.cpp's (the functions declared below are defined there and are all of the two that these files see),
-// and the protocol of the four sequence searches (kgma_exact.cpp, kgma_motif.cpp, kgma_approx.cpp, kgma_pwm.cpp):
+// and the protocol of the five sequence searches (kgma_exact.cpp, kgma_motif.cpp, kgma_approx.cpp, kgma_pwm.cpp, kgma_codon.cpp):
 //
 //   a per-record prefix of workgroup counts (tile_prefix) that must fit one launch (one_launch); a genome whose packed copy and
 //   residue check are current (genome_searchable); a buffer of hit records kept on the context (HitBuffer): 65,536 records at

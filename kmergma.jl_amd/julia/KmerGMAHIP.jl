@@ -687,6 +687,119 @@ end
 pwmMatch(matrix::AbstractMatrix{<:Integer}, genome::Union{String, DeviceGenome}; threshold::Integer, ctx::Context = default_context()) =
     pwmMatch([matrix], genome; threshold = threshold, ctx = ctx)[1]
 
+# ---- protMatch: amino-acid profiles in all reading frames (kgma_codon_match, kgma_codon_fold) -------------------------------
+
+struct KgmaCodonHit       # kgma_codon_hit: 0-based matrix and contig, the 1-based nucleotide start
+    matrix::Int32
+    contig::Int32
+    start::Int64
+    score::Int32
+    reserved::Int32
+end
+
+struct KgmaCodonStats     # kgma_codon_stats
+    lane_starts::Int32
+    wave_starts::Int32
+    wg_starts::Int32
+    n_launches::Int32
+    n_candidates::Int64
+    n_hits::Int64
+    search_ms::Float64
+end
+
+function codon_stats(ctx::Context)
+    s = Ref{KgmaCodonStats}()
+    check(ctx, ccall((:kgma_get_codon_stats, libkgma), Cint, (Ptr{Cvoid}, Ref{KgmaCodonStats}), ctx.h, s))
+    return s[]
+end
+
+const AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY*"        # the 21 columns of an amino-acid profile; '*' is the stop
+const GENETIC_CODE_1 = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"   # NCBI table 1, TCAG order
+
+"""
+    genetic_code(letters = GENETIC_CODE_1)
+64 column numbers (0 ... 20, into AMINO_ACIDS) indexed by the codon 16 b0 + 4 b1 + b2 (A 0, C 1, G 2, T 3), from an NCBI-style
+string of 64 letters in TCAG order: what kgma_codon_fold takes.
+"""
+function genetic_code(letters::AbstractString = GENETIC_CODE_1)
+    length(letters) == 64 || throw(ArgumentError("a genetic code has 64 letters"))
+    tcag = (2, 1, 3, 0)                                # where A, C, G, T stand in T, C, A, G
+    code = Vector{UInt8}(undef, 64)
+    for c in 0:63
+        i = 16 * tcag[(c >> 4) + 1] + 4 * tcag[((c >> 2) & 3) + 1] + tcag[(c & 3) + 1]
+        col = findfirst(==(uppercase(letters[i + 1])), AMINO_ACIDS)
+        col === nothing && throw(ArgumentError("genetic code: letter $(i + 1) is none of $AMINO_ACIDS"))
+        code[c + 1] = UInt8(col - 1)
+    end
+    return code
+end
+
+"""
+    codon_fold(profile; code = genetic_code(), x_weight = minimum(profile, dims = 2), minus = false)
+The m x 65 codon matrix of one strand (kgma_codon_fold; host only) from an m x 21 amino-acid profile (columns AMINO_ACIDS):
+entry 64 (0-based) of a row, a codon with an N, is `x_weight`; `minus`: the rows reversed, each codon read as its reverse complement.
+"""
+function codon_fold(profile::AbstractMatrix{<:Integer}; code::Vector{UInt8} = genetic_code(),
+                    x_weight = vec(minimum(profile, dims = 2)), minus::Bool = false)
+    size(profile, 2) == 21 || throw(ArgumentError("a profile has 21 columns: $AMINO_ACIDS"))
+    m = size(profile, 1)
+    aa = Int16[profile[i, a] for i in 1:m for a in 1:21]   # rows of 21
+    out = Vector{Int16}(undef, 65 * m)
+    st = ccall((:kgma_codon_fold, libkgma), Cint, (Ptr{Int16}, Int32, Ptr{UInt8}, Ptr{Int16}, Int32, Ptr{Int16}),
+               aa, m, code, Int16.(x_weight), minus ? 1 : 0, out)
+    st == 0 || throw(ArgumentError("kgma_codon_fold: 1 ... 64 rows and code entries 0 ... 20"))
+    return permutedims(reshape(Int.(out), 65, m))          # m x 65
+end
+
+"""
+    protMatch(profiles, genome; threshold, strand = "+", code = genetic_code())   -- `genome`: a FASTA path or an open DeviceGenome
+Amino-acid profiles (m x 21 integer weights, columns AMINO_ACIDS, 1 <= m <= 64) laid on every nucleotide start of every record in
+every reading frame of the strands asked for, all in one pass over the genome (kgma_codon_match): per profile the vector of
+(record identifier, range, strand, frame, score) with score >= `threshold` (one number, or one per profile; it must exceed the sum
+of the row minima).  A codon with an N scores its row's minimum.  Ranges are forward coordinates; frame is (lo - 1) mod 3 + 1 on the
+plus strand and -((L - hi) mod 3 + 1) on the minus strand.
+"""
+function protMatch(profiles::Vector{<:AbstractMatrix{<:Integer}}, genome::Union{String, DeviceGenome}; threshold, strand::String = "+",
+                   code::Vector{UInt8} = genetic_code(), ctx::Context = default_context())
+    strand in ("+", "-", "both") || throw(ArgumentError("strand is \"+\", \"-\" or \"both\""))
+    ts = threshold isa Integer ? fill(Int32(threshold), length(profiles)) : Int32.(threshold)
+    length(ts) == length(profiles) || throw(ArgumentError("need one threshold per profile"))
+    g = genome isa String ? genome_from_fasta(ctx, genome) : genome
+    try
+        weights, rows, sent_t, tags = Int16[], Int64[], Int32[], Tuple{Int, String}[]
+        for (i, p) in enumerate(profiles), st in ("+", "-")
+            (strand == "both" || strand == st) || continue
+            W = codon_fold(p; code = code, minus = st == "-")
+            for r in 1:size(W, 1), e in 1:65
+                push!(weights, Int16(W[r, e]))                # rows of 65, matrices back to back
+            end
+            push!(rows, size(W, 1)); push!(sent_t, ts[i]); push!(tags, (i, st))
+        end
+        offsets = Int64[0; cumsum(rows)]
+        check(ctx, ccall((:kgma_codon_match, libkgma), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int16}, Ptr{Int64}, Int32, Ptr{Int32}),
+                         ctx.h, g.h, weights, offsets, length(rows), sent_t))
+        n = Ref{Int64}(0)
+        check(ctx, ccall((:kgma_get_codon_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaCodonHit}, Int64, Ref{Int64}), ctx.h, C_NULL, 0, n))
+        hits = Vector{KgmaCodonHit}(undef, n[])
+        check(ctx, ccall((:kgma_get_codon_matches, libkgma), Cint, (Ptr{Cvoid}, Ptr{KgmaCodonHit}, Int64, Ref{Int64}), ctx.h, hits, n[], n))
+        out = [Tuple{String, UnitRange{Int64}, String, Int, Int}[] for _ in profiles]
+        for h in hits
+            i, st = tags[h.matrix + 1]
+            lo = h.start
+            hi = lo + 3 * size(profiles[i], 1) - 1
+            L = ccall((:kgma_genome_contig_len, libkgma), Int64, (Ptr{Cvoid}, Int64), g.h, h.contig)
+            frame = st == "+" ? Int(mod(lo - 1, 3) + 1) : -Int(mod(L - hi, 3) + 1)
+            push!(out[i], (identifier(g, h.contig), lo:hi, st, frame, Int(h.score)))
+        end
+        return out
+    finally
+        genome isa String && free!(g)
+    end
+end
+protMatch(profile::AbstractMatrix{<:Integer}, genome::Union{String, DeviceGenome}; threshold::Integer, strand::String = "+",
+          code::Vector{UInt8} = genetic_code(), ctx::Context = default_context()) =
+    protMatch([profile], genome; threshold = threshold, strand = strand, code = code, ctx = ctx)[1]
+
 # ---- threshold calibration (the working form of src/DistanceTesting.jl): kgma_window_dists, kgma_mutation_dists -------------
 
 """
@@ -946,7 +1059,7 @@ function genome_kmer_count(g::DeviceGenome, k::Integer, contig::Vector{Int32}, l
     return counts, skipped
 end
 
-export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, approxMatch, pwmMatch, pwm_revcomp, HumanRSSV, HumanRSSD, Context
+export ac_gma_testing!, Omn_KmerGMA!, record_KmerGMA!, StrobeGMA!, exactMatch, exactMatch_batch, motifMatch, approxMatch, pwmMatch, pwm_revcomp, protMatch, codon_fold, genetic_code, HumanRSSV, HumanRSSD, Context
 export dist_layout, dist_bins, dist_sweep
 export window_dists, mutation_dists, strobe_window_dists, strobe_mutation_dists, assignGenes, assign_ranges
 export kmer_dist_matrix, kmer_dist_matrix_ranges, nearest_refs, assignGenes_screened

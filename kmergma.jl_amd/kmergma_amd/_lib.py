@@ -38,6 +38,7 @@ EXPORTS = [
     "kgma_motif_match", "kgma_get_motif_matches",
     "kgma_approx_match", "kgma_get_approx_matches", "kgma_get_approx_stats",
     "kgma_pwm_match", "kgma_get_pwm_matches", "kgma_get_pwm_stats",
+    "kgma_codon_match", "kgma_get_codon_matches", "kgma_get_codon_stats", "kgma_codon_fold",
     "kgma_get_filter_stats", "kgma_get_filter_candidates", "kgma_genome_revcomp", "kgma_genome_revcomp_into",
     "kgma_get_block_sums", "kgma_genome_from_2bit_file", "kgma_get_2bit_unpack_ms", "kgma_twobit_inspect",
     "kgma_window_dists", "kgma_mutation_dists", "kgma_strobe_window_dists", "kgma_strobe_mutation_dists",
@@ -109,6 +110,15 @@ class KgmaPwmStats(C.Structure):
                 ("n_candidates", C.c_int64), ("n_hits", C.c_int64), ("search_ms", C.c_double)]
 
 
+class KgmaCodonHit(C.Structure):
+    _fields_ = [("matrix", C.c_int32), ("contig", C.c_int32), ("start", C.c_int64), ("score", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KgmaCodonStats(C.Structure):
+    _fields_ = [("lane_starts", C.c_int32), ("wave_starts", C.c_int32), ("wg_starts", C.c_int32), ("n_launches", C.c_int32),
+                ("n_candidates", C.c_int64), ("n_hits", C.c_int64), ("search_ms", C.c_double)]
+
+
 class KgmaTwobitInfo(C.Structure):
     _fields_ = [("version", C.c_int32), ("reserved", C.c_int32), ("n_records", C.c_int64), ("total_bases", C.c_int64),
                 ("n_blocks", C.c_int64), ("mask_blocks", C.c_int64), ("packed_bytes", C.c_int64)]
@@ -169,6 +179,9 @@ MOTIF_HIT_DTYPE = np.dtype([("motif", "<i4"), ("contig", "<i4"), ("start", "<i8"
 APPROX_HIT_DTYPE = np.dtype([("query", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("end", "<i8"), ("edits", "<i4"), ("reserved", "<i4")])
 
 PWM_HIT_DTYPE = np.dtype([("matrix", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("score", "<i4"), ("reserved", "<i4")])
+
+CODON_HIT_DTYPE = np.dtype([("matrix", "<i4"), ("contig", "<i4"), ("start", "<i8"), ("score", "<i4"), ("reserved", "<i4")])
+CODON_ENTRIES, CODON_MAX_ROWS, CODON_AA_COLUMNS = 65, 64, 21   # KGMA_CODON_ENTRIES, KGMA_CODON_MAX_ROWS, KGMA_CODON_AA_COLUMNS
 
 ASSIGNMENT_DTYPE = np.dtype([("ref", "<i4"), ("score", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"),
                              ("q_lo", "<i4"), ("q_hi", "<i4")])   # kgma_assignment
@@ -232,6 +245,10 @@ def load():
     L.kgma_pwm_match.argtypes = [vp, vp, P(C.c_int16), P(i64), i32, P(i32)]
     L.kgma_get_pwm_matches.argtypes = [vp, P(KgmaPwmHit), i64, P(i64)]
     L.kgma_get_pwm_stats.argtypes = [vp, P(KgmaPwmStats)]
+    L.kgma_codon_match.argtypes = [vp, vp, P(C.c_int16), P(i64), i32, P(i32)]
+    L.kgma_get_codon_matches.argtypes = [vp, P(KgmaCodonHit), i64, P(i64)]
+    L.kgma_get_codon_stats.argtypes = [vp, P(KgmaCodonStats)]
+    L.kgma_codon_fold.argtypes = [P(C.c_int16), i32, P(C.c_uint8), P(C.c_int16), i32, P(C.c_int16)]
     L.kgma_genome_from_host.argtypes = [vp, P(C.c_char_p), P(i64), i64, P(vp)]
     L.kgma_genome_from_fasta.argtypes = [vp, vp, i64, P(vp)]
     L.kgma_genome_from_fasta_file.argtypes = [vp, C.c_char_p, P(vp)]
@@ -347,6 +364,32 @@ def twobit_inspect(path) -> dict:
     if st != KGMA_OK:
         raise KgmaError(st, err.value.decode("utf-8", "replace"))
     return {f: int(getattr(info, f)) for f, _ in KgmaTwobitInfo._fields_ if f != "reserved"}
+
+
+def codon_fold(aa_weights, code, x_weight, minus: bool = False) -> np.ndarray:
+    """kgma_codon_fold: the (m, 65) codon matrix of one strand from an amino-acid profile -- `aa_weights` (m, 21) integers, the
+    columns in the order ACDEFGHIKLMNPQRSTVWY*; `code` 64 column numbers (0 ... 20) indexed by the codon 16 b0 + 4 b1 + b2
+    (A 0, C 1, G 2, T 3); `x_weight` (m,) the weight of a codon with an N.  minus: the rows reversed and each codon read as
+    its reverse complement.  Host only: needs no GPU."""
+    aa = np.asarray(aa_weights)
+    cd = np.asarray(code)
+    xw = np.asarray(x_weight)
+    if aa.ndim != 2 or aa.shape[1] != CODON_AA_COLUMNS or not np.issubdtype(aa.dtype, np.integer):
+        raise ValueError(f"aa_weights: need an (m, {CODON_AA_COLUMNS}) array of integers")
+    if xw.shape != (aa.shape[0],) or not np.issubdtype(xw.dtype, np.integer):
+        raise ValueError("x_weight: need one integer per row")
+    if cd.shape != (64,) or not np.issubdtype(cd.dtype, np.integer) or (cd < 0).any() or (cd > 255).any():
+        raise ValueError("code: need 64 column numbers")
+    for a in (aa, xw):
+        if a.size and (int(a.min()) < -32768 or int(a.max()) > 32767):
+            raise ValueError("a weight is outside -32768 ... 32767")
+    aa16, x16, cd8 = np.ascontiguousarray(aa, dtype=np.int16), np.ascontiguousarray(xw, dtype=np.int16), np.ascontiguousarray(cd, dtype=np.uint8)
+    out = np.zeros((max(aa.shape[0], 1), CODON_ENTRIES), dtype=np.int16)
+    st = load().kgma_codon_fold(_np_ptr(aa16, C.c_int16), aa.shape[0], _np_ptr(cd8, C.c_uint8), _np_ptr(x16, C.c_int16), int(bool(minus)),
+                                _np_ptr(out, C.c_int16))
+    if st != KGMA_OK:
+        raise KgmaError(st, f"kgma_codon_fold: 1 ... {CODON_MAX_ROWS} rows and code entries 0 ... {CODON_AA_COLUMNS - 1}")
+    return out[:aa.shape[0]].astype(np.int64)
 
 
 def is_twobit(path) -> bool:
@@ -690,6 +733,47 @@ class Context:
         s = KgmaPwmStats()
         self._check(load().kgma_get_pwm_stats(self._h, C.byref(s)))
         return {name: getattr(s, name) for name, _ in KgmaPwmStats._fields_}
+
+    def codon_match(self, genome: Genome, matrices: Sequence, thresholds: Sequence[int]) -> None:
+        """kgma_codon_match: every nucleotide start in every record of `genome` at which codon matrix i -- (m, 65) integer
+        weights, 1 <= m <= 64, each in -32768 ... 32767; entry 16 b0 + 4 b1 + b2 (A 0, C 1, G 2, T 3) the codon b0 b1 b2,
+        entry 64 a codon with an N -- scores at least thresholds[i], all three frames.  One pass over the genome for the whole
+        batch.  Needs no references.  codon_matches() afterwards."""
+        mats = [np.asarray(m) for m in matrices]
+        for i, m in enumerate(mats):
+            if m.ndim != 2 or m.shape[1] != CODON_ENTRIES or not np.issubdtype(m.dtype, np.integer):
+                raise ValueError(f"matrix {i}: need an (m, {CODON_ENTRIES}) array of integers")
+            bad = np.argwhere((m < -32768) | (m > 32767))
+            if bad.size:
+                raise ValueError(f"matrix {i}, row {int(bad[0][0]) + 1}: weight {int(m[tuple(bad[0])])} is outside -32768 ... 32767")
+        thr = [int(t) for t in thresholds]
+        if len(thr) != len(mats):
+            raise ValueError("need one threshold per matrix")
+        for i, t in enumerate(thr):
+            if not -2 ** 31 <= t < 2 ** 31:
+                raise ValueError(f"matrix {i}: threshold {t} does not fit an int32")
+        w = np.ascontiguousarray(np.concatenate([m.reshape(-1, CODON_ENTRIES) for m in mats]
+                                                + [np.zeros((1, CODON_ENTRIES), np.int64)]).astype(np.int16))
+        off = np.zeros(len(mats) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([m.shape[0] for m in mats])
+        th = np.asarray(thr + [0], dtype=np.int32)                  # (never empty: a pointer to take)
+        self._check(load().kgma_codon_match(self._h, genome._h, _np_ptr(w, C.c_int16), _np_ptr(off, C.c_int64), len(mats),
+                                            _np_ptr(th, C.c_int32)))
+
+    def codon_matches(self) -> np.ndarray:
+        """Hits of the last codon_match as a structured array (CODON_HIT_DTYPE: 0-based matrix and contig, 1-based nucleotide
+        start, score), sorted by (matrix, contig, start)."""
+        n = C.c_int64(0)
+        self._check(load().kgma_get_codon_matches(self._h, None, 0, C.byref(n)))
+        arr = np.zeros(max(n.value, 1), dtype=CODON_HIT_DTYPE)
+        self._check(load().kgma_get_codon_matches(self._h, arr.ctypes.data_as(C.POINTER(KgmaCodonHit)), n.value, C.byref(n)))
+        return arr[:n.value]
+
+    def codon_stats(self) -> dict:
+        """kgma_get_codon_stats: the kernel's geometry, candidates, hits, launches and device time of the last codon_match."""
+        s = KgmaCodonStats()
+        self._check(load().kgma_get_codon_stats(self._h, C.byref(s)))
+        return {name: getattr(s, name) for name, _ in KgmaCodonStats._fields_}
 
     def set_thresholds(self, thr: Sequence[float]) -> None:
         th = np.asarray(list(thr)[:self.m], dtype=np.float64)

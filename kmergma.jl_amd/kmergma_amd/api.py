@@ -1034,6 +1034,370 @@ def findRSS_pwm(genome_or_path, sites_or_matrix, *, pvalue: float = 1e-6, strand
     return pwmMatch(matrix, genome_or_path, pvalue=pvalue, strand=strand, background=background, ctx=ctx)
 
 
+# ---- amino-acid profile search in all six reading frames (kgma_codon_match) --------------------------------------------------
+
+AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY*"      # the 21 columns of an amino-acid profile; '*' is the stop
+PROT_MAX_ROWS = 64
+# NCBI translation tables as 64 letters in the order TTT, TTC, TTA, TTG, TCT, ... GGG (bases in the order T, C, A, G)
+GENETIC_CODES = {1: "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"}
+_AA_COLUMN = {ch: i for i, ch in enumerate(AMINO_ACIDS)}
+_TCAG_OF_BASE = (2, 1, 3, 0)               # where A, C, G, T stand in T, C, A, G
+_COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def genetic_code(table=1) -> np.ndarray:
+    """A genetic code as kgma_codon_fold takes it: 64 column numbers (0 ... 20, into AMINO_ACIDS) indexed by the codon
+    16 b0 + 4 b1 + b2 with A 0, C 1, G 2, T 3.  `table`: the number of a shipped NCBI table (1, the standard code), any
+    NCBI-style string of 64 letters in TCAG order (TTT, TTC, TTA, TTG, TCT, ...; '*' the stop), or such an array itself."""
+    if isinstance(table, np.ndarray):
+        if table.shape != (64,) or table.dtype.kind not in "iu" or (table < 0).any() or (table > 20).any():
+            raise ValueError("a genetic code array holds 64 column numbers 0 ... 20")
+        return table.astype(np.int64)
+    if isinstance(table, (int, np.integer)):
+        if int(table) not in GENETIC_CODES:
+            raise ValueError(f"genetic code {int(table)} is not shipped (have {sorted(GENETIC_CODES)}): pass its 64 letters in TCAG order")
+        table = GENETIC_CODES[int(table)]
+    if isinstance(table, (bytes, bytearray)):
+        table = bytes(table).decode("ascii", "replace")
+    if not isinstance(table, str):
+        raise TypeError("genetic code: a table number or a string of 64 letters")
+    letters = table.upper()
+    if len(letters) != 64:
+        raise ValueError(f"a genetic code has 64 letters, not {len(letters)}")
+    for i, ch in enumerate(letters):
+        if ch not in _AA_COLUMN:
+            raise ValueError(f"genetic code, letter {i + 1}: {ch!r} is none of {AMINO_ACIDS}")
+    T = _TCAG_OF_BASE
+    return np.array([_AA_COLUMN[letters[16 * T[c >> 4] + 4 * T[(c >> 2) & 3] + T[c & 3]]] for c in range(64)], dtype=np.int64)
+
+
+_code_of = genetic_code                   # (the functions below have a parameter of that name)
+
+
+def _codon_codes(seq: bytes) -> np.ndarray:
+    """Codon code 0 ... 63, or 64 with a residue other than A/C/G/T, of every whole codon of `seq` from its first residue."""
+    t = np.frombuffer(seq.upper(), dtype=np.uint8)
+    t = t[:t.size - t.size % 3]
+    b = np.full(256, 4, dtype=np.int64)
+    b[list(b"ACGT")] = (0, 1, 2, 3)
+    x = b[t].reshape(-1, 3)
+    return np.where((x > 3).any(axis=1), 64, 16 * x[:, 0] + 4 * x[:, 1] + x[:, 2])
+
+
+def translate(seq, frame: int = 1, genetic_code=1) -> str:
+    """The amino acids (letters of AMINO_ACIDS, '*' the stop) of reading frame `frame` of `seq` (bytes / str / Record; case
+    folded): 1, 2, 3 begin at the first, second, third residue; -1, -2, -3 read the reverse complement from its first,
+    second, third residue.  A codon that holds any residue other than A/C/G/T is 'X', also where every base at that place
+    gives the same amino acid: CTN is X, not Leu.  A trailing part of a codon is dropped."""
+    if frame not in (1, 2, 3, -1, -2, -3):
+        raise ValueError("frame is one of 1, 2, 3, -1, -2, -3")
+    s = _query_bytes(seq)
+    if frame < 0:
+        s = s.translate(_COMPLEMENT)[::-1]
+    col = _code_of(genetic_code)
+    codes = _codon_codes(s[abs(frame) - 1:])
+    letters = np.frombuffer((AMINO_ACIDS + "X").encode(), dtype=np.uint8)
+    return letters[np.where(codes == 64, 21, col[np.minimum(codes, 63)])].tobytes().decode()
+
+
+def _prot_matrix(matrix, which: str = "profile") -> np.ndarray:
+    """The checks on one amino-acid profile, made before any device call: an (m, 21) int64 array."""
+    if isinstance(matrix, (str, bytes, bytearray, memoryview, Record)) or matrix is None:
+        raise TypeError("Invalid profile type")
+    a = np.asarray(matrix)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"{which}: the weights must be integers (scale and round a log-odds matrix: prot_matrix_from_sequences)")
+    if a.ndim != 2 or a.shape[1] != len(AMINO_ACIDS):
+        raise ValueError(f"{which}: need rows of 21 weights ({AMINO_ACIDS}), got shape {a.shape}")
+    if not 1 <= a.shape[0] <= PROT_MAX_ROWS:
+        raise ValueError(f"{which} has {a.shape[0]} rows (1 ... {PROT_MAX_ROWS})")
+    a = a.astype(np.int64)
+    bad = np.argwhere((a < PWM_WEIGHT_MIN) | (a > PWM_WEIGHT_MAX))
+    if bad.size:
+        raise ValueError(f"{which}, row {int(bad[0][0]) + 1}: weight {int(a[tuple(bad[0])])} is outside {PWM_WEIGHT_MIN} ... {PWM_WEIGHT_MAX}")
+    return a
+
+
+def prot_pattern(pattern: str):
+    """The 0/-1 profile of a PROSITE-style pattern and its length in residues: (matrix, m), matrix (m, 21) over AMINO_ACIDS.
+    Elements, separated by '-' (the separator may be left out): a residue `W`; a set `[VIFY]` (any of them); an excluded set
+    `{PG}` (anything but them -- the stop included unless it is listed); `x` (anything, the stop included: a row of 21 zeros,
+    which costs nothing); `*` the stop; each may be followed by a repeat count `(n)`, as in `x(3)`.  Letters are those of
+    AMINO_ACIDS, in either case.  A position scores 0 where the element admits the amino acid and -1 where it does not, so
+    score = -mismatches and protMatch(..., max_mismatch=d) is the threshold -d.  Ranges `x(2,4)` and the anchors `<` `>`
+    have no fixed-length form and are refused (ValueError)."""
+    if not isinstance(pattern, str):
+        raise TypeError("a pattern is a string")
+    text = pattern.strip()
+    if text.endswith("."):
+        text = text[:-1]
+    if not text:
+        raise ValueError("empty pattern")
+    rows, i = [], 0
+
+    def letters(body, what):
+        if not body:
+            raise ValueError(f"pattern, position {i + 1}: an empty {what}")
+        cols = []
+        for ch in body.upper():
+            if ch not in _AA_COLUMN:
+                raise ValueError(f"pattern, position {i + 1}: {ch!r} is none of {AMINO_ACIDS}" + (" (x stands alone)" if ch == "X" else ""))
+            cols.append(_AA_COLUMN[ch])
+        return cols
+
+    while i < len(text):
+        ch = text[i]
+        if ch == "-":
+            i += 1
+            continue
+        row = np.full(len(AMINO_ACIDS), -1, dtype=np.int64)
+        if ch in "[{":
+            close = text.find("]" if ch == "[" else "}", i)
+            if close < 0:
+                raise ValueError(f"pattern, position {i + 1}: {ch!r} is not closed")
+            cols = letters(text[i + 1:close], "set")
+            if ch == "[":
+                row[cols] = 0
+            else:
+                row[:] = 0
+                row[cols] = -1
+            end = close + 1
+        elif ch in "xX":
+            row[:] = 0
+            end = i + 1
+        else:
+            row[letters(ch, "element")] = 0
+            end = i + 1
+        n = 1
+        if end < len(text) and text[end] == "(":
+            close = text.find(")", end)
+            count = text[end + 1:close] if close > 0 else ""
+            if not count.isdigit() or int(count) < 1:
+                raise ValueError(f"pattern, position {end + 1}: a repeat count is one positive number, as in x(3)")
+            n, end = int(count), close + 1
+        rows += [row] * n
+        if len(rows) > PROT_MAX_ROWS:
+            raise ValueError(f"the pattern has more than {PROT_MAX_ROWS} positions")
+        i = end
+    if not rows:
+        raise ValueError("empty pattern")
+    return np.stack(rows), len(rows)
+
+
+def prot_matrix_from_sequences(aa_seqs, *, pseudocount: float = 1.0, background=None, scale: float = 100) -> np.ndarray:
+    """Log-odds amino-acid profile of equal-length example peptides (the 20 amino-acid letters, either case): the (m, 21)
+    int64 array whose first 20 columns are np.rint(scale * log2(((count + pseudocount * bg) / (n + pseudocount)) / bg)) in
+    the order of AMINO_ACIDS and whose stop column is the row's minimum.  `background`: 20 positive probabilities that sum to
+    1 (None: 1/20 each).  With scale = 100 the weights are centibits, like pwm_from_sequences'.  ValueError when a weight
+    leaves the int16 range (a count of 0 without a pseudocount, a scale too large)."""
+    rows = []
+    for q in aa_seqs:
+        s = (q.decode("ascii", "replace") if isinstance(q, (bytes, bytearray)) else q).upper() if isinstance(q, (str, bytes, bytearray)) else None
+        if s is None:
+            raise TypeError("a peptide is a str or bytes")
+        rows.append(s)
+    if not rows:
+        raise ValueError("need at least one sequence")
+    m = len(rows[0])
+    if not 1 <= m <= PROT_MAX_ROWS:
+        raise ValueError(f"the sequences have {m} residues (1 ... {PROT_MAX_ROWS})")
+    if any(len(r) != m for r in rows):
+        raise ValueError("the sequences differ in length")
+    bg = np.full(20, 0.05) if background is None else np.asarray(background, dtype=np.float64)
+    if bg.shape != (20,) or not np.isfinite(bg).all() or (bg <= 0).any() or not math.isclose(float(bg.sum()), 1.0, rel_tol=0, abs_tol=1e-9):
+        raise ValueError("background: twenty positive probabilities (ACDEFGHIKLMNPQRSTVWY) that sum to 1")
+    if not (math.isfinite(pseudocount) and pseudocount >= 0 and math.isfinite(scale) and scale > 0):
+        raise ValueError("pseudocount must be >= 0 and scale > 0")
+    count = np.zeros((m, 20), dtype=np.float64)
+    for r in rows:
+        for i, ch in enumerate(r):
+            if _AA_COLUMN.get(ch, 20) >= 20:
+                raise ValueError("the sequences may hold the 20 amino-acid letters only")
+            count[i, _AA_COLUMN[ch]] += 1
+    with np.errstate(divide="ignore"):
+        w = np.rint(scale * np.log2(((count + pseudocount * bg) / (len(rows) + pseudocount)) / bg))
+    if not np.isfinite(w).all() or (w < PWM_WEIGHT_MIN).any() or (w > PWM_WEIGHT_MAX).any():
+        i = int(np.argwhere(~np.isfinite(w) | (w < PWM_WEIGHT_MIN) | (w > PWM_WEIGHT_MAX))[0][0])
+        raise ValueError(f"row {i + 1}: a weight leaves {PWM_WEIGHT_MIN} ... {PWM_WEIGHT_MAX} (give a pseudocount or a smaller scale)")
+    w = w.astype(np.int64)
+    return np.concatenate([w, w.min(axis=1, keepdims=True)], axis=1)
+
+
+def prot_fold(matrix, *, genetic_code=1, x_weight=None, minus: bool = False) -> np.ndarray:
+    """The (m, 65) codon matrix kgma_codon_match searches one strand with (kgma_codon_fold): entry 16 b0 + 4 b1 + b2 of row i
+    is matrix[i][amino acid of the codon]; entry 64, a codon with an N, is x_weight[i] -- by default the row's minimum over
+    its 21 columns, so an assembly gap never looks like a signal.  minus: the matrix of the other strand (rows reversed,
+    each codon read as its reverse complement)."""
+    a = _prot_matrix(matrix)
+    x = a.min(axis=1) if x_weight is None else np.asarray(x_weight, dtype=np.int64)
+    return _lib.codon_fold(a, _code_of(genetic_code), x, minus)
+
+
+def prot_score_distribution(matrix, background=_UNIFORM, genetic_code=1):
+    """(lowest, p): p[k] is the probability that m independent codons score lowest + k, a codon's probability being the
+    product of its three base frequencies in `background` (A, C, G, T) -- exactly, on the integer lattice, one convolution
+    per row."""
+    a, bg, col = _prot_matrix(matrix), _background(background), _code_of(genetic_code)
+    c = np.arange(64)
+    pc = bg[c >> 4] * bg[(c >> 2) & 3] * bg[c & 3]
+    total, p = 0, np.ones(1, dtype=np.float64)
+    for row in a:
+        w = row[col]                                             # the weight of each codon
+        base = int(w.min())
+        mass = np.bincount(w - base, weights=pc)
+        p = np.convolve(p, mass)
+        total += base
+    return total, p
+
+
+def prot_threshold(matrix, pvalue: float, background=_UNIFORM, genetic_code=1) -> int:
+    """The smallest integer t with P(score >= t) <= pvalue for independent codons of independent bases drawn from `background`
+    (A, C, G, T; the default is uniform), from the exact score distribution (prot_score_distribution).  One above the highest
+    score when even that one is likelier than pvalue."""
+    if not 0 < float(pvalue) < 1:
+        raise ValueError("pvalue must lie strictly between 0 and 1")
+    lowest, p = prot_score_distribution(matrix, background, genetic_code)
+    tail = np.cumsum(p[::-1])[::-1]
+    ok = np.flatnonzero(tail <= float(pvalue))
+    return lowest + (int(ok[0]) if ok.size else p.size)
+
+
+def _prot_args(profiles, threshold, max_mismatch, pvalue, strand, code, background=None):
+    _check_strand(strand)
+    given = [x is not None for x in (threshold, max_mismatch, pvalue)]
+    is_pattern = [isinstance(p, str) for p in profiles]
+    if sum(given) > 1 or (sum(given) == 0 and not all(is_pattern)):
+        raise ValueError("give exactly one of threshold, max_mismatch and pvalue (a pattern alone means max_mismatch=0)")
+    if max_mismatch is not None and not all(is_pattern):
+        raise ValueError("max_mismatch counts the mismatches of a pattern: give a matrix a threshold or a pvalue")
+    ms = [prot_pattern(p)[0] if isinstance(p, str) else _prot_matrix(p, f"profile {i}") for i, p in enumerate(profiles)]
+
+    def per_matrix(x, what, conv):
+        if isinstance(x, (int, float, np.integer, np.floating)):
+            return [conv(x)] * len(ms)
+        xs = [conv(v) for v in x]
+        if len(xs) != len(ms):
+            raise ValueError(f"need one {what} per profile")
+        return xs
+
+    if pvalue is not None:
+        bg = _UNIFORM if background is None else background
+        ts = [prot_threshold(m, x, bg, code) for m, x in zip(ms, per_matrix(pvalue, "pvalue", float))]
+    elif threshold is not None:
+        ts = per_matrix(threshold, "threshold", int)
+    else:
+        ds = per_matrix(0 if max_mismatch is None else max_mismatch, "max_mismatch", int)
+        for i, (m, d) in enumerate(zip(ms, ds)):
+            informative = int((m.min(axis=1) < 0).sum())
+            if not 0 <= d < informative:
+                raise ValueError(f"pattern {i}: max_mismatch {d} must be at least 0 and smaller than its {informative} positions other than x")
+        ts = [-d for d in ds]
+    sent, tags = [], []
+    for i, (m, t) in enumerate(zip(ms, ts)):
+        plus = prot_fold(m, genetic_code=code)
+        lowest = int(plus.min(axis=1).sum())
+        if t <= lowest:
+            raise ValueError(f"profile {i}: threshold {t} does not exceed the sum of its row minima, {lowest}: every start would match")
+        if not t < 2 ** 31:
+            raise ValueError(f"profile {i}: threshold {t} does not fit an int32")
+        # the minus strand: the matrix folded for it, on the SAME genome, in the same pass
+        if strand != "-":
+            sent.append((plus, t)); tags.append((i, "+"))
+        if strand != "+":
+            sent.append((prot_fold(m, genetic_code=code, minus=True), t)); tags.append((i, "-"))
+    return ms, sent, tags
+
+
+def _prot_run(ctx, g, ms, sent, tags) -> list:
+    """Per profile the hits (record, lo, hi, strand, frame, score), sorted by (record, lo, strand)."""
+    ctx.codon_match(g, [m for m, _ in sent], [t for _, t in sent])
+    out = [[] for _ in ms]
+    length = {}
+    for h in ctx.codon_matches().tolist():
+        i, st = tags[h[0]]
+        c, lo = h[1], h[2]
+        hi = lo + 3 * ms[i].shape[0] - 1
+        if st == "+":
+            frame = (lo - 1) % 3 + 1
+        else:
+            if c not in length:
+                length[c] = g.contig_len(c)
+            frame = -((length[c] - hi) % 3 + 1)
+        out[i].append((c, lo, hi, st, frame, h[3]))
+    for lst in out:
+        lst.sort(key=lambda t: (t[0], t[1], t[3]))              # ("+" sorts before "-")
+    return out
+
+
+def _prot_checked(profiles, threshold, max_mismatch, pvalue, strand, genetic_code, background):
+    """The argument checks of protMatch, made before the device is touched: (profiles, genetic code, background)."""
+    profiles, bg, code = list(profiles), _pwm_background(background, None if pvalue is not None else 0), _code_of(genetic_code)
+    _prot_args(profiles, threshold, max_mismatch, pvalue, strand, code, None if isinstance(bg, str) else bg)
+    return profiles, code, bg
+
+
+def _prot_search(ctx, g, profiles, threshold, max_mismatch, pvalue, strand, code, bg) -> list:
+    if isinstance(bg, str):                                      # "genome": the open subject's own composition
+        bg = genome_background(g, ctx=ctx)
+    return _prot_run(ctx, g, *_prot_args(profiles, threshold, max_mismatch, pvalue, strand, code, bg))
+
+
+def protMatch_batch(profiles, genome_or_path, *, threshold=None, max_mismatch=None, pvalue=None, strand: str = "+", genetic_code=1,
+                    background=None, ctx=None) -> list:
+    """Many profiles or patterns, on the strands asked for, in ONE pass over the genome (kgma_codon_match): per profile the
+    list of (record_index, identifier, lo, hi, strand, frame, score) -- 0-based record, 1-based inclusive nucleotide lo:hi in
+    forward coordinates -- sorted by (record, lo, strand).  `threshold` / `max_mismatch` / `pvalue`: one number for all or
+    one per profile.  Semantics: protMatch.  `genome_or_path`: a FASTA or .2bit path, or a device genome that is already open
+    (it stays open)."""
+    profiles, code, bg = _prot_checked(profiles, threshold, max_mismatch, pvalue, strand, genetic_code, background)
+    if not isinstance(genome_or_path, (str, _GenomeView, _lib.Genome)):
+        raise TypeError("Invalid subject sequence type")
+    ctx = ctx or default_context()
+    g, src, owned = _open_subject(ctx, genome_or_path)
+    try:
+        res = _prot_search(ctx, g, profiles, threshold, max_mismatch, pvalue, strand, code, bg)
+        ids = {c: _identifier(src, c) for c in {t[0] for lst in res for t in lst}}
+    finally:
+        if owned:
+            g.free()
+    return [[(c, ids[c], lo, hi, st, fr, sc) for c, lo, hi, st, fr, sc in lst] for lst in res]
+
+
+def protMatch(profile_or_pattern, subject, *, threshold=None, max_mismatch=None, pvalue=None, strand: str = "+", genetic_code=1,
+              background=None, ctx=None):
+    """Every place of the subject that could encode the protein signal, in every reading frame of the strands asked for.
+    `profile_or_pattern`: a PROSITE-style pattern string (prot_pattern; score = -mismatches) or an amino-acid profile of
+    1 ... 64 rows of 21 integer weights (AMINO_ACIDS: ACDEFGHIKLMNPQRSTVWY and '*', the stop; each -32768 ... 32767).  Laid at
+    the nucleotide start s, score(s) = sum over the rows i of profile[i][amino acid of the codon t[s + 3i .. s + 3i + 2]];
+    every start is scored, so the three frames of a strand are found in one pass, overlapping places included, none spanning
+    two records.  Case is folded.  A codon that holds an N is the amino acid X and scores its row's minimum over the 21
+    columns -- also where all four bases give the same amino acid: CTN is X, not Leu.  The subject may hold A/C/G/T/N only
+    (KgmaError KGMA_E_BADBASE otherwise).
+    Give one of `threshold` (an integer that exceeds the sum of the row minima), `max_mismatch` (patterns only: the threshold
+    -d; d smaller than the number of positions other than x; a pattern with none of the three means 0) and `pvalue` (the
+    threshold becomes prot_threshold(profile, pvalue, background, genetic_code); `background` None is uniform, four
+    probabilities (A, C, G, T) are used as given, "genome" is genome_background(subject)).  `genetic_code`: genetic_code()'s
+    argument.
+    strand: "+" as written; "-" the profile read on the reverse complement -- the codon matrix folded for the minus strand,
+    searched on the same genome -- reported at the forward lo:hi it covers; "both" the two together.  frame is
+    (lo - 1) mod 3 + 1 on the plus strand and -((L - hi) mod 3 + 1) on the minus strand, L the record's length: translate's.
+    A `subject` of residues (bytes, or a Record) returns [(lo, hi, strand, frame, score)] sorted by (lo, strand); a FASTA or
+    .2bit path or an open device genome returns protMatch_batch(...)[0].  An empty list when there is no hit.
+    A profile of rows 0 for every amino acid and -1 for the stop, at threshold 0, finds every stop-free stretch of m codons."""
+    if isinstance(subject, (Record, bytes, bytearray, memoryview)):
+        profiles, code, bg = _prot_checked([profile_or_pattern], threshold, max_mismatch, pvalue, strand, genetic_code, background)
+        seq = bytes(subject.sequence if isinstance(subject, Record) else subject)
+        ctx = ctx or default_context()
+        g = ctx.genome_from_host([seq])
+        try:
+            res = _prot_search(ctx, g, profiles, threshold, max_mismatch, pvalue, strand, code, bg)[0]
+        finally:
+            g.free()
+        return [(lo, hi, st, fr, sc) for _, lo, hi, st, fr, sc in res]
+    return protMatch_batch([profile_or_pattern], subject, threshold=threshold, max_mismatch=max_mismatch, pvalue=pvalue, strand=strand,
+                           genetic_code=genetic_code, background=background, ctx=ctx)[0]
+
+
 # ---- threshold calibration (kgma_window_dists, kgma_mutation_dists): the working form of src/DistanceTesting.jl --------------
 
 _M64 = (1 << 64) - 1
