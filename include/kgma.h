@@ -189,12 +189,22 @@ void kgma_destroy(kgma_ctx *ctx);
  *     histograms) is scanned in EXACT integers, S = round(ref*N).  n_refs[m] gives N per KFV; n_refs == NULL: N is inferred
  *     (smallest N <= 2^20 with every ref*N within a relative 1e-14 of an integer);
  *   - any other finite vector (weighted averages, smoothed or hand-edited profiles; also a KFV that is not S/n_refs for the
- *     n_refs given) is scanned in Float64 by the generic kernel: every window's distance within ~1e-12 relative of the
- *     reference's running value; the decisions rounding noise could take either way in the reference -- a window within a
- *     relative 2^-30 of thr, two minima within 2^-30 of each other -- are flagged exactly like the integer form's exact ties
- *     (KGMA_HIT_AT_THRESHOLD / KGMA_HIT_TIE), and KGMA_F_CHAIN_REPLAY decides them from the reference's own running value
- *     (replayed on the device from the caller's table, bit for bit).  kgma_hit.D / kgma_dip.D_* are then round(d * 2kN^2) with N a power of
- *     two (kgma_kfv_scale), kgma_hit.dist the Float64 distance.
+ *     n_refs given) is scanned in Float64 by the generic kernel.  Window q's distance (q = 0, 1, ... within its record) lies
+ *     within an ABSOLUTE bound of the exact rational distance d_q = (1/2k) sum (ref - c_q)^2, and so does the reference's
+ *     running value:  u [(max(P, n) + 5) A / 2k + (q + 4) M / k],  u = 2^-53, P the KFV's non-zero entries, n the k-mers per
+ *     window, A = sum ref^2 + 2 sum_{p in window} |ref[K_p]| + n + 2 pairs at its largest over the record's windows up to q,
+ *     M the sum over the steps up to q of (1 + c[r]) + |ref[l]| + |ref[r]| + c[l] ("The Float64 scan in exact
+ *     arithmetic"; measured: the device at most 0.05 of it, the reference 0.3).  That is a relative 1e-13 ... 1e-11 where the
+ *     distance is of the order of A -- an ordinary profile -- and no relative statement at all where the KFV nearly equals a
+ *     window's own counts: there the distance is smaller than the bound and the value is rounding noise.  What the scan itself
+ *     computes is never below zero: a sum the rounding took below zero is 0.0 in kgma_get_dists, in the dips and hits of a
+ *     default-mode scan and (as D = 0) in kgma_get_first_window.  The decisions rounding noise could take either way in the
+ *     reference -- a window within a relative 2^-30 of thr, two minima within 2^-30 of each other -- are flagged exactly like
+ *     the integer form's exact ties (KGMA_HIT_AT_THRESHOLD / KGMA_HIT_TIE), and KGMA_F_CHAIN_REPLAY decides them from the
+ *     reference's own running value (replayed on the device from the caller's table, bit for bit).  That value is the
+ *     reference's with its sign: a chain-decided hit (KGMA_HIT_CHAIN) at such a window may carry a dist, and a D, a few ulps
+ *     of the window's terms below zero, as the reference's own hit does.  kgma_hit.D / kgma_dip.D_* are round(d * 2kN^2) with
+ *     N a power of two (kgma_kfv_scale), kgma_hit.dist the Float64 distance.
  * Requires 1 <= k <= 15 (a k-mer is at most 30 bits of the 2-bit genome), k < min(windowsizes) (src/API.jl:70,177) and at most
  * 65535 k-mers per window (windowsize - k + 1; the reference itself has no bound, src/ReferenceGeneration.jl:35-40);
  * KGMA_E_UNSUPPORTED otherwise, and for S/N KFVs whose largest possible D = sum S^2 + N^2 n^2 does not fit 61 bits.
@@ -371,7 +381,8 @@ int kgma_get_dists(kgma_ctx *ctx, int32_t kfv, double *out, int64_t cap, int64_t
  * All three: KGMA_E_UNSUPPORTED for strobemer references (their distance vector follows another window convention).  The two
  * device calls: KGMA_E_STATE when the last scan kept no distances, KGMA_E_ARG for kfv outside the KFVs the last scan evaluated,
  * bin < 1, n_thr out of range, or a threshold that is not finite or not above the one before it.  The values are taken as
- * non-negative doubles, as every scan writes them.  Nothing stays allocated after a call; the results of the scan are untouched. */
+ * non-negative doubles, as every scan writes them (the integer forms by construction, the Float64 form because it writes 0.0
+ * for a distance whose rounding noise went below zero: kgma_set_refs).  Nothing stays allocated after a call; the results of the scan are untouched. */
 #define KGMA_SWEEP_MAX_THRESHOLDS 4096
 int kgma_dist_layout(kgma_ctx *ctx, int64_t *offset, int64_t cap, int64_t *n);
 int kgma_dist_bins(kgma_ctx *ctx, int32_t kfv, int64_t bin, double *bin_min, int64_t *bin_argmin, int64_t *bin_offset /* records + 1, or NULL */,

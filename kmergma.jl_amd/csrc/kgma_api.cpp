@@ -3724,7 +3724,9 @@ int collect_results(kgma_ctx *ctx, kgma_genome *g, const ScanPlan &p, const Scan
         for (int64_t s = 0; s < n_scan; s++) {
             double dv;
             memcpy(&dv, &ctx->D0[(size_t)j * (size_t)n_scan + (size_t)s], sizeof dv);
-            ctx->D0[(size_t)j * (size_t)n_scan + (size_t)s] = lattice_of(kf, k, dv);
+            // (a first distance whose rounding noise went below zero -- the KFV is that window's counts up to noise -- is 0, as the
+            //  kernel writes it for every later window; -1 in kgma_get_first_window means "record skipped")
+            ctx->D0[(size_t)j * (size_t)n_scan + (size_t)s] = lattice_of(kf, k, dv < 0.0 ? 0.0 : dv);
         }
     }
     ctx->firstD.assign((size_t)ctx->m * (size_t)nc, -1);

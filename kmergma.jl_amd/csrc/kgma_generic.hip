@@ -680,7 +680,17 @@ __global__ __launch_bounds__(1024) void gen_kernel(ScanArgs a, GenParams g)
                 }
             }
             carry = O::lane_of(val, 63);
-            if constexpr (FP) val = d0 + val;
+            if constexpr (FP) {
+                // A distance is a sum of squares; d0's identity cancels (sum ref^2 - 2 sum ref[K_p] against n + 2 pairs), so where
+                // the KFV is a window's own count vector up to noise the sum d0 + val is rounding noise of either sign (seen on
+                // the device: -2e-14 at k = 1, -4e-15 at k = 3).  A value below zero is replaced by zero: that only moves it
+                // towards the exact distance, equal values stay equal (the plateaus above), and every consumer of the distances --
+                // kgma_get_dists, the dip records, the landscape reductions, which order them by their bit patterns -- keeps the
+                // non-negative doubles kgma.h promises.  (d0 itself stays as computed: it is the anchor of the later windows.
+                // The sum is never -0.0: carry starts at +0.0 and no operand above is -0.0.)
+                val = d0 + val;
+                val = val < 0.0 ? 0.0 : val;
+            }
             const int q = p - nk + 1;                                 // window start (local) this transition leads to
             const bool tested = q >= first_test && q < n_valid;
             bool under, att;

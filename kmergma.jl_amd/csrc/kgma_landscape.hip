@@ -8,7 +8,8 @@
 //   LS_WG_VALUES consecutive values, a wave LS_WAVE_VALUES of them in stretches of LS_STRETCH (one 16-byte load per lane, all of a
 //   wave's loads issued before the first is used).  The bins a workgroup touches are consecutive, so they index a table in LDS.
 //   Minima are compared as 64-bit patterns (the distances are non-negative, so that is their order, and the result is the stored
-//   double bit for bit).  Phase 0 folds the values into the table's minima, phase 1 the local index of every value that equals its
+//   double bit for bit; the integer forms cannot write a negative one, and gen_kernel's Float64 form writes 0.0 for a value its
+//   rounding took below zero -- kgma_generic.hip).  Phase 0 folds the values into the table's minima, phase 1 the local index of every value that equals its
 //   bin's minimum into the table's index (the smallest wins: the first window).  A stretch inside one record with bin >= LS_STRETCH
 //   holds at most two bins, known to the whole wave: one butterfly per bin and one LDS atomic per wave in phase 0, two ballots in
 //   phase 1.  Every other stretch (short bins, record boundaries) goes lane by lane with one LDS atomic per value.
